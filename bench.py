@@ -19,6 +19,11 @@ search their embeddings, top-100, over the resident corpus.
           BEFORE anything touches a GPU (children are separate processes, nothing is re-exec'ed).
 
 Rank 0 prints ONE JSON line; DESIGN.md §5 has the roofline arithmetic.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line.  Everything else (the CPU
+baseline, the extras of --extras, the N > 1 self-checks of the collective layer) runs with --full.
+  --dump-outputs DIR   after the timed steps, rank 0 writes what the last timed step returned (query embeddings, top-k scores,
+                       top-k ids) as DIR/<name>.npy in float32 / float64; the inputs are seeded, the same from run to run.
 """
 import argparse
 import json
@@ -50,12 +55,18 @@ def parse_args(argv=None):
     ap.add_argument("--nq", type=int, default=1000)
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--query-len", type=int, default=512, help="padded query length (TopiOCQA: 512, QReCC: 256)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline, the extras (--extras, default 'default') and, at N > 1, the "
+                         "self-verification of the collective layer; without it the run is the headline step alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true", help="only the headline step (profiling runs); = --extras none")
-    ap.add_argument("--extras", choices=("none", "verify", "default", "full"), default="default",
-                    help="default: the step's parts, kernel classes, north-star corpus, configs[1] / [3] / [4] shapes (the driver's run: "
-                         "finishes in ~2 min); full: + sustained 30-s loops, the encoder batch sweep and peaked attention; verify: only the "
-                         "north-star corpus step with its N > 1 self-verification; none: the headline step alone")
+    ap.add_argument("--extras", choices=("none", "verify", "default", "full"), default=None,
+                    help="what --full adds (default: 'default'; any other value than 'none' needs --full).  default: the step's parts, "
+                         "kernel classes, north-star corpus, configs[1] / [3] / [4] shapes (finishes in ~2 min); full: + sustained 30-s "
+                         "loops, the encoder batch sweep and peaked attention; verify: only the north-star corpus step with its N > 1 "
+                         "self-verification; none: the headline step alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's outputs to DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--north-star-rows", type=int, default=NORTH_STAR_ROWS, help="tests only: a smaller north-star corpus for rehearsals")
     ap.add_argument("--search-only", action="store_true", help="BASELINE configs[1] style: pre-encoded embeddings, no encoder in the step")
     ap.add_argument("--dump-results", default=None, metavar="NPZ",
@@ -63,8 +74,14 @@ def parse_args(argv=None):
     ap.add_argument("--spawn-selftest", type=int, default=None, metavar="RC",
                     help="tests only: every rank prints its RANK/WORLD_SIZE and exits (rank 1 with code RC); nothing touches a GPU")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.no_extras:
         args.extras = "none"
+    if args.extras is None:
+        args.extras = "default" if args.full else "none"
+    elif args.extras != "none" and not args.full:
+        ap.error(f"--extras {args.extras} needs --full")
     return args
 
 
@@ -237,7 +254,7 @@ def main():
         rows, block_rows, wl_name = CFG4_SHARD_ROWS * world, CFG4_SHARD_ROWS, "BASELINE configs[3] shard size"
     lo, hi = shard_range(rows, rank, world)
     n_local = hi - lo
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = rank == 0 and world == 1 and args.full and not args.no_cpu_baseline
     index = FlatIPIndex(D_EMB, devices=(local_rank,))
     kept = fill_index(index, lo, hi, dev, block_rows, keep_first=1_000_000 if want_cpu else 0)
     searcher = ShardedSearcher(index, shard_base=lo)
@@ -277,22 +294,25 @@ def main():
         gath_keys = torch.empty((world * nq, k), dtype=torch.int64, device=dev)
         dist.all_gather_into_tensor(gath_keys, warm_keys)
         sync()
-        # Self-verification of the collective layer (nobody can rehearse the 8-GPU RCCL run): did the backend see N ranks, does an
-        # all-gather deliver every rank's slab in rank order, and what do the step's two collectives cost by themselves
-        ones = torch.ones(1, device=dev, dtype=torch.int64)
-        dist.all_reduce(ones)
-        warm_keys.fill_(rank + 1)
-        dist.all_gather_into_tensor(gath_keys, warm_keys)
-        slabs = gath_keys.view(world, -1)[:, 0].cpu().tolist()
-        emb_probe = torch.zeros((nq_loc, D_EMB), dtype=torch.float32, device=dev)
-        t_ag_emb = max_over_ranks(timed(lambda: dist.all_gather_into_tensor(allq, emb_probe), 10, sync, barrier)) if enc is not None else None
-        t_ag_keys = max_over_ranks(timed(lambda: dist.all_gather_into_tensor(gath_keys, warm_keys), 10, sync, barrier))
-        collective = {"backend": dist.get_backend(), "world": world, "ranks_seen": int(ones.item()),
-                      "allgather_slabs_in_rank_order": slabs == list(range(1, world + 1)),
-                      "allgather_emb_ms": None if t_ag_emb is None else round(t_ag_emb * 1e3, 4), "allgather_emb_bytes_per_rank": nq_loc * D_EMB * 4,
-                      "allgather_keys_ms": round(t_ag_keys * 1e3, 4), "allgather_keys_bytes_per_rank": nq * k * 8,
-                      "devices": f"rank {rank} on cuda:{local_rank} of {torch.cuda.device_count()} visible"}
-        del gath_keys, emb_probe
+        collective = None
+        if args.full:
+            # Self-verification of the collective layer (nobody can rehearse the 8-GPU RCCL run): did the backend see N ranks, does an
+            # all-gather deliver every rank's slab in rank order, and what do the step's two collectives cost by themselves
+            ones = torch.ones(1, device=dev, dtype=torch.int64)
+            dist.all_reduce(ones)
+            warm_keys.fill_(rank + 1)
+            dist.all_gather_into_tensor(gath_keys, warm_keys)
+            slabs = gath_keys.view(world, -1)[:, 0].cpu().tolist()
+            emb_probe = torch.zeros((nq_loc, D_EMB), dtype=torch.float32, device=dev)
+            t_ag_emb = max_over_ranks(timed(lambda: dist.all_gather_into_tensor(allq, emb_probe), 10, sync, barrier)) if enc is not None else None
+            t_ag_keys = max_over_ranks(timed(lambda: dist.all_gather_into_tensor(gath_keys, warm_keys), 10, sync, barrier))
+            collective = {"backend": dist.get_backend(), "world": world, "ranks_seen": int(ones.item()),
+                          "allgather_slabs_in_rank_order": slabs == list(range(1, world + 1)),
+                          "allgather_emb_ms": None if t_ag_emb is None else round(t_ag_emb * 1e3, 4), "allgather_emb_bytes_per_rank": nq_loc * D_EMB * 4,
+                          "allgather_keys_ms": round(t_ag_keys * 1e3, 4), "allgather_keys_bytes_per_rank": nq * k * 8,
+                          "devices": f"rank {rank} on cuda:{local_rank} of {torch.cuda.device_count()} visible"}
+            del emb_probe
+        del gath_keys
     for _ in range(args.warmup):
         step()
     index.set_profiling(True)
@@ -317,6 +337,15 @@ def main():
     timed_emb = last["local_emb"].clone() if enc is not None else None      # this rank's embeddings of the last timed step
     if args.dump_results and rank == 0:
         np.savez(args.dump_results, emb=last["emb"].cpu().numpy(), D=D.cpu().numpy(), I=I.cpu().numpy(), rows=rows, k=k, block_rows=block_rows)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives from its last timed run: the merged top-k (scores fp32, ids as float64: exact for any
+        # row count) and, when the step encodes, the query embeddings that were searched
+        dump = {"topk_scores": D.cpu().numpy().astype(np.float32), "topk_ids": I.cpu().numpy().astype(np.float64)}
+        if enc is not None:
+            dump["query_embeddings"] = last["emb"].cpu().numpy().astype(np.float32)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
     index.set_profiling(False)
     stack_ms, ffn_up_ms, class_ms = [], [], {}
     if enc is not None:
@@ -474,9 +503,10 @@ def main():
     }
     if world > 1:
         out["like_for_like_n1"] = "extras.cfg4_shard_step.queries_per_sec of the N = 1 line (one 6.75M-row shard, all 1000 queries encoded on that GPU)"
-        out["collective"] = collective
-        if collective["ranks_seen"] != world or not collective["allgather_slabs_in_rank_order"]:
-            out["collective"]["error"] = "the process group did not deliver every rank's contribution in rank order"
+        if collective is not None:
+            out["collective"] = collective
+            if collective["ranks_seen"] != world or not collective["allgather_slabs_in_rank_order"]:
+                out["collective"]["error"] = "the process group did not deliver every rank's contribution in rank order"
     if rehearsal:
         out["rehearsal"] = f"NOT a measurement: {world} ranks share {torch.cuda.device_count()} GPU(s) over gloo (HAC_BENCH_REHEARSAL=1)"
     extras = {}

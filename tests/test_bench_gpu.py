@@ -19,7 +19,7 @@ def test_bench_two_rank_rehearsal_matches_single_process(tmp_path):
     dump = str(tmp_path / "step.npz")
     env = dict(os.environ, HAC_BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "2000000", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--extras", "default", "--north-star-rows", "1500000", "--dump-results", dump]      # (default = what the driver's N > 1 runs execute)
+           "--full", "--no-cpu-baseline", "--extras", "default", "--north-star-rows", "1500000", "--dump-results", dump]      # (default = the extras of a --full N > 1 run)
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -71,8 +71,8 @@ def test_bench_launched_the_drivers_way_through_torch_distributed_run():
         port = sk.getsockname()[1]
     env = dict(os.environ, HAC_BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "1000000", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
-           "--north-star-rows", "800000"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "1000000", "--steps", "1", "--warmup", "1", "--full",
+           "--no-cpu-baseline", "--north-star-rows", "800000"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -98,7 +98,7 @@ def test_bench_four_rank_rehearsal_with_a_query_count_the_ranks_do_not_divide(tm
     dump = str(tmp_path / "step4.npz")
     env = dict(os.environ, HAC_BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--rows", "1200000", "--nq", "1001", "--steps", "1", "--warmup", "1",
-           "--no-cpu-baseline", "--no-extras", "--dump-results", dump]
+           "--full", "--no-cpu-baseline", "--no-extras", "--dump-results", dump]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -121,6 +121,44 @@ def test_bench_four_rank_rehearsal_with_a_query_count_the_ranks_do_not_divide(tm
     np.testing.assert_array_equal(I.cpu().numpy(), g["I"])
     np.testing.assert_array_equal(D.cpu().numpy(), g["D"])
     assert len(np.unique(g["I"] // 300_000)) == 4      # every shard contributes
+
+
+def test_plain_bench_dumps_the_last_timed_step_the_same_every_run(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the headline line alone (no CPU baseline, no extras), K timed steps,
+    and the last timed step's outputs as .npy files in float32 / float64 -- identical over two runs (seeded inputs), and the top-k
+    equal to a single-process search of the dumped embeddings over the same rows."""
+    import torch
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rows", "1000000", "--steps", "3", "--warmup", "1",
+               "--dump-outputs", str(out)]
+        p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        js = json.loads(lines[0])
+        assert js["steps"] == 3 and js["warmup"] == 1 and js["unit"] == "queries/s" and js["higher_is_better"] is True and "dtype" in js
+        assert js["value"] > 0 and abs(js["value"] - 1000 / (js["ms_per_step"] * 1e-3)) < 1e-3 * js["value"]
+        assert js["cpu_baseline"] is None and "step_parts" not in js and "north_star_10M" not in js and "extras_done" in js["wall_clock_s"]
+        assert sorted(os.listdir(out)) == ["query_embeddings.npy", "topk_ids.npy", "topk_scores.npy"]
+        g = {name: np.load(out / (name + ".npy")) for name in ("query_embeddings", "topk_scores", "topk_ids")}
+        assert g["query_embeddings"].dtype == np.float32 and g["query_embeddings"].shape == (1000, 768)
+        assert g["topk_scores"].dtype == np.float32 and g["topk_scores"].shape == (1000, 100)
+        assert g["topk_ids"].dtype == np.float64 and g["topk_ids"].shape == (1000, 100)
+        dumps.append(g)
+    for name in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][name], dumps[1][name])
+    sys.path.insert(0, ROOT)
+    import bench
+    from haconvdr_amd.index import FlatIPIndex
+    dev = torch.device("cuda", 0)
+    idx = FlatIPIndex(768)
+    bench.fill_index(idx, 0, 1_000_000, dev, max(bench.CH, -(-1_000_000 // bench.CFG3_BLOCKS)))
+    D, I = idx.search_tensor(torch.from_numpy(dumps[0]["query_embeddings"]).to(dev), 100)
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(I.cpu().numpy().astype(np.float64), dumps[0]["topk_ids"])
+    np.testing.assert_array_equal(D.cpu().numpy(), dumps[0]["topk_scores"])
 
 
 def test_last_clock_reports_a_plausible_shader_clock():

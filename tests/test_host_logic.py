@@ -198,6 +198,23 @@ def test_bench_starts_its_own_ranks():
     assert len(err) == 1 and err[0]["failed_rank"] == 1 and err[0]["exit_code"] == 7 and err[0]["n_gpus"] == 3 and "stderr_tail" in err[0], bad.stdout
 
 
+def test_bench_plain_run_is_the_headline_alone():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times the headline step and nothing else; the CPU baseline and the extras
+    come with --full (extras 'default' unless --extras says otherwise), and an --extras level without --full is an error."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.full, a.extras, a.steps, a.warmup, a.dump_outputs) == (False, "none", 7, 3, None)
+    a = bench.parse_args(["--full"])
+    assert a.full and a.extras == "default" and not a.no_cpu_baseline
+    assert bench.parse_args(["--full", "--extras", "full"]).extras == "full"
+    assert bench.parse_args(["--full", "--no-extras"]).extras == "none"
+    assert bench.parse_args(["--dump-outputs", "out"]).dump_outputs == "out"
+    for bad in (["--extras", "default"], ["--steps", "0"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
 def test_large_batch_gemm_kernels_keep_everything_in_registers():
     """gemm8_kernel's k-loop keeps an LDS-DMA stream in flight behind counted waits.  A register spill would add scratch
     loads to that stream, and hipcc drains the whole queue (vmcnt(0)) for each of them: measured at half the k-loop rate.

@@ -2,7 +2,7 @@
 # One profiling campaign of bench.py on the GPU box (run through gpurun from the repo root):
 #   bash tools/profile_round.sh r02
 # Four rocprofv3 runs, the program directly after `--` (no wrapper between the profiler and python):
-#   <tag>_trace  --kernel-trace --stats              the default bench (headline + extras), no CPU baseline
+#   <tag>_trace  --kernel-trace --stats              the --full bench (headline + default extras), no CPU baseline
 #   <tag>_fetch  --pmc FETCH_SIZE                     headline step only
 #   <tag>_write  --pmc WRITE_SIZE                     headline step only
 #   <tag>_sq     --pmc SQ_* GRBM_GUI_ACTIVE           headline step only: matrix-pipe busy cycles, wave-time split, clock
@@ -14,7 +14,7 @@ RAW=/tmp/hac_prof                      # raw rocprofv3 output stays on the box (
 OUT=$R/gpurun_out/${TAG}_profiles      # summaries + bench lines: copied back, then `cp` into profiles/
 rm -rf $RAW && mkdir -p $RAW $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/${TAG}_trace -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/${TAG}_trace_bench.json 2> $OUT/${TAG}_trace.err || { echo "trace run failed"; tail -5 $OUT/${TAG}_trace.err; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/${TAG}_trace -- python3 $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline > $OUT/${TAG}_trace_bench.json 2> $OUT/${TAG}_trace.err || { echo "trace run failed"; tail -5 $OUT/${TAG}_trace.err; exit 1; }
 echo "trace done"
 for pass in fetch write sq; do
   case $pass in
