@@ -1325,6 +1325,40 @@ __global__ __launch_bounds__(256) void cls_q_kernel(const bf16 *__restrict__ yb,
     }
 }
 
+// Test entry point (hac_encoder_layer_state): the residual stream of a forward stopped after one layer, unpacked to [B][L][768].
+// One workgroup per (token, sequence); rows t >= len are written as zeros (statistics (0, 0)).  rows: the stored pre-LayerNorm
+// values (x_f32 on the classic path, x_bf on gemm8); stats: their (mean, rstd), (0, 1) where the stored rows are already
+// normalized (null); norm (optional): (v - mean) * rstd * gamma + beta as the consuming RESID epilogues form it (gamma null:
+// the rows themselves).
+__global__ __launch_bounds__(192) void layer_state_kernel(const float *__restrict__ x_f32, const bf16 *__restrict__ x_bf, const float2 *__restrict__ stats,
+                                                          const float *__restrict__ gamma, const float *__restrict__ beta, SeqInfo s, int L,
+                                                          float *__restrict__ rows, float2 *__restrict__ st_out, float *__restrict__ norm) {
+    const int t = blockIdx.x, b = blockIdx.y, c = threadIdx.x * 4;
+    const size_t o = ((size_t)b * L + t) * H + c;
+    f4v v = {0.f, 0.f, 0.f, 0.f}, n = {0.f, 0.f, 0.f, 0.f};
+    float2 ms = make_float2(0.f, 0.f);
+    if (t < s.lens[b]) {
+        const size_t row = (size_t)s.off[b] + t;
+        if (x_f32) {
+            v = *reinterpret_cast<const f4v *>(x_f32 + row * H + c);
+        } else {
+            const bf16x4 vb = *reinterpret_cast<const bf16x4 *>(x_bf + row * H + c);
+            v = (f4v){(float)vb.x, (float)vb.y, (float)vb.z, (float)vb.w};
+        }
+        ms = stats ? stats[row] : make_float2(0.f, 1.f);
+        n = v;
+        if (gamma) {
+            n.x = fmaf((v.x - ms.x) * ms.y, gamma[c + 0], beta[c + 0]);
+            n.y = fmaf((v.y - ms.x) * ms.y, gamma[c + 1], beta[c + 1]);
+            n.z = fmaf((v.z - ms.x) * ms.y, gamma[c + 2], beta[c + 2]);
+            n.w = fmaf((v.w - ms.x) * ms.y, gamma[c + 3], beta[c + 3]);
+        }
+    }
+    *reinterpret_cast<f4v *>(rows + o) = v;
+    if (norm) *reinterpret_cast<f4v *>(norm + o) = n;
+    if (threadIdx.x == 0) st_out[(size_t)b * L + t] = ms;
+}
+
 __global__ void f32_to_bf16_kernel(const float *__restrict__ src, bf16 *__restrict__ dst, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = (bf16)src[i];
@@ -1418,6 +1452,7 @@ struct hac_encoder {
     hipEvent_t graph_done = nullptr;      // recorded behind every replay on the caller's stream: an exec is destroyed only after it
     bool graph_done_armed = false;
     GrowBuf ws_gids, ws_gmask, ws_gout;
+    GrowBuf ws_dump;                      // hac_encoder_layer_state: the unpacked rows, statistics and normalized rows
     GrowBuf ws_identgb;                   // [2][768]: gamma = 1, beta = 0
     GrowBuf ws_redo;                      // [16] per-layer counts | [B * 12] item flags of the attention fix-up pass (attn_pipe.inc)
     // Layers whose items mostly fail the woven kernel's check (near one-hot attention: a property of the weights more than of the batch) would
@@ -1506,9 +1541,17 @@ int pick_family(const hac_encoder *e, long rows) {
     if (e->gemm_mode == 1 || (e->gemm_mode < 0 && big)) return FAM_GEMM8;
     return big ? FAM_CLASSIC256 : FAM_CLASSIC128;
 }
+// hac_encoder_layer_state: stop the forward after layer `layer` (-1: the embedding LayerNorm) and unpack its residual stream
+// (device buffers of [B][L][768] / [B][L] / [B][L][768] or null)
+struct LayerDump {
+    int layer;
+    float *rows;
+    float2 *stats;
+    float *norm;
+};
 template <typename IT>
 int run_forward(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, float *out_dev, hipStream_t st, long rows_hint = 0, int family = -1,
-                long rows_plan = 0) {
+                long rows_plan = 0, const LayerDump *dump = nullptr) {
     const hac_encoder_config &c = e->cfg;
     const int L32 = (L + SEQ_ALIGN - 1) / SEQ_ALIGN * SEQ_ALIGN;
     bool fw_capturing = false;           // (inside a stream capture -- the small-batch graphs -- an event query is an error that kills the capture)
@@ -1566,6 +1609,18 @@ int run_forward(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, flo
     // dead tail rows of the last M tile (fewer than MT) feed the GEMMs: keep them finite
     zero_tail_rows_kernel<<<dim3(MT), dim3(192), 0, st>>>(g8 ? nullptr : x, xb, total, Mp);
     HAC_HIP(hipGetLastError());
+    // (test entry point: the same launches as a forward up to the requested layer, then the unpacked state instead of the rest)
+    auto dump_state = [&](int li) {
+        const bool emb = li < 0;
+        layer_state_kernel<<<dim3((unsigned)L, (unsigned)B), dim3(192), 0, st>>>(g8 ? nullptr : x, xb, emb ? nullptr : statsF,
+                                                                                   emb ? nullptr : e->layers[li].ln2g, emb ? nullptr : e->layers[li].ln2b,
+                                                                                   s, L, dump->rows, dump->stats, dump->norm);
+        e->plan_sub_batches += 1;
+        e->plan_rows += Mp;
+        e->plan_gemm = g8 ? "gemm8" : (big ? "classic256" : "classic128");
+        return hipGetLastError() == hipSuccess ? HAC_OK : fail(HAC_ERR_HIP, "layer_state_kernel launch failed");
+    };
+    if (dump && dump->layer < 0) return dump_state(-1);
     const int bt = big ? 256 : 128;
     const size_t lds = (size_t)4 * bt * 128 + (size_t)(big ? 8 : 4) * 4096;   // 2 stages + per-wave patches
     // Small batches (128^2 tiles): the two RESID GEMMs have only Mp / 128 x 6 output tiles -- 96 for the reference's 4 x 512 query
@@ -1817,6 +1872,7 @@ int run_forward(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, flo
             ln_rows_kernel<<<dim3((unsigned)(Mc / 4)), dim3(256), 0, st>>>(y_c, s.nb, w.ln2g, w.ln2b, c.ln_eps, x_c, xb_c);
         }
         HAC_HIP(hipGetLastError());
+        if (dump && dump->layer == li) return dump_state(li);
     }
 #undef HAC_GEMM
     HAC_TRY(prof_end(e, 0, st));
@@ -2073,7 +2129,7 @@ void hac_encoder_destroy(hac_encoder *e) {
     }
     if (e->h_redo) (void)hipHostFree(e->h_redo);
     for (GrowBuf *b : {&e->ws_x, &e->ws_xb, &e->ws_q, &e->ws_k, &e->ws_vt, &e->ws_ctx, &e->ws_y, &e->ws_h, &e->ws_seq, &e->ws_ids, &e->ws_mask, &e->ws_out, &e->ws_cls, &e->ws_stats, &e->ws_yb, &e->ws_part, &e->ws_idstats,
-                       &e->ws_gids, &e->ws_gmask, &e->ws_gout, &e->ws_ksplit, &e->ws_identgb, &e->ws_clk, &e->ws_redo})
+                       &e->ws_gids, &e->ws_gmask, &e->ws_gout, &e->ws_ksplit, &e->ws_identgb, &e->ws_clk, &e->ws_redo, &e->ws_dump})
         b->release();
     if (e->h_pin) (void)hipHostFree(e->h_pin);
     if (e->h_len) (void)hipHostFree(e->h_len);
@@ -2223,6 +2279,48 @@ int hac_encoder_forward(hac_encoder *e, const int32_t *ids, const int32_t *mask,
         if (out[i] != out[i])
             return fail(HAC_ERR_INVALID, "forward: sequence %zu: attention_mask must be a non-empty prefix mask (first len ones) and attended token ids "
                                          "must lie in [0, %d)", i / H, e->cfg.vocab);
+    return HAC_OK;
+}
+
+int hac_encoder_layer_state(hac_encoder *e, const int32_t *ids, const int32_t *mask, int B, int L, int layer, float *rows_out, float *stats_out,
+                            float *norm_out) {
+    if (!e) return fail(HAC_ERR_INVALID, "null encoder");
+    if (!e->finalized) return fail(HAC_ERR_INVALID, "encoder weights not finalized (hac_encoder_finalize)");
+    if (B < 1 || L < 1 || L > 512 || L + 2 > e->cfg.max_pos || !ids || !mask || !rows_out || !stats_out)
+        return fail(HAC_ERR_INVALID, "layer_state: bad arguments (B=%d, L=%d)", B, L);
+    if (layer < -1 || layer > e->cfg.n_layers - 2)
+        return fail(HAC_ERR_INVALID, "layer_state: layer %d outside [-1, %d] (the last layer continues the <s> rows only)", layer, e->cfg.n_layers - 2);
+    const int L32 = (L + SEQ_ALIGN - 1) / SEQ_ALIGN * SEQ_ALIGN;
+    if ((long)B * L32 > e->max_tokens) return fail(HAC_ERR_INVALID, "layer_state: %d x %d rows exceed one pass (max_tokens %ld)", B, L32, e->max_tokens);
+    for (int b = 0; b < B; ++b) {   // (the forward reports such a sequence as a NaN embedding; there is no embedding here)
+        int len = 0;
+        while (len < L && mask[(size_t)b * L + len]) ++len;
+        bool ok = len > 0;
+        for (int t = 0; t < L; ++t) {
+            if (t >= len && mask[(size_t)b * L + t]) ok = false;
+            if (t < len && (ids[(size_t)b * L + t] < 0 || ids[(size_t)b * L + t] >= e->cfg.vocab)) ok = false;
+        }
+        if (!ok) return fail(HAC_ERR_INVALID, "layer_state: sequence %d: attention_mask must be a non-empty prefix mask and attended token ids must lie in [0, %d)", b, e->cfg.vocab);
+    }
+    DeviceGuard g(e->device);
+    const size_t n = (size_t)B * L, nv = n * H;
+    HAC_TRY(e->ws_ids.reserve(n * 4));
+    HAC_TRY(e->ws_mask.reserve(n * 4));
+    HAC_TRY(e->ws_dump.reserve(nv * 4 * 2 + n * 8));
+    float *d_rows = (float *)e->ws_dump.p, *d_norm = d_rows + nv;
+    float2 *d_stats = (float2 *)(d_norm + nv);
+    HAC_HIP(hipStreamSynchronize(e->stream));
+    HAC_HIP(hipMemcpy(e->ws_ids.p, ids, n * 4, hipMemcpyHostToDevice));
+    HAC_HIP(hipMemcpy(e->ws_mask.p, mask, n * 4, hipMemcpyHostToDevice));
+    e->plan_sub_batches = 0;
+    e->plan_rows = 0;
+    e->plan_graph = "off";   // never captured: plain launches of the forward's own kernels
+    const LayerDump dump{layer, d_rows, d_stats, norm_out ? d_norm : nullptr};
+    HAC_TRY(run_forward<int>(e, (const int *)e->ws_ids.p, (const int *)e->ws_mask.p, B, L, nullptr, e->stream, 0, -1, 0, &dump));
+    HAC_HIP(hipStreamSynchronize(e->stream));
+    HAC_HIP(hipMemcpy(rows_out, d_rows, nv * 4, hipMemcpyDeviceToHost));
+    HAC_HIP(hipMemcpy(stats_out, d_stats, n * 8, hipMemcpyDeviceToHost));
+    if (norm_out) HAC_HIP(hipMemcpy(norm_out, d_norm, nv * 4, hipMemcpyDeviceToHost));
     return HAC_OK;
 }
 

@@ -119,6 +119,27 @@ class ANCEEncoder:
 
     forward = query_emb = doc_emb = __call__       # models.py:39-49,63-64
 
+    def layer_state(self, input_ids, attention_mask, layer, normalized=False):
+        """Test aid (hac_encoder_layer_state): the residual stream after encoder layer ``layer`` (-1: the embedding LayerNorm,
+        at most n_layers - 2), from the same kernels a forward of this batch runs.  Returns a dict of numpy arrays over
+        [B, L] (rows t >= len are zeros): ``rows`` float32 [B, L, 768], the pre-LayerNorm rows as stored (fp32 on the classic
+        path, bf16 values on gemm8); ``mean``, ``rstd`` float32 [B, L]; with ``normalized`` also ``norm`` [B, L, 768], the
+        normalized rows the next layer's residual add forms."""
+        ids = np.ascontiguousarray(np.asarray(input_ids), dtype=np.int32)
+        mask = np.ascontiguousarray(np.asarray(attention_mask), dtype=np.int32)
+        B, L = ids.shape
+        rows = np.empty((B, L, 768), np.float32)
+        stats = np.empty((B, L, 2), np.float32)
+        norm = np.empty((B, L, 768), np.float32) if normalized else None
+        i32p, f32p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+        _lib.check(_lib.lib().hac_encoder_layer_state(self._h, ids.ctypes.data_as(i32p), mask.ctypes.data_as(i32p), B, L, int(layer),
+                                                      rows.ctypes.data_as(f32p), stats.ctypes.data_as(f32p),
+                                                      norm.ctypes.data_as(f32p) if normalized else None))
+        out = {"rows": rows, "mean": stats[..., 0], "rstd": stats[..., 1]}
+        if normalized:
+            out["norm"] = norm
+        return out
+
     def eval(self):
         return self
 

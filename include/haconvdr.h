@@ -288,6 +288,18 @@ int hac_encoder_last_clock(hac_encoder *enc, uint64_t out[2]);
  * bound of the items, 0 iff none.  Waits for the device.  The results do not depend on it: the fix-up pass is the one-block
  * kernel, whose outputs the woven kernel's equal bit for bit wherever it does not flag. */
 int hac_encoder_attention_redo(hac_encoder *enc, long long *items_out);
+/* Test entry point: the residual stream after encoder layer `layer` (-1: the embedding LayerNorm; at most n_layers - 2, the last
+ * layer continues the <s> rows only).  Runs the launches of a forward of (ids, mask) -- same routing, options and workspaces,
+ * never captured into a graph -- up to that layer, then unpacks every valid row t < len of sequence b to index b * L + t:
+ *   rows_out  float32 [B][L][768]: the rows as stored, BEFORE that layer's output LayerNorm (the classic kernels keep them in
+ *             fp32, the large-batch gemm8 path in bf16; layer -1: the normalized embedding rows);
+ *   stats_out float32 [B][L][2]: their (mean, rstd) as the next layer reads them ((0, 1) for layer -1);
+ *   norm_out  float32 [B][L][768] or NULL: (row - mean) * rstd * gamma + beta in fp32, the normalized rows the next layer's
+ *             residual add forms (layer -1: the rows themselves).
+ * Rows t >= len are zeros (statistics (0, 0)).  ids, mask: host int32 [B, L] as for hac_encoder_forward; B * roundup(L, 32) must
+ * fit one pass ("max_tokens").  Synchronous; waits for the encoder's stream.  Not for the timed path. */
+int hac_encoder_layer_state(hac_encoder *enc, const int32_t *ids, const int32_t *mask, int B, int L, int layer, float *rows_out,
+                            float *stats_out, float *norm_out);
 
 #ifdef __cplusplus
 }

@@ -26,9 +26,11 @@ def _t(sd, name):
     return v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))
 
 
-def ance_forward(sd, input_ids, attention_mask, n_layers=None, n_heads=12, eps=1e-5, pad_id=1):
+def ance_forward(sd, input_ids, attention_mask, n_layers=None, n_heads=12, eps=1e-5, pad_id=1, hidden=False):
     """sd: name -> float32 array (reference checkpoint names).  input_ids/attention_mask: int [B, L].
-    Returns float32 ndarray [B, 768] (= the reference's model(input_ids, attention_mask))."""
+    Returns float32 ndarray [B, 768] (= the reference's model(input_ids, attention_mask)); hidden=True: instead the list of
+    hidden states [B, L, 768] (float32 ndarrays) after the embedding LayerNorm and after every layer (rows beyond a sequence's
+    length are whatever the padded forward makes of them)."""
     ids = torch.as_tensor(np.asarray(input_ids), dtype=torch.long)
     mask = torch.as_tensor(np.asarray(attention_mask), dtype=torch.long)
     B, L = ids.shape
@@ -43,6 +45,7 @@ def ance_forward(sd, input_ids, attention_mask, n_layers=None, n_heads=12, eps=1
     x = F.layer_norm(x, (H,), _t(sd, p + "LayerNorm.weight"), _t(sd, p + "LayerNorm.bias"), eps)
     dh = H // n_heads
     add_mask = (1.0 - mask.float())[:, None, None, :] * torch.finfo(torch.float32).min
+    hs = [x]
     for i in range(n_layers):
         q = f"roberta.encoder.layer.{i}."
 
@@ -59,7 +62,190 @@ def ance_forward(sd, input_ids, attention_mask, n_layers=None, n_heads=12, eps=1
         h = F.gelu(lin("intermediate.dense", x))                         # exact erf GELU (hidden_act = "gelu")
         x = F.layer_norm(x + lin("output.dense", h), (H,), _t(sd, q + "output.LayerNorm.weight"),
                          _t(sd, q + "output.LayerNorm.bias"), eps)
+        hs.append(x)
+    if hidden:
+        return [h.numpy().astype(np.float32) for h in hs]
     cls = x[:, 0]                                                        # masked_mean_or_first, use_mean=False
     e = F.linear(cls, _t(sd, "embeddingHead.weight"), _t(sd, "embeddingHead.bias"))
     out = F.layer_norm(e, (e.shape[-1],), _t(sd, "norm.weight"), _t(sd, "norm.bias"), 1e-5)
     return out.numpy().astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# One stage at a time, fp64, with the HIP kernels' bf16 rounding points (tests/test_encoder_layers_gpu.py: teacher-forced parity)
+
+LAYER_MUTATIONS = ("eps", "logits", "key_plus", "key_minus", "bias", "gelu_tanh")   # what ance_layer(mutate=...) knows
+EMBED_MUTATIONS = ("eps", "pos")                                                    # what ance_embed(mutate=...) knows
+LOG2E = 1.4426950408889634
+
+
+def bf16(t):
+    """Round to bf16 (nearest even) and back: the kernels' (bf16) conversions of fp32 values."""
+    return t.to(torch.float32).to(torch.bfloat16).to(torch.float64)
+
+
+def _t64(sd, name):
+    return _t(sd, name).to(torch.float64)
+
+
+def _stats(y, eps):
+    mean = y.mean(-1)
+    var = ((y - mean[..., None]) ** 2).mean(-1)
+    return mean, 1.0 / torch.sqrt(var + eps)
+
+
+def _state(rows, mean, rstd, gamma, beta):
+    return {"rows": rows, "mean": mean, "rstd": rstd, "norm": (rows - mean[..., None]) * rstd[..., None] * gamma + beta}
+
+
+def ance_embed(sd, input_ids, attention_mask, family=None, eps=1e-5, pad_id=1, mutate=None):
+    """Embedding stage, fp64: LN(word[id] + type[0] + pos[HF position id]) of every token (mask: the prefix of valid tokens).
+    Returns the state dict of ance_layer ({rows, mean, rstd, norm} as torch float64 over [B, L]); the rows are already
+    normalized (mean 0, rstd 1, norm = rows).  family "classic": rows are fp32 (embed_ln_kernel, encoder.hip: ln768_store writes
+    x_f32 unrounded) -- modelled as exact; "gemm8": the rows are stored only as bf16 (ln768_store's x_bf; run_forward passes
+    x_f32 = nullptr on that path).  mutate: "eps" (LayerNorm eps 1e-12) or "pos" (position ids one too high, the last one clamped to the table)."""
+    ids = torch.as_tensor(np.asarray(input_ids), dtype=torch.long)
+    mask = torch.as_tensor(np.asarray(attention_mask), dtype=torch.long)
+    p = "roberta.embeddings."
+    nonpad = (ids != pad_id).long()
+    pos = torch.cumsum(nonpad, 1) * nonpad + pad_id
+    if mutate == "pos":
+        pos = torch.clamp(pos + 1, max=_t(sd, p + "position_embeddings.weight").shape[0] - 1)
+    x = (_t64(sd, p + "word_embeddings.weight")[ids] + _t64(sd, p + "token_type_embeddings.weight")[0]) \
+        + _t64(sd, p + "position_embeddings.weight")[pos]
+    mean, rstd = _stats(x, 1e-12 if mutate == "eps" else eps)
+    x = (x - mean[..., None]) * rstd[..., None] * _t64(sd, p + "LayerNorm.weight") + _t64(sd, p + "LayerNorm.bias")
+    if family == "gemm8":
+        x = bf16(x)
+    x = x * mask[..., None]
+    one = mask.to(torch.float64)
+    return {"rows": x, "mean": torch.zeros_like(one), "rstd": one, "norm": x}
+
+
+ATT_TAU = 64.0   # encoder.hip ATT_TAU: how far (log2) a score may rise above the streaming kernels' softmax reference
+
+
+def _window_reference(lg):
+    """The streaming attention kernels' softmax reference per query row and 32-key block (attention_stream_kernel, round 6
+    rule, shared by attn_pipe.inc and the fix-up pass): m starts at 0 and moves to the block's maximum only when that
+    lies more than ATT_TAU above it (or, first block, more than ATT_TAU below).  lg: base-2 logits [..., n, nk].
+    Returns m after each block, [..., n, nblocks]."""
+    ms, m = [], torch.zeros(lg.shape[:-1], dtype=lg.dtype)
+    for kb in range(0, lg.shape[-1], 32):
+        d = lg[..., kb:kb + 32].max(-1).values - m
+        move = (d > ATT_TAU) | ((d < -ATT_TAU) if kb == 0 else torch.zeros_like(d, dtype=torch.bool))
+        m = torch.where(move, m + d, m)
+        ms.append(m)
+    return torch.stack(ms, -1)
+
+
+def ance_layer(sd, i, x_in, attention_mask, family=None, n_heads=12, eps=1e-5, mutate=None, attn="stream"):
+    """Encoder layer i in fp64 from the state the layers before it left: x_in = {rows, mean, rstd} over [B, L, ...] (arrays or
+    tensors: the kernels' own hac_encoder_layer_state output -- teacher forcing -- or this function's / ance_embed's), the rows
+    being pre-LayerNorm with layer i-1's output LayerNorm still to apply (i = 0: the normalized embedding rows, statistics
+    (0, 1)).  Returns {rows, mean, rstd, norm} of layer i (float64 tensors, zeros beyond each sequence's length): pre-LayerNorm
+    rows, their exact statistics, and LN(rows) with this layer's output LayerNorm.
+
+    family None: no rounding at all -- layer for layer the arithmetic of ance_forward.  Otherwise bf16 exactly where the
+    kernels round (haconvdr_amd/csrc; everything else is fp64: true erf, exact softmax, exact statistics):
+      both families
+        * weights of every GEMM are bf16 (hac_encoder_finalize: f32_to_bf16_kernel / to_bf16 for wqkv, wo, w1, w2; gemm8
+          reads wo, w2 unfolded, and fold_ln_kernel rounds W.diag(gamma).scale for wqkv8, w18);
+        * Q is scaled by log2(e)/8 BEFORE its rounding (gemm_bf16_nt_kernel EPI_QKV "sc"; gemm8: the scale is folded into
+          wqkv8's q rows and cvec, finalize "qscale"); Q, K, V are bf16 (EPI_QKV / EPI8_QKV pack_bf16);
+        * attention (attention_stream_kernel / attention_kernel / attn_pipe.inc): logits s = Q.K in base 2, P = 2^(s - m)
+          unrounded in the row sum l, bf16(P) as the PV MFMA operand, context = bf16(O / l).  The reference m is where
+          bf16(P) rounds: attn="twopass" (attention_kernel) takes the exact row maximum; attn="stream" (the streaming,
+          woven and query-split kernels) the window rule of _window_reference, a block's P rounded relative to the m of
+          that block and rescaled exactly (fp32 factor 2^-delta on l and O) when m moves later;
+      classic (gemm_bf16_nt_kernel, ln_stats_rows_kernel): the residual stream is fp32 (modelled exact); the A operands of QKV
+        and FFN-up are bf16(LN(y)) (ln_stats_rows_kernel x_bf, embed: ln768_store x_bf); FFN-up stores bf16(gelu(.))
+        (EPI_GELU); the RESID epilogues add the fp32 residual LN(y) recomputed from (mean, rstd) (fmaf form);
+      gemm8 (gemm8.inc): the residual stream is bf16 -- the RESID epilogue stores bf16(acc + bias + residual) and takes
+        (mean, rstd) from the fp32 values before that rounding (partial sums -> ln_combine_kernel); the consumer's LayerNorm
+        is folded: out = rstd (A.W'^T - mean wsum) + cvec with W' = bf16(W.diag(gamma)), wsum = sum_k W' (of the rounded
+        values), cvec = bias + W.beta (fold_ln_kernel); layer 0 folds nothing (gamma = 1, beta = 0: the embedding rows are
+        normalized); the residual of the RESID epilogues is (bf16 row - mean) rstd gamma + beta; FFN-up stores bf16(gelu).
+
+    mutate (the self-checks of the tests): "eps" (both LayerNorms with eps 1e-12), "logits" (x 1.01), "key_plus" /
+    "key_minus" (every sequence attends one key more -- the pad row behind it -- or one fewer), "bias" (the value
+    projection's bias dropped), "gelu_tanh" (tanh-approximate GELU)."""
+    assert family in (None, "classic", "gemm8") and attn in ("stream", "twopass") and (mutate is None or mutate in LAYER_MUTATIONS), \
+        (family, attn, mutate)
+    R = bf16 if family else (lambda t: t)
+    mask = torch.as_tensor(np.asarray(attention_mask), dtype=torch.long)
+    lens = mask.sum(1).tolist()
+    x, mean, rstd = (torch.as_tensor(np.asarray(x_in[k])).to(torch.float64) for k in ("rows", "mean", "rstd"))
+    B, L, H = x.shape
+    dh = H // n_heads
+    q = f"roberta.encoder.layer.{i}."
+    pq = f"roberta.encoder.layer.{i - 1}.output.LayerNorm."
+    g_in = _t64(sd, pq + "weight") if i else torch.ones(H, dtype=torch.float64)
+    b_in = _t64(sd, pq + "bias") if i else torch.zeros(H, dtype=torch.float64)
+    leps = 1e-12 if mutate == "eps" else eps
+
+    def W(name):
+        return _t64(sd, q + name + ".weight")
+
+    def b(name):
+        return _t64(sd, q + name + ".bias")
+
+    def folded(A, m, r, Wf, bias, gamma, beta, scale=1.0):
+        """rstd (A.W'^T - mean wsum) + cvec (gemm8 QKV / FFN-up epilogue), W' = bf16(W.diag(gamma).scale)."""
+        Wp = bf16(Wf * gamma * scale)
+        return r[..., None] * (A @ Wp.T - m[..., None] * Wp.sum(1)) + (bias + Wf @ beta) * scale
+
+    xn = (x - mean[..., None]) * rstd[..., None] * g_in + b_in          # LN of the input rows (kernel: fp32, both families)
+    c = LOG2E / math.sqrt(dh)
+    bv = torch.zeros(H, dtype=torch.float64) if mutate == "bias" else b("attention.self.value")
+    if family == "gemm8":
+        Q = bf16(folded(x, mean, rstd, W("attention.self.query"), b("attention.self.query"), g_in, b_in, c))
+        K = bf16(folded(x, mean, rstd, W("attention.self.key"), b("attention.self.key"), g_in, b_in))
+        V = bf16(folded(x, mean, rstd, W("attention.self.value"), bv, g_in, b_in))
+    else:
+        A = R(xn)
+        Q = R((A @ R(W("attention.self.query")).T + b("attention.self.query")) * c)
+        K = R(A @ R(W("attention.self.key")).T + b("attention.self.key"))
+        V = R(A @ R(W("attention.self.value")).T + bv)
+    ctx = torch.zeros(B, L, H, dtype=torch.float64)
+    for s in range(B):
+        n = lens[s]
+        nk = min(L, n + 1) if mutate == "key_plus" else (max(1, n - 1) if mutate == "key_minus" else n)
+        qh = Q[s, :n].view(n, n_heads, dh).transpose(0, 1)
+        kh = K[s, :nk].view(nk, n_heads, dh).transpose(0, 1)
+        vh = V[s, :nk].view(nk, n_heads, dh).transpose(0, 1)
+        lg = qh @ kh.transpose(-1, -2)                                     # base-2 logits
+        if mutate == "logits":
+            lg = lg * 1.01
+        if family and attn == "stream":
+            mb = _window_reference(lg)                                     # [heads, n, blocks]
+            mk = mb.repeat_interleave(32, -1)[..., :nk]                    # the reference in force at each key's block
+            P = torch.exp2(lg - mb[..., -1:])
+            Pr = R(torch.exp2(lg - mk)) * torch.exp2(mk - mb[..., -1:])
+        else:
+            P = torch.exp2(lg - lg.max(-1, keepdim=True).values)
+            Pr = R(P)
+        o = (Pr @ vh) / P.sum(-1, keepdim=True)
+        ctx[s, :n] = R(o).transpose(0, 1).reshape(n, H)
+    gelu = (lambda t: F.gelu(t, approximate="tanh")) if mutate == "gelu_tanh" else F.gelu
+    if family == "gemm8":
+        yA = ctx @ bf16(W("attention.output.dense")).T + b("attention.output.dense") + xn
+        mA, rA = _stats(yA, leps)
+        yA = bf16(yA)
+        g1, b1 = _t64(sd, q + "attention.output.LayerNorm.weight"), _t64(sd, q + "attention.output.LayerNorm.bias")
+        h = bf16(gelu(folded(yA, mA, rA, W("intermediate.dense"), b("intermediate.dense"), g1, b1)))
+        xa = (yA - mA[..., None]) * rA[..., None] * g1 + b1
+        yF = h @ bf16(W("output.dense")).T + b("output.dense") + xa
+        mF, rF = _stats(yF, leps)
+        yF = bf16(yF)
+    else:
+        yA = ctx @ R(W("attention.output.dense")).T + b("attention.output.dense") + xn
+        mA, rA = _stats(yA, leps)
+        xa = (yA - mA[..., None]) * rA[..., None] * _t64(sd, q + "attention.output.LayerNorm.weight") \
+            + _t64(sd, q + "attention.output.LayerNorm.bias")
+        h = R(gelu(R(xa) @ R(W("intermediate.dense")).T + b("intermediate.dense")))
+        yF = h @ R(W("output.dense")).T + b("output.dense") + xa
+        mF, rF = _stats(yF, leps)
+    valid = (torch.arange(L)[None, :] < torch.as_tensor(lens)[:, None]).to(torch.float64)
+    out = _state(yF, mF, rF, _t64(sd, q + "output.LayerNorm.weight"), _t64(sd, q + "output.LayerNorm.bias"))
+    return {k: v * (valid[..., None] if v.dim() == 3 else valid) for k, v in out.items()}

@@ -62,3 +62,43 @@ def test_oracle_varlen_equals_padded():
         n = int(lens[b])
         cut = ance_oracle.ance_forward(sd, ids[b:b + 1, :n], mask[b:b + 1, :n])
         np.testing.assert_allclose(cut[0], full[b], atol=1e-4, rtol=0)
+
+
+def test_layer_reference_without_rounding_equals_ance_forward():
+    """oracle.ance_embed / ance_layer (family None: fp64, no rounding), chained stage by stage, give ance_forward's hidden
+    states on every valid row: the per-layer reference of tests/test_encoder_layers_gpu.py restates the same model."""
+    from oracle import ance_oracle
+    from tests.golden.make_golden_encoder import encoder_case_inputs
+    sd = state_dict(3, 0.08)
+    ids, mask = encoder_case_inputs(0x1A7, [1, 7, 32, 33, 64], 64)
+    hs = ance_oracle.ance_forward(sd, ids, mask, hidden=True)
+    valid = mask.astype(bool)
+    st = ance_oracle.ance_embed(sd, ids, mask)
+    np.testing.assert_allclose(st["norm"].numpy()[valid], hs[0][valid], atol=2e-6, rtol=0)
+    for i in range(3):
+        st = ance_oracle.ance_layer(sd, i, st, mask)
+        np.testing.assert_allclose(st["norm"].numpy()[valid], hs[i + 1][valid], atol=1e-4, rtol=0)   # fp32 vs fp64, values up to ~5
+
+
+@pytest.mark.parametrize("family", ["classic", "gemm8"])
+def test_layer_reference_rounding_and_mutations_change_the_output(family):
+    """The bf16-faithful reference differs from the exact one by the bf16 path's noise (~1e-2 relative per layer); each
+    mutation of the self-checks changes the output (the GPU tests require them to clear the bounds by 3x)."""
+    from oracle import ance_oracle
+    from tests.golden.make_golden_encoder import encoder_case_inputs
+    sd = state_dict(2, 0.08)
+    ids, mask = encoder_case_inputs(0x1A8, [1, 33, 64], 64)
+    valid = mask.astype(bool)
+
+    def rel(a, b):
+        a, b = a["norm"].numpy()[valid], b["norm"].numpy()[valid]
+        return np.sqrt(((a - b) ** 2).mean() / (b ** 2).mean())
+    emb = ance_oracle.ance_embed(sd, ids, mask, family)
+    assert (rel(emb, ance_oracle.ance_embed(sd, ids, mask)) > 1e-4) == (family == "gemm8")   # classic keeps the fp32 rows
+    for m in ance_oracle.EMBED_MUTATIONS:
+        assert rel(ance_oracle.ance_embed(sd, ids, mask, family, mutate=m), emb) > 1e-3, m
+    base = ance_oracle.ance_layer(sd, 0, emb, mask, family)
+    assert 1e-3 < rel(base, ance_oracle.ance_layer(sd, 0, emb, mask)) < 5e-2
+    assert 0 < rel(base, ance_oracle.ance_layer(sd, 0, emb, mask, family, attn="twopass")) < 1e-2
+    for m in ance_oracle.LAYER_MUTATIONS:
+        assert rel(ance_oracle.ance_layer(sd, 0, emb, mask, family, mutate=m), base) > 1e-5, m
