@@ -139,6 +139,64 @@ def _window_reference(lg):
     return torch.stack(ms, -1)
 
 
+def _layer_input(sd, i, x_in):
+    """Layer i's input state as float64 tensors: (rows, mean, rstd, gamma, beta, LN(rows)) with the previous layer's output
+    LayerNorm (gamma, beta) -- layer 0: (1, 0), the embedding rows are already normalized.  LN(rows) is what both families
+    form in fp32 for the residual adds (and the classic family rounds to bf16 for its QKV A operand)."""
+    x, mean, rstd = (torch.as_tensor(np.asarray(x_in[k])).to(torch.float64) for k in ("rows", "mean", "rstd"))
+    H = x.shape[-1]
+    pq = f"roberta.encoder.layer.{i - 1}.output.LayerNorm."
+    g_in = _t64(sd, pq + "weight") if i else torch.ones(H, dtype=torch.float64)
+    b_in = _t64(sd, pq + "bias") if i else torch.zeros(H, dtype=torch.float64)
+    xn = (x - mean[..., None]) * rstd[..., None] * g_in + b_in
+    return x, mean, rstd, g_in, b_in, xn
+
+
+def _folded(A, m, r, Wf, bias, gamma, beta, scale=1.0):
+    """rstd (A.W'^T - mean wsum) + cvec (gemm8 QKV / FFN-up epilogue, cls_q_kernel), W' = bf16(W.diag(gamma).scale)."""
+    Wp = bf16(Wf * gamma * scale)
+    return r[..., None] * (A @ Wp.T - m[..., None] * Wp.sum(1)) + (bias + Wf @ beta) * scale
+
+
+def _project(sd, i, nm, x, mean, rstd, xn, g_in, b_in, family, n_heads, mutate=None):
+    """Layer i's attention projection nm ("query": scaled by log2(e)/sqrt(dh) before its rounding, "key", "value") of the
+    input rows x [..., H] with their (mean, rstd) and LN(x) = xn (_layer_input), bf16 as the family stores it."""
+    p = f"roberta.encoder.layer.{i}.attention.self.{nm}."
+    Wf = _t64(sd, p + "weight")
+    bias = torch.zeros(Wf.shape[0], dtype=torch.float64) if (nm == "value" and mutate == "bias") else _t64(sd, p + "bias")
+    c = LOG2E / math.sqrt(x.shape[-1] // n_heads)
+    if family == "gemm8":
+        return bf16(_folded(x, mean, rstd, Wf, bias, g_in, b_in, c if nm == "query" else 1.0))
+    R = bf16 if family else (lambda t: t)
+    A = R(xn)
+    return R((A @ R(Wf).T + bias) * c) if nm == "query" else R(A @ R(Wf).T + bias)
+
+
+def _attend(Qs, K, V, n, n_heads, family, attn, mutate=None):
+    """Attention context [nq, H] of the query rows Qs [nq, H] (base 2, _project) of one sequence of n valid rows over its
+    keys and values K, V [>= n, H]: the arithmetic of ance_layer's docstring (mutations "logits", "key_plus", "key_minus")."""
+    R = bf16 if family else (lambda t: t)
+    nq, H = Qs.shape
+    dh = H // n_heads
+    nk = min(K.shape[0], n + 1) if mutate == "key_plus" else (max(1, n - 1) if mutate == "key_minus" else n)
+    qh = Qs.reshape(nq, n_heads, dh).transpose(0, 1)
+    kh = K[:nk].reshape(nk, n_heads, dh).transpose(0, 1)
+    vh = V[:nk].reshape(nk, n_heads, dh).transpose(0, 1)
+    lg = qh @ kh.transpose(-1, -2)                                         # base-2 logits
+    if mutate == "logits":
+        lg = lg * 1.01
+    if family and attn == "stream":
+        mb = _window_reference(lg)                                         # [heads, nq, blocks]
+        mk = mb.repeat_interleave(32, -1)[..., :nk]                        # the reference in force at each key's block
+        P = torch.exp2(lg - mb[..., -1:])
+        Pr = R(torch.exp2(lg - mk)) * torch.exp2(mk - mb[..., -1:])
+    else:
+        P = torch.exp2(lg - lg.max(-1, keepdim=True).values)
+        Pr = R(P)
+    o = (Pr @ vh) / P.sum(-1, keepdim=True)
+    return R(o).transpose(0, 1).reshape(nq, H)
+
+
 def ance_layer(sd, i, x_in, attention_mask, family=None, n_heads=12, eps=1e-5, mutate=None, attn="stream"):
     """Encoder layer i in fp64 from the state the layers before it left: x_in = {rows, mean, rstd} over [B, L, ...] (arrays or
     tensors: the kernels' own hac_encoder_layer_state output -- teacher forcing -- or this function's / ance_embed's), the rows
@@ -173,15 +231,10 @@ def ance_layer(sd, i, x_in, attention_mask, family=None, n_heads=12, eps=1e-5, m
     assert family in (None, "classic", "gemm8") and attn in ("stream", "twopass") and (mutate is None or mutate in LAYER_MUTATIONS), \
         (family, attn, mutate)
     R = bf16 if family else (lambda t: t)
-    mask = torch.as_tensor(np.asarray(attention_mask), dtype=torch.long)
-    lens = mask.sum(1).tolist()
-    x, mean, rstd = (torch.as_tensor(np.asarray(x_in[k])).to(torch.float64) for k in ("rows", "mean", "rstd"))
+    lens = torch.as_tensor(np.asarray(attention_mask), dtype=torch.long).sum(1).tolist()
+    x, mean, rstd, g_in, b_in, xn = _layer_input(sd, i, x_in)
     B, L, H = x.shape
-    dh = H // n_heads
     q = f"roberta.encoder.layer.{i}."
-    pq = f"roberta.encoder.layer.{i - 1}.output.LayerNorm."
-    g_in = _t64(sd, pq + "weight") if i else torch.ones(H, dtype=torch.float64)
-    b_in = _t64(sd, pq + "bias") if i else torch.zeros(H, dtype=torch.float64)
     leps = 1e-12 if mutate == "eps" else eps
 
     def W(name):
@@ -190,50 +243,18 @@ def ance_layer(sd, i, x_in, attention_mask, family=None, n_heads=12, eps=1e-5, m
     def b(name):
         return _t64(sd, q + name + ".bias")
 
-    def folded(A, m, r, Wf, bias, gamma, beta, scale=1.0):
-        """rstd (A.W'^T - mean wsum) + cvec (gemm8 QKV / FFN-up epilogue), W' = bf16(W.diag(gamma).scale)."""
-        Wp = bf16(Wf * gamma * scale)
-        return r[..., None] * (A @ Wp.T - m[..., None] * Wp.sum(1)) + (bias + Wf @ beta) * scale
-
-    xn = (x - mean[..., None]) * rstd[..., None] * g_in + b_in          # LN of the input rows (kernel: fp32, both families)
-    c = LOG2E / math.sqrt(dh)
-    bv = torch.zeros(H, dtype=torch.float64) if mutate == "bias" else b("attention.self.value")
-    if family == "gemm8":
-        Q = bf16(folded(x, mean, rstd, W("attention.self.query"), b("attention.self.query"), g_in, b_in, c))
-        K = bf16(folded(x, mean, rstd, W("attention.self.key"), b("attention.self.key"), g_in, b_in))
-        V = bf16(folded(x, mean, rstd, W("attention.self.value"), bv, g_in, b_in))
-    else:
-        A = R(xn)
-        Q = R((A @ R(W("attention.self.query")).T + b("attention.self.query")) * c)
-        K = R(A @ R(W("attention.self.key")).T + b("attention.self.key"))
-        V = R(A @ R(W("attention.self.value")).T + bv)
+    Q, K, V = (_project(sd, i, nm, x, mean, rstd, xn, g_in, b_in, family, n_heads, mutate) for nm in ("query", "key", "value"))
     ctx = torch.zeros(B, L, H, dtype=torch.float64)
     for s in range(B):
         n = lens[s]
-        nk = min(L, n + 1) if mutate == "key_plus" else (max(1, n - 1) if mutate == "key_minus" else n)
-        qh = Q[s, :n].view(n, n_heads, dh).transpose(0, 1)
-        kh = K[s, :nk].view(nk, n_heads, dh).transpose(0, 1)
-        vh = V[s, :nk].view(nk, n_heads, dh).transpose(0, 1)
-        lg = qh @ kh.transpose(-1, -2)                                     # base-2 logits
-        if mutate == "logits":
-            lg = lg * 1.01
-        if family and attn == "stream":
-            mb = _window_reference(lg)                                     # [heads, n, blocks]
-            mk = mb.repeat_interleave(32, -1)[..., :nk]                    # the reference in force at each key's block
-            P = torch.exp2(lg - mb[..., -1:])
-            Pr = R(torch.exp2(lg - mk)) * torch.exp2(mk - mb[..., -1:])
-        else:
-            P = torch.exp2(lg - lg.max(-1, keepdim=True).values)
-            Pr = R(P)
-        o = (Pr @ vh) / P.sum(-1, keepdim=True)
-        ctx[s, :n] = R(o).transpose(0, 1).reshape(n, H)
+        ctx[s, :n] = _attend(Q[s, :n], K[s], V[s], n, n_heads, family, attn, mutate)
     gelu = (lambda t: F.gelu(t, approximate="tanh")) if mutate == "gelu_tanh" else F.gelu
     if family == "gemm8":
         yA = ctx @ bf16(W("attention.output.dense")).T + b("attention.output.dense") + xn
         mA, rA = _stats(yA, leps)
         yA = bf16(yA)
         g1, b1 = _t64(sd, q + "attention.output.LayerNorm.weight"), _t64(sd, q + "attention.output.LayerNorm.bias")
-        h = bf16(gelu(folded(yA, mA, rA, W("intermediate.dense"), b("intermediate.dense"), g1, b1)))
+        h = bf16(gelu(_folded(yA, mA, rA, W("intermediate.dense"), b("intermediate.dense"), g1, b1)))
         xa = (yA - mA[..., None]) * rA[..., None] * g1 + b1
         yF = h @ bf16(W("output.dense")).T + b("output.dense") + xa
         mF, rF = _stats(yF, leps)
@@ -249,3 +270,75 @@ def ance_layer(sd, i, x_in, attention_mask, family=None, n_heads=12, eps=1e-5, m
     valid = (torch.arange(L)[None, :] < torch.as_tensor(lens)[:, None]).to(torch.float64)
     out = _state(yF, mF, rF, _t64(sd, q + "output.LayerNorm.weight"), _t64(sd, q + "output.LayerNorm.bias"))
     return {k: v * (valid[..., None] if v.dim() == 3 else valid) for k, v in out.items()}
+
+
+# the last layer and the ANCE head (tests/test_encoder_tail_gpu.py): the layer's mutations, then the tail's own
+TAIL_MUTATIONS = LAYER_MUTATIONS + ("prev_ln", "pool_mean", "pool_row1", "head_eps", "head_bias", "head_bf16")
+
+
+def _head(sd, x, mutate=None):
+    """ANCE head on the pooled rows x [B, H]: LN_768(embeddingHead(x)), fp32 weights and activations (cls_head_proj_kernel,
+    cls_head_norm_kernel: eps 1e-5 whatever the layers' eps).  mutate: "head_eps" (eps 1e-12), "head_bias" (embeddingHead's
+    bias dropped), "head_bf16" (its weight and input rounded to bf16)."""
+    Wh, bh = _t64(sd, "embeddingHead.weight"), _t64(sd, "embeddingHead.bias")
+    if mutate == "head_bias":
+        bh = torch.zeros_like(bh)
+    if mutate == "head_bf16":
+        Wh, x = bf16(Wh), bf16(x)
+    e = x @ Wh.T + bh
+    m, r = _stats(e, 1e-12 if mutate == "head_eps" else 1e-5)
+    return (e - m[:, None]) * r[:, None] * _t64(sd, "norm.weight") + _t64(sd, "norm.bias")
+
+
+def ance_tail(sd, i, x_in, attention_mask, family=None, n_heads=12, eps=1e-5, mutate=None, attn="stream"):
+    """The last encoder layer i and the ANCE head in fp64 from the state the layers before it left (x_in as for ance_layer;
+    i = 0: ance_embed's state).  Returns the embeddings, float64 [B, H] (= ance_forward's output when family is None).
+
+    Only what the kernels compute (run_forward, `last`): keys and values of every row, the query of row 0 of each sequence,
+    its attention (cls_only), then out-projection, LayerNorm, FFN and LayerNorm on the gathered <s> rows, and the head.
+      classic: Q, K, V as in ance_layer;
+      gemm8: K, V folded as in ance_layer; the <s> query in the same folded form, scale folded in, bf16 (cls_q_kernel);
+      both, the <s> rows (gather_cls_kernel, then gemm_bf16_nt_kernel and ln_rows_kernel on the compact matrices, on gemm8
+      too): x_c = LN_prev(row) in fp32 (gemm8: of the bf16 row); y = bf16(ctx).bf16(Wo)^T + bo + x_c and x2 = LN1(y) in
+      fp32; h = bf16(gelu(bf16(x2).bf16(W1)^T + b1)); x_out = LN2(h.bf16(W2)^T + b2 + x2) in fp32; then _head.
+
+    mutate: LAYER_MUTATIONS for this layer, or "prev_ln" (the gather normalizes with this layer's own output LayerNorm
+    instead of the previous layer's), "pool_mean" (masked mean of every row's layer output -- ance_layer's -- instead of
+    row 0), "pool_row1" (row min(1, len - 1) instead of row 0), and the head's of _head."""
+    assert family in (None, "classic", "gemm8") and attn in ("stream", "twopass") and (mutate is None or mutate in TAIL_MUTATIONS), \
+        (family, attn, mutate)
+    R = bf16 if family else (lambda t: t)
+    mask = torch.as_tensor(np.asarray(attention_mask), dtype=torch.long)
+    lens = mask.sum(1).tolist()
+    lmut = mutate if mutate in LAYER_MUTATIONS else None
+    q = f"roberta.encoder.layer.{i}."
+    if mutate == "pool_mean":
+        st = ance_layer(sd, i, x_in, attention_mask, family, n_heads, eps, attn=attn)
+        return _head(sd, st["norm"].sum(1) / torch.as_tensor(lens, dtype=torch.float64)[:, None])
+    x, mean, rstd, g_in, b_in, xn = _layer_input(sd, i, x_in)
+    B = x.shape[0]
+    sel = (torch.arange(B), torch.as_tensor([min(1, n - 1) if mutate == "pool_row1" else 0 for n in lens]))
+    Q = _project(sd, i, "query", x[sel], mean[sel], rstd[sel], xn[sel], g_in, b_in, family, n_heads)
+    K, V = (_project(sd, i, nm, x, mean, rstd, xn, g_in, b_in, family, n_heads, lmut) for nm in ("key", "value"))
+    ctx = torch.cat([_attend(Q[s:s + 1], K[s], V[s], lens[s], n_heads, family, attn, lmut) for s in range(B)])
+    if mutate == "prev_ln":
+        x_c = (x[sel] - mean[sel][:, None]) * rstd[sel][:, None] * _t64(sd, q + "output.LayerNorm.weight") \
+            + _t64(sd, q + "output.LayerNorm.bias")
+    else:
+        x_c = xn[sel]
+    leps = 1e-12 if mutate == "eps" else eps
+
+    def W(name):
+        return R(_t64(sd, q + name + ".weight"))
+
+    def b(name):
+        return _t64(sd, q + name + ".bias")
+
+    def ln(y, name):
+        m, r = _stats(y, leps)
+        return (y - m[:, None]) * r[:, None] * _t64(sd, q + name + ".weight") + _t64(sd, q + name + ".bias")
+    gelu = (lambda t: F.gelu(t, approximate="tanh")) if mutate == "gelu_tanh" else F.gelu
+    x2 = ln(ctx @ W("attention.output.dense").T + b("attention.output.dense") + x_c, "attention.output.LayerNorm")
+    h = R(gelu(R(x2) @ W("intermediate.dense").T + b("intermediate.dense")))
+    x_out = ln(h @ W("output.dense").T + b("output.dense") + x2, "output.LayerNorm")
+    return _head(sd, x_out, mutate)

@@ -102,3 +102,57 @@ def test_layer_reference_rounding_and_mutations_change_the_output(family):
     assert 0 < rel(base, ance_oracle.ance_layer(sd, 0, emb, mask, family, attn="twopass")) < 1e-2
     for m in ance_oracle.LAYER_MUTATIONS:
         assert rel(ance_oracle.ance_layer(sd, 0, emb, mask, family, mutate=m), base) > 1e-5, m
+
+
+def _tail_batch(kind):
+    from haconvdr_amd import synth
+    from tests.golden.make_golden_encoder import encoder_case_inputs
+    if kind == "padded":
+        return encoder_case_inputs(0x1A9, [1, 2, 31, 33, 64], 64)
+    ids, lens = synth.token_batch(0x1AA, 6, 96, min_len=1)              # mixed lengths, token id 0 behind each
+    return ids.astype(np.int64), (np.arange(96)[None, :] < lens[:, None]).astype(np.int64)
+
+
+def _tail_chain(sd, n_layers, ids, mask, family=None, **kw):
+    """ance_embed, ance_layer 0 .. n-2, then ance_tail(**kw) on that state."""
+    from oracle import ance_oracle
+    st = ance_oracle.ance_embed(sd, ids, mask, family)
+    for i in range(n_layers - 1):
+        st = ance_oracle.ance_layer(sd, i, st, mask, family)
+    return st, ance_oracle.ance_tail(sd, n_layers - 1, st, mask, family, **kw)
+
+
+@pytest.mark.parametrize("kind", ["padded", "varlen"])
+@pytest.mark.parametrize("n_layers", [1, 3])
+def test_tail_reference_without_rounding_equals_ance_forward(n_layers, kind):
+    """oracle.ance_tail (family None) on the chained per-layer state restates ance_forward's last layer and head: the
+    reference of tests/test_encoder_tail_gpu.py computes the same embeddings from only the <s> rows' queries."""
+    from oracle import ance_oracle
+    sd = {k: v for k, v in state_dict(3, 0.08).items() if not k.startswith(tuple(f"roberta.encoder.layer.{i}." for i in range(n_layers, 3)))}
+    ids, mask = _tail_batch(kind)
+    out = _tail_chain(sd, n_layers, ids, mask)[1]
+    assert tuple(out.shape) == (len(ids), 768)
+    np.testing.assert_allclose(out.numpy(), ance_oracle.ance_forward(sd, ids, mask), atol=1e-4, rtol=0)
+
+
+@pytest.mark.parametrize("family", ["classic", "gemm8"])
+def test_tail_reference_rounding_and_mutations_change_the_output(family):
+    """The bf16-faithful tail differs from the exact one by a bounded, non-zero amount, the window softmax reference from
+    the exact maximum, and every tail mutation moves the embeddings clearly (the GPU tests require them to clear the
+    bounds by 3x).  Weights of std 0.02: with larger ones the rows' variance (~40) hides the layers' eps 1e-12 entirely."""
+    from oracle import ance_oracle
+    sd = state_dict(2, 0.02)
+    ids, mask = _tail_batch("padded")
+    st = ance_oracle.ance_layer(sd, 0, ance_oracle.ance_embed(sd, ids, mask, family), mask, family)
+
+    def rel(a, b):
+        a, b = a.numpy(), b.numpy()
+        return np.sqrt(((a - b) ** 2).mean() / (b ** 2).mean())
+    base = ance_oracle.ance_tail(sd, 1, st, mask, family)
+    assert 1e-4 < rel(base, ance_oracle.ance_tail(sd, 1, st, mask)) < 5e-2
+    assert 0 < rel(base, ance_oracle.ance_tail(sd, 1, st, mask, family, attn="twopass")) < 1e-2
+    for m in ance_oracle.TAIL_MUTATIONS:
+        assert rel(ance_oracle.ance_tail(sd, 1, st, mask, family, mutate=m), base) > 1e-5, m
+    if family == "classic":      # the tail's <s> row is the classic layer's row 0 (same fp32 residual, same roundings)
+        full = ance_oracle.ance_layer(sd, 1, st, mask, family)["norm"][:, 0]
+        np.testing.assert_allclose(ance_oracle._head(sd, full).numpy(), base.numpy(), atol=1e-9, rtol=0)
