@@ -1178,6 +1178,7 @@ __global__ __launch_bounds__(WAVES * 64, 4) void attention_stream_kernel(AttnArg
 }
 
 #include "attn_pipe.inc"
+#include "split.inc"
 
 // Last layer: everything after attention is only needed for the <s> row of each sequence
 // (masked_mean_or_first with use_mean=False, src/models.py:52-56): gather those B rows into compact
@@ -1371,6 +1372,8 @@ struct LayerW {
     // large-batch path (gemm8.inc): the preceding LayerNorm folded into the weights that consume its output
     bf16 *wqkv8 = nullptr, *w18 = nullptr;      // [2304][768] (q rows also carry log2(e)/8), [3072][768]
     float *fold = nullptr;                      // wsum_qkv[2304] | cvec_qkv[2304] | wsum_1[3072] | cvec_1[3072]
+    // precision = split (split.inc): the lo twins of the classic family's weights, made by the first forward that needs them
+    bf16 *wqkv_lo = nullptr, *wo_lo = nullptr, *w1_lo = nullptr, *w2_lo = nullptr;
 };
 
 }  // namespace
@@ -1390,6 +1393,9 @@ struct hac_encoder {
     GrowBuf ws_ksplit;                    // classic path, small batches: split-K partial sums of the RESID GEMMs
     GrowBuf ws_yb, ws_part, ws_idstats;   // gemm8 path: bf16 copy of the attention-block rows, row-sum partials, (0, 1) statistics
     size_t idstats_rows = 0;
+    int precision = 0;                    // 0: bf16 operands; 1: split (hi + lo pairs, three MFMAs per product: split.inc)
+    bool split_weights = false;           // the lo twins of the weights exist
+    GrowBuf ws_xb_lo, ws_q_lo, ws_k_lo, ws_vt_lo, ws_ctx_lo, ws_h_lo, ws_cls_lo;   // the lo twins of the activations an MFMA reads
     int attn_mode = 0;                    // 0: streaming single-pass attention; 1: two-pass kernels (cross-check)
     int attn_pipe = -1;                   // streaming attention of whole items (no query split, not the <s>-only layer): two query blocks per wave, woven (attn_pipe.inc); 0: the one-block kernel everywhere
     int plan_attn_pipe = 0;               // what the most recent forward's layers used
@@ -1415,6 +1421,7 @@ struct hac_encoder {
     int plan_sub_batches = 0;
     long plan_rows = 0;
     const char *plan_graph = "off";
+    int plan_precision = 0;
     char last_plan[160] = "none";
     // Small batches (the reference's own call shape is 4 queries per GPU, test_HAConvDR_topiocqa.py:173,406) are bound by
     // launches, not arithmetic: ~110 kernels for ~0.4 TFLOP.  Their forward is captured ONCE per (B, L, options) into a HIP
@@ -1535,9 +1542,211 @@ struct LayerDump {
     float2 *stats;
     float *norm;
 };
+// ---- precision = split (split.inc)
+// The lo twins of the classic family's packed weights (+1 x the bf16 weights in HBM), from the checkpoint's fp32 tensors: made by
+// the first forward that needs them, outside any capture, never by hac_encoder_finalize.
+int ensure_split_weights(hac_encoder *e) {
+    if (e->split_weights) return HAC_OK;
+    auto lo = [&](const float *src, size_t n, bf16 *dst) {
+        f32_to_bf16_lo_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream>>>(src, dst, n);
+    };
+    for (int i = 0; i < e->cfg.n_layers; ++i) {
+        const std::string q = "roberta.encoder.layer." + std::to_string(i) + ".";
+        LayerW &l = e->layers[i];
+        float *t;
+        if (!l.wqkv_lo) HAC_HIP(hipMalloc((void **)&l.wqkv_lo, (size_t)3 * H * H * sizeof(bf16)));
+        if (!l.wo_lo) HAC_HIP(hipMalloc((void **)&l.wo_lo, (size_t)H * H * sizeof(bf16)));
+        if (!l.w1_lo) HAC_HIP(hipMalloc((void **)&l.w1_lo, (size_t)FF * H * sizeof(bf16)));
+        if (!l.w2_lo) HAC_HIP(hipMalloc((void **)&l.w2_lo, (size_t)H * FF * sizeof(bf16)));
+        const char *qkv[3] = {"attention.self.query.weight", "attention.self.key.weight", "attention.self.value.weight"};
+        for (int j = 0; j < 3; ++j) {
+            HAC_TRY(get_raw(e, q + qkv[j], (size_t)H * H, &t));
+            lo(t, (size_t)H * H, l.wqkv_lo + (size_t)j * H * H);
+        }
+        HAC_TRY(get_raw(e, q + "attention.output.dense.weight", (size_t)H * H, &t));
+        lo(t, (size_t)H * H, l.wo_lo);
+        HAC_TRY(get_raw(e, q + "intermediate.dense.weight", (size_t)FF * H, &t));
+        lo(t, (size_t)FF * H, l.w1_lo);
+        HAC_TRY(get_raw(e, q + "output.dense.weight", (size_t)H * FF, &t));
+        lo(t, (size_t)H * FF, l.w2_lo);
+        HAC_HIP(hipGetLastError());
+    }
+    HAC_HIP(hipStreamSynchronize(e->stream));
+    e->split_weights = true;
+    return HAC_OK;
+}
+
+// The forward in split mode: always the fp32-residual structure of the classic family, whatever the batch size and whatever
+// "gemm" says (embedding LN -> [QKV -> attention -> out-proj + residual -> LN statistics -> FFN-up -> FFN-down + residual -> LN
+// statistics] x (n - 1) -> the last layer on the <s> rows with the compact tail -> fp32 head); every bf16 tensor an MFMA reads
+// has its lo twin beside it.
+template <typename IT>
+int run_forward_split(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, float *out_dev, hipStream_t st, long rows_hint, long rows_plan,
+                      const LayerDump *dump) {
+    const hac_encoder_config &c = e->cfg;
+    const int L32 = (L + SEQ_ALIGN - 1) / SEQ_ALIGN * SEQ_ALIGN;
+    const long rows_max = rows_hint > 0 ? std::min<long>(rows_hint, (long)B * L32) : (long)B * L32;
+    const long Mp = (rows_max + MT - 1) / MT * MT;
+    HAC_TRY(e->ws_x.reserve((size_t)Mp * H * 4));
+    HAC_TRY(e->ws_y.reserve((size_t)Mp * H * 4));
+    HAC_TRY(e->ws_stats.reserve((size_t)Mp * 8 * 2));
+    HAC_TRY(e->ws_xb.reserve((size_t)Mp * H * 2));
+    HAC_TRY(e->ws_q.reserve((size_t)Mp * H * 2));
+    HAC_TRY(e->ws_k.reserve((size_t)(Mp + 64) * H * 2));
+    HAC_TRY(e->ws_vt.reserve((size_t)H * Mp * 2));
+    HAC_TRY(e->ws_ctx.reserve((size_t)Mp * H * 2));
+    HAC_TRY(e->ws_h.reserve((size_t)Mp * FF * 2));
+    HAC_TRY(e->ws_xb_lo.reserve((size_t)Mp * H * 2));
+    HAC_TRY(e->ws_q_lo.reserve((size_t)Mp * H * 2));
+    HAC_TRY(e->ws_k_lo.reserve((size_t)(Mp + 64) * H * 2));
+    HAC_TRY(e->ws_vt_lo.reserve((size_t)H * Mp * 2));
+    HAC_TRY(e->ws_ctx_lo.reserve((size_t)Mp * H * 2));
+    HAC_TRY(e->ws_h_lo.reserve((size_t)Mp * FF * 2));
+    SeqInfo s;
+    HAC_TRY(seq_layout(e, B, L, s));
+    seq_prep_kernel<IT><<<dim3(B), dim3(512), 0, st>>>(ids, mask, L, s, c.pad_token_id, c.vocab);
+    seq_offsets_kernel<<<dim3(1), dim3(256), 0, st>>>(s, B);
+    attn_order_kernel<<<dim3(1), dim3(256), 0, st>>>(s, B);
+    float *x = (float *)e->ws_x.p, *y = (float *)e->ws_y.p;
+    float2 *statsA = (float2 *)e->ws_stats.p, *statsF = statsA + Mp;
+    bf16 *xb = (bf16 *)e->ws_xb.p, *q = (bf16 *)e->ws_q.p, *k = (bf16 *)e->ws_k.p, *vt = (bf16 *)e->ws_vt.p, *ctx = (bf16 *)e->ws_ctx.p, *h = (bf16 *)e->ws_h.p;
+    bf16 *xb_lo = (bf16 *)e->ws_xb_lo.p, *q_lo = (bf16 *)e->ws_q_lo.p, *k_lo = (bf16 *)e->ws_k_lo.p, *vt_lo = (bf16 *)e->ws_vt_lo.p;
+    bf16 *ctx_lo = (bf16 *)e->ws_ctx_lo.p, *h_lo = (bf16 *)e->ws_h_lo.p;
+    const int *total = s.off + B;
+    // embedding rows: the shipped kernels write the fp32 rows and their bf16 rounding (= hi) for all Mp rows; lo from the fp32 rows
+    embed_ln_kernel<IT><<<dim3(L32 / 4, B), dim3(256), 0, st>>>(ids, L, s, e->word, e->posw, e->typew, e->embg, e->embb, c.ln_eps, c.vocab, x, xb);
+    zero_tail_rows_kernel<<<dim3(MT), dim3(192), 0, st>>>(x, xb, total, Mp);
+    f32_to_bf16_lo_kernel<<<dim3((unsigned)(((size_t)Mp * H + 255) / 256)), dim3(256), 0, st>>>(x, xb_lo, (size_t)Mp * H);
+    HAC_HIP(hipGetLastError());
+    auto dump_state = [&](int li) {
+        const bool emb = li < 0;
+        layer_state_kernel<<<dim3((unsigned)L, (unsigned)B), dim3(192), 0, st>>>(x, xb, emb ? nullptr : statsF, emb ? nullptr : e->layers[li].ln2g,
+                                                                                   emb ? nullptr : e->layers[li].ln2b, s, L, dump->rows, dump->stats, dump->norm);
+        e->plan_sub_batches += 1;
+        e->plan_rows += Mp;
+        e->plan_gemm = "split128";
+        return hipGetLastError() == hipSuccess ? HAC_OK : fail(HAC_ERR_HIP, "layer_state_kernel launch failed");
+    };
+    e->plan_attn_pipe = 0;
+    // (the woven kernel and its fix-up pass are never reached here: hac_encoder_attention_redo reports this forward, i.e. nothing)
+    if (e->ws_redo.p) HAC_HIP(hipMemsetAsync(e->ws_redo.p, 0, 64, st));
+    if (dump && dump->layer < 0) return dump_state(-1);
+    // Split-K of the two RESID GEMMs on small batches: the classic family's model (run_forward) with one workgroup slot per CU.
+    // Decided once per hac_encoder_forward* call (rows_plan): a sequence's embedding must not depend on its sub-batch.
+    const long Mp_plan = rows_plan > 0 ? (rows_plan + MT - 1) / MT * MT : Mp;
+    auto pick_ksplit = [&](int K) {
+        if (e->ksplit_mode == 0) return 1;
+        const int KT = K / 64, min_kt = KT >= 48 ? 8 : 4;
+        const int pin = K == H ? e->ks_pin_out : e->ks_pin_down;
+        if (pin > 0 && KT % pin == 0 && KT / pin >= 3) return pin;
+        const long tiles = (Mp_plan / 128) * (H / 128);
+        int S = 1;
+        double best = KT * 0.6;
+        for (int cand : {2, 3, 4, 6}) {
+            if (KT % cand || KT / cand < min_kt || tiles * cand > (long)e->n_cu) continue;
+            const double cost = (double)KT / cand * 0.6 + (cand - 1) * (double)Mp_plan * 1.3e-3;
+            if (cost < best) {
+                best = cost;
+                S = cand;
+            }
+        }
+        return S;
+    };
+    const int ks_out = pick_ksplit(H), ks_down = pick_ksplit(FF);
+    e->plan_ks_out = ks_out;
+    e->plan_ks_down = ks_down;
+    const size_t part_stride = (size_t)Mp * H;
+    if (std::max(ks_out, ks_down) > 1) HAC_TRY(e->ws_ksplit.reserve((size_t)(std::max(ks_out, ks_down) - 1) * part_stride * 4));
+    float *kpart = (float *)e->ws_ksplit.p;
+    const dim3 grid_g((unsigned)e->n_cu), blk_g(256);
+#define HAC_GEMM_SPLIT(EPI, CLS)                                                        \
+    do {                                                                              \
+        HAC_TRY(prof_begin(e, 1 + (CLS), st));                                        \
+        gemm_split_nt_kernel<EPI><<<grid_g, blk_g, SPLIT_GEMM_LDS, st>>>(ga);          \
+        HAC_TRY(prof_end(e, 1 + (CLS), st));                                          \
+    } while (0)
+    HAC_TRY(prof_begin(e, 0, st));
+    // compact buffers of the <s>-only tail of the last layer, and their twins
+    const long Mc = ((long)B + MT - 1) / MT * MT;
+    HAC_TRY(e->ws_cls.reserve((size_t)Mc * (H * 2 + H * 4 * 3 + H * 2 + FF * 2)));
+    HAC_TRY(e->ws_cls_lo.reserve((size_t)Mc * (H * 2 + H * 2 + FF * 2)));
+    bf16 *ctx_c = (bf16 *)e->ws_cls.p;
+    float *x_c = (float *)(ctx_c + Mc * H);
+    float *y_c = x_c + Mc * H;
+    float *x2_c = y_c + Mc * H;
+    bf16 *xb_c = (bf16 *)(x2_c + Mc * H);
+    bf16 *h_c = xb_c + Mc * H;
+    bf16 *ctx_c_lo = (bf16 *)e->ws_cls_lo.p, *xb_c_lo = ctx_c_lo + Mc * H, *h_c_lo = xb_c_lo + Mc * H;
+    for (int li = 0; li < c.n_layers; ++li) {
+        const LayerW &w = e->layers[li];
+        const bool last = (li == c.n_layers - 1);
+        GemmSplitArgs ga{};
+        GemmArgs &g = ga.g;
+        g.total_rows = total;
+        g.A = xb; ga.A_lo = xb_lo; g.W = w.wqkv; ga.W_lo = w.wqkv_lo; g.bias = w.bqkv; g.N = 3 * H; g.K = H;
+        g.q = q; g.k = k; g.v16 = vt; ga.q_lo = q_lo; ga.k_lo = k_lo; ga.v16_lo = vt_lo;
+        HAC_GEMM_SPLIT(EPI_QKV, HAC_ENC_CLASS_QKV);
+        const AttnSplitArgs a{q, q_lo, k, k_lo, vt, vt_lo, ctx, ctx_lo, s, last ? 1 : 0};
+        HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_ATTN, st));
+        attention_split_kernel<<<dim3(NH, (unsigned)B, last ? 1u : (unsigned)((L32 + 127) / 128)), dim3(256), 2 * ATS_STAGE, st>>>(a);
+        HAC_TRY(prof_end(e, 1 + HAC_ENC_CLASS_ATTN, st));
+        const bool defer_in = li > 0;
+        const float *ln2g_prev = defer_in ? e->layers[li - 1].ln2g : nullptr, *ln2b_prev = defer_in ? e->layers[li - 1].ln2b : nullptr;
+        if (!last) {
+            // attention output projection + residual, LN statistics
+            g.A = ctx; ga.A_lo = ctx_lo; g.W = w.wo; ga.W_lo = w.wo_lo; g.bias = w.bo; g.N = H; g.K = H; g.resid = x; g.y = y;
+            g.rstats = defer_in ? statsF : nullptr; g.rgamma = ln2g_prev; g.rbeta = ln2b_prev;
+            g.ksplit = ks_out; g.part = kpart; g.part_stride = part_stride;
+            HAC_GEMM_SPLIT(EPI_RESID, HAC_ENC_CLASS_OUTPROJ);
+            g.ksplit = 1;
+            HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_LN, st));
+            ln_split_rows_kernel<<<dim3((unsigned)(Mp / 4)), dim3(256), 0, st>>>(y, total, w.ln1g, w.ln1b, c.ln_eps, statsA, nullptr, xb, xb_lo, kpart, ks_out - 1, part_stride);
+            HAC_TRY(prof_end(e, 1 + HAC_ENC_CLASS_LN, st));
+            // FFN
+            g.A = xb; ga.A_lo = xb_lo; g.W = w.w1; ga.W_lo = w.w1_lo; g.bias = w.b1; g.N = FF; g.K = H; g.h = h; ga.h_lo = h_lo;
+            HAC_GEMM_SPLIT(EPI_GELU, HAC_ENC_CLASS_FFN_UP);
+            g.A = h; ga.A_lo = h_lo; g.W = w.w2; ga.W_lo = w.w2_lo; g.bias = w.b2; g.N = H; g.K = FF; g.resid = y; g.y = x;
+            g.rstats = statsA; g.rgamma = w.ln1g; g.rbeta = w.ln1b;
+            g.ksplit = ks_down; g.part = kpart; g.part_stride = part_stride;
+            HAC_GEMM_SPLIT(EPI_RESID, HAC_ENC_CLASS_FFN_DOWN);
+            g.ksplit = 1;
+            HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_LN, st));
+            ln_split_rows_kernel<<<dim3((unsigned)(Mp / 4)), dim3(256), 0, st>>>(x, total, w.ln2g, w.ln2b, c.ln_eps, statsF, nullptr, xb, xb_lo, kpart, ks_down - 1, part_stride);
+            HAC_TRY(prof_end(e, 1 + HAC_ENC_CLASS_LN, st));
+        } else {
+            // only the <s> row of every sequence continues (B rows instead of T): same kernels, compact matrices.  (The gather runs
+            // once per twin; both passes write the same fp32 residual rows.)
+            gather_cls_kernel<<<dim3((unsigned)Mc), dim3(256), 0, st>>>(ctx, x, nullptr, defer_in ? statsF : nullptr, ln2g_prev, ln2b_prev, s, B, ctx_c, x_c);
+            gather_cls_kernel<<<dim3((unsigned)Mc), dim3(256), 0, st>>>(ctx_lo, x, nullptr, defer_in ? statsF : nullptr, ln2g_prev, ln2b_prev, s, B, ctx_c_lo, x_c);
+            g.total_rows = s.nb;
+            g.A = ctx_c; ga.A_lo = ctx_c_lo; g.W = w.wo; ga.W_lo = w.wo_lo; g.bias = w.bo; g.N = H; g.K = H; g.resid = x_c; g.y = y_c; g.rstats = nullptr;
+            gemm_split_nt_kernel<EPI_RESID><<<grid_g, blk_g, SPLIT_GEMM_LDS, st>>>(ga);
+            ln_split_rows_kernel<<<dim3((unsigned)(Mc / 4)), dim3(256), 0, st>>>(y_c, s.nb, w.ln1g, w.ln1b, c.ln_eps, nullptr, x2_c, xb_c, xb_c_lo, nullptr, 0, 0);
+            g.A = xb_c; ga.A_lo = xb_c_lo; g.W = w.w1; ga.W_lo = w.w1_lo; g.bias = w.b1; g.N = FF; g.K = H; g.h = h_c; ga.h_lo = h_c_lo;
+            gemm_split_nt_kernel<EPI_GELU><<<grid_g, blk_g, SPLIT_GEMM_LDS, st>>>(ga);
+            g.A = h_c; ga.A_lo = h_c_lo; g.W = w.w2; ga.W_lo = w.w2_lo; g.bias = w.b2; g.N = H; g.K = FF; g.resid = x2_c; g.y = y_c;
+            gemm_split_nt_kernel<EPI_RESID><<<grid_g, blk_g, SPLIT_GEMM_LDS, st>>>(ga);
+            ln_split_rows_kernel<<<dim3((unsigned)(Mc / 4)), dim3(256), 0, st>>>(y_c, s.nb, w.ln2g, w.ln2b, c.ln_eps, nullptr, x_c, xb_c, xb_c_lo, nullptr, 0, 0);
+        }
+        HAC_HIP(hipGetLastError());
+        if (dump && dump->layer == li) return dump_state(li);
+    }
+#undef HAC_GEMM_SPLIT
+    HAC_TRY(prof_end(e, 0, st));
+    const int head_ns = B <= 64 ? 8 : CLS_NS;
+    cls_head_proj_kernel<<<dim3((unsigned)((B + CLS_SB - 1) / CLS_SB), H / head_ns), dim3(256), 0, st>>>(x_c, s, 1, B, e->wh, e->bh, y_c, head_ns);
+    cls_head_norm_kernel<<<dim3((unsigned)B), dim3(256), 0, st>>>(y_c, s, e->ng, e->nb, 1e-5f, out_dev);
+    HAC_HIP(hipGetLastError());
+    e->plan_sub_batches += 1;
+    e->plan_rows += Mp;
+    e->plan_gemm = "split128";
+    return HAC_OK;
+}
+
 template <typename IT>
 int run_forward(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, float *out_dev, hipStream_t st, long rows_hint = 0, int family = -1,
                 long rows_plan = 0, const LayerDump *dump = nullptr) {
+    if (e->precision == 1) return run_forward_split<IT>(e, ids, mask, B, L, out_dev, st, rows_hint, rows_plan, dump);
     const hac_encoder_config &c = e->cfg;
     const int L32 = (L + SEQ_ALIGN - 1) / SEQ_ALIGN * SEQ_ALIGN;
     bool fw_capturing = false;           // (inside a stream capture -- the small-batch graphs -- an event query is an error that kills the capture)
@@ -1887,7 +2096,8 @@ constexpr long GRAPH_MAX_ROWS = 16384;   // beyond this a forward is millisecond
 uint64_t ws_signature(const hac_encoder *e) {
     uint64_t h = 1469598103934665603ull;
     for (const GrowBuf *b : {&e->ws_x, &e->ws_xb, &e->ws_q, &e->ws_k, &e->ws_vt, &e->ws_ctx, &e->ws_y, &e->ws_h, &e->ws_seq, &e->ws_cls, &e->ws_stats,
-                             &e->ws_yb, &e->ws_part, &e->ws_idstats, &e->ws_gids, &e->ws_gmask, &e->ws_gout, &e->ws_ksplit, &e->ws_redo})
+                             &e->ws_yb, &e->ws_part, &e->ws_idstats, &e->ws_gids, &e->ws_gmask, &e->ws_gout, &e->ws_ksplit, &e->ws_redo,
+                             &e->ws_xb_lo, &e->ws_q_lo, &e->ws_k_lo, &e->ws_vt_lo, &e->ws_ctx_lo, &e->ws_h_lo, &e->ws_cls_lo})
         h = (h ^ (uint64_t)(uintptr_t)b->p) * 1099511628211ull;
     return h;
 }
@@ -1923,7 +2133,8 @@ int forward_graph(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, f
     HAC_TRY(e->ws_gout.reserve(n_out));
     const uint64_t key = ((uint64_t)B << 40) | ((uint64_t)L << 24) | ((uint64_t)sizeof(IT) << 16) | ((uint64_t)(e->attn_mode & 1) << 8) |
                          ((uint64_t)((e->gemm_mode + 1) & 3) << 4) | ((uint64_t)(e->ksplit_mode & 1) << 12) |
-                         ((uint64_t)(e->attn_qsplit & 1) << 13) | ((uint64_t)(e->g8_stagger & 1) << 14) | ((uint64_t)((e->attn_pipe + 1) & 3) << 15);
+                         ((uint64_t)(e->attn_qsplit & 1) << 13) | ((uint64_t)(e->g8_stagger & 1) << 14) | ((uint64_t)((e->attn_pipe + 1) & 3) << 15) |
+                         ((uint64_t)(e->precision & 1) << 20);
     // (a caller that pads every batch to its own longest sequence can show hundreds of shapes: the cache is bounded, and starting
     // over costs each live shape one plain forward and one capture)
     if (e->graphs.size() >= GRAPH_MAX_SHAPES && e->graphs.find(key) == e->graphs.end()) drop_graphs(e);
@@ -1991,6 +2202,8 @@ int forward_batched(hac_encoder *e, const IT *ids, const IT *mask, int B, int L,
     e->plan_sub_batches = 0;
     e->plan_rows = 0;
     e->plan_graph = "off";
+    e->plan_precision = e->precision;
+    if (e->precision == 1) HAC_TRY(ensure_split_weights(e));
     if (graph_eligible(e, B, L, st)) return forward_graph<IT>(e, ids, mask, B, L, out_dev, st);
     if ((long)B * L32 <= e->max_tokens) return run_forward<IT>(e, ids, mask, B, L, out_dev, st);
     // More rows than one pass holds if every sequence were full length: size the sub-batches by the REAL padded
@@ -2068,6 +2281,10 @@ int hac_encoder_create(const hac_encoder_config *cfg, int device, hac_encoder **
     (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_QKV, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
     (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_RESID, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
     (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_GELU, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
+    (void)hipFuncSetAttribute((const void *)gemm_split_nt_kernel<EPI_QKV>, hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_GEMM_LDS);
+    (void)hipFuncSetAttribute((const void *)gemm_split_nt_kernel<EPI_RESID>, hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_GEMM_LDS);
+    (void)hipFuncSetAttribute((const void *)gemm_split_nt_kernel<EPI_GELU>, hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_GEMM_LDS);
+    (void)hipFuncSetAttribute((const void *)attention_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * ATS_STAGE);
     (void)hipFuncSetAttribute((const void *)gemm8_kernel<EPI8_QKV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
     (void)hipFuncSetAttribute((const void *)gemm8_kernel<EPI8_RESID, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
     (void)hipFuncSetAttribute((const void *)gemm8_kernel<EPI8_GELU, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
@@ -2093,7 +2310,7 @@ void hac_encoder_destroy(hac_encoder *e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (auto &kv : e->raw) (void)hipFree(kv.second);
     for (auto &l : e->layers)
-        for (bf16 *p : {l.wqkv, l.wo, l.w1, l.w2})
+        for (bf16 *p : {l.wqkv, l.wo, l.w1, l.w2, l.wqkv_lo, l.wo_lo, l.w1_lo, l.w2_lo})
             if (p) (void)hipFree(p);
     for (auto &l : e->layers) {
         if (l.bqkv) (void)hipFree(l.bqkv);
@@ -2110,7 +2327,8 @@ void hac_encoder_destroy(hac_encoder *e) {
     }
     if (e->h_redo) (void)hipHostFree(e->h_redo);
     for (GrowBuf *b : {&e->ws_x, &e->ws_xb, &e->ws_q, &e->ws_k, &e->ws_vt, &e->ws_ctx, &e->ws_y, &e->ws_h, &e->ws_seq, &e->ws_ids, &e->ws_mask, &e->ws_out, &e->ws_cls, &e->ws_stats, &e->ws_yb, &e->ws_part, &e->ws_idstats,
-                       &e->ws_gids, &e->ws_gmask, &e->ws_gout, &e->ws_ksplit, &e->ws_identgb, &e->ws_clk, &e->ws_redo, &e->ws_dump})
+                       &e->ws_gids, &e->ws_gmask, &e->ws_gout, &e->ws_ksplit, &e->ws_identgb, &e->ws_clk, &e->ws_redo, &e->ws_dump,
+                       &e->ws_xb_lo, &e->ws_q_lo, &e->ws_k_lo, &e->ws_vt_lo, &e->ws_ctx_lo, &e->ws_h_lo, &e->ws_cls_lo})
         b->release();
     if (e->h_pin) (void)hipHostFree(e->h_pin);
     if (e->h_len) (void)hipHostFree(e->h_len);
@@ -2157,12 +2375,13 @@ int hac_encoder_finalize(hac_encoder *e) {
     HAC_TRY(get_raw(e, "norm.weight", H, &e->ng));
     HAC_TRY(get_raw(e, "norm.bias", H, &e->nb));
     for (auto &l : e->layers) {
-        for (bf16 *pp : {l.wqkv, l.wo, l.w1, l.w2, l.wqkv8, l.w18})
+        for (bf16 *pp : {l.wqkv, l.wo, l.w1, l.w2, l.wqkv8, l.w18, l.wqkv_lo, l.wo_lo, l.w1_lo, l.w2_lo})
             if (pp) (void)hipFree(pp);
         if (l.bqkv) (void)hipFree(l.bqkv);
         if (l.fold) (void)hipFree(l.fold);
     }
     e->layers.assign(c.n_layers, LayerW());
+    e->split_weights = false;
     for (int i = 0; i < c.n_layers; ++i) {
         const std::string q = "roberta.encoder.layer." + std::to_string(i) + ".";
         LayerW &l = e->layers[i];
@@ -2296,6 +2515,8 @@ int hac_encoder_layer_state(hac_encoder *e, const int32_t *ids, const int32_t *m
     e->plan_sub_batches = 0;
     e->plan_rows = 0;
     e->plan_graph = "off";   // never captured: plain launches of the forward's own kernels
+    e->plan_precision = e->precision;
+    if (e->precision == 1) HAC_TRY(ensure_split_weights(e));
     const LayerDump dump{layer, d_rows, d_stats, norm_out ? d_norm : nullptr};
     HAC_TRY(run_forward<int>(e, (const int *)e->ws_ids.p, (const int *)e->ws_mask.p, B, L, nullptr, e->stream, 0, -1, 0, &dump));
     HAC_HIP(hipStreamSynchronize(e->stream));
@@ -2313,6 +2534,9 @@ int hac_encoder_set_option(hac_encoder *e, const char *name, const char *value) 
     if (n == "gemm") {
         if (v != "auto" && v != "classic" && v != "8phase") return fail(HAC_ERR_INVALID, "encoder option gemm = '%s': auto | classic | 8phase", value);
         e->gemm_mode = v == "classic" ? 0 : (v == "8phase" ? 1 : -1);
+    } else if (n == "precision") {
+        if (v != "bf16" && v != "split") return fail(HAC_ERR_INVALID, "encoder option precision = '%s': bf16 | split", value);
+        e->precision = v == "split" ? 1 : 0;
     } else if (n == "attn") {
         if (v != "stream" && v != "twopass") return fail(HAC_ERR_INVALID, "encoder option attn = '%s': stream | twopass", value);
         e->attn_mode = v == "twopass" ? 1 : 0;
@@ -2354,8 +2578,10 @@ int hac_encoder_set_option(hac_encoder *e, const char *name, const char *value) 
 
 const char *hac_encoder_last_plan(hac_encoder *e) {
     if (!e) return "none";
-    snprintf(e->last_plan, sizeof e->last_plan, "gemm=%s attn=%s sub_batches=%d rows=%ld graph=%s ksplit=%d/%d attn_form=%s", e->plan_gemm, e->attn_mode ? "twopass" : "stream",
-             e->plan_sub_batches, e->plan_rows, e->plan_graph, e->plan_ks_out, e->plan_ks_down, e->attn_mode ? "twopass" : (e->plan_attn_pipe ? "woven" : "single"));
+    const bool split = e->plan_precision == 1;   // (what the most recent forward ran, not what the option says now)
+    snprintf(e->last_plan, sizeof e->last_plan, "gemm=%s attn=%s sub_batches=%d rows=%ld graph=%s ksplit=%d/%d attn_form=%s%s", e->plan_gemm, e->attn_mode ? "twopass" : "stream",
+             e->plan_sub_batches, e->plan_rows, e->plan_graph, e->plan_ks_out, e->plan_ks_down,
+             split ? "split" : (e->attn_mode ? "twopass" : (e->plan_attn_pipe ? "woven" : "single")), split ? " precision=split" : "");
     return e->last_plan;
 }
 

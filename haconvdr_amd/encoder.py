@@ -14,13 +14,26 @@ import numpy as np
 from . import _lib
 
 
+def split_bf16(x):
+    """Host twin of the kernels' split_bf16 (csrc/split.inc): the pair (hi, lo) = (bf16(x), bf16(x - float(hi))) of a float32
+    array, both returned as float32.  hi + lo reproduces x to 2^-16 relative (round to nearest even twice: 2^-9 of 2^-9 is the
+    bound, 2^-17 the typical figure) wherever lo is a normal bf16 value, and is never worse than hi alone."""
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    hi = t.to(torch.bfloat16).to(torch.float32)
+    lo = (t - hi).to(torch.bfloat16).to(torch.float32)
+    return hi.numpy(), lo.numpy()
+
+
 class ANCEEncoder:
-    def __init__(self, n_layers=12, vocab=50265, max_pos=514, type_vocab=1, pad_token_id=1, ln_eps=1e-5, device=0):
+    def __init__(self, n_layers=12, vocab=50265, max_pos=514, type_vocab=1, pad_token_id=1, ln_eps=1e-5, device=0, precision="bf16"):
         self.device = int(device)
         self.n_layers = int(n_layers)
         cfg = _lib.EncoderConfig(self.n_layers, 768, 12, 3072, int(vocab), int(max_pos), int(type_vocab), int(pad_token_id), float(ln_eps))
         self._h = ctypes.c_void_p()
         _lib.check(_lib.lib().hac_encoder_create(ctypes.byref(cfg), self.device, ctypes.byref(self._h)))
+        if precision != "bf16":     # "split": hi + lo bf16 operand pairs, three MFMAs per product (include/haconvdr.h, "precision")
+            self.set_option("precision", precision)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -52,7 +65,7 @@ class ANCEEncoder:
         return cls(n_layers=n_layers, vocab=vocab, max_pos=max_pos, type_vocab=tv, device=device, **kw).load_state_dict(sd)
 
     @classmethod
-    def from_pretrained(cls, path, device=0):
+    def from_pretrained(cls, path, device=0, precision="bf16"):
         """Checkpoint directory as ``ANCE.from_pretrained(model_path, config=RobertaConfig.from_pretrained(model_path))``
         reads it (src/models.py:113-122): ``config.json`` + ``pytorch_model.bin`` or ``model.safetensors``.
 
@@ -90,7 +103,7 @@ class ANCEEncoder:
             if cfg.get("position_embedding_type", "absolute") != "absolute":
                 raise ValueError(f"{cfg_path}: position_embedding_type = {cfg['position_embedding_type']!r} is not supported")
             kw = {"ln_eps": float(cfg.get("layer_norm_eps", 1e-5)), "pad_token_id": int(cfg.get("pad_token_id", 1))}
-        return cls.from_state_dict(sd, device=device, **kw)
+        return cls.from_state_dict(sd, device=device, precision=precision, **kw)
 
     # ---- forward -----------------------------------------------------------
     def __call__(self, input_ids, attention_mask, wrap_pooler=False):
@@ -151,7 +164,8 @@ class ANCEEncoder:
         _lib.check(_lib.lib().hac_encoder_set_option(self._h, str(name).encode(), str(value).encode()))
 
     def last_plan(self):
-        """Kernel families of the most recent forward: "gemm=gemm8|classic256|classic128 attn=... sub_batches=N rows=R"."""
+        """Kernel families of the most recent forward: "gemm=gemm8|classic256|classic128|split128 attn=... sub_batches=N rows=R ...",
+        with " precision=split" appended when it ran in split mode."""
         return _lib.lib().hac_encoder_last_plan(self._h).decode()
 
     KERNEL_CLASSES = ("qkv", "attention", "out_proj", "ffn_up", "ffn_down", "layernorm")   # HAC_ENC_CLASS_* of include/haconvdr.h

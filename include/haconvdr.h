@@ -249,7 +249,20 @@ int hac_encoder_forward_device(hac_encoder *enc, const void *ids_dev, const void
  * timing only, same bits).  Any other name or value is HAC_ERR_INVALID (never a
  * silent default).  HAC_ENC_GEMM gives the default of "gemm" and is read once, in hac_encoder_create.
  * "auto" decides ONCE per forward call, from the rows of the whole batch: every sub-batch of a call runs the same
- * GEMM family and tile size, so a sequence's embedding does not depend on the sub-batch it fell into. */
+ * GEMM family and tile size, so a sequence's embedding does not depend on the sub-batch it fell into.
+ *
+ * "precision" = "bf16" (default) | "split".  "bf16": every operand of every matrix product is rounded to bf16 (2^-9 relative);
+ * whether a checkpoint stays inside the 1e-3 cosine contract then depends on its weights.  "split": every
+ * matrix product of the forward -- QKV / out-projection / FFN, Q.K^T, P.V and the last layer's <s>-row tail -- takes both
+ * operands as a pair hi = bf16(v), lo = bf16(v - hi) and accumulates a_lo.b_hi + a_hi.b_lo + a_hi.b_hi in fp32, in one fixed
+ * order (deterministic; eager launches, capture and replay give the same bits): operand error 2^-17 relative, GELU by an erf
+ * good to fp32, fp32 residual stream, LayerNorm, softmax and head.  The forward then always has the structure of the classic
+ * family with 128^2 tiles ("gemm" is ignored; "ksplit", "graph", "max_tokens" work as usual; hac_encoder_last_plan reports
+ * gemm=split128 ... attn_form=split precision=split).  Cost: three MFMAs per product and twice the staged operand bytes --
+ * several times the bf16 forward's time ("Precision") -- plus one more copy of the bf16 layer weights and
+ * of the bf16 activation workspaces in HBM, allocated by the first forward that runs in the mode, not by hac_encoder_finalize.
+ * Use it for a checkpoint whose embeddings differ between the two modes by more than a small fraction of 1e-3 in 1-cos
+ * (INTEGRATION.md).  Switching back to "bf16" restores the default path bit for bit. */
 int hac_encoder_set_option(hac_encoder *enc, const char *name, const char *value);
 /* What the most recent forward ran: "gemm=gemm8|classic256|classic128 attn=stream|twopass sub_batches=N rows=R graph=off|eager-first|replay ksplit=S_out/S_down attn_form=woven|single|twopass"
  * (tests and bench.py assert the kernel family they mean to check).  The GEMM family and, with the classic kernels, the tile

@@ -50,7 +50,7 @@ def sweep():
     lens = [512 if i % 3 == 0 else 64 + (i * 37) % 449 for i in range(64)]
     ids, mask = encoder_case_inputs(0x5EED, lens, 512)
     pick = [0, 1, 2, 5, 9, 17, 30, 31, 32, 45, 62, 63]
-    print("std outlier | classic 1-cos max (centred) | gemm8 1-cos max (centred) | rows min apart | attention redo", flush=True)
+    print("std outlier | classic 1-cos max (centred) | gemm8 1-cos max (centred) | split 1-cos max (centred) | rows min apart | attention redo", flush=True)
     for std in (0.08, 0.10, 0.12, 0.16):
         for scale in (1.0, 60.0, 200.0, 600.0):
             sd = dict(synth.ance_state_dict(0x0D17, 12, layer_matrix_std=std))
@@ -73,7 +73,12 @@ def sweep():
                 out = enc(ids.astype(np.int32), mask.astype(np.int32))[pick]
                 m = parity.measure(out, ref)
                 cells.append(f"{m['raw']:.2e} ({m['centred']:.2e}, L2 {m['rel_l2']:.3f}){'' if np.isfinite(out).all() else ' NONFINITE'}")
-            print(f"{std:.2f} {scale:5.0f} | {cells[0]} | {cells[1]} | {m['spread']['raw_min']:.2e} | {enc.attention_redo()}", flush=True)
+            redo = enc.attention_redo()
+            enc.set_option("precision", "split")      # hi + lo operand pairs (the forward's structure is then the classic family's whatever "gemm" says)
+            out = enc(ids.astype(np.int32), mask.astype(np.int32))[pick]
+            m = parity.measure(out, ref)
+            cells.append(f"{m['raw']:.2e} ({m['centred']:.2e}, L2 {m['rel_l2']:.3f}){'' if np.isfinite(out).all() else ' NONFINITE'}")
+            print(f"{std:.2f} {scale:5.0f} | {cells[0]} | {cells[1]} | {cells[2]} | {m['spread']['raw_min']:.2e} | {redo}", flush=True)
             del enc
 
 
