@@ -75,6 +75,7 @@ def ance_forward(sd, input_ids, attention_mask, n_layers=None, n_heads=12, eps=1
 # One stage at a time, fp64, with the HIP kernels' bf16 rounding points (tests/test_encoder_layers_gpu.py: teacher-forced parity)
 
 LAYER_MUTATIONS = ("eps", "logits", "key_plus", "key_minus", "bias", "gelu_tanh")   # what ance_layer(mutate=...) knows
+CHUNK_MUTATIONS = ("key_chunk",)      # of the split attention kernel's 64-key chunk loop (tests/test_encoder_precision_shapes_gpu.py)
 EMBED_MUTATIONS = ("eps", "pos")                                                    # what ance_embed(mutate=...) knows
 LOG2E = 1.4426950408889634
 
@@ -82,6 +83,24 @@ LOG2E = 1.4426950408889634
 def bf16(t):
     """Round to bf16 (nearest even) and back: the kernels' (bf16) conversions of fp32 values."""
     return t.to(torch.float32).to(torch.bfloat16).to(torch.float64)
+
+
+def split2(t):
+    """The pair rounding of precision = split: v -> bf16(v) + bf16(v - bf16(v)), hi + lo summed in fp64 (host twin of the
+    kernels' helper: haconvdr_amd.encoder.split_bf16; the difference is formed in fp32 as there -- it is exact)."""
+    t32 = t.to(torch.float32)
+    hi = t32.to(torch.bfloat16).to(torch.float32)
+    lo = (t32 - hi).to(torch.bfloat16)
+    return hi.to(torch.float64) + lo.to(torch.float64)
+
+
+FAMILIES = (None, "classic", "gemm8", "split")
+
+
+def _rounding(family):
+    """The rounding a family applies where the classic kernels convert to bf16: none (family None), bf16, or the hi + lo pair
+    ("split": the arithmetic of "classic" with every bf16(.) replaced by split2(.))."""
+    return (lambda t: t) if not family else (split2 if family == "split" else bf16)
 
 
 def _t64(sd, name):
@@ -103,7 +122,7 @@ def ance_embed(sd, input_ids, attention_mask, family=None, eps=1e-5, pad_id=1, m
     Returns the state dict of ance_layer ({rows, mean, rstd, norm} as torch float64 over [B, L]); the rows are already
     normalized (mean 0, rstd 1, norm = rows).  family "classic": rows are fp32 (embed_ln_kernel, encoder.hip: ln768_store writes
     x_f32 unrounded) -- modelled as exact; "gemm8": the rows are stored only as bf16 (ln768_store's x_bf; run_forward passes
-    x_f32 = nullptr on that path).  mutate: "eps" (LayerNorm eps 1e-12) or "pos" (position ids one too high, the last one clamped to the table)."""
+    x_f32 = nullptr on that path); "split": as classic (the pair of the rows is formed by the consumer).  mutate: "eps" (LayerNorm eps 1e-12) or "pos" (position ids one too high, the last one clamped to the table)."""
     ids = torch.as_tensor(np.asarray(input_ids), dtype=torch.long)
     mask = torch.as_tensor(np.asarray(attention_mask), dtype=torch.long)
     p = "roberta.embeddings."
@@ -167,7 +186,7 @@ def _project(sd, i, nm, x, mean, rstd, xn, g_in, b_in, family, n_heads, mutate=N
     c = LOG2E / math.sqrt(x.shape[-1] // n_heads)
     if family == "gemm8":
         return bf16(_folded(x, mean, rstd, Wf, bias, g_in, b_in, c if nm == "query" else 1.0))
-    R = bf16 if family else (lambda t: t)
+    R = _rounding(family)
     A = R(xn)
     return R((A @ R(Wf).T + bias) * c) if nm == "query" else R(A @ R(Wf).T + bias)
 
@@ -175,10 +194,12 @@ def _project(sd, i, nm, x, mean, rstd, xn, g_in, b_in, family, n_heads, mutate=N
 def _attend(Qs, K, V, n, n_heads, family, attn, mutate=None):
     """Attention context [nq, H] of the query rows Qs [nq, H] (base 2, _project) of one sequence of n valid rows over its
     keys and values K, V [>= n, H]: the arithmetic of ance_layer's docstring (mutations "logits", "key_plus", "key_minus")."""
-    R = bf16 if family else (lambda t: t)
+    R = _rounding(family)
     nq, H = Qs.shape
     dh = H // n_heads
     nk = min(K.shape[0], n + 1) if mutate == "key_plus" else (max(1, n - 1) if mutate == "key_minus" else n)
+    if mutate == "key_chunk":
+        nk = min(K.shape[0], (n + 63) // 64 * 64)
     qh = Qs.reshape(nq, n_heads, dh).transpose(0, 1)
     kh = K[:nk].reshape(nk, n_heads, dh).transpose(0, 1)
     vh = V[:nk].reshape(nk, n_heads, dh).transpose(0, 1)
@@ -225,12 +246,19 @@ def ance_layer(sd, i, x_in, attention_mask, family=None, n_heads=12, eps=1e-5, m
         values), cvec = bias + W.beta (fold_ln_kernel); layer 0 folds nothing (gamma = 1, beta = 0: the embedding rows are
         normalized); the residual of the RESID epilogues is (bf16 row - mean) rstd gamma + beta; FFN-up stores bf16(gelu).
 
+      split (split.inc, precision = split): the classic family's arithmetic with every bf16(.) above replaced by the pair rounding
+        split2(.) = bf16(v) + bf16(v - bf16(v)), hi + lo summed exactly (the dropped lo.lo terms and the fp32 accumulation are
+        not modelled).  Not what the split kernels are compared with -- that is family None -- but the yardstick of their
+        bounds (tests/split_parity.py: E_emul).
+
     mutate (the self-checks of the tests): "eps" (both LayerNorms with eps 1e-12), "logits" (x 1.01), "key_plus" /
     "key_minus" (every sequence attends one key more -- the pad row behind it -- or one fewer), "bias" (the value
-    projection's bias dropped), "gelu_tanh" (tanh-approximate GELU)."""
-    assert family in (None, "classic", "gemm8") and attn in ("stream", "twopass") and (mutate is None or mutate in LAYER_MUTATIONS), \
+    projection's bias dropped), "gelu_tanh" (tanh-approximate GELU); of CHUNK_MUTATIONS, "key_chunk" (every sequence whose
+    length is no multiple of 64 attends the keys up to the next multiple of 64, clamped to the rows that exist: a wrong
+    masked-step condition in the split attention kernel's 64-key chunk loop)."""
+    assert family in FAMILIES and attn in ("stream", "twopass") and (mutate is None or mutate in LAYER_MUTATIONS + CHUNK_MUTATIONS), \
         (family, attn, mutate)
-    R = bf16 if family else (lambda t: t)
+    R = _rounding(family)
     lens = torch.as_tensor(np.asarray(attention_mask), dtype=torch.long).sum(1).tolist()
     x, mean, rstd, g_in, b_in, xn = _layer_input(sd, i, x_in)
     B, L, H = x.shape
@@ -296,7 +324,7 @@ def ance_tail(sd, i, x_in, attention_mask, family=None, n_heads=12, eps=1e-5, mu
 
     Only what the kernels compute (run_forward, `last`): keys and values of every row, the query of row 0 of each sequence,
     its attention (cls_only), then out-projection, LayerNorm, FFN and LayerNorm on the gathered <s> rows, and the head.
-      classic: Q, K, V as in ance_layer;
+      classic (and split, with its pair rounding): Q, K, V as in ance_layer;
       gemm8: K, V folded as in ance_layer; the <s> query in the same folded form, scale folded in, bf16 (cls_q_kernel);
       both, the <s> rows (gather_cls_kernel, then gemm_bf16_nt_kernel and ln_rows_kernel on the compact matrices, on gemm8
       too): x_c = LN_prev(row) in fp32 (gemm8: of the bf16 row); y = bf16(ctx).bf16(Wo)^T + bo + x_c and x2 = LN1(y) in
@@ -305,12 +333,12 @@ def ance_tail(sd, i, x_in, attention_mask, family=None, n_heads=12, eps=1e-5, mu
     mutate: LAYER_MUTATIONS for this layer, or "prev_ln" (the gather normalizes with this layer's own output LayerNorm
     instead of the previous layer's), "pool_mean" (masked mean of every row's layer output -- ance_layer's -- instead of
     row 0), "pool_row1" (row min(1, len - 1) instead of row 0), and the head's of _head."""
-    assert family in (None, "classic", "gemm8") and attn in ("stream", "twopass") and (mutate is None or mutate in TAIL_MUTATIONS), \
+    assert family in FAMILIES and attn in ("stream", "twopass") and (mutate is None or mutate in TAIL_MUTATIONS + CHUNK_MUTATIONS), \
         (family, attn, mutate)
-    R = bf16 if family else (lambda t: t)
+    R = _rounding(family)
     mask = torch.as_tensor(np.asarray(attention_mask), dtype=torch.long)
     lens = mask.sum(1).tolist()
-    lmut = mutate if mutate in LAYER_MUTATIONS else None
+    lmut = mutate if mutate in LAYER_MUTATIONS + CHUNK_MUTATIONS else None
     q = f"roberta.encoder.layer.{i}."
     if mutate == "pool_mean":
         st = ance_layer(sd, i, x_in, attention_mask, family, n_heads, eps, attn=attn)

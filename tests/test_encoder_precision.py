@@ -142,3 +142,100 @@ def test_split_kernels_are_in_the_library_with_three_mfmas_per_product(tmp_path)
     # the one-block step: 4 k-steps of S^T = K.Q^T and 2 x 2 of O^T = V^T.P^T, in the common and the masked form
     assert mfma[of("attention_split_kernel")] == 3 * 2 * (4 + 4), mfma[of("attention_split_kernel")]
     assert not [n for n in scratch if "split" in n], scratch
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the yardstick of the teacher-forced bounds (tests/split_parity.py): oracle.ance_oracle family="split" against family=None
+
+
+def test_split_family_is_the_classic_arithmetic_with_the_pair_rounding(monkeypatch):
+    """family="split" = family="classic" with every bf16(.) replaced by v -> bf16(v) + bf16(v - bf16(v)) (the host twin
+    split_bf16, hi + lo summed in fp64), embed, layer and tail; and it is far closer to the unrounded chain than classic."""
+    from tests import split_parity as sp
+    from tests.golden.make_golden_encoder import encoder_case_inputs
+    sd = sp.weights("std012", 3)
+    ids, mask = encoder_case_inputs(3, [1, 33, 64, 70], 96)
+    x = torch.randn(1000, dtype=torch.float64) * 10.0 ** torch.randint(-6, 6, (1000,))
+    hi, lo = split_bf16(x.numpy().astype(np.float32))
+    assert np.array_equal(ance_oracle.split2(x).numpy(), hi.astype(np.float64) + lo.astype(np.float64))
+    st = ance_oracle.ance_embed(sd, ids, mask)
+    got = [ance_oracle.ance_embed(sd, ids, mask, family="split")["norm"], ance_oracle.ance_layer(sd, 0, st, mask, family="split")["norm"],
+           ance_oracle.ance_tail(sd, 0, st, mask, family="split")]
+    classic = ance_oracle.ance_layer(sd, 0, st, mask, family="classic")["norm"]
+    exact = ance_oracle.ance_layer(sd, 0, st, mask)["norm"]
+    monkeypatch.setattr(ance_oracle, "bf16", ance_oracle.split2)
+    want = [ance_oracle.ance_embed(sd, ids, mask, family="classic")["norm"], ance_oracle.ance_layer(sd, 0, st, mask, family="classic")["norm"],
+            ance_oracle.ance_tail(sd, 0, st, mask, family="classic")]
+    for g, w in zip(got, want):
+        assert torch.equal(g, w)
+    valid = np.asarray(mask, bool)
+    assert sp.rel(got[1].numpy(), exact.numpy(), valid) * 100 < sp.rel(classic.numpy(), exact.numpy(), valid)
+
+
+def test_recorded_emulation_constants_match_the_split_faithful_reference():
+    """E_emul(stage) = rel(family "split", family None) on the unrounded chain run freely from ance_embed, recomputed for every
+    (recipe, batch, stage) whose bound tests/test_encoder_precision_shapes_gpu.py derives from it: the recorded constants are
+    within 5 %; the layer figure does not depend on the batch (the two std-0.08 edge batches agree within 2 %), which is what
+    lets the committed LAYER_BOUNDS carry over to new batches; those bounds stand EMUL_FACTOR (within 5 %) above the emulation;
+    and the key_chunk mutation lies >= 3 x beyond every bound of the SPLIT_EDGES batch it is asserted on."""
+    from tests import split_parity as sp
+    from tests import test_encoder_precision_shapes_gpu as shapes
+    cases = {k: set(v) for k, v in shapes.E_EMUL.items()}
+    for recipe, batch in shapes.LAYER_EMUL:
+        cases.setdefault((recipe, 3, batch), set()).update({("layer", 0), ("layer", 1)})
+    got = {}
+    with torch.no_grad():
+        for (recipe, depth, batch), stages in cases.items():
+            sd = sp.weights(recipe, depth)
+            ids, mask = sp.batch(batch)
+            chain = sp.unrounded_chain(sd, ids, mask, depth)
+            got[(recipe, depth, batch)] = e = sp.emulation(sd, ids, mask, depth, layers=any(s[0] == "layer" for s in stages),
+                                                            tail=any(s[0] == "tail" for s in stages), chain=chain)
+            if batch == "split_edges" and recipe in shapes.STD:
+                valid = np.asarray(mask, bool)
+                for n in range(depth - 1):
+                    mut = ance_oracle.ance_layer(sd, n, chain[n - 1], mask, mutate="key_chunk")["norm"].numpy()
+                    assert sp.rel(mut, chain[n]["norm"].numpy(), valid) >= 3.0 * shapes.bound(recipe, depth, batch, "layer", n), (recipe, n)
+                base = ance_oracle.ance_tail(sd, depth - 1, chain[depth - 2], mask).numpy()
+                mut = ance_oracle.ance_tail(sd, depth - 1, chain[depth - 2], mask, mutate="key_chunk").numpy()
+                assert sp.rel(mut, base) >= 3.0 * shapes.bound(recipe, depth, batch, "tail", depth - 1), recipe
+    for key, rec in shapes.E_EMUL.items():
+        for stage, v in rec.items():
+            print(key, stage, f"recorded {v:.3e} recomputed {got[key][stage]:.4e}")
+            assert abs(v / got[key][stage] - 1.0) <= 0.05, (key, stage, v, got[key][stage])
+    for (recipe, batch), rec in shapes.LAYER_EMUL.items():
+        e = got[(recipe, 3, batch)]
+        print(recipe, batch, f"layers {e[('layer', 0)]:.4e} {e[('layer', 1)]:.4e}")
+        for n in (0, 1):
+            assert abs(rec[n] / e[("layer", n)] - 1.0) <= 0.05, (recipe, batch, n, rec[n], e[("layer", n)])
+        worst = max(e[("layer", 0)], e[("layer", 1)])
+        assert abs(shapes.LAYER_BOUNDS[shapes.STD[recipe]]["layer"] / worst / sp.EMUL_FACTOR - 1.0) <= 0.05, (recipe, batch, worst)
+    for n in (0, 1):
+        a, b = got[("std008", 3, "edges")][("layer", n)], got[("std008", 3, "split_edges")][("layer", n)]
+        assert abs(a / b - 1.0) <= 0.02, (n, a, b)
+
+
+def test_peaked_recipe_moves_the_softmax_reference():
+    """The peaked recipe (Q and K x PEAKED_SCALE) does what it is for, on the reference alone: the window rule
+    (_window_reference on the unrounded chain's base-2 logits) moves its reference -- the split attention kernel's ballot
+    branch, delta, the rescaling of lsum and o -- on at least 10 % of the (sequence, head) items of layer 0 of SPLIT_EDGES;
+    the plain std-0.08 weights never move it."""
+    from tests import split_parity as sp
+    ids, mask = sp.batch("split_edges")
+    lens = mask.sum(1).tolist()
+    frac = {}
+    for recipe in ("std008", "peaked"):
+        sd = sp.weights(recipe, 3)
+        x, mean, rstd, g_in, b_in, xn = ance_oracle._layer_input(sd, 0, ance_oracle.ance_embed(sd, ids, mask))
+        Q, K = (ance_oracle._project(sd, 0, nm, x, mean, rstd, xn, g_in, b_in, None, 12) for nm in ("query", "key"))
+        moved = later = total = 0
+        for s, n in enumerate(lens):
+            qh, kh = (t[s, :n].reshape(n, 12, 64).transpose(0, 1) for t in (Q, K))
+            m = ance_oracle._window_reference(qh @ kh.transpose(-1, -2))          # [heads, n, blocks]
+            moved += int((m != 0).flatten(1).any(1).sum())
+            later += int((m[..., 1:] != m[..., :-1]).flatten(1).any(1).sum())      # moved after the first block: l and O are rescaled
+            total += 12
+        frac[recipe] = (moved / total, later / total)
+    print("share of (sequence, head) items whose reference moves (at all, after the first block):", frac)
+    assert frac["std008"][0] == 0.0, frac
+    assert frac["peaked"][0] >= 0.10 and frac["peaked"][1] >= 0.10, (sp.PEAKED_SCALE, frac)

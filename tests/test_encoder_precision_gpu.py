@@ -13,8 +13,9 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from tests import parity  # noqa: E402
+from tests import parity, split_parity  # noqa: E402
 from tests.parity import one_minus_cos  # noqa: E402
+from tests.split_parity import EDGE_LENS  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
@@ -40,17 +41,7 @@ def sens_weights(std, outlier=1.0):
     if key not in _CACHE:
         sd = dict(synth.ance_state_dict(0x0D17, 12, layer_matrix_std=std))
         if outlier != 1.0:
-            dims = [7, 300, 701]
-            g = sd["roberta.embeddings.LayerNorm.weight"].copy()
-            g[dims] *= outlier
-            sd["roberta.embeddings.LayerNorm.weight"] = g
-            for i in range(3):
-                for nm in ("attention.output.dense", "output.dense"):
-                    w = sd[f"roberta.encoder.layer.{i}.{nm}.weight"].copy()
-                    w[dims, :] *= outlier
-                    sd[f"roberta.encoder.layer.{i}.{nm}.weight"] = w
-                b = sd[f"roberta.encoder.layer.{i}.output.dense.bias"].copy()
-                sd[f"roberta.encoder.layer.{i}.output.dense.bias"] = (b + 3.0).astype(np.float32)
+            sd = split_parity.add_outlier_channels(sd, outlier)
         _CACHE[key] = sd
     return _CACHE[key]
 
@@ -258,42 +249,20 @@ LAYER_BOUNDS = {0.08: {"embed": 1.4e-7, "layer": 2.9e-5, "tail": 2.9e-5}, 0.12: 
 NOT_SEPARABLE = {(std, nl, st, n, m) for std in (0.08, 0.12) for nl, stages in ((1, [("tail", 0)]), (3, [("layer", 0), ("layer", 1), ("tail", 2)]))
                  for st, n in stages for m in (("eps", "head_eps") if st == "tail" else ("eps",))}
 NOT_SEPARABLE |= {(0.12, nl, st, n, "gelu_tanh") for nl, stages in ((1, [("tail", 0)]), (3, [("layer", 0), ("layer", 1), ("tail", 2)])) for st, n in stages}
-EDGE_LENS = [1, 31, 32, 33, 255, 256, 257, 512]
-
-
-def _rel(out, ref, valid=None):
-    out, ref = np.asarray(out, np.float64), np.asarray(ref, np.float64)
-    if valid is not None:
-        out, ref = out[valid], ref[valid]
-    return float(np.sqrt(((out - ref) ** 2).mean()) / np.sqrt((ref ** 2).mean()))
 
 
 def _teacher_forced(std, n_layers):
+    """(figures, separations of every mutation) of the EDGE_LENS batch: the loop is tests/split_parity.teacher_forced."""
     from haconvdr_amd import synth
     from haconvdr_amd.encoder import ANCEEncoder
     from oracle import ance_oracle
-    from tests.golden.make_golden_encoder import encoder_case_inputs
     key = ("tf", std, n_layers)
     if key in _CACHE:
         return _CACHE[key]
-    sd = synth.ance_state_dict(0x1A7E, n_layers, layer_matrix_std=std)
-    ids, mask = encoder_case_inputs(0x5EED, EDGE_LENS, 512)
+    sd = synth.ance_state_dict(split_parity.SEED, n_layers, layer_matrix_std=std)
+    ids, mask = split_parity.batch("edges")
     enc = ANCEEncoder.from_state_dict(sd, precision="split")
-    states = {n: enc.layer_state(ids, mask, n, normalized=True) for n in range(-1, n_layers - 1)}
-    assert "gemm=split128" in enc.last_plan() and "precision=split" in enc.last_plan(), enc.last_plan()
-    emb = enc(ids.astype(np.int32), mask.astype(np.int32))
-    valid = np.asarray(mask, bool)
-    figs, sep = {}, {}
-    figs[("embed", -1)] = _rel(states[-1]["norm"], ance_oracle.ance_embed(sd, ids, mask)["norm"].numpy(), valid)
-    for n in range(n_layers - 1):
-        base = ance_oracle.ance_layer(sd, n, states[n - 1], mask)["norm"].numpy()
-        figs[("layer", n)] = _rel(states[n]["norm"], base, valid)
-        for m in ance_oracle.LAYER_MUTATIONS:
-            sep[("layer", n, m)] = _rel(ance_oracle.ance_layer(sd, n, states[n - 1], mask, mutate=m)["norm"].numpy(), base, valid)
-    base = ance_oracle.ance_tail(sd, n_layers - 1, states[n_layers - 2], mask).numpy()
-    figs[("tail", n_layers - 1)] = _rel(emb, base)
-    for m in ance_oracle.TAIL_MUTATIONS:
-        sep[("tail", n_layers - 1, m)] = _rel(ance_oracle.ance_tail(sd, n_layers - 1, states[n_layers - 2], mask, mutate=m).numpy(), base)
+    figs, sep, _, _ = split_parity.teacher_forced(enc, sd, ids, mask, n_layers, ance_oracle.LAYER_MUTATIONS, ance_oracle.TAIL_MUTATIONS)
     _CACHE[key] = (figs, sep)
     return figs, sep
 
