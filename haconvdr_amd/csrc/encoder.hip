@@ -1282,6 +1282,77 @@ __global__ __launch_bounds__(256) void cls_head_norm_kernel(const float *__restr
     }
 }
 
+// pooling = mean (masked_mean_or_first with use_mean = True, src/models.py:57-61): the last layer ran on every row, and
+//   pooled[b] = (1 / len_b) sum_{t < len_b} ((y_t - mean_t) rstd_t gamma + beta)
+// over the packed rows as the next layer would have read them: y un-normalized (T = bf16 on gemm8, float on the classic and
+// split paths), their (mean, rstd), and the last layer's output LayerNorm.  Only rows t < len are touched: a dead row of the
+// sequence's 32-row padding would contribute beta, and its statistics are whatever the producer left.
+// One workgroup = one sequence x POOL_COLS columns (grid (B, 6): a lone sequence still spreads over six workgroups); a thread
+// owns one 16-byte piece of a row and walks rows rg, rg + RG, ... in order, the RG partial sums meet in LDS and are added in
+// the order rg = 0 .. RG - 1, then divided by len: fp32 throughout, an order fixed by (T, len) alone -- no atomics, nothing
+// that depends on the batch or on the grid.  A flagged sequence's rows are summed like any other (len <= L, its own rows
+// only); cls_head_norm_kernel overwrites its embedding with NaN.
+constexpr int POOL_COLS = 128;
+template <typename T>
+__global__ __launch_bounds__(256) void pool_mean_kernel(const T *__restrict__ y, const float2 *__restrict__ stats, const float *__restrict__ gamma,
+                                                        const float *__restrict__ beta, SeqInfo s, float *__restrict__ pooled) {
+    constexpr int V = 16 / sizeof(T);      // elements of a 16-byte load: 8 (bf16) or 4 (fp32)
+    constexpr int CL = POOL_COLS / V;      // threads across the column chunk: 16 or 32
+    constexpr int RG = 256 / CL;           // row groups: 16 or 8
+    __shared__ float red[RG][POOL_COLS];
+    const int b = blockIdx.x, c0 = blockIdx.y * POOL_COLS, tid = threadIdx.x;
+    const int cl = tid % CL, rg = tid / CL;
+    const int len = s.lens[b];
+    const size_t row0 = (size_t)s.off[b];
+    const int c = c0 + cl * V;
+    float g[V], bt[V], acc[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        g[i] = gamma[c + i];
+        bt[i] = beta[c + i];
+        acc[i] = 0.f;
+    }
+    typedef typename std::conditional<std::is_same<T, float>::value, f4v, bf16x8>::type vec16;
+    auto add_row = [&](const vec16 &a, const float2 st) {
+        // (every value pinned to a VGPR of its own: no packed-fp32 op_sel form may be built from the statistics pair, see the
+        // RESID epilogue of gemm_bf16_nt_kernel)
+        float mean = st.x, rstd = st.y;
+        asm volatile("" : "+v"(mean), "+v"(rstd));
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            float x = (float)a[i];
+            asm volatile("" : "+v"(x));
+            x = fmaf((x - mean) * rstd, g[i], bt[i]);
+            asm volatile("" : "+v"(x));
+            acc[i] += x;
+        }
+    };
+    const T *yc = y + row0 * H + c;
+    const float2 *sc = stats + row0;
+    int t = rg;
+    for (; t + 3 * RG < len; t += 4 * RG) {   // four rows' loads in flight, added in row order
+        vec16 a[4];
+        float2 st[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            a[u] = *reinterpret_cast<const vec16 *>(yc + (size_t)(t + u * RG) * H);
+            st[u] = sc[t + u * RG];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) add_row(a[u], st[u]);
+    }
+    for (; t < len; t += RG) add_row(*reinterpret_cast<const vec16 *>(yc + (size_t)t * H), sc[t]);
+#pragma unroll
+    for (int i = 0; i < V; ++i) red[rg][cl * V + i] = acc[i];
+    __syncthreads();
+    if (tid < POOL_COLS) {
+        float sum = 0.f;
+#pragma unroll
+        for (int r = 0; r < RG; ++r) sum += red[r][tid];
+        pooled[(size_t)b * H + c0 + tid] = len > 0 ? sum / (float)len : 0.f;   // (an empty mask is flagged: NaN row)
+    }
+}
+
 // Last layer, large-batch path: the query projection of the <s> rows only (the other rows' queries are never used: the
 // attention kernel runs the first query block of each sequence and only its row 0 is kept).  Same arithmetic as the QKV GEMM's
 // epilogue -- q = rstd (y . W'q^T - mean wsum) + cvec on the bf16 row y and the folded weights -- in fp32, written into row
@@ -1395,6 +1466,9 @@ struct hac_encoder {
     size_t idstats_rows = 0;
     int precision = 0;                    // 0: bf16 operands; 1: split (hi + lo pairs, three MFMAs per product: split.inc)
     bool split_weights = false;           // the lo twins of the weights exist
+    int pooling = 0;                      // 0: first (the <s> row, models.py:56); 1: mean (masked mean of the last layer's rows, models.py:57-61)
+    int plan_pooling = 0;                 // what the most recent forward ran
+    GrowBuf ws_pool;                      // pooling = mean: [2][B][768] fp32, the pooled rows | the head's projection
     GrowBuf ws_xb_lo, ws_q_lo, ws_k_lo, ws_vt_lo, ws_ctx_lo, ws_h_lo, ws_cls_lo;   // the lo twins of the activations an MFMA reads
     int attn_mode = 0;                    // 0: streaming single-pass attention; 1: two-pass kernels (cross-check)
     int attn_pipe = -1;                   // streaming attention of whole items (no query split, not the <s>-only layer): two query blocks per wave, woven (attn_pipe.inc); 0: the one-block kernel everywhere
@@ -1542,6 +1616,22 @@ struct LayerDump {
     float2 *stats;
     float *norm;
 };
+// pooling = mean, behind the last layer of every forward structure: the masked mean of its rows (pool_mean_kernel), then the
+// fp32 head on the B pooled rows.  ws_pool was reserved at the top of the forward (outside any capture).
+template <typename T>
+int pool_and_head(hac_encoder *e, const T *rows, const float2 *stats, const SeqInfo &s, int B, float *out_dev, hipStream_t st) {
+    const LayerW &w = e->layers[e->cfg.n_layers - 1];
+    float *pooled = (float *)e->ws_pool.p, *proj = pooled + (size_t)B * H;
+    HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_LN, st));
+    pool_mean_kernel<T><<<dim3((unsigned)B, H / POOL_COLS), dim3(256), 0, st>>>(rows, stats, w.ln2g, w.ln2b, s, pooled);
+    HAC_TRY(prof_end(e, 1 + HAC_ENC_CLASS_LN, st));
+    const int head_ns = B <= 64 ? 8 : CLS_NS;
+    cls_head_proj_kernel<<<dim3((unsigned)((B + CLS_SB - 1) / CLS_SB), H / head_ns), dim3(256), 0, st>>>(pooled, s, 1, B, e->wh, e->bh, proj, head_ns);
+    cls_head_norm_kernel<<<dim3((unsigned)B), dim3(256), 0, st>>>(proj, s, e->ng, e->nb, 1e-5f, out_dev);
+    HAC_HIP(hipGetLastError());
+    return HAC_OK;
+}
+
 // ---- precision = split (split.inc)
 // The lo twins of the classic family's packed weights (+1 x the bf16 weights in HBM), from the checkpoint's fp32 tensors: made by
 // the first forward that needs them, outside any capture, never by hac_encoder_finalize.
@@ -1602,6 +1692,8 @@ int run_forward_split(hac_encoder *e, const IT *ids, const IT *mask, int B, int 
     HAC_TRY(e->ws_vt_lo.reserve((size_t)H * Mp * 2));
     HAC_TRY(e->ws_ctx_lo.reserve((size_t)Mp * H * 2));
     HAC_TRY(e->ws_h_lo.reserve((size_t)Mp * FF * 2));
+    const bool mean = e->pooling == 1;   // every layer on every row, then pool_mean_kernel: no compact tail
+    if (mean) HAC_TRY(e->ws_pool.reserve((size_t)2 * B * H * 4));
     SeqInfo s;
     HAC_TRY(seq_layout(e, B, L, s));
     seq_prep_kernel<IT><<<dim3(B), dim3(512), 0, st>>>(ids, mask, L, s, c.pad_token_id, c.vocab);
@@ -1668,18 +1760,24 @@ int run_forward_split(hac_encoder *e, const IT *ids, const IT *mask, int B, int 
     HAC_TRY(prof_begin(e, 0, st));
     // compact buffers of the <s>-only tail of the last layer, and their twins
     const long Mc = ((long)B + MT - 1) / MT * MT;
-    HAC_TRY(e->ws_cls.reserve((size_t)Mc * (H * 2 + H * 4 * 3 + H * 2 + FF * 2)));
-    HAC_TRY(e->ws_cls_lo.reserve((size_t)Mc * (H * 2 + H * 2 + FF * 2)));
-    bf16 *ctx_c = (bf16 *)e->ws_cls.p;
-    float *x_c = (float *)(ctx_c + Mc * H);
-    float *y_c = x_c + Mc * H;
-    float *x2_c = y_c + Mc * H;
-    bf16 *xb_c = (bf16 *)(x2_c + Mc * H);
-    bf16 *h_c = xb_c + Mc * H;
-    bf16 *ctx_c_lo = (bf16 *)e->ws_cls_lo.p, *xb_c_lo = ctx_c_lo + Mc * H, *h_c_lo = xb_c_lo + Mc * H;
+    bf16 *ctx_c = nullptr, *xb_c = nullptr, *h_c = nullptr, *ctx_c_lo = nullptr, *xb_c_lo = nullptr, *h_c_lo = nullptr;
+    float *x_c = nullptr, *y_c = nullptr, *x2_c = nullptr;
+    if (!mean) {   // (pooling = mean has no last-layer special case: nothing reserved, no pointer formed)
+        HAC_TRY(e->ws_cls.reserve((size_t)Mc * (H * 2 + H * 4 * 3 + H * 2 + FF * 2)));
+        HAC_TRY(e->ws_cls_lo.reserve((size_t)Mc * (H * 2 + H * 2 + FF * 2)));
+        ctx_c = (bf16 *)e->ws_cls.p;
+        x_c = (float *)(ctx_c + Mc * H);
+        y_c = x_c + Mc * H;
+        x2_c = y_c + Mc * H;
+        xb_c = (bf16 *)(x2_c + Mc * H);
+        h_c = xb_c + Mc * H;
+        ctx_c_lo = (bf16 *)e->ws_cls_lo.p;
+        xb_c_lo = ctx_c_lo + Mc * H;
+        h_c_lo = xb_c_lo + Mc * H;
+    }
     for (int li = 0; li < c.n_layers; ++li) {
         const LayerW &w = e->layers[li];
-        const bool last = (li == c.n_layers - 1);
+        const bool last = !mean && (li == c.n_layers - 1);
         GemmSplitArgs ga{};
         GemmArgs &g = ga.g;
         g.total_rows = total;
@@ -1733,10 +1831,14 @@ int run_forward_split(hac_encoder *e, const IT *ids, const IT *mask, int B, int 
     }
 #undef HAC_GEMM_SPLIT
     HAC_TRY(prof_end(e, 0, st));
-    const int head_ns = B <= 64 ? 8 : CLS_NS;
-    cls_head_proj_kernel<<<dim3((unsigned)((B + CLS_SB - 1) / CLS_SB), H / head_ns), dim3(256), 0, st>>>(x_c, s, 1, B, e->wh, e->bh, y_c, head_ns);
-    cls_head_norm_kernel<<<dim3((unsigned)B), dim3(256), 0, st>>>(y_c, s, e->ng, e->nb, 1e-5f, out_dev);
-    HAC_HIP(hipGetLastError());
+    if (mean) {
+        HAC_TRY(pool_and_head<float>(e, x, statsF, s, B, out_dev, st));
+    } else {
+        const int head_ns = B <= 64 ? 8 : CLS_NS;
+        cls_head_proj_kernel<<<dim3((unsigned)((B + CLS_SB - 1) / CLS_SB), H / head_ns), dim3(256), 0, st>>>(x_c, s, 1, B, e->wh, e->bh, y_c, head_ns);
+        cls_head_norm_kernel<<<dim3((unsigned)B), dim3(256), 0, st>>>(y_c, s, e->ng, e->nb, 1e-5f, out_dev);
+        HAC_HIP(hipGetLastError());
+    }
     e->plan_sub_batches += 1;
     e->plan_rows += Mp;
     e->plan_gemm = "split128";
@@ -1780,6 +1882,8 @@ int run_forward(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, flo
     HAC_TRY(e->ws_vt.reserve((size_t)H * Mp * 2));
     HAC_TRY(e->ws_ctx.reserve((size_t)Mp * H * 2));
     HAC_TRY(e->ws_h.reserve((size_t)Mp * FF * 2));
+    const bool mean = e->pooling == 1;   // every layer on every row, then pool_mean_kernel: no compact tail
+    if (mean) HAC_TRY(e->ws_pool.reserve((size_t)2 * B * H * 4));
     SeqInfo s;
     HAC_TRY(seq_layout(e, B, L, s));
     seq_prep_kernel<IT><<<dim3(B), dim3(512), 0, st>>>(ids, mask, L, s, c.pad_token_id, c.vocab);
@@ -1887,16 +1991,20 @@ int run_forward(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, flo
     HAC_TRY(prof_begin(e, 0, st));
     // compact buffers of the CLS-only tail of the last layer
     const long Mc = ((long)B + MT - 1) / MT * MT;
-    HAC_TRY(e->ws_cls.reserve((size_t)Mc * (H * 2 + H * 4 * 3 + H * 2 + FF * 2)));
-    bf16 *ctx_c = (bf16 *)e->ws_cls.p;
-    float *x_c = (float *)(ctx_c + Mc * H);
-    float *y_c = x_c + Mc * H;
-    float *x2_c = y_c + Mc * H;
-    bf16 *xb_c = (bf16 *)(x2_c + Mc * H);
-    bf16 *h_c = xb_c + Mc * H;
+    bf16 *ctx_c = nullptr, *xb_c = nullptr, *h_c = nullptr;
+    float *x_c = nullptr, *y_c = nullptr, *x2_c = nullptr;
+    if (!mean) {   // (pooling = mean has no last-layer special case: nothing reserved, no pointer formed)
+        HAC_TRY(e->ws_cls.reserve((size_t)Mc * (H * 2 + H * 4 * 3 + H * 2 + FF * 2)));
+        ctx_c = (bf16 *)e->ws_cls.p;
+        x_c = (float *)(ctx_c + Mc * H);
+        y_c = x_c + Mc * H;
+        x2_c = y_c + Mc * H;
+        xb_c = (bf16 *)(x2_c + Mc * H);
+        h_c = xb_c + Mc * H;
+    }
     for (int li = 0; li < c.n_layers; ++li) {
         const LayerW &w = e->layers[li];
-        const bool last = (li == c.n_layers - 1);
+        const bool last = !mean && (li == c.n_layers - 1);
         GemmArgs g{};
         g.total_rows = total;
         Gemm8Args g8a{};
@@ -2070,11 +2178,17 @@ int run_forward(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, flo
     }
 #undef HAC_GEMM
     HAC_TRY(prof_end(e, 0, st));
-    // ANCE head on the compact <s> rows: projection (y_c is free again), then LayerNorm_768 and the per-sequence error flag
-    const int head_ns = B <= 64 ? 8 : CLS_NS;
-    cls_head_proj_kernel<<<dim3((unsigned)((B + CLS_SB - 1) / CLS_SB), H / head_ns), dim3(256), 0, st>>>(x_c, s, 1, B, e->wh, e->bh, y_c, head_ns);
-    cls_head_norm_kernel<<<dim3((unsigned)B), dim3(256), 0, st>>>(y_c, s, e->ng, e->nb, 1e-5f, out_dev);
-    HAC_HIP(hipGetLastError());
+    if (mean) {
+        // the stream after the last layer: un-normalized rows (gemm8: bf16 in xb; classic: fp32 in x) + statsF, as a next layer would read them
+        if (g8) HAC_TRY(pool_and_head<bf16>(e, xb, statsF, s, B, out_dev, st));
+        else HAC_TRY(pool_and_head<float>(e, x, statsF, s, B, out_dev, st));
+    } else {
+        // ANCE head on the compact <s> rows: projection (y_c is free again), then LayerNorm_768 and the per-sequence error flag
+        const int head_ns = B <= 64 ? 8 : CLS_NS;
+        cls_head_proj_kernel<<<dim3((unsigned)((B + CLS_SB - 1) / CLS_SB), H / head_ns), dim3(256), 0, st>>>(x_c, s, 1, B, e->wh, e->bh, y_c, head_ns);
+        cls_head_norm_kernel<<<dim3((unsigned)B), dim3(256), 0, st>>>(y_c, s, e->ng, e->nb, 1e-5f, out_dev);
+        HAC_HIP(hipGetLastError());
+    }
     if (e->plan_attn_pipe && e->attn_pipe < 0 && !e->redo_pending) {
         if (!fw_capturing) {
             if (!e->h_redo) HAC_HIP(hipHostMalloc((void **)&e->h_redo, 64, hipHostMallocDefault));
@@ -2097,7 +2211,7 @@ uint64_t ws_signature(const hac_encoder *e) {
     uint64_t h = 1469598103934665603ull;
     for (const GrowBuf *b : {&e->ws_x, &e->ws_xb, &e->ws_q, &e->ws_k, &e->ws_vt, &e->ws_ctx, &e->ws_y, &e->ws_h, &e->ws_seq, &e->ws_cls, &e->ws_stats,
                              &e->ws_yb, &e->ws_part, &e->ws_idstats, &e->ws_gids, &e->ws_gmask, &e->ws_gout, &e->ws_ksplit, &e->ws_redo,
-                             &e->ws_xb_lo, &e->ws_q_lo, &e->ws_k_lo, &e->ws_vt_lo, &e->ws_ctx_lo, &e->ws_h_lo, &e->ws_cls_lo})
+                             &e->ws_xb_lo, &e->ws_q_lo, &e->ws_k_lo, &e->ws_vt_lo, &e->ws_ctx_lo, &e->ws_h_lo, &e->ws_cls_lo, &e->ws_pool})
         h = (h ^ (uint64_t)(uintptr_t)b->p) * 1099511628211ull;
     return h;
 }
@@ -2134,7 +2248,7 @@ int forward_graph(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, f
     const uint64_t key = ((uint64_t)B << 40) | ((uint64_t)L << 24) | ((uint64_t)sizeof(IT) << 16) | ((uint64_t)(e->attn_mode & 1) << 8) |
                          ((uint64_t)((e->gemm_mode + 1) & 3) << 4) | ((uint64_t)(e->ksplit_mode & 1) << 12) |
                          ((uint64_t)(e->attn_qsplit & 1) << 13) | ((uint64_t)(e->g8_stagger & 1) << 14) | ((uint64_t)((e->attn_pipe + 1) & 3) << 15) |
-                         ((uint64_t)(e->precision & 1) << 20);
+                         ((uint64_t)(e->precision & 1) << 20) | ((uint64_t)(e->pooling & 1) << 21);
     // (a caller that pads every batch to its own longest sequence can show hundreds of shapes: the cache is bounded, and starting
     // over costs each live shape one plain forward and one capture)
     if (e->graphs.size() >= GRAPH_MAX_SHAPES && e->graphs.find(key) == e->graphs.end()) drop_graphs(e);
@@ -2203,6 +2317,7 @@ int forward_batched(hac_encoder *e, const IT *ids, const IT *mask, int B, int L,
     e->plan_rows = 0;
     e->plan_graph = "off";
     e->plan_precision = e->precision;
+    e->plan_pooling = e->pooling;
     if (e->precision == 1) HAC_TRY(ensure_split_weights(e));
     if (graph_eligible(e, B, L, st)) return forward_graph<IT>(e, ids, mask, B, L, out_dev, st);
     if ((long)B * L32 <= e->max_tokens) return run_forward<IT>(e, ids, mask, B, L, out_dev, st);
@@ -2328,7 +2443,7 @@ void hac_encoder_destroy(hac_encoder *e) {
     if (e->h_redo) (void)hipHostFree(e->h_redo);
     for (GrowBuf *b : {&e->ws_x, &e->ws_xb, &e->ws_q, &e->ws_k, &e->ws_vt, &e->ws_ctx, &e->ws_y, &e->ws_h, &e->ws_seq, &e->ws_ids, &e->ws_mask, &e->ws_out, &e->ws_cls, &e->ws_stats, &e->ws_yb, &e->ws_part, &e->ws_idstats,
                        &e->ws_gids, &e->ws_gmask, &e->ws_gout, &e->ws_ksplit, &e->ws_identgb, &e->ws_clk, &e->ws_redo, &e->ws_dump,
-                       &e->ws_xb_lo, &e->ws_q_lo, &e->ws_k_lo, &e->ws_vt_lo, &e->ws_ctx_lo, &e->ws_h_lo, &e->ws_cls_lo})
+                       &e->ws_xb_lo, &e->ws_q_lo, &e->ws_k_lo, &e->ws_vt_lo, &e->ws_ctx_lo, &e->ws_h_lo, &e->ws_cls_lo, &e->ws_pool})
         b->release();
     if (e->h_pin) (void)hipHostFree(e->h_pin);
     if (e->h_len) (void)hipHostFree(e->h_len);
@@ -2488,7 +2603,10 @@ int hac_encoder_layer_state(hac_encoder *e, const int32_t *ids, const int32_t *m
     if (!e->finalized) return fail(HAC_ERR_INVALID, "encoder weights not finalized (hac_encoder_finalize)");
     if (B < 1 || L < 1 || L > 512 || L + 2 > e->cfg.max_pos || !ids || !mask || !rows_out || !stats_out)
         return fail(HAC_ERR_INVALID, "layer_state: bad arguments (B=%d, L=%d)", B, L);
-    if (layer < -1 || layer > e->cfg.n_layers - 2)
+    // (pooling = mean runs the last layer on every row: its state exists and means what every other layer's does)
+    if (e->pooling == 1 && (layer < -1 || layer > e->cfg.n_layers - 1))
+        return fail(HAC_ERR_INVALID, "layer_state: layer %d outside [-1, %d]", layer, e->cfg.n_layers - 1);
+    if (e->pooling == 0 && (layer < -1 || layer > e->cfg.n_layers - 2))
         return fail(HAC_ERR_INVALID, "layer_state: layer %d outside [-1, %d] (the last layer continues the <s> rows only)", layer, e->cfg.n_layers - 2);
     const int L32 = (L + SEQ_ALIGN - 1) / SEQ_ALIGN * SEQ_ALIGN;
     if ((long)B * L32 > e->max_tokens) return fail(HAC_ERR_INVALID, "layer_state: %d x %d rows exceed one pass (max_tokens %ld)", B, L32, e->max_tokens);
@@ -2516,6 +2634,7 @@ int hac_encoder_layer_state(hac_encoder *e, const int32_t *ids, const int32_t *m
     e->plan_rows = 0;
     e->plan_graph = "off";   // never captured: plain launches of the forward's own kernels
     e->plan_precision = e->precision;
+    e->plan_pooling = e->pooling;
     if (e->precision == 1) HAC_TRY(ensure_split_weights(e));
     const LayerDump dump{layer, d_rows, d_stats, norm_out ? d_norm : nullptr};
     HAC_TRY(run_forward<int>(e, (const int *)e->ws_ids.p, (const int *)e->ws_mask.p, B, L, nullptr, e->stream, 0, -1, 0, &dump));
@@ -2537,6 +2656,9 @@ int hac_encoder_set_option(hac_encoder *e, const char *name, const char *value) 
     } else if (n == "precision") {
         if (v != "bf16" && v != "split") return fail(HAC_ERR_INVALID, "encoder option precision = '%s': bf16 | split", value);
         e->precision = v == "split" ? 1 : 0;
+    } else if (n == "pooling") {
+        if (v != "first" && v != "mean") return fail(HAC_ERR_INVALID, "encoder option pooling = '%s': first | mean", value);
+        e->pooling = v == "mean" ? 1 : 0;
     } else if (n == "attn") {
         if (v != "stream" && v != "twopass") return fail(HAC_ERR_INVALID, "encoder option attn = '%s': stream | twopass", value);
         e->attn_mode = v == "twopass" ? 1 : 0;
@@ -2579,9 +2701,9 @@ int hac_encoder_set_option(hac_encoder *e, const char *name, const char *value) 
 const char *hac_encoder_last_plan(hac_encoder *e) {
     if (!e) return "none";
     const bool split = e->plan_precision == 1;   // (what the most recent forward ran, not what the option says now)
-    snprintf(e->last_plan, sizeof e->last_plan, "gemm=%s attn=%s sub_batches=%d rows=%ld graph=%s ksplit=%d/%d attn_form=%s%s", e->plan_gemm, e->attn_mode ? "twopass" : "stream",
+    snprintf(e->last_plan, sizeof e->last_plan, "gemm=%s attn=%s sub_batches=%d rows=%ld graph=%s ksplit=%d/%d attn_form=%s%s%s", e->plan_gemm, e->attn_mode ? "twopass" : "stream",
              e->plan_sub_batches, e->plan_rows, e->plan_graph, e->plan_ks_out, e->plan_ks_down,
-             split ? "split" : (e->attn_mode ? "twopass" : (e->plan_attn_pipe ? "woven" : "single")), split ? " precision=split" : "");
+             split ? "split" : (e->attn_mode ? "twopass" : (e->plan_attn_pipe ? "woven" : "single")), split ? " precision=split" : "", e->plan_pooling == 1 ? " pool=mean" : "");
     return e->last_plan;
 }
 

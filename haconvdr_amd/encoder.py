@@ -26,7 +26,8 @@ def split_bf16(x):
 
 
 class ANCEEncoder:
-    def __init__(self, n_layers=12, vocab=50265, max_pos=514, type_vocab=1, pad_token_id=1, ln_eps=1e-5, device=0, precision="bf16"):
+    def __init__(self, n_layers=12, vocab=50265, max_pos=514, type_vocab=1, pad_token_id=1, ln_eps=1e-5, device=0, precision="bf16",
+                 pooling="first"):
         self.device = int(device)
         self.n_layers = int(n_layers)
         cfg = _lib.EncoderConfig(self.n_layers, 768, 12, 3072, int(vocab), int(max_pos), int(type_vocab), int(pad_token_id), float(ln_eps))
@@ -34,6 +35,9 @@ class ANCEEncoder:
         _lib.check(_lib.lib().hac_encoder_create(ctypes.byref(cfg), self.device, ctypes.byref(self._h)))
         if precision != "bf16":     # "split": hi + lo bf16 operand pairs, three MFMAs per product (include/haconvdr.h, "precision")
             self.set_option("precision", precision)
+        self._pooling = "first"
+        if pooling != "first":      # "mean": the reference's use_mean = True (src/models.py:52-61), see the use_mean property
+            self.set_option("pooling", pooling)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -65,7 +69,7 @@ class ANCEEncoder:
         return cls(n_layers=n_layers, vocab=vocab, max_pos=max_pos, type_vocab=tv, device=device, **kw).load_state_dict(sd)
 
     @classmethod
-    def from_pretrained(cls, path, device=0, precision="bf16"):
+    def from_pretrained(cls, path, device=0, precision="bf16", pooling="first"):
         """Checkpoint directory as ``ANCE.from_pretrained(model_path, config=RobertaConfig.from_pretrained(model_path))``
         reads it (src/models.py:113-122): ``config.json`` + ``pytorch_model.bin`` or ``model.safetensors``.
 
@@ -103,7 +107,7 @@ class ANCEEncoder:
             if cfg.get("position_embedding_type", "absolute") != "absolute":
                 raise ValueError(f"{cfg_path}: position_embedding_type = {cfg['position_embedding_type']!r} is not supported")
             kw = {"ln_eps": float(cfg.get("layer_norm_eps", 1e-5)), "pad_token_id": int(cfg.get("pad_token_id", 1))}
-        return cls.from_state_dict(sd, device=device, precision=precision, **kw)
+        return cls.from_state_dict(sd, device=device, precision=precision, pooling=pooling, **kw)
 
     # ---- forward -----------------------------------------------------------
     def __call__(self, input_ids, attention_mask, wrap_pooler=False):
@@ -134,7 +138,7 @@ class ANCEEncoder:
 
     def layer_state(self, input_ids, attention_mask, layer, normalized=False):
         """Test aid (hac_encoder_layer_state): the residual stream after encoder layer ``layer`` (-1: the embedding LayerNorm,
-        at most n_layers - 2), from the same kernels a forward of this batch runs.  Returns a dict of numpy arrays over
+        at most n_layers - 2; with pooling = "mean" the last layer too, n_layers - 1), from the same kernels a forward of this batch runs.  Returns a dict of numpy arrays over
         [B, L] (rows t >= len are zeros): ``rows`` float32 [B, L, 768], the pre-LayerNorm rows as stored (fp32 on the classic
         path, bf16 values on gemm8); ``mean``, ``rstd`` float32 [B, L]; with ``normalized`` also ``norm`` [B, L, 768], the
         normalized rows the next layer's residual add forms."""
@@ -162,10 +166,23 @@ class ANCEEncoder:
     def set_option(self, name, value):
         """Tuning / test switch of this handle (include/haconvdr.h: hac_encoder_set_option), e.g. ("gemm", "classic")."""
         _lib.check(_lib.lib().hac_encoder_set_option(self._h, str(name).encode(), str(value).encode()))
+        if str(name) == "pooling":
+            self._pooling = str(value)
+
+    @property
+    def use_mean(self):
+        """The reference class's public switch (src/models.py:30, :52-61): False, the default, pools the <s> row
+        (``emb_all[:, 0]``); True the masked mean of the last layer's rows over each sequence's attended tokens.  Setting it is
+        ``set_option("pooling", "mean" | "first")``: the kernels run the last layer on every row in mean mode."""
+        return self._pooling == "mean"
+
+    @use_mean.setter
+    def use_mean(self, value):
+        self.set_option("pooling", "mean" if value else "first")
 
     def last_plan(self):
         """Kernel families of the most recent forward: "gemm=gemm8|classic256|classic128|split128 attn=... sub_batches=N rows=R ...",
-        with " precision=split" appended when it ran in split mode."""
+        with " precision=split" appended when it ran in split mode and " pool=mean" when it pooled the masked mean."""
         return _lib.lib().hac_encoder_last_plan(self._h).decode()
 
     KERNEL_CLASSES = ("qkv", "attention", "out_proj", "ffn_up", "ffn_down", "layernorm")   # HAC_ENC_CLASS_* of include/haconvdr.h

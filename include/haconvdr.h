@@ -262,10 +262,23 @@ int hac_encoder_forward_device(hac_encoder *enc, const void *ids_dev, const void
  * several times the bf16 forward's time ("Precision") -- plus one more copy of the bf16 layer weights and
  * of the bf16 activation workspaces in HBM, allocated by the first forward that runs in the mode, not by hac_encoder_finalize.
  * Use it for a checkpoint whose embeddings differ between the two modes by more than a small fraction of 1e-3 in 1-cos
- * (INTEGRATION.md).  Switching back to "bf16" restores the default path bit for bit. */
+ * (INTEGRATION.md).  Switching back to "bf16" restores the default path bit for bit.
+ *
+ * "pooling" = "first" (default) | "mean": the two arms of the reference's masked_mean_or_first (src/models.py:52-61).  "first"
+ * is use_mean = False, emb_all[:, 0]: the last layer computes keys and values of every row but everything else for the <s>
+ * rows only.  "mean" is use_mean = True, sum(t * mask) / sum(mask) over each sequence's attended tokens: the last layer runs on
+ * every row like the others (full QKV, full attention, out-projection, FFN, statistics) in all three forward structures (gemm8,
+ * classic, "precision" = "split"), pool_mean_kernel then averages the len valid rows of each sequence under the last layer's
+ * output LayerNorm in fp32, in an order fixed by the sequence's length alone (deterministic: eager launches, capture and replay
+ * and any batch around the sequence give the same bits), and the fp32 head follows unchanged.  Cost: the last layer's full
+ * price instead of a third of its QKV GEMM plus a B-row tail, about one layer in n_layers more per forward, and one pass over
+ * the last layer's rows ("Pooling").  Family choice, "ksplit", "graph" (the mode is part of a captured
+ * shape's key), "max_tokens" and the profiling classes work as in "first" (the pool kernel counts in HAC_ENC_CLASS_LN);
+ * hac_encoder_last_plan appends " pool=mean"; hac_encoder_layer_state accepts the last layer, n_layers - 1, in this mode only.
+ * A sequence the device flags is a NaN row in either mode.  Switching back to "first" restores the default path bit for bit. */
 int hac_encoder_set_option(hac_encoder *enc, const char *name, const char *value);
 /* What the most recent forward ran: "gemm=gemm8|classic256|classic128 attn=stream|twopass sub_batches=N rows=R graph=off|eager-first|replay ksplit=S_out/S_down attn_form=woven|single|twopass"
- * (tests and bench.py assert the kernel family they mean to check).  The GEMM family and, with the classic kernels, the tile
+ * (+ " precision=split" and / or " pool=mean" when the forward ran in those modes; tests and bench.py assert the kernel family they mean to check).  The GEMM family and, with the classic kernels, the tile
  * size are chosen once per call, from the rows of the whole batch: every sub-batch runs the same kernels. */
 const char *hac_encoder_last_plan(hac_encoder *enc);
 
@@ -280,7 +293,7 @@ enum {
     HAC_ENC_CLASS_OUTPROJ = 2,   /* <EPI8_RESID | EPI_RESID>: [T,768] x [768,768]^T + bias + residual (+ LayerNorm statistics) */
     HAC_ENC_CLASS_FFN_UP = 3,    /* <EPI8_GELU | EPI_GELU>:   [T,768] x [3072,768]^T (+ folded LayerNorm) + bias + erf GELU */
     HAC_ENC_CLASS_FFN_DOWN = 4,  /* <EPI8_RESID | EPI_RESID>: [T,3072] x [768,3072]^T + bias + residual (+ LayerNorm statistics) */
-    HAC_ENC_CLASS_LN = 5,        /* LayerNorm passes that are their own kernel (ln_combine_kernel / ln_stats_rows_kernel) */
+    HAC_ENC_CLASS_LN = 5,        /* LayerNorm passes that are their own kernel (ln_combine_kernel / ln_stats_rows_kernel; "pooling" = "mean": pool_mean_kernel too) */
     HAC_ENC_NCLASS = 6
 };
 int hac_encoder_set_profiling(hac_encoder *enc, int mask);
@@ -300,7 +313,8 @@ int hac_encoder_last_clock(hac_encoder *enc, uint64_t out[2]);
  * kernel, whose outputs the woven kernel's equal bit for bit wherever it does not flag. */
 int hac_encoder_attention_redo(hac_encoder *enc, long long *items_out);
 /* Test entry point: the residual stream after encoder layer `layer` (-1: the embedding LayerNorm; at most n_layers - 2, the last
- * layer continues the <s> rows only).  Runs the launches of a forward of (ids, mask) -- same routing, options and workspaces,
+ * layer continues the <s> rows only -- except with "pooling" = "mean", where the last layer, n_layers - 1, is a layer like the
+ * others and its state is what pool_mean_kernel reads).  Runs the launches of a forward of (ids, mask) -- same routing, options and workspaces,
  * never captured into a graph -- up to that layer, then unpacks every valid row t < len of sequence b to index b * L + t:
  *   rows_out  float32 [B][L][768]: the rows as stored, BEFORE that layer's output LayerNorm (the classic kernels keep them in
  *             fp32, the large-batch gemm8 path in bf16; layer -1: the normalized embedding rows);
