@@ -64,7 +64,10 @@ typedef struct hac_index hac_index;
 
 /* faiss.IndexFlatIP(d) [+ index_cpu_to_gpu_multiple(shard=True)]:
  * src/test_HAConvDR_topiocqa.py:52,55-66.  d must be a multiple of 32, <= HAC_MAX_D
- * (the reference fixes d = 768).  device_ids[0..n_dev) are HIP ordinals; with
+ * (the reference fixes d = 768).  A d with d % 64 == 32 (32, 96, ..., 992) always takes
+ * scan16_kernel, at every query count, and never the half-precision prefilter (both the
+ * many-query kernel and the prefilter stage the queries in whole 64-element slices); results
+ * are the same bits, only slower for many queries.  device_ids[0..n_dev) are HIP ordinals; with
  * n_dev > 1 the rows of every add() are split contiguously across the devices and
  * search() merges the per-device top-k (faiss IndexShards semantics; the devices are
  * searched concurrently, one host thread per device, rows stay numbered by insertion
