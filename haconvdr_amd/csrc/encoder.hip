@@ -1436,6 +1436,8 @@ using namespace hac;
 
 namespace {
 
+inline int pad_len(int L) { return (L + SEQ_ALIGN - 1) / SEQ_ALIGN * SEQ_ALIGN; }   // rows a sequence of L tokens occupies
+
 struct LayerW {
     bf16 *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr;
     float *bqkv = nullptr, *bo = nullptr, *b1 = nullptr, *b2 = nullptr;
@@ -1445,6 +1447,22 @@ struct LayerW {
     float *fold = nullptr;                      // wsum_qkv[2304] | cvec_qkv[2304] | wsum_1[3072] | cvec_1[3072]
     // precision = split (split.inc): the lo twins of the classic family's weights, made by the first forward that needs them
     bf16 *wqkv_lo = nullptr, *wo_lo = nullptr, *w1_lo = nullptr, *w2_lo = nullptr;
+};
+// (bo, b1, b2 and the LayerNorm affines point into hac_encoder::raw: not owned)
+void free_layer(LayerW &l) {
+    for (void *p : std::initializer_list<void *>{l.wqkv, l.wo, l.w1, l.w2, l.wqkv8, l.w18, l.wqkv_lo, l.wo_lo, l.w1_lo, l.w2_lo, l.bqkv, l.fold})
+        if (p) (void)hipFree(p);
+    l = LayerW();
+}
+// what the most recent forward ran (hac_encoder_last_plan)
+struct Plan {
+    const char *gemm = "none";
+    int sub_batches = 0;
+    long rows = 0;
+    const char *graph = "off";
+    int precision = 0, pooling = 0;
+    int ks_out = 1, ks_down = 1;
+    int attn_pipe = 0;                    // the layers used the woven attention form
 };
 
 }  // namespace
@@ -1467,12 +1485,10 @@ struct hac_encoder {
     int precision = 0;                    // 0: bf16 operands; 1: split (hi + lo pairs, three MFMAs per product: split.inc)
     bool split_weights = false;           // the lo twins of the weights exist
     int pooling = 0;                      // 0: first (the <s> row, models.py:56); 1: mean (masked mean of the last layer's rows, models.py:57-61)
-    int plan_pooling = 0;                 // what the most recent forward ran
     GrowBuf ws_pool;                      // pooling = mean: [2][B][768] fp32, the pooled rows | the head's projection
     GrowBuf ws_xb_lo, ws_q_lo, ws_k_lo, ws_vt_lo, ws_ctx_lo, ws_h_lo, ws_cls_lo;   // the lo twins of the activations an MFMA reads
     int attn_mode = 0;                    // 0: streaming single-pass attention; 1: two-pass kernels (cross-check)
     int attn_pipe = -1;                   // streaming attention of whole items (no query split, not the <s>-only layer): two query blocks per wave, woven (attn_pipe.inc); 0: the one-block kernel everywhere
-    int plan_attn_pipe = 0;               // what the most recent forward's layers used
     int gemm_mode = -1;                   // -1: by size, 0: classic kernels only, 1: gemm8 whenever the batch has a full tile (tests)
     int attn_qsplit = -1;  // -1 auto (small batches: query rows of an item dealt to 2 or 4 workgroups), 0 off
     int g8_stagger = -1;   // -1 auto (phased workgroup starts of the K = 768 RESID / QKV classes on long tile runs), 0 off
@@ -1490,12 +1506,7 @@ struct hac_encoder {
     long max_tokens = 524288;  // packed rows per sub-batch (workspaces: ~9 GB).  1000 x 512 then runs as ONE pass: no host read-back of the
                                // lengths at all, -0.6 % against two passes of 262144 with round 3's kernels (196608: +0.9 %)
     int n_cu = 256;
-    // what the most recent forward ran (hac_encoder_last_plan)
-    const char *plan_gemm = "none";
-    int plan_sub_batches = 0;
-    long plan_rows = 0;
-    const char *plan_graph = "off";
-    int plan_precision = 0;
+    Plan plan;
     char last_plan[160] = "none";
     // Small batches (the reference's own call shape is 4 queries per GPU, test_HAConvDR_topiocqa.py:173,406) are bound by
     // launches, not arithmetic: ~110 kernels for ~0.4 TFLOP.  Their forward is captured ONCE per (B, L, options) into a HIP
@@ -1504,16 +1515,12 @@ struct hac_encoder {
     int attn_qs_pin = 0;                  // development ("attn_qs_pin" = 1 | 2 | 4 | 8 | 16; 0: by the rule)
     int ks_pin_out = 0, ks_pin_down = 0;  // development ("ksplit_pin" = "a/b"): the slices of out-proj / FFN-down pinned (0: by the model)
     int ksplit_mode = -1;                 // -1: split-K of the small-batch RESID GEMMs by tile count, 0: never (tests that compare batches of different sizes bit for bit)
-    int plan_ks_out = 1, plan_ks_down = 1;
     struct GraphEntry {
         hipGraph_t graph = nullptr;
         hipGraphExec_t exec = nullptr;
         uint64_t sig = 0;                 // digest of every workspace pointer the captured launches hold
         int seen = 0;                     // eager passes so far (the first call sizes the workspaces)
-        const char *gemm = "none";
-        long rows = 0;
-        int ks_out = 1, ks_down = 1;      // the plan of the captured forward (a replay runs no host-side planning)
-        int attn_pipe = 0;
+        Plan plan;                        // of the captured forward (a replay runs no host-side planning)
     };
     std::map<uint64_t, GraphEntry> graphs;
     hipEvent_t graph_done = nullptr;      // recorded behind every replay on the caller's stream: an exec is destroyed only after it
@@ -1575,6 +1582,13 @@ int prof_end(hac_encoder *e, int pool, hipStream_t st) {
     ++pl.used;
     return HAC_OK;
 }
+// a launch between the events of its kernel class
+#define HAC_PROFILED(E, ST, CLS, ...)               \
+    do {                                            \
+        HAC_TRY(prof_begin(E, 1 + (CLS), ST));      \
+        __VA_ARGS__;                                \
+        HAC_TRY(prof_end(E, 1 + (CLS), ST));        \
+    } while (0)
 
 // carve the sequence bookkeeping of a (sub-)batch out of ws_seq
 int seq_layout(hac_encoder *e, int B, int L, SeqInfo &s) {
@@ -1594,15 +1608,20 @@ int seq_layout(hac_encoder *e, int B, int L, SeqInfo &s) {
     return HAC_OK;
 }
 
-// rows_hint: an upper bound of the packed rows of this sub-batch when the caller knows one (sum of its
-// sequences' padded lengths), 0 = every sequence may be full length
-// family: the GEMM family of the whole hac_encoder_forward* call -- FAM_CLASSIC128 / FAM_CLASSIC256 / FAM_GEMM8 -- or -1:
-// decide here, from this (only) sub-batch's rows
-enum { FAM_CLASSIC128 = 0, FAM_GEMM8 = 1, FAM_CLASSIC256 = 2 };
+// the GEMM family of a hac_encoder_forward* call
+enum { FAM_CLASSIC128 = 0, FAM_GEMM8 = 1, FAM_CLASSIC256 = 2, FAM_SPLIT = 3 };
 // 256^2 tiles (gemm8's folded-LayerNorm, bf16-residual path) from this many out-proj tiles on: 9472 rows.  Measured at L = 512
 // (tools/ab_option.py gemm classic 8phase): 16 x 512 classic 2.58 ms against 2.68, 20 x 512 2.91 against 2.75, 24 x 512 3.83 / 3.26.
 constexpr long FAMILY_BIG_TILES = 111;
+// "gemm" option / HAC_ENC_GEMM: auto | classic | 8phase -> hac_encoder::gemm_mode; false (mode untouched): none of them
+bool parse_gemm_mode(const char *v, int *mode) {
+    const std::string s(v);
+    if (s != "auto" && s != "classic" && s != "8phase") return false;
+    *mode = s == "classic" ? 0 : (s == "8phase" ? 1 : -1);
+    return true;
+}
 int pick_family(const hac_encoder *e, long rows) {
+    if (e->precision == 1) return FAM_SPLIT;
     const long Mp = (rows + MT - 1) / MT * MT;
     const bool big = (Mp / 256) * (H / 256) >= FAMILY_BIG_TILES;
     if (e->gemm_mode == 1 || (e->gemm_mode < 0 && big)) return FAM_GEMM8;
@@ -1616,20 +1635,22 @@ struct LayerDump {
     float2 *stats;
     float *norm;
 };
-// pooling = mean, behind the last layer of every forward structure: the masked mean of its rows (pool_mean_kernel), then the
+// the fp32 ANCE head on B rows: projection, then LayerNorm_768 and the per-sequence error flag
+int launch_head(hac_encoder *e, const float *rows, float *proj, const SeqInfo &s, int B, float *out_dev, hipStream_t st) {
+    const int head_ns = B <= 64 ? 8 : CLS_NS;
+    cls_head_proj_kernel<<<dim3((unsigned)((B + CLS_SB - 1) / CLS_SB), H / head_ns), dim3(256), 0, st>>>(rows, s, 1, B, e->wh, e->bh, proj, head_ns);
+    cls_head_norm_kernel<<<dim3((unsigned)B), dim3(256), 0, st>>>(proj, s, e->ng, e->nb, 1e-5f, out_dev);
+    HAC_HIP(hipGetLastError());
+    return HAC_OK;
+}
+// pooling = mean, behind the last layer of every family: the masked mean of its rows (pool_mean_kernel), then the
 // fp32 head on the B pooled rows.  ws_pool was reserved at the top of the forward (outside any capture).
 template <typename T>
 int pool_and_head(hac_encoder *e, const T *rows, const float2 *stats, const SeqInfo &s, int B, float *out_dev, hipStream_t st) {
     const LayerW &w = e->layers[e->cfg.n_layers - 1];
     float *pooled = (float *)e->ws_pool.p, *proj = pooled + (size_t)B * H;
-    HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_LN, st));
-    pool_mean_kernel<T><<<dim3((unsigned)B, H / POOL_COLS), dim3(256), 0, st>>>(rows, stats, w.ln2g, w.ln2b, s, pooled);
-    HAC_TRY(prof_end(e, 1 + HAC_ENC_CLASS_LN, st));
-    const int head_ns = B <= 64 ? 8 : CLS_NS;
-    cls_head_proj_kernel<<<dim3((unsigned)((B + CLS_SB - 1) / CLS_SB), H / head_ns), dim3(256), 0, st>>>(pooled, s, 1, B, e->wh, e->bh, proj, head_ns);
-    cls_head_norm_kernel<<<dim3((unsigned)B), dim3(256), 0, st>>>(proj, s, e->ng, e->nb, 1e-5f, out_dev);
-    HAC_HIP(hipGetLastError());
-    return HAC_OK;
+    HAC_PROFILED(e, st, HAC_ENC_CLASS_LN, pool_mean_kernel<T><<<dim3((unsigned)B, H / POOL_COLS), dim3(256), 0, st>>>(rows, stats, w.ln2g, w.ln2b, s, pooled));
+    return launch_head(e, pooled, proj, s, B, out_dev, st);
 }
 
 // ---- precision = split (split.inc)
@@ -1665,199 +1686,497 @@ int ensure_split_weights(hac_encoder *e) {
     e->split_weights = true;
     return HAC_OK;
 }
+// the top of every hac_encoder_forward* / hac_encoder_layer_state call (the other plan fields are written by the forward itself)
+int begin_call(hac_encoder *e) {
+    e->plan.sub_batches = 0;
+    e->plan.rows = 0;
+    e->plan.graph = "off";
+    e->plan.precision = e->precision;
+    e->plan.pooling = e->pooling;
+    return e->precision == 1 ? ensure_split_weights(e) : HAC_OK;
+}
 
-// The forward in split mode: always the fp32-residual structure of the classic family, whatever the batch size and whatever
-// "gemm" says (embedding LN -> [QKV -> attention -> out-proj + residual -> LN statistics -> FFN-up -> FFN-down + residual -> LN
-// statistics] x (n - 1) -> the last layer on the <s> rows with the compact tail -> fp32 head); every bf16 tensor an MFMA reads
-// has its lo twin beside it.
-template <typename IT>
-int run_forward_split(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, float *out_dev, hipStream_t st, long rows_hint, long rows_plan,
-                      const LayerDump *dump) {
-    const hac_encoder_config &c = e->cfg;
-    const int L32 = (L + SEQ_ALIGN - 1) / SEQ_ALIGN * SEQ_ALIGN;
-    const long rows_max = rows_hint > 0 ? std::min<long>(rows_hint, (long)B * L32) : (long)B * L32;
-    const long Mp = (rows_max + MT - 1) / MT * MT;
+// ---- one forward of one (sub-)batch: the context every stage reads, a layer body per GEMM family, the skeleton (run_forward)
+struct Fwd {
+    int B, L, L32;
+    long Mp, Mc;                // packed rows / rows of the compact <s>-row tail, both padded to MT
+    SeqInfo s;
+    const int *total;           // device: packed rows in use
+    int family;                 // FAM_*
+    bool big, mean;             // 256^2 classic tiles; pooling = mean (every layer on every row, then pool_mean_kernel: no compact tail)
+    hipStream_t st;
+    float *x, *y;               // fp32 residual stream (gemm8 keeps it in xb alone)
+    float2 *statsA, *statsF;
+    bf16 *xb, *q, *k, *vt, *ctx, *h;
+    bf16 *xb_lo, *q_lo, *k_lo, *vt_lo, *ctx_lo, *h_lo;   // split: the lo twin of every bf16 tensor an MFMA reads (null otherwise)
+    bf16 *yAb;                  // gemm8: bf16 copy of the attention-block rows, row-sum partials, (0, 1) statistics
+    float2 *part, *idstats;
+    int ks_out, ks_down;        // split-K slices of out-proj / FFN-down and where slices 1.. go
+    float *kpart;
+    size_t part_stride;
+    bf16 *ctx_c, *xb_c, *h_c, *ctx_c_lo, *xb_c_lo, *h_c_lo;   // compact buffers of the <s>-only tail of the last layer (null with mean)
+    float *x_c, *y_c, *x2_c;
+};
+
+// Small batches (128^2 tiles): the two RESID GEMMs have only Mp / 128 x 6 output tiles -- 96 for the reference's 4 x 512 query
+// batch, on 256 CUs -- and walk their whole K behind one exposed load latency per k-tile, so their K loop is split into S
+// slices (GemmArgs::ksplit; ln_stats_rows_kernel adds the slices up).  How far: a slice more saves k-tiles at ~0.6 us each
+// and costs one more fp32 copy of the rows written and read back, ~1.3 us per 1000 rows; below 8 (K = 3072) / 4 (K = 768)
+// k-tiles per item nothing is gained, and more items than workgroup slots is a second round of them.  The minimum
+// of that model is within 0.3 % of the best of all 28 (S_out, S_down) pairs at 1 x 256, 4 x 256, 4 x 512, 8 x 384 and 8 x 512
+// (tools/ks_sweep.py on the whole forward, profiles/r05_ksplit_sweep.txt; tools/probes/gemm_small_probe.hip for the kernels
+// alone).  Round 4's rule -- split until 1.5 items per CU exist -- went 2-3 x too far on the smallest batches: 1 x 256 ran
+// 4 / 16 slices (0.962 ms) where 3 / 6 is 0.893.
+// The split -- i.e. the summation order -- is decided ONCE per hac_encoder_forward* call, from the rows of its first
+// sub-batch (Mp_plan), like the family: a sequence's embedding must not depend on the sub-batch it fell into.
+// wg_slots: workgroups of the family's 128^2 kernel resident at once (ksplit_slots); 0: the family has no split-K form.
+int pick_ksplit(int K, long Mp_plan, long wg_slots, int pin, int ksplit_mode) {
+    if (wg_slots == 0 || ksplit_mode == 0) return 1;
+    const int KT = K / 64, min_kt = KT >= 48 ? 8 : 4;
+    if (pin > 0 && KT % pin == 0 && KT / pin >= 3) return pin;
+    const long tiles = (Mp_plan / 128) * (H / 128);
+    int S = 1;
+    double best = KT * 0.6;
+    for (int cand : {2, 3, 4, 6}) {
+        if (KT % cand || KT / cand < min_kt || tiles * cand > wg_slots) continue;
+        const double cost = (double)KT / cand * 0.6 + (cand - 1) * (double)Mp_plan * 1.3e-3;
+        if (cost < best) {
+            best = cost;
+            S = cand;
+        }
+    }
+    return S;
+}
+// The classic 128^2 kernel holds 80 KB of LDS and is launched two workgroups to a CU; the split kernel stages the lo twins of
+// both operands too (SPLIT_GEMM_LDS = 144 KB) and runs one to a CU: half the slots, so half the items fit one round.  gemm8 and
+// the 256^2 tile serve batches that fill the chip without slices.
+long ksplit_slots(int family, int n_cu) { return family == FAM_SPLIT ? n_cu : (family == FAM_CLASSIC128 ? 2L * n_cu : 0); }
+
+// gemm8 only: its extra workspaces, the (0, 1) statistics and the identity affine of rows that are already final
+int reserve_gemm8(hac_encoder *e, Fwd &f) {
+    HAC_TRY(e->ws_yb.reserve((size_t)f.Mp * H * 2));
+    HAC_TRY(e->ws_part.reserve((size_t)f.Mp * (H / 64) * 8));
+    if (e->idstats_rows < (size_t)f.Mp) {
+        HAC_TRY(e->ws_idstats.reserve((size_t)f.Mp * 8));
+        e->idstats_rows = e->ws_idstats.cap / 8;
+        fill_identity_stats_kernel<<<dim3((unsigned)((e->idstats_rows + 255) / 256)), dim3(256), 0, f.st>>>((float2 *)e->ws_idstats.p, e->idstats_rows);
+        HAC_HIP(hipGetLastError());
+    }
+    f.yAb = (bf16 *)e->ws_yb.p;
+    f.part = (float2 *)e->ws_part.p;
+    f.idstats = (float2 *)e->ws_idstats.p;
+    if (!e->ws_identgb.p) {   // gamma = 1 | beta = 0: residual rows that are final (layer 0's embedding rows) take the same epilogue
+        HAC_TRY(e->ws_identgb.reserve((size_t)2 * H * 4));
+        std::vector<float> gb((size_t)2 * H, 0.f);
+        std::fill(gb.begin(), gb.begin() + H, 1.f);
+        HAC_HIP(hipMemcpy(e->ws_identgb.p, gb.data(), gb.size() * 4, hipMemcpyHostToDevice));
+    }
+    return HAC_OK;
+}
+
+// compact buffers of the <s>-only tail of the last layer out of ws_cls, and in split mode their twins out of ws_cls_lo
+int carve_tail(hac_encoder *e, Fwd &f) {
+    const long Mc = f.Mc;
+    HAC_TRY(e->ws_cls.reserve((size_t)Mc * (H * 2 + H * 4 * 3 + H * 2 + FF * 2)));
+    f.ctx_c = (bf16 *)e->ws_cls.p;
+    f.x_c = (float *)(f.ctx_c + Mc * H);
+    f.y_c = f.x_c + Mc * H;
+    f.x2_c = f.y_c + Mc * H;
+    f.xb_c = (bf16 *)(f.x2_c + Mc * H);
+    f.h_c = f.xb_c + Mc * H;
+    if (f.family != FAM_SPLIT) return HAC_OK;
+    HAC_TRY(e->ws_cls_lo.reserve((size_t)Mc * (H * 2 + H * 2 + FF * 2)));
+    f.ctx_c_lo = (bf16 *)e->ws_cls_lo.p;
+    f.xb_c_lo = f.ctx_c_lo + Mc * H;
+    f.h_c_lo = f.xb_c_lo + Mc * H;
+    return HAC_OK;
+}
+
+// the workspaces every family's rows live in (Fwd::Mp rows), the lo twins in split mode, the pooled rows with pooling = mean
+int reserve_rows(hac_encoder *e, Fwd &f) {
+    const long Mp = f.Mp;
     HAC_TRY(e->ws_x.reserve((size_t)Mp * H * 4));
     HAC_TRY(e->ws_y.reserve((size_t)Mp * H * 4));
     HAC_TRY(e->ws_stats.reserve((size_t)Mp * 8 * 2));
+    f.x = (float *)e->ws_x.p; f.y = (float *)e->ws_y.p;
+    f.statsA = (float2 *)e->ws_stats.p; f.statsF = f.statsA + Mp;
     HAC_TRY(e->ws_xb.reserve((size_t)Mp * H * 2));
     HAC_TRY(e->ws_q.reserve((size_t)Mp * H * 2));
     HAC_TRY(e->ws_k.reserve((size_t)(Mp + 64) * H * 2));
     HAC_TRY(e->ws_vt.reserve((size_t)H * Mp * 2));
     HAC_TRY(e->ws_ctx.reserve((size_t)Mp * H * 2));
     HAC_TRY(e->ws_h.reserve((size_t)Mp * FF * 2));
-    HAC_TRY(e->ws_xb_lo.reserve((size_t)Mp * H * 2));
-    HAC_TRY(e->ws_q_lo.reserve((size_t)Mp * H * 2));
-    HAC_TRY(e->ws_k_lo.reserve((size_t)(Mp + 64) * H * 2));
-    HAC_TRY(e->ws_vt_lo.reserve((size_t)H * Mp * 2));
-    HAC_TRY(e->ws_ctx_lo.reserve((size_t)Mp * H * 2));
-    HAC_TRY(e->ws_h_lo.reserve((size_t)Mp * FF * 2));
-    const bool mean = e->pooling == 1;   // every layer on every row, then pool_mean_kernel: no compact tail
-    if (mean) HAC_TRY(e->ws_pool.reserve((size_t)2 * B * H * 4));
-    SeqInfo s;
-    HAC_TRY(seq_layout(e, B, L, s));
-    seq_prep_kernel<IT><<<dim3(B), dim3(512), 0, st>>>(ids, mask, L, s, c.pad_token_id, c.vocab);
-    seq_offsets_kernel<<<dim3(1), dim3(256), 0, st>>>(s, B);
-    attn_order_kernel<<<dim3(1), dim3(256), 0, st>>>(s, B);
-    float *x = (float *)e->ws_x.p, *y = (float *)e->ws_y.p;
-    float2 *statsA = (float2 *)e->ws_stats.p, *statsF = statsA + Mp;
-    bf16 *xb = (bf16 *)e->ws_xb.p, *q = (bf16 *)e->ws_q.p, *k = (bf16 *)e->ws_k.p, *vt = (bf16 *)e->ws_vt.p, *ctx = (bf16 *)e->ws_ctx.p, *h = (bf16 *)e->ws_h.p;
-    bf16 *xb_lo = (bf16 *)e->ws_xb_lo.p, *q_lo = (bf16 *)e->ws_q_lo.p, *k_lo = (bf16 *)e->ws_k_lo.p, *vt_lo = (bf16 *)e->ws_vt_lo.p;
-    bf16 *ctx_lo = (bf16 *)e->ws_ctx_lo.p, *h_lo = (bf16 *)e->ws_h_lo.p;
-    const int *total = s.off + B;
-    // embedding rows: the shipped kernels write the fp32 rows and their bf16 rounding (= hi) for all Mp rows; lo from the fp32 rows
-    embed_ln_kernel<IT><<<dim3(L32 / 4, B), dim3(256), 0, st>>>(ids, L, s, e->word, e->posw, e->typew, e->embg, e->embb, c.ln_eps, c.vocab, x, xb);
-    zero_tail_rows_kernel<<<dim3(MT), dim3(192), 0, st>>>(x, xb, total, Mp);
-    f32_to_bf16_lo_kernel<<<dim3((unsigned)(((size_t)Mp * H + 255) / 256)), dim3(256), 0, st>>>(x, xb_lo, (size_t)Mp * H);
-    HAC_HIP(hipGetLastError());
-    auto dump_state = [&](int li) {
-        const bool emb = li < 0;
-        layer_state_kernel<<<dim3((unsigned)L, (unsigned)B), dim3(192), 0, st>>>(x, xb, emb ? nullptr : statsF, emb ? nullptr : e->layers[li].ln2g,
-                                                                                   emb ? nullptr : e->layers[li].ln2b, s, L, dump->rows, dump->stats, dump->norm);
-        e->plan_sub_batches += 1;
-        e->plan_rows += Mp;
-        e->plan_gemm = "split128";
-        return hipGetLastError() == hipSuccess ? HAC_OK : fail(HAC_ERR_HIP, "layer_state_kernel launch failed");
-    };
-    e->plan_attn_pipe = 0;
-    // (the woven kernel and its fix-up pass are never reached here: hac_encoder_attention_redo reports this forward, i.e. nothing)
-    if (e->ws_redo.p) HAC_HIP(hipMemsetAsync(e->ws_redo.p, 0, 64, st));
-    if (dump && dump->layer < 0) return dump_state(-1);
-    // Split-K of the two RESID GEMMs on small batches: the classic family's model (run_forward) with one workgroup slot per CU.
-    // Decided once per hac_encoder_forward* call (rows_plan): a sequence's embedding must not depend on its sub-batch.
-    const long Mp_plan = rows_plan > 0 ? (rows_plan + MT - 1) / MT * MT : Mp;
-    auto pick_ksplit = [&](int K) {
-        if (e->ksplit_mode == 0) return 1;
-        const int KT = K / 64, min_kt = KT >= 48 ? 8 : 4;
-        const int pin = K == H ? e->ks_pin_out : e->ks_pin_down;
-        if (pin > 0 && KT % pin == 0 && KT / pin >= 3) return pin;
-        const long tiles = (Mp_plan / 128) * (H / 128);
-        int S = 1;
-        double best = KT * 0.6;
-        for (int cand : {2, 3, 4, 6}) {
-            if (KT % cand || KT / cand < min_kt || tiles * cand > (long)e->n_cu) continue;
-            const double cost = (double)KT / cand * 0.6 + (cand - 1) * (double)Mp_plan * 1.3e-3;
-            if (cost < best) {
-                best = cost;
-                S = cand;
-            }
-        }
-        return S;
-    };
-    const int ks_out = pick_ksplit(H), ks_down = pick_ksplit(FF);
-    e->plan_ks_out = ks_out;
-    e->plan_ks_down = ks_down;
-    const size_t part_stride = (size_t)Mp * H;
-    if (std::max(ks_out, ks_down) > 1) HAC_TRY(e->ws_ksplit.reserve((size_t)(std::max(ks_out, ks_down) - 1) * part_stride * 4));
-    float *kpart = (float *)e->ws_ksplit.p;
-    const dim3 grid_g((unsigned)e->n_cu), blk_g(256);
-#define HAC_GEMM_SPLIT(EPI, CLS)                                                        \
-    do {                                                                              \
-        HAC_TRY(prof_begin(e, 1 + (CLS), st));                                        \
-        gemm_split_nt_kernel<EPI><<<grid_g, blk_g, SPLIT_GEMM_LDS, st>>>(ga);          \
-        HAC_TRY(prof_end(e, 1 + (CLS), st));                                          \
-    } while (0)
-    HAC_TRY(prof_begin(e, 0, st));
-    // compact buffers of the <s>-only tail of the last layer, and their twins
-    const long Mc = ((long)B + MT - 1) / MT * MT;
-    bf16 *ctx_c = nullptr, *xb_c = nullptr, *h_c = nullptr, *ctx_c_lo = nullptr, *xb_c_lo = nullptr, *h_c_lo = nullptr;
-    float *x_c = nullptr, *y_c = nullptr, *x2_c = nullptr;
-    if (!mean) {   // (pooling = mean has no last-layer special case: nothing reserved, no pointer formed)
-        HAC_TRY(e->ws_cls.reserve((size_t)Mc * (H * 2 + H * 4 * 3 + H * 2 + FF * 2)));
-        HAC_TRY(e->ws_cls_lo.reserve((size_t)Mc * (H * 2 + H * 2 + FF * 2)));
-        ctx_c = (bf16 *)e->ws_cls.p;
-        x_c = (float *)(ctx_c + Mc * H);
-        y_c = x_c + Mc * H;
-        x2_c = y_c + Mc * H;
-        xb_c = (bf16 *)(x2_c + Mc * H);
-        h_c = xb_c + Mc * H;
-        ctx_c_lo = (bf16 *)e->ws_cls_lo.p;
-        xb_c_lo = ctx_c_lo + Mc * H;
-        h_c_lo = xb_c_lo + Mc * H;
+    f.xb = (bf16 *)e->ws_xb.p; f.q = (bf16 *)e->ws_q.p; f.k = (bf16 *)e->ws_k.p;
+    f.vt = (bf16 *)e->ws_vt.p; f.ctx = (bf16 *)e->ws_ctx.p; f.h = (bf16 *)e->ws_h.p;
+    if (f.family == FAM_SPLIT) {
+        HAC_TRY(e->ws_xb_lo.reserve((size_t)Mp * H * 2));
+        HAC_TRY(e->ws_q_lo.reserve((size_t)Mp * H * 2));
+        HAC_TRY(e->ws_k_lo.reserve((size_t)(Mp + 64) * H * 2));
+        HAC_TRY(e->ws_vt_lo.reserve((size_t)H * Mp * 2));
+        HAC_TRY(e->ws_ctx_lo.reserve((size_t)Mp * H * 2));
+        HAC_TRY(e->ws_h_lo.reserve((size_t)Mp * FF * 2));
+        f.xb_lo = (bf16 *)e->ws_xb_lo.p; f.q_lo = (bf16 *)e->ws_q_lo.p; f.k_lo = (bf16 *)e->ws_k_lo.p;
+        f.vt_lo = (bf16 *)e->ws_vt_lo.p; f.ctx_lo = (bf16 *)e->ws_ctx_lo.p; f.h_lo = (bf16 *)e->ws_h_lo.p;
     }
-    for (int li = 0; li < c.n_layers; ++li) {
-        const LayerW &w = e->layers[li];
-        const bool last = !mean && (li == c.n_layers - 1);
-        GemmSplitArgs ga{};
-        GemmArgs &g = ga.g;
-        g.total_rows = total;
-        g.A = xb; ga.A_lo = xb_lo; g.W = w.wqkv; ga.W_lo = w.wqkv_lo; g.bias = w.bqkv; g.N = 3 * H; g.K = H;
-        g.q = q; g.k = k; g.v16 = vt; ga.q_lo = q_lo; ga.k_lo = k_lo; ga.v16_lo = vt_lo;
-        HAC_GEMM_SPLIT(EPI_QKV, HAC_ENC_CLASS_QKV);
-        const AttnSplitArgs a{q, q_lo, k, k_lo, vt, vt_lo, ctx, ctx_lo, s, last ? 1 : 0};
-        HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_ATTN, st));
-        attention_split_kernel<<<dim3(NH, (unsigned)B, last ? 1u : (unsigned)((L32 + 127) / 128)), dim3(256), 2 * ATS_STAGE, st>>>(a);
-        HAC_TRY(prof_end(e, 1 + HAC_ENC_CLASS_ATTN, st));
-        const bool defer_in = li > 0;
-        const float *ln2g_prev = defer_in ? e->layers[li - 1].ln2g : nullptr, *ln2b_prev = defer_in ? e->layers[li - 1].ln2b : nullptr;
-        if (!last) {
-            // attention output projection + residual, LN statistics
-            g.A = ctx; ga.A_lo = ctx_lo; g.W = w.wo; ga.W_lo = w.wo_lo; g.bias = w.bo; g.N = H; g.K = H; g.resid = x; g.y = y;
-            g.rstats = defer_in ? statsF : nullptr; g.rgamma = ln2g_prev; g.rbeta = ln2b_prev;
-            g.ksplit = ks_out; g.part = kpart; g.part_stride = part_stride;
-            HAC_GEMM_SPLIT(EPI_RESID, HAC_ENC_CLASS_OUTPROJ);
-            g.ksplit = 1;
-            HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_LN, st));
-            ln_split_rows_kernel<<<dim3((unsigned)(Mp / 4)), dim3(256), 0, st>>>(y, total, w.ln1g, w.ln1b, c.ln_eps, statsA, nullptr, xb, xb_lo, kpart, ks_out - 1, part_stride);
-            HAC_TRY(prof_end(e, 1 + HAC_ENC_CLASS_LN, st));
-            // FFN
-            g.A = xb; ga.A_lo = xb_lo; g.W = w.w1; ga.W_lo = w.w1_lo; g.bias = w.b1; g.N = FF; g.K = H; g.h = h; ga.h_lo = h_lo;
-            HAC_GEMM_SPLIT(EPI_GELU, HAC_ENC_CLASS_FFN_UP);
-            g.A = h; ga.A_lo = h_lo; g.W = w.w2; ga.W_lo = w.w2_lo; g.bias = w.b2; g.N = H; g.K = FF; g.resid = y; g.y = x;
-            g.rstats = statsA; g.rgamma = w.ln1g; g.rbeta = w.ln1b;
-            g.ksplit = ks_down; g.part = kpart; g.part_stride = part_stride;
-            HAC_GEMM_SPLIT(EPI_RESID, HAC_ENC_CLASS_FFN_DOWN);
-            g.ksplit = 1;
-            HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_LN, st));
-            ln_split_rows_kernel<<<dim3((unsigned)(Mp / 4)), dim3(256), 0, st>>>(x, total, w.ln2g, w.ln2b, c.ln_eps, statsF, nullptr, xb, xb_lo, kpart, ks_down - 1, part_stride);
-            HAC_TRY(prof_end(e, 1 + HAC_ENC_CLASS_LN, st));
-        } else {
-            // only the <s> row of every sequence continues (B rows instead of T): same kernels, compact matrices.  (The gather runs
-            // once per twin; both passes write the same fp32 residual rows.)
-            gather_cls_kernel<<<dim3((unsigned)Mc), dim3(256), 0, st>>>(ctx, x, nullptr, defer_in ? statsF : nullptr, ln2g_prev, ln2b_prev, s, B, ctx_c, x_c);
-            gather_cls_kernel<<<dim3((unsigned)Mc), dim3(256), 0, st>>>(ctx_lo, x, nullptr, defer_in ? statsF : nullptr, ln2g_prev, ln2b_prev, s, B, ctx_c_lo, x_c);
-            g.total_rows = s.nb;
-            g.A = ctx_c; ga.A_lo = ctx_c_lo; g.W = w.wo; ga.W_lo = w.wo_lo; g.bias = w.bo; g.N = H; g.K = H; g.resid = x_c; g.y = y_c; g.rstats = nullptr;
-            gemm_split_nt_kernel<EPI_RESID><<<grid_g, blk_g, SPLIT_GEMM_LDS, st>>>(ga);
-            ln_split_rows_kernel<<<dim3((unsigned)(Mc / 4)), dim3(256), 0, st>>>(y_c, s.nb, w.ln1g, w.ln1b, c.ln_eps, nullptr, x2_c, xb_c, xb_c_lo, nullptr, 0, 0);
-            g.A = xb_c; ga.A_lo = xb_c_lo; g.W = w.w1; ga.W_lo = w.w1_lo; g.bias = w.b1; g.N = FF; g.K = H; g.h = h_c; ga.h_lo = h_c_lo;
-            gemm_split_nt_kernel<EPI_GELU><<<grid_g, blk_g, SPLIT_GEMM_LDS, st>>>(ga);
-            g.A = h_c; ga.A_lo = h_c_lo; g.W = w.w2; ga.W_lo = w.w2_lo; g.bias = w.b2; g.N = H; g.K = FF; g.resid = x2_c; g.y = y_c;
-            gemm_split_nt_kernel<EPI_RESID><<<grid_g, blk_g, SPLIT_GEMM_LDS, st>>>(ga);
-            ln_split_rows_kernel<<<dim3((unsigned)(Mc / 4)), dim3(256), 0, st>>>(y_c, s.nb, w.ln2g, w.ln2b, c.ln_eps, nullptr, x_c, xb_c, xb_c_lo, nullptr, 0, 0);
-        }
-        HAC_HIP(hipGetLastError());
-        if (dump && dump->layer == li) return dump_state(li);
-    }
-#undef HAC_GEMM_SPLIT
-    HAC_TRY(prof_end(e, 0, st));
-    if (mean) {
-        HAC_TRY(pool_and_head<float>(e, x, statsF, s, B, out_dev, st));
-    } else {
-        const int head_ns = B <= 64 ? 8 : CLS_NS;
-        cls_head_proj_kernel<<<dim3((unsigned)((B + CLS_SB - 1) / CLS_SB), H / head_ns), dim3(256), 0, st>>>(x_c, s, 1, B, e->wh, e->bh, y_c, head_ns);
-        cls_head_norm_kernel<<<dim3((unsigned)B), dim3(256), 0, st>>>(y_c, s, e->ng, e->nb, 1e-5f, out_dev);
-        HAC_HIP(hipGetLastError());
-    }
-    e->plan_sub_batches += 1;
-    e->plan_rows += Mp;
-    e->plan_gemm = "split128";
+    if (f.mean) HAC_TRY(e->ws_pool.reserve((size_t)2 * f.B * H * 4));
+    return HAC_OK;
+}
+// Split-K of the two RESID GEMMs, decided once per hac_encoder_forward* call (rows_plan; 0: this is its only sub-batch)
+int plan_ksplit(hac_encoder *e, Fwd &f, long rows_plan) {
+    const long Mp_plan = rows_plan > 0 ? (rows_plan + MT - 1) / MT * MT : f.Mp, slots = ksplit_slots(f.family, e->n_cu);
+    e->plan.ks_out = f.ks_out = pick_ksplit(H, Mp_plan, slots, e->ks_pin_out, e->ksplit_mode);
+    e->plan.ks_down = f.ks_down = pick_ksplit(FF, Mp_plan, slots, e->ks_pin_down, e->ksplit_mode);
+    f.part_stride = (size_t)f.Mp * H;
+    if (std::max(f.ks_out, f.ks_down) > 1) HAC_TRY(e->ws_ksplit.reserve((size_t)(std::max(f.ks_out, f.ks_down) - 1) * f.part_stride * 4));
+    f.kpart = (float *)e->ws_ksplit.p;
     return HAC_OK;
 }
 
+// Fills the context: workspaces, sequence bookkeeping and the embedding rows, then (unless the caller only wants the embedding
+// state) what the layer stack needs -- the split-K plan, gemm8's extras, the compact tail.
+// rows_hint: an upper bound of the packed rows of this sub-batch when the caller knows one (sum of its
+// sequences' padded lengths), 0 = every sequence may be full length
+// family: the GEMM family of the whole hac_encoder_forward* call (FAM_*), or -1: decide here, from this (only) sub-batch's rows.
+// The family -- and with the classic kernels the tile -- is chosen ONCE per call, from the whole batch (forward_batched): a small
+// tail sub-batch of a large forward runs the same kernels as the others, so a sequence's embedding does not depend on which
+// sub-batch it fell into.
 template <typename IT>
-int run_forward(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, float *out_dev, hipStream_t st, long rows_hint = 0, int family = -1,
-                long rows_plan = 0, const LayerDump *dump = nullptr) {
-    if (e->precision == 1) return run_forward_split<IT>(e, ids, mask, B, L, out_dev, st, rows_hint, rows_plan, dump);
+int fwd_build(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, hipStream_t st, long rows_hint, int family, long rows_plan, bool embed_only,
+              Fwd &f) {
     const hac_encoder_config &c = e->cfg;
-    const int L32 = (L + SEQ_ALIGN - 1) / SEQ_ALIGN * SEQ_ALIGN;
-    bool fw_capturing = false;           // (inside a stream capture -- the small-batch graphs -- an event query is an error that kills the capture)
-    {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
-        else fw_capturing = cs != hipStreamCaptureStatusNone;
+    f = Fwd{};
+    f.B = B; f.L = L; f.L32 = pad_len(L); f.st = st;
+    const long rows_max = rows_hint > 0 ? std::min<long>(rows_hint, (long)B * f.L32) : (long)B * f.L32;
+    const long Mp = f.Mp = (rows_max + MT - 1) / MT * MT;
+    f.Mc = ((long)B + MT - 1) / MT * MT;
+    f.family = family < 0 ? pick_family(e, rows_max) : family;
+    const bool split = f.family == FAM_SPLIT, g8 = f.family == FAM_GEMM8;
+    f.big = f.family == FAM_CLASSIC256;
+    f.mean = e->pooling == 1;
+    HAC_TRY(reserve_rows(e, f));
+    HAC_TRY(seq_layout(e, B, L, f.s));
+    seq_prep_kernel<IT><<<dim3(B), dim3(512), 0, st>>>(ids, mask, L, f.s, c.pad_token_id, c.vocab);
+    seq_offsets_kernel<<<dim3(1), dim3(256), 0, st>>>(f.s, B);
+    attn_order_kernel<<<dim3(1), dim3(256), 0, st>>>(f.s, B);
+    f.total = f.s.off + B;
+    // (gemm8's residual stream is bf16 from the embedding rows on: no fp32 copy of them, 3 KB per token less to write)
+    embed_ln_kernel<IT><<<dim3(f.L32 / 4, B), dim3(256), 0, st>>>(ids, L, f.s, e->word, e->posw, e->typew, e->embg, e->embb, c.ln_eps, c.vocab, g8 ? nullptr : f.x, f.xb);
+    HAC_HIP(hipGetLastError());
+    // dead tail rows of the last M tile (fewer than MT) feed the GEMMs: keep them finite
+    zero_tail_rows_kernel<<<dim3(MT), dim3(192), 0, st>>>(g8 ? nullptr : f.x, f.xb, f.total, Mp);
+    // (split: the shipped kernels write the fp32 rows and their bf16 rounding (= hi) for all Mp rows; lo from the fp32 rows)
+    if (split) f32_to_bf16_lo_kernel<<<dim3((unsigned)(((size_t)Mp * H + 255) / 256)), dim3(256), 0, st>>>(f.x, f.xb_lo, (size_t)Mp * H);
+    HAC_HIP(hipGetLastError());
+    if (split) {   // (the woven kernel and its fix-up pass are never reached: hac_encoder_attention_redo reports this forward, i.e. nothing)
+        e->plan.attn_pipe = 0;
+        if (e->ws_redo.p) HAC_HIP(hipMemsetAsync(e->ws_redo.p, 0, 64, st));
     }
-    if (e->redo_pending && !fw_capturing) {
+    if (embed_only) return HAC_OK;
+    HAC_TRY(plan_ksplit(e, f, rows_plan));
+    if (g8) HAC_TRY(reserve_gemm8(e, f));
+    if (!f.mean) HAC_TRY(carve_tail(e, f));   // (pooling = mean has no last-layer special case: nothing reserved, no pointer formed)
+    return HAC_OK;
+}
+
+// what hac_encoder_last_plan reports of a (sub-)batch that ran
+void plan_add(hac_encoder *e, const Fwd &f) {
+    static const char *const names[] = {"classic128", "gemm8", "classic256", "split128"};
+    e->plan.sub_batches += 1;
+    e->plan.rows += f.Mp;
+    e->plan.gemm = names[f.family];
+}
+
+// (test entry point: the same launches as a forward up to the requested layer, then the unpacked state instead of the rest)
+int dump_state(hac_encoder *e, const Fwd &f, const LayerDump &d, int li) {
+    const bool emb = li < 0;
+    layer_state_kernel<<<dim3((unsigned)f.L, (unsigned)f.B), dim3(192), 0, f.st>>>(f.family == FAM_GEMM8 ? nullptr : f.x, f.xb, emb ? nullptr : f.statsF, emb ? nullptr : e->layers[li].ln2g,
+                                                                                     emb ? nullptr : e->layers[li].ln2b, f.s, f.L, d.rows, d.stats, d.norm);
+    plan_add(e, f);
+    return hipGetLastError() == hipSuccess ? HAC_OK : fail(HAC_ERR_HIP, "layer_state_kernel launch failed");
+}
+
+// Attention of the bf16 families, inside its profiling class: the query split, then the woven / one-block / two-pass kernels.
+int attention(hac_encoder *e, const Fwd &f, int li, bool last) {
+    const hipStream_t st = f.st;
+    const int B = f.B, L32 = f.L32;
+    // (streaming kernels: few sequences -> an item's query rows go to 2 or 4 workgroups while B * NH * qsplit items still fit the CUs)
+    int att_qs = 1;
+    while (e->attn_qsplit != 0 && att_qs < 16 && (long)B * NH * att_qs * 2 <= e->n_cu) att_qs *= 2;
+    if (e->attn_qs_pin > 0) att_qs = e->attn_qs_pin;   // development (tools/ks_sweep.py attn)
+    const bool att_one = att_qs > 1 && L32 > 256;   // few sequences: one launch (an empty second one is 5 us of a ~100-us layer)
+    AttnArgs a{f.q, f.k, f.vt, f.ctx, f.s, last ? 1 : 0, att_qs, att_one ? 1 : 0, nullptr, nullptr, 0};
+    if (li == 0) e->plan.attn_pipe = 0;
+    // (measured, 512 sequences of one length, woven / one-block: 512 rows 0.475 / 0.589 ms, 448 rows 0.413 / 0.507, 384 rows 0.313 / 0.373;
+    // 256 rows 0.174 / 0.174, 128 rows 0.086 / 0.086 -- the 8-wave instantiation wins wherever it applies, the 4-wave one ties: the woven
+    // form takes the long class (sequences of more than 256 rows), the one-block kernel the short class; same bits either way)
+    const bool att_pipe = e->attn_mode == 0 && e->attn_pipe != 0 && att_qs == 1 && !last && (L32 > 256 || e->attn_pipe > 0) &&
+                          !(e->attn_pipe < 0 && ((e->pipe_skip_mask >> li) & 1u));      // ("all" pins the woven form: tests of the fix-up pass)
+    if (att_pipe) {
+        if (!e->plan.attn_pipe) {      // the forward's first woven layer: workspace, per-layer counts to zero (the flags are zero whenever no pass is pending)
+            HAC_TRY(e->ws_redo.reserve(((size_t)B * NH + 16) * 4));
+            HAC_HIP(hipMemsetAsync(e->ws_redo.p, 0, 64, st));
+        }
+        a.redo_count = (int *)e->ws_redo.p + (li & 15);
+        a.redo_flags = (int *)e->ws_redo.p + 16;
+    }
+    // sequences of <= 256 rows: 4-wave workgroups; longer ones: 8-wave workgroups (each skips the other's)
+    HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_ATTN, st));
+    if (e->attn_mode == 0) {           // persistent streaming kernels, one launch per length class
+        if (att_pipe) {   // whole items: the woven two-blocks-per-wave form, then the items it flagged through the one-block kernels (bit-identical results)
+            const bool both = e->attn_pipe > 0;   // "all" (tests): the short class through the 4-wave instantiation too
+            if (L32 > 256) attention_pipe_kernel<8><<<dim3(e->n_cu), dim3(512), 163840, st>>>(a);
+            if (both) attention_pipe_kernel<4><<<dim3(2 * e->n_cu), dim3(256), 81920, st>>>(a);
+            else attention_stream_kernel<8><<<dim3(2 * e->n_cu), dim3(512), 81920, st>>>(a);
+            a.fixup = 1;
+            if (L32 > 256) attention_stream_kernel<16><<<dim3(e->n_cu), dim3(1024), 163840, st>>>(a);
+            if (both) attention_stream_kernel<8><<<dim3(2 * e->n_cu), dim3(512), 81920, st>>>(a);
+            e->plan.attn_pipe = 1;
+        } else {
+            if (L32 > 256) attention_stream_kernel<16><<<dim3(e->n_cu), dim3(1024), 163840, st>>>(a);
+            if (!att_one) attention_stream_kernel<8><<<dim3(2 * e->n_cu), dim3(512), 81920, st>>>(a);
+        }
+    } else {                           // two-pass kernels, one workgroup per (sequence, head): kept as a cross-check
+        attention_kernel<8, 1><<<dim3(NH, B), dim3(512), (size_t)(L32 < 256 ? L32 : 256) * 256, st>>>(a);
+        if (L32 > 256) attention_kernel<16, 1><<<dim3(NH, B), dim3(1024), (size_t)L32 * 256, st>>>(a);
+    }
+    return prof_end(e, 1 + HAC_ENC_CLASS_ATTN, st);
+}
+
+// Residual stream between layers: layer 0 reads the embedding rows x (normalized); afterwards the
+// stream lives as pre-LayerNorm rows + (mean, rstd): yF/statsF after a layer's FFN, yA/statsA after its
+// attention block.  yF shares x's buffer (x is dead once layer 0's out-projection has read it).
+// The LayerNorm a layer's input rows still have to go through (the previous layer's output LayerNorm; none in front of layer 0).
+struct PrevLN {
+    const float2 *stats;
+    const float *g, *b;
+};
+PrevLN prev_ln(const hac_encoder *e, const Fwd &f, int li) {
+    if (li == 0) return {nullptr, nullptr, nullptr};
+    return {f.statsF, e->layers[li - 1].ln2g, e->layers[li - 1].ln2b};
+}
+
+// ---- classic family: persistent bf16 GEMMs on 128^2 tiles, or 256^2 tiles once those fill the chip (Fwd::big)
+template <int EPI>
+void launch_gemm128(const hac_encoder *e, const GemmArgs &g, hipStream_t st) {
+    gemm_bf16_nt_kernel<EPI, 2><<<dim3((unsigned)(e->n_cu * 2)), dim3(256), (size_t)4 * 128 * 128 + (size_t)4 * 4096, st>>>(g);   // 2 stages + per-wave patches
+}
+template <int EPI>
+int gemm_classic(hac_encoder *e, const Fwd &f, const GemmArgs &g, int cls) {
+    if (f.big)
+        HAC_PROFILED(e, f.st, cls, gemm_bf16_nt_kernel<EPI, 4><<<dim3((unsigned)e->n_cu), dim3(512), (size_t)4 * 256 * 128 + (size_t)8 * 4096, f.st>>>(g));
+    else HAC_PROFILED(e, f.st, cls, launch_gemm128<EPI>(e, g, f.st));
+    return HAC_OK;
+}
+int qkv_classic(hac_encoder *e, const Fwd &f, int li, GemmArgs &g) {
+    const LayerW &w = e->layers[li];
+    g.total_rows = f.total;
+    g.A = f.xb; g.W = w.wqkv; g.bias = w.bqkv; g.N = 3 * H; g.K = H; g.q = f.q; g.k = f.k; g.v16 = f.vt;
+    return gemm_classic<EPI_QKV>(e, f, g, HAC_ENC_CLASS_QKV);
+}
+int layer_classic(hac_encoder *e, const Fwd &f, int li) {
+    const LayerW &w = e->layers[li];
+    const PrevLN p = prev_ln(e, f, li);
+    const hipStream_t st = f.st;
+    GemmArgs g{};
+    HAC_TRY(qkv_classic(e, f, li, g));
+    HAC_TRY(attention(e, f, li, false));
+    // attention output projection + residual, LN statistics
+    g.A = f.ctx; g.W = w.wo; g.bias = w.bo; g.N = H; g.K = H; g.resid = f.x; g.y = f.y;
+    g.rstats = p.stats; g.rgamma = p.g; g.rbeta = p.b;
+    g.ksplit = f.ks_out; g.part = f.kpart; g.part_stride = f.part_stride;
+    HAC_TRY(gemm_classic<EPI_RESID>(e, f, g, HAC_ENC_CLASS_OUTPROJ));
+    g.ksplit = 1;
+    HAC_PROFILED(e, st, HAC_ENC_CLASS_LN, ln_stats_rows_kernel<<<dim3((unsigned)(f.Mp / 4)), dim3(256), 0, st>>>(f.y, f.total, w.ln1g, w.ln1b, e->cfg.ln_eps, f.statsA,
+                                                                                                           f.xb, f.kpart, f.ks_out - 1, f.part_stride));
+    // FFN
+    g.A = f.xb; g.W = w.w1; g.bias = w.b1; g.N = FF; g.K = H; g.h = f.h;
+    HAC_TRY(gemm_classic<EPI_GELU>(e, f, g, HAC_ENC_CLASS_FFN_UP));
+    g.A = f.h; g.W = w.w2; g.bias = w.b2; g.N = H; g.K = FF; g.resid = f.y; g.y = f.x;
+    g.rstats = f.statsA; g.rgamma = w.ln1g; g.rbeta = w.ln1b;
+    g.ksplit = f.ks_down; g.part = f.kpart; g.part_stride = f.part_stride;
+    HAC_TRY(gemm_classic<EPI_RESID>(e, f, g, HAC_ENC_CLASS_FFN_DOWN));
+    HAC_PROFILED(e, st, HAC_ENC_CLASS_LN, ln_stats_rows_kernel<<<dim3((unsigned)(f.Mp / 4)), dim3(256), 0, st>>>(f.x, f.total, w.ln2g, w.ln2b, e->cfg.ln_eps, f.statsF,
+                                                                                                           f.xb, f.kpart, f.ks_down - 1, f.part_stride));
+    return HAC_OK;
+}
+
+// ---- gemm8 family (gemm8.inc): the ping-pong GEMM with the LayerNorms folded into the consuming weights, bf16 residual stream
+// Phased starts (Gemm8Args::stagger): workgroups that start together stay together -- every tile takes the same time --
+// and reach their epilogues, the phases that write (and, RESID, read) the residual stream, all at once.  Delaying the
+// XCDs by 0..3 quarter-steps at the start spreads those bursts: QKV -3.8 % and out-proj -3.5 % at 512000 rows
+// (tools/probes/gemm8_stagger_probe.hip: 1.786 -> 1.718 ms, 0.803 -> 0.775 ms); the FFN classes did not move (their
+// tile times are longer and already drift apart) and stay unphased.  Only on runs of >= 16 tiles per workgroup: the
+// delay (<= 3 steps of ~1 us x stagger) is paid once per launch.
+int stagger8(const hac_encoder *e, const Fwd &f, int N, int n_tile0, int steps) {
+    const long tiles = (f.Mp / 256) * (long)(N / 256 - n_tile0);
+    return (e->g8_stagger != 0 && tiles >= 16L * e->n_cu) ? steps : 0;
+}
+// (non-temporal output stores for the q / k / v and h streams, not for the residual stream: see g8_store16)
+template <int EPI>
+void launch_gemm8(const hac_encoder *e, const Gemm8Args &a, hipStream_t st) {
+    gemm8_kernel<EPI, EPI != EPI8_RESID><<<dim3((unsigned)e->n_cu), dim3(512), 163840, st>>>(a);
+}
+// A = the previous layer's un-normalized output rows (bf16) + their statistics; layer 0: the normalized embedding rows
+int qkv_gemm8(hac_encoder *e, const Fwd &f, int li, bool last, Gemm8Args &a) {
+    const LayerW &w = e->layers[li];
+    a.total_rows = f.total;
+    a.n_groups = 1;
+    HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_QKV, f.st));
+    a.A = f.xb; a.K = H; a.astats = li ? f.statsF : f.idstats;
+    a.W = w.wqkv8; a.N = 3 * H; a.wsum = w.fold; a.cvec = w.fold + 3 * H; a.q = f.q; a.k = f.k; a.v16 = f.vt;
+    // last layer: keys and values of every row, queries of the <s> rows only (a third of the GEMM: 0.6 ms per 1000 x 512 forward)
+    a.n_tile0 = last ? H / 256 : 0;
+    a.stagger = stagger8(e, f, 3 * H, a.n_tile0, 6);
+    launch_gemm8<EPI8_QKV>(e, a, f.st);
+    a.n_tile0 = 0;
+    a.stagger = 0;
+    if (last) cls_q_kernel<<<dim3((unsigned)((f.B + CLS_SB - 1) / CLS_SB), H / CLS_NS), dim3(256), 0, f.st>>>(f.xb, a.astats, f.s, f.B, w.wqkv8, w.fold, w.fold + 3 * H, f.q);
+    return prof_end(e, 1 + HAC_ENC_CLASS_QKV, f.st);
+}
+int layer_gemm8(hac_encoder *e, const Fwd &f, int li) {
+    const LayerW &w = e->layers[li];
+    const PrevLN p = prev_ln(e, f, li);
+    const hipStream_t st = f.st;
+    Gemm8Args a{};
+    HAC_TRY(qkv_gemm8(e, f, li, false, a));
+    HAC_TRY(attention(e, f, li, false));
+    // attention output projection + residual -> yA (bf16) and row-sum partials of its fp32 values -> (mean, rstd)
+    a.A = f.ctx; a.W = w.wo; a.N = H; a.K = H; a.cvec = w.bo; a.resid = f.xb; a.yb = f.yAb; a.part = f.part;
+    a.rstats = li ? p.stats : f.idstats;
+    a.rgamma = li ? p.g : (const float *)e->ws_identgb.p;
+    a.rbeta = li ? p.b : (const float *)e->ws_identgb.p + H;
+    a.stagger = stagger8(e, f, H, 0, 8);
+    HAC_PROFILED(e, st, HAC_ENC_CLASS_OUTPROJ, launch_gemm8<EPI8_RESID>(e, a, st));
+    a.stagger = 0;
+    HAC_PROFILED(e, st, HAC_ENC_CLASS_LN, ln_combine_kernel<<<dim3((unsigned)(f.Mp / 256)), dim3(256), 0, st>>>(f.part, H / 64, H, f.total, e->cfg.ln_eps, f.statsA));
+    // FFN up: A = bf16(yA), the attention LayerNorm folded into W1
+    a.A = f.yAb; a.astats = f.statsA; a.W = w.w18; a.N = FF; a.K = H; a.wsum = w.fold + 6 * H; a.cvec = w.fold + 6 * H + FF; a.h = f.h;
+    a.n_groups = 2;   // W1' is 4.7 MB against 4 MB of L2 per XCD; each XCD owns half of its column tiles (measured: -2 %)
+    if (e->prof_mask >> 1) {   // class profiling on: this launch also reads the clock counters (hac_encoder_last_clock)
+        HAC_TRY(e->ws_clk.reserve(32));
+        a.clk = (unsigned long long *)e->ws_clk.p;
+        e->clk_valid = true;
+    }
+    HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_FFN_UP, st));
+    launch_gemm8<EPI8_GELU>(e, a, st);
+    if (a.clk) {      // (class profiling is never on inside a captured forward: graph_eligible)
+        if (!e->clk_ev) HAC_HIP(hipEventCreateWithFlags(&e->clk_ev, hipEventDisableTiming));
+        HAC_HIP(hipEventRecord(e->clk_ev, st));
+    }
+    a.clk = nullptr;
+    HAC_TRY(prof_end(e, 1 + HAC_ENC_CLASS_FFN_UP, st));
+    a.n_groups = 1;
+    // FFN down + residual LN1(yA) -> yF (bf16, in xb's buffer: the next layer's A operand and residual), partials
+    a.A = f.h; a.W = w.w2; a.N = H; a.K = FF; a.cvec = w.b2; a.resid = f.yAb; a.yb = f.xb;
+    a.rstats = f.statsA; a.rgamma = w.ln1g; a.rbeta = w.ln1b;
+    HAC_PROFILED(e, st, HAC_ENC_CLASS_FFN_DOWN, launch_gemm8<EPI8_RESID>(e, a, st));
+    HAC_PROFILED(e, st, HAC_ENC_CLASS_LN, ln_combine_kernel<<<dim3((unsigned)(f.Mp / 256)), dim3(256), 0, st>>>(f.part, H / 64, H, f.total, e->cfg.ln_eps, f.statsF));
+    return HAC_OK;
+}
+
+// The last layer of the bf16 families with pooling = first: QKV by the family's own kernel (gemm8: no queries but the <s> rows',
+// cls_q_kernel), attention of the <s> rows, then only those rows continue (B rows instead of T) through the classic 128^2
+// kernels on compact matrices; that compact part stays outside the per-class profiling events.
+int tail_classic(hac_encoder *e, const Fwd &f, int li) {
+    const LayerW &w = e->layers[li];
+    const PrevLN p = prev_ln(e, f, li);
+    const hipStream_t st = f.st;
+    const bool g8 = f.family == FAM_GEMM8;
+    GemmArgs g{};
+    Gemm8Args a{};
+    HAC_TRY(g8 ? qkv_gemm8(e, f, li, true, a) : qkv_classic(e, f, li, g));
+    HAC_TRY(attention(e, f, li, true));
+    gather_cls_kernel<<<dim3((unsigned)f.Mc), dim3(256), 0, st>>>(f.ctx, f.x, g8 ? f.xb : nullptr, p.stats, p.g, p.b, f.s, f.B, f.ctx_c, f.x_c);
+    g.total_rows = f.s.nb;
+    g.A = f.ctx_c; g.W = w.wo; g.bias = w.bo; g.N = H; g.K = H; g.resid = f.x_c; g.y = f.y_c; g.rstats = nullptr;
+    launch_gemm128<EPI_RESID>(e, g, st);
+    ln_rows_kernel<<<dim3((unsigned)(f.Mc / 4)), dim3(256), 0, st>>>(f.y_c, f.s.nb, w.ln1g, w.ln1b, e->cfg.ln_eps, f.x2_c, f.xb_c);
+    g.A = f.xb_c; g.W = w.w1; g.bias = w.b1; g.N = FF; g.K = H; g.h = f.h_c;
+    launch_gemm128<EPI_GELU>(e, g, st);
+    g.A = f.h_c; g.W = w.w2; g.bias = w.b2; g.N = H; g.K = FF; g.resid = f.x2_c; g.y = f.y_c;
+    launch_gemm128<EPI_RESID>(e, g, st);
+    ln_rows_kernel<<<dim3((unsigned)(f.Mc / 4)), dim3(256), 0, st>>>(f.y_c, f.s.nb, w.ln2g, w.ln2b, e->cfg.ln_eps, f.x_c, f.xb_c);
+    return HAC_OK;
+}
+
+// ---- precision = split (split.inc): always the fp32-residual structure of the classic family on 128^2 tiles, whatever the batch
+// size and whatever "gemm" says; every bf16 tensor an MFMA reads has its lo twin beside it.
+template <int EPI>
+void launch_gemm_split(const hac_encoder *e, const GemmSplitArgs &ga, hipStream_t st) {
+    gemm_split_nt_kernel<EPI><<<dim3((unsigned)e->n_cu), dim3(256), SPLIT_GEMM_LDS, st>>>(ga);
+}
+int qkv_attention_split(hac_encoder *e, const Fwd &f, int li, bool last, GemmSplitArgs &ga) {
+    const LayerW &w = e->layers[li];
+    const hipStream_t st = f.st;
+    GemmArgs &g = ga.g;
+    g.total_rows = f.total;
+    g.A = f.xb; ga.A_lo = f.xb_lo; g.W = w.wqkv; ga.W_lo = w.wqkv_lo; g.bias = w.bqkv; g.N = 3 * H; g.K = H;
+    g.q = f.q; g.k = f.k; g.v16 = f.vt; ga.q_lo = f.q_lo; ga.k_lo = f.k_lo; ga.v16_lo = f.vt_lo;
+    HAC_PROFILED(e, st, HAC_ENC_CLASS_QKV, launch_gemm_split<EPI_QKV>(e, ga, st));
+    const AttnSplitArgs a{f.q, f.q_lo, f.k, f.k_lo, f.vt, f.vt_lo, f.ctx, f.ctx_lo, f.s, last ? 1 : 0};
+    const dim3 grid(NH, (unsigned)f.B, last ? 1u : (unsigned)((f.L32 + 127) / 128));
+    HAC_PROFILED(e, st, HAC_ENC_CLASS_ATTN, attention_split_kernel<<<grid, dim3(256), 2 * ATS_STAGE, st>>>(a));
+    return HAC_OK;
+}
+int layer_split(hac_encoder *e, const Fwd &f, int li) {
+    const LayerW &w = e->layers[li];
+    const PrevLN p = prev_ln(e, f, li);
+    const hipStream_t st = f.st;
+    GemmSplitArgs ga{};
+    GemmArgs &g = ga.g;
+    HAC_TRY(qkv_attention_split(e, f, li, false, ga));
+    // attention output projection + residual, LN statistics
+    g.A = f.ctx; ga.A_lo = f.ctx_lo; g.W = w.wo; ga.W_lo = w.wo_lo; g.bias = w.bo; g.N = H; g.K = H; g.resid = f.x; g.y = f.y;
+    g.rstats = p.stats; g.rgamma = p.g; g.rbeta = p.b;
+    g.ksplit = f.ks_out; g.part = f.kpart; g.part_stride = f.part_stride;
+    HAC_PROFILED(e, st, HAC_ENC_CLASS_OUTPROJ, launch_gemm_split<EPI_RESID>(e, ga, st));
+    g.ksplit = 1;
+    HAC_PROFILED(e, st, HAC_ENC_CLASS_LN,
+                 ln_split_rows_kernel<<<dim3((unsigned)(f.Mp / 4)), dim3(256), 0, st>>>(f.y, f.total, w.ln1g, w.ln1b, e->cfg.ln_eps, f.statsA, nullptr,
+                                                                                        f.xb, f.xb_lo, f.kpart, f.ks_out - 1, f.part_stride));
+    // FFN
+    g.A = f.xb; ga.A_lo = f.xb_lo; g.W = w.w1; ga.W_lo = w.w1_lo; g.bias = w.b1; g.N = FF; g.K = H; g.h = f.h; ga.h_lo = f.h_lo;
+    HAC_PROFILED(e, st, HAC_ENC_CLASS_FFN_UP, launch_gemm_split<EPI_GELU>(e, ga, st));
+    g.A = f.h; ga.A_lo = f.h_lo; g.W = w.w2; ga.W_lo = w.w2_lo; g.bias = w.b2; g.N = H; g.K = FF; g.resid = f.y; g.y = f.x;
+    g.rstats = f.statsA; g.rgamma = w.ln1g; g.rbeta = w.ln1b;
+    g.ksplit = f.ks_down; g.part = f.kpart; g.part_stride = f.part_stride;
+    HAC_PROFILED(e, st, HAC_ENC_CLASS_FFN_DOWN, launch_gemm_split<EPI_RESID>(e, ga, st));
+    HAC_PROFILED(e, st, HAC_ENC_CLASS_LN,
+                 ln_split_rows_kernel<<<dim3((unsigned)(f.Mp / 4)), dim3(256), 0, st>>>(f.x, f.total, w.ln2g, w.ln2b, e->cfg.ln_eps, f.statsF, nullptr,
+                                                                                        f.xb, f.xb_lo, f.kpart, f.ks_down - 1, f.part_stride));
+    return HAC_OK;
+}
+// The last layer with pooling = first: only the <s> row of every sequence continues (B rows instead of T): same kernels, compact
+// matrices, outside the per-class profiling events.  (The gather runs once per twin; both passes write the same fp32 residual rows.)
+int tail_split(hac_encoder *e, const Fwd &f, int li) {
+    const LayerW &w = e->layers[li];
+    const PrevLN p = prev_ln(e, f, li);
+    const hipStream_t st = f.st;
+    GemmSplitArgs ga{};
+    GemmArgs &g = ga.g;
+    HAC_TRY(qkv_attention_split(e, f, li, true, ga));
+    gather_cls_kernel<<<dim3((unsigned)f.Mc), dim3(256), 0, st>>>(f.ctx, f.x, nullptr, p.stats, p.g, p.b, f.s, f.B, f.ctx_c, f.x_c);
+    gather_cls_kernel<<<dim3((unsigned)f.Mc), dim3(256), 0, st>>>(f.ctx_lo, f.x, nullptr, p.stats, p.g, p.b, f.s, f.B, f.ctx_c_lo, f.x_c);
+    g.total_rows = f.s.nb;
+    g.A = f.ctx_c; ga.A_lo = f.ctx_c_lo; g.W = w.wo; ga.W_lo = w.wo_lo; g.bias = w.bo; g.N = H; g.K = H; g.resid = f.x_c; g.y = f.y_c; g.rstats = nullptr;
+    launch_gemm_split<EPI_RESID>(e, ga, st);
+    ln_split_rows_kernel<<<dim3((unsigned)(f.Mc / 4)), dim3(256), 0, st>>>(f.y_c, f.s.nb, w.ln1g, w.ln1b, e->cfg.ln_eps, nullptr, f.x2_c, f.xb_c, f.xb_c_lo, nullptr, 0, 0);
+    g.A = f.xb_c; ga.A_lo = f.xb_c_lo; g.W = w.w1; ga.W_lo = w.w1_lo; g.bias = w.b1; g.N = FF; g.K = H; g.h = f.h_c; ga.h_lo = f.h_c_lo;
+    launch_gemm_split<EPI_GELU>(e, ga, st);
+    g.A = f.h_c; ga.A_lo = f.h_c_lo; g.W = w.w2; ga.W_lo = w.w2_lo; g.bias = w.b2; g.N = H; g.K = FF; g.resid = f.x2_c; g.y = f.y_c;
+    launch_gemm_split<EPI_RESID>(e, ga, st);
+    ln_split_rows_kernel<<<dim3((unsigned)(f.Mc / 4)), dim3(256), 0, st>>>(f.y_c, f.s.nb, w.ln2g, w.ln2b, e->cfg.ln_eps, nullptr, f.x_c, f.xb_c, f.xb_c_lo, nullptr, 0, 0);
+    return HAC_OK;
+}
+
+// ---- the woven attention's fix-up counts (hac_encoder::pipe_skip_mask), before and behind a forward of the bf16 families
+// returns whether st is being captured (inside a stream capture -- the small-batch graphs -- an event query is an error that kills the capture)
+bool redo_poll(hac_encoder *e, hipStream_t st) {
+    bool capturing = false;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
+    else capturing = cs != hipStreamCaptureStatusNone;
+    if (e->redo_pending && !capturing) {
         const hipError_t qe = hipEventQuery(e->redo_ev);
         if (qe == hipSuccess) {          // the fix-up counts of an earlier forward have arrived (never waited for)
             e->redo_pending = false;
@@ -1871,337 +2190,49 @@ int run_forward(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, flo
         e->forwards_since_retry = 0;
         e->pipe_skip_mask = 0;
     }
-    const long rows_max = rows_hint > 0 ? std::min<long>(rows_hint, (long)B * L32) : (long)B * L32;
-    const long Mp = (rows_max + MT - 1) / MT * MT;
-    HAC_TRY(e->ws_x.reserve((size_t)Mp * H * 4));
-    HAC_TRY(e->ws_y.reserve((size_t)Mp * H * 4));
-    HAC_TRY(e->ws_stats.reserve((size_t)Mp * 8 * 2));
-    HAC_TRY(e->ws_xb.reserve((size_t)Mp * H * 2));
-    HAC_TRY(e->ws_q.reserve((size_t)Mp * H * 2));
-    HAC_TRY(e->ws_k.reserve((size_t)(Mp + 64) * H * 2));
-    HAC_TRY(e->ws_vt.reserve((size_t)H * Mp * 2));
-    HAC_TRY(e->ws_ctx.reserve((size_t)Mp * H * 2));
-    HAC_TRY(e->ws_h.reserve((size_t)Mp * FF * 2));
-    const bool mean = e->pooling == 1;   // every layer on every row, then pool_mean_kernel: no compact tail
-    if (mean) HAC_TRY(e->ws_pool.reserve((size_t)2 * B * H * 4));
-    SeqInfo s;
-    HAC_TRY(seq_layout(e, B, L, s));
-    seq_prep_kernel<IT><<<dim3(B), dim3(512), 0, st>>>(ids, mask, L, s, c.pad_token_id, c.vocab);
-    seq_offsets_kernel<<<dim3(1), dim3(256), 0, st>>>(s, B);
-    attn_order_kernel<<<dim3(1), dim3(256), 0, st>>>(s, B);
-    float *x = (float *)e->ws_x.p, *y = (float *)e->ws_y.p;
-    float2 *statsA = (float2 *)e->ws_stats.p, *statsF = statsA + Mp;
-    bf16 *xb = (bf16 *)e->ws_xb.p, *q = (bf16 *)e->ws_q.p, *k = (bf16 *)e->ws_k.p, *vt = (bf16 *)e->ws_vt.p;
-    bf16 *ctx = (bf16 *)e->ws_ctx.p, *h = (bf16 *)e->ws_h.p;
-    // tile choice: 256^2 tiles once they fill the chip, 128^2 tiles for small batches; persistent grids.
-    // Large batches: the ping-pong GEMM with the LayerNorms folded into the consuming weights (gemm8.inc).  The family -- and
-    // with the classic kernels the tile -- is chosen ONCE per hac_encoder_forward* call, from the whole batch
-    // (forward_batched): a small tail sub-batch of a large forward runs the same kernels as the others, so a sequence's
-    // embedding does not depend on which sub-batch it fell into.
-    if (family < 0) family = pick_family(e, rows_max);
-    const bool g8 = family == FAM_GEMM8;
-    const bool big = family == FAM_CLASSIC256 || (g8 && (Mp / 256) * (H / 256) >= FAMILY_BIG_TILES);
-    // (that path's residual stream is bf16 from the embedding rows on: no fp32 copy of them, 3 KB per token less to write)
-    embed_ln_kernel<IT><<<dim3(L32 / 4, B), dim3(256), 0, st>>>(ids, L, s, e->word, e->posw, e->typew, e->embg, e->embb, c.ln_eps, c.vocab, g8 ? nullptr : x, xb);
-    HAC_HIP(hipGetLastError());
-    const int *total = s.off + B;
-    // dead tail rows of the last M tile (fewer than MT) feed the GEMMs: keep them finite
-    zero_tail_rows_kernel<<<dim3(MT), dim3(192), 0, st>>>(g8 ? nullptr : x, xb, total, Mp);
-    HAC_HIP(hipGetLastError());
-    // (test entry point: the same launches as a forward up to the requested layer, then the unpacked state instead of the rest)
-    auto dump_state = [&](int li) {
-        const bool emb = li < 0;
-        layer_state_kernel<<<dim3((unsigned)L, (unsigned)B), dim3(192), 0, st>>>(g8 ? nullptr : x, xb, emb ? nullptr : statsF,
-                                                                                   emb ? nullptr : e->layers[li].ln2g, emb ? nullptr : e->layers[li].ln2b,
-                                                                                   s, L, dump->rows, dump->stats, dump->norm);
-        e->plan_sub_batches += 1;
-        e->plan_rows += Mp;
-        e->plan_gemm = g8 ? "gemm8" : (big ? "classic256" : "classic128");
-        return hipGetLastError() == hipSuccess ? HAC_OK : fail(HAC_ERR_HIP, "layer_state_kernel launch failed");
-    };
-    if (dump && dump->layer < 0) return dump_state(-1);
-    const int bt = big ? 256 : 128;
-    const size_t lds = (size_t)4 * bt * 128 + (size_t)(big ? 8 : 4) * 4096;   // 2 stages + per-wave patches
-    // Small batches (128^2 tiles): the two RESID GEMMs have only Mp / 128 x 6 output tiles -- 96 for the reference's 4 x 512 query
-    // batch, on 256 CUs -- and walk their whole K behind one exposed load latency per k-tile, so their K loop is split into S
-    // slices (GemmArgs::ksplit; ln_stats_rows_kernel adds the slices up).  How far: a slice more saves k-tiles at ~0.6 us each
-    // and costs one more fp32 copy of the rows written and read back, ~1.3 us per 1000 rows; below 8 (K = 3072) / 4 (K = 768)
-    // k-tiles per item nothing is gained, and more items than workgroup slots (2 per CU) is a second round of them.  The minimum
-    // of that model is within 0.3 % of the best of all 28 (S_out, S_down) pairs at 1 x 256, 4 x 256, 4 x 512, 8 x 384 and 8 x 512
-    // (tools/ks_sweep.py on the whole forward, profiles/r05_ksplit_sweep.txt; tools/probes/gemm_small_probe.hip for the kernels
-    // alone).  Round 4's rule -- split until 1.5 items per CU exist -- went 2-3 x too far on the smallest batches: 1 x 256 ran
-    // 4 / 16 slices (0.962 ms) where 3 / 6 is 0.893.
-    // The split -- i.e. the summation order -- is decided ONCE per hac_encoder_forward* call, from the rows of its first
-    // sub-batch (rows_plan), like the family: a sequence's embedding must not depend on the sub-batch it fell into.
-    const long Mp_plan = rows_plan > 0 ? (rows_plan + MT - 1) / MT * MT : Mp;
-    auto pick_ksplit = [&](int K) {
-        if (g8 || big || e->ksplit_mode == 0) return 1;
-        const int KT = K / 64, min_kt = KT >= 48 ? 8 : 4;
-        const int pin = K == H ? e->ks_pin_out : e->ks_pin_down;
-        if (pin > 0 && KT % pin == 0 && KT / pin >= 3) return pin;
-        const long tiles = (Mp_plan / 128) * (H / 128);
-        int S = 1;
-        double best = KT * 0.6;
-        for (int cand : {2, 3, 4, 6}) {
-            if (KT % cand || KT / cand < min_kt || tiles * cand > 2L * e->n_cu) continue;
-            const double cost = (double)KT / cand * 0.6 + (cand - 1) * (double)Mp_plan * 1.3e-3;
-            if (cost < best) {
-                best = cost;
-                S = cand;
-            }
-        }
-        return S;
-    };
-    const int ks_out = pick_ksplit(H), ks_down = pick_ksplit(FF);
-    e->plan_ks_out = ks_out;
-    e->plan_ks_down = ks_down;
-    const size_t part_stride = (size_t)Mp * H;
-    if (std::max(ks_out, ks_down) > 1) HAC_TRY(e->ws_ksplit.reserve((size_t)(std::max(ks_out, ks_down) - 1) * part_stride * 4));
-    float *kpart = (float *)e->ws_ksplit.p;
-    const dim3 blk(big ? 512 : 256);
-    const unsigned n_wg = (unsigned)(e->n_cu * (big ? 1 : 2));
-#define HAC_GEMM(EPI, CLS)                                                            \
-    do {                                                                              \
-        HAC_TRY(prof_begin(e, 1 + (CLS), st));                                        \
-        if (big) gemm_bf16_nt_kernel<EPI, 4><<<dim3(n_wg), blk, lds, st>>>(g);         \
-        else gemm_bf16_nt_kernel<EPI, 2><<<dim3(n_wg), blk, lds, st>>>(g);             \
-        HAC_TRY(prof_end(e, 1 + (CLS), st));                                          \
-    } while (0)
-    bf16 *yAb = nullptr;
-    float2 *part = nullptr, *idstats = nullptr;
-    if (g8) {
-        HAC_TRY(e->ws_yb.reserve((size_t)Mp * H * 2));
-        HAC_TRY(e->ws_part.reserve((size_t)Mp * (H / 64) * 8));
-        if (e->idstats_rows < (size_t)Mp) {
-            HAC_TRY(e->ws_idstats.reserve((size_t)Mp * 8));
-            e->idstats_rows = e->ws_idstats.cap / 8;
-            fill_identity_stats_kernel<<<dim3((unsigned)((e->idstats_rows + 255) / 256)), dim3(256), 0, st>>>((float2 *)e->ws_idstats.p, e->idstats_rows);
-            HAC_HIP(hipGetLastError());
-        }
-        yAb = (bf16 *)e->ws_yb.p;
-        part = (float2 *)e->ws_part.p;
-        idstats = (float2 *)e->ws_idstats.p;
-        if (!e->ws_identgb.p) {   // gamma = 1 | beta = 0: residual rows that are final (layer 0's embedding rows) take the same epilogue
-            HAC_TRY(e->ws_identgb.reserve((size_t)2 * H * 4));
-            std::vector<float> gb((size_t)2 * H, 0.f);
-            std::fill(gb.begin(), gb.begin() + H, 1.f);
-            HAC_HIP(hipMemcpy(e->ws_identgb.p, gb.data(), gb.size() * 4, hipMemcpyHostToDevice));
-        }
-    }
+    return capturing;
+}
+int redo_fetch(hac_encoder *e, const Fwd &f, bool capturing) {
+    if (!e->plan.attn_pipe || e->attn_pipe >= 0 || e->redo_pending || capturing) return HAC_OK;
+    if (!e->h_redo) HAC_HIP(hipHostMalloc((void **)&e->h_redo, 64, hipHostMallocDefault));
+    if (!e->redo_ev) HAC_HIP(hipEventCreateWithFlags(&e->redo_ev, hipEventDisableTiming));
+    HAC_HIP(hipMemcpyAsync(e->h_redo, e->ws_redo.p, 64, hipMemcpyDeviceToHost, f.st));
+    HAC_HIP(hipEventRecord(e->redo_ev, f.st));
+    e->redo_pending = true;
+    e->redo_items = (long)f.B * NH;
+    return HAC_OK;
+}
+
+// One (sub-)batch: embedding LN -> [QKV -> attention -> out-proj + residual -> LN statistics -> FFN-up -> FFN-down + residual -> LN
+// statistics] per layer -- the last one on the <s> rows with the compact tail unless pooling = mean -> fp32 head.
+// dump: stop behind that layer (hac_encoder_layer_state).  A split forward never reaches the woven attention: no redo bookkeeping.
+template <typename IT>
+int run_forward(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, float *out_dev, hipStream_t st, long rows_hint = 0, int family = -1,
+                long rows_plan = 0, const LayerDump *dump = nullptr) {
+    const bool split = e->precision == 1, embed_only = dump && dump->layer < 0;
+    const bool capturing = split ? false : redo_poll(e, st);
+    Fwd f;
+    HAC_TRY(fwd_build<IT>(e, ids, mask, B, L, st, rows_hint, family, rows_plan, embed_only, f));
+    if (embed_only) return dump_state(e, f, *dump, -1);
     HAC_TRY(prof_begin(e, 0, st));
-    // compact buffers of the CLS-only tail of the last layer
-    const long Mc = ((long)B + MT - 1) / MT * MT;
-    bf16 *ctx_c = nullptr, *xb_c = nullptr, *h_c = nullptr;
-    float *x_c = nullptr, *y_c = nullptr, *x2_c = nullptr;
-    if (!mean) {   // (pooling = mean has no last-layer special case: nothing reserved, no pointer formed)
-        HAC_TRY(e->ws_cls.reserve((size_t)Mc * (H * 2 + H * 4 * 3 + H * 2 + FF * 2)));
-        ctx_c = (bf16 *)e->ws_cls.p;
-        x_c = (float *)(ctx_c + Mc * H);
-        y_c = x_c + Mc * H;
-        x2_c = y_c + Mc * H;
-        xb_c = (bf16 *)(x2_c + Mc * H);
-        h_c = xb_c + Mc * H;
-    }
-    for (int li = 0; li < c.n_layers; ++li) {
-        const LayerW &w = e->layers[li];
-        const bool last = !mean && (li == c.n_layers - 1);
-        GemmArgs g{};
-        g.total_rows = total;
-        Gemm8Args g8a{};
-        g8a.total_rows = total;
-        g8a.n_groups = 1;
-        const int ng_up = 2;   // FFN-up: W1' is 4.7 MB against 4 MB of L2 per XCD; each XCD owns half of its column tiles (measured: -2 %)
-        const dim3 grid8((unsigned)e->n_cu), blk8(512);
-        // Phased starts (Gemm8Args::stagger): workgroups that start together stay together -- every tile takes the same time --
-        // and reach their epilogues, the phases that write (and, RESID, read) the residual stream, all at once.  Delaying the
-        // XCDs by 0..3 quarter-steps at the start spreads those bursts: QKV -3.8 % and out-proj -3.5 % at 512000 rows
-        // (tools/probes/gemm8_stagger_probe.hip: 1.786 -> 1.718 ms, 0.803 -> 0.775 ms); the FFN classes did not move (their
-        // tile times are longer and already drift apart) and stay unphased.  Only on runs of >= 16 tiles per workgroup: the
-        // delay (<= 3 steps of ~1 us x stagger) is paid once per launch.
-        auto stagger8 = [&](int N, int n_tile0, int steps) {
-            const long tiles = (Mp / 256) * (long)(N / 256 - n_tile0);
-            g8a.stagger = (e->g8_stagger != 0 && tiles >= 16L * e->n_cu) ? steps : 0;
-            g8a.stagger_mode = 0;
-        };
-        // (non-temporal output stores for the q / k / v and h streams, not for the residual stream: see g8_store16)
-        auto launch8 = [&](auto epi) {
-            constexpr int EPI = decltype(epi)::value;
-            gemm8_kernel<EPI, EPI != EPI8_RESID><<<grid8, blk8, 163840, st>>>(g8a);
-        };
-        constexpr std::integral_constant<int, EPI8_QKV> epi_qkv{};
-        constexpr std::integral_constant<int, EPI8_RESID> epi_resid{};
-        constexpr std::integral_constant<int, EPI8_GELU> epi_gelu{};
-        // QKV
-        if (g8) {
-            // A = the previous layer's un-normalized output rows (bf16) + their statistics; layer 0: the normalized embedding rows
-            HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_QKV, st));
-            g8a.A = xb; g8a.K = H; g8a.astats = li ? statsF : idstats;
-            g8a.W = w.wqkv8; g8a.N = 3 * H; g8a.wsum = w.fold; g8a.cvec = w.fold + 3 * H; g8a.q = q; g8a.k = k; g8a.v16 = vt;
-            // last layer: keys and values of every row, queries of the <s> rows only (a third of the GEMM: 0.6 ms per 1000 x 512 forward)
-            g8a.n_tile0 = last ? H / 256 : 0;
-            stagger8(3 * H, g8a.n_tile0, 6);
-            launch8(epi_qkv);
-            g8a.n_tile0 = 0;
-            g8a.stagger = 0;
-            if (last) cls_q_kernel<<<dim3((unsigned)((B + CLS_SB - 1) / CLS_SB), H / CLS_NS), dim3(256), 0, st>>>(xb, g8a.astats, s, B, w.wqkv8, w.fold, w.fold + 3 * H, q);
-            HAC_TRY(prof_end(e, 1 + HAC_ENC_CLASS_QKV, st));
-        } else {
-            g.A = xb; g.W = w.wqkv; g.bias = w.bqkv; g.N = 3 * H; g.K = H; g.q = q; g.k = k; g.v16 = vt;
-            HAC_GEMM(EPI_QKV, HAC_ENC_CLASS_QKV);
-        }
-        // (streaming kernels: few sequences -> an item's query rows go to 2 or 4 workgroups while B * NH * qsplit items still fit the CUs)
-        int att_qs = 1;
-        while (e->attn_qsplit != 0 && att_qs < 16 && (long)B * NH * att_qs * 2 <= e->n_cu) att_qs *= 2;
-        if (e->attn_qs_pin > 0) att_qs = e->attn_qs_pin;   // development (tools/ks_sweep.py attn)
-        const bool att_one = att_qs > 1 && L32 > 256;   // few sequences: one launch (an empty second one is 5 us of a ~100-us layer)
-        AttnArgs a{q, k, vt, ctx, s, last ? 1 : 0, att_qs, att_one ? 1 : 0, nullptr, nullptr, 0};
-        if (li == 0) e->plan_attn_pipe = 0;
-        // (measured, 512 sequences of one length, woven / one-block: 512 rows 0.475 / 0.589 ms, 448 rows 0.413 / 0.507, 384 rows 0.313 / 0.373;
-        // 256 rows 0.174 / 0.174, 128 rows 0.086 / 0.086 -- the 8-wave instantiation wins wherever it applies, the 4-wave one ties: the woven
-        // form takes the long class (sequences of more than 256 rows), the one-block kernel the short class; same bits either way)
-        const bool att_pipe = e->attn_mode == 0 && e->attn_pipe != 0 && att_qs == 1 && !last && (L32 > 256 || e->attn_pipe > 0) &&
-                              !(e->attn_pipe < 0 && ((e->pipe_skip_mask >> li) & 1u));      // ("all" pins the woven form: tests of the fix-up pass)
-        if (att_pipe) {
-            if (!e->plan_attn_pipe) {      // the forward's first woven layer: workspace, per-layer counts to zero (the flags are zero whenever no pass is pending)
-                HAC_TRY(e->ws_redo.reserve(((size_t)B * NH + 16) * 4));
-                HAC_HIP(hipMemsetAsync(e->ws_redo.p, 0, 64, st));
-            }
-            a.redo_count = (int *)e->ws_redo.p + (li & 15);
-            a.redo_flags = (int *)e->ws_redo.p + 16;
-        }
-        // sequences of <= 256 rows: 4-wave workgroups; longer ones: 8-wave workgroups (each skips the other's)
-        HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_ATTN, st));
-        if (e->attn_mode == 0) {           // persistent streaming kernels, one launch per length class
-            if (att_pipe) {   // whole items: the woven two-blocks-per-wave form, then the items it flagged through the one-block kernels (bit-identical results)
-                const bool both = e->attn_pipe > 0;   // "all" (tests): the short class through the 4-wave instantiation too
-                if (L32 > 256) attention_pipe_kernel<8><<<dim3(e->n_cu), dim3(512), 163840, st>>>(a);
-                if (both) attention_pipe_kernel<4><<<dim3(2 * e->n_cu), dim3(256), 81920, st>>>(a);
-                else attention_stream_kernel<8><<<dim3(2 * e->n_cu), dim3(512), 81920, st>>>(a);
-                a.fixup = 1;
-                if (L32 > 256) attention_stream_kernel<16><<<dim3(e->n_cu), dim3(1024), 163840, st>>>(a);
-                if (both) attention_stream_kernel<8><<<dim3(2 * e->n_cu), dim3(512), 81920, st>>>(a);
-                e->plan_attn_pipe = 1;
-            } else {
-                if (L32 > 256) attention_stream_kernel<16><<<dim3(e->n_cu), dim3(1024), 163840, st>>>(a);
-                if (!att_one) attention_stream_kernel<8><<<dim3(2 * e->n_cu), dim3(512), 81920, st>>>(a);
-            }
-        } else {                           // two-pass kernels, one workgroup per (sequence, head): kept as a cross-check
-            attention_kernel<8, 1><<<dim3(NH, B), dim3(512), (size_t)(L32 < 256 ? L32 : 256) * 256, st>>>(a);
-            if (L32 > 256) attention_kernel<16, 1><<<dim3(NH, B), dim3(1024), (size_t)L32 * 256, st>>>(a);
-        }
-        HAC_TRY(prof_end(e, 1 + HAC_ENC_CLASS_ATTN, st));
-        // Residual stream between layers: layer 0 reads the embedding rows x (normalized); afterwards the
-        // stream lives as pre-LayerNorm rows + (mean, rstd): yF/statsF after a layer's FFN, yA/statsA after its
-        // attention block.  yF shares x's buffer (x is dead once layer 0's out-projection has read it).
-        const bool defer_in = li > 0;
-        const float *ln2g_prev = defer_in ? e->layers[li - 1].ln2g : nullptr, *ln2b_prev = defer_in ? e->layers[li - 1].ln2b : nullptr;
-        if (!last && g8) {
-            // attention output projection + residual -> yA (bf16) and row-sum partials of its fp32 values -> (mean, rstd)
-            g8a.A = ctx; g8a.W = w.wo; g8a.N = H; g8a.K = H; g8a.cvec = w.bo; g8a.resid = xb; g8a.yb = yAb; g8a.part = part;
-            g8a.rstats = defer_in ? statsF : idstats;
-            g8a.rgamma = defer_in ? ln2g_prev : (const float *)e->ws_identgb.p;
-            g8a.rbeta = defer_in ? ln2b_prev : (const float *)e->ws_identgb.p + H;
-            HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_OUTPROJ, st));
-            stagger8(H, 0, 8);
-            launch8(epi_resid);
-            g8a.stagger = 0;
-            HAC_TRY(prof_end(e, 1 + HAC_ENC_CLASS_OUTPROJ, st));
-            HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_LN, st));
-            ln_combine_kernel<<<dim3((unsigned)(Mp / 256)), dim3(256), 0, st>>>(part, H / 64, H, total, c.ln_eps, statsA);
-            HAC_TRY(prof_end(e, 1 + HAC_ENC_CLASS_LN, st));
-            // FFN up: A = bf16(yA), the attention LayerNorm folded into W1
-            g8a.A = yAb; g8a.astats = statsA; g8a.W = w.w18; g8a.N = FF; g8a.K = H; g8a.wsum = w.fold + 6 * H; g8a.cvec = w.fold + 6 * H + FF; g8a.h = h;
-            g8a.n_groups = ng_up;
-            if (e->prof_mask >> 1) {   // class profiling on: this launch also reads the clock counters (hac_encoder_last_clock)
-                HAC_TRY(e->ws_clk.reserve(32));
-                g8a.clk = (unsigned long long *)e->ws_clk.p;
-                e->clk_valid = true;
-            }
-            HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_FFN_UP, st));
-            launch8(epi_gelu);
-            if (g8a.clk) {      // (class profiling is never on inside a captured forward: graph_usable)
-                if (!e->clk_ev) HAC_HIP(hipEventCreateWithFlags(&e->clk_ev, hipEventDisableTiming));
-                HAC_HIP(hipEventRecord(e->clk_ev, st));
-            }
-            g8a.clk = nullptr;
-            HAC_TRY(prof_end(e, 1 + HAC_ENC_CLASS_FFN_UP, st));
-            g8a.n_groups = 1;
-            // FFN down + residual LN1(yA) -> yF (bf16, in xb's buffer: the next layer's A operand and residual), partials
-            g8a.A = h; g8a.W = w.w2; g8a.N = H; g8a.K = FF; g8a.cvec = w.b2; g8a.resid = yAb; g8a.yb = xb;
-            g8a.rstats = statsA; g8a.rgamma = w.ln1g; g8a.rbeta = w.ln1b;
-            HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_FFN_DOWN, st));
-            launch8(epi_resid);
-            HAC_TRY(prof_end(e, 1 + HAC_ENC_CLASS_FFN_DOWN, st));
-            HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_LN, st));
-            ln_combine_kernel<<<dim3((unsigned)(Mp / 256)), dim3(256), 0, st>>>(part, H / 64, H, total, c.ln_eps, statsF);
-            HAC_TRY(prof_end(e, 1 + HAC_ENC_CLASS_LN, st));
-        } else if (!last) {
-            // attention output projection + residual, LN statistics
-            g.A = ctx; g.W = w.wo; g.bias = w.bo; g.N = H; g.K = H; g.resid = x; g.y = y;
-            g.rstats = defer_in ? statsF : nullptr; g.rgamma = ln2g_prev; g.rbeta = ln2b_prev;
-            g.ksplit = ks_out; g.part = kpart; g.part_stride = part_stride;
-            HAC_GEMM(EPI_RESID, HAC_ENC_CLASS_OUTPROJ);
-            g.ksplit = 1;
-            HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_LN, st));
-            ln_stats_rows_kernel<<<dim3((unsigned)(Mp / 4)), dim3(256), 0, st>>>(y, total, w.ln1g, w.ln1b, c.ln_eps, statsA, xb, kpart, ks_out - 1, part_stride);
-            HAC_TRY(prof_end(e, 1 + HAC_ENC_CLASS_LN, st));
-
-            // FFN
-            g.A = xb; g.W = w.w1; g.bias = w.b1; g.N = FF; g.K = H; g.h = h;
-            HAC_GEMM(EPI_GELU, HAC_ENC_CLASS_FFN_UP);
-            g.A = h; g.W = w.w2; g.bias = w.b2; g.N = H; g.K = FF; g.resid = y; g.y = x;
-            g.rstats = statsA; g.rgamma = w.ln1g; g.rbeta = w.ln1b;
-            g.ksplit = ks_down; g.part = kpart; g.part_stride = part_stride;
-            HAC_GEMM(EPI_RESID, HAC_ENC_CLASS_FFN_DOWN);
-            g.ksplit = 1;
-            HAC_TRY(prof_begin(e, 1 + HAC_ENC_CLASS_LN, st));
-            ln_stats_rows_kernel<<<dim3((unsigned)(Mp / 4)), dim3(256), 0, st>>>(x, total, w.ln2g, w.ln2b, c.ln_eps, statsF, xb, kpart, ks_down - 1, part_stride);
-            HAC_TRY(prof_end(e, 1 + HAC_ENC_CLASS_LN, st));
-
-        } else {
-            // only the <s> row of every sequence continues (B rows instead of T): same kernels, compact matrices
-            gather_cls_kernel<<<dim3((unsigned)Mc), dim3(256), 0, st>>>(ctx, x, g8 ? xb : nullptr, defer_in ? statsF : nullptr, ln2g_prev, ln2b_prev, s, B, ctx_c, x_c);
-            const size_t lds_s = (size_t)4 * 128 * 128 + (size_t)4 * 4096;
-            const dim3 grid_s((unsigned)(e->n_cu * 2)), blk_s(256);
-            g.total_rows = s.nb;
-            g.A = ctx_c; g.W = w.wo; g.bias = w.bo; g.N = H; g.K = H; g.resid = x_c; g.y = y_c; g.rstats = nullptr;
-            gemm_bf16_nt_kernel<EPI_RESID, 2><<<grid_s, blk_s, lds_s, st>>>(g);
-            ln_rows_kernel<<<dim3((unsigned)(Mc / 4)), dim3(256), 0, st>>>(y_c, s.nb, w.ln1g, w.ln1b, c.ln_eps, x2_c, xb_c);
-            g.A = xb_c; g.W = w.w1; g.bias = w.b1; g.N = FF; g.K = H; g.h = h_c;
-            gemm_bf16_nt_kernel<EPI_GELU, 2><<<grid_s, blk_s, lds_s, st>>>(g);
-            g.A = h_c; g.W = w.w2; g.bias = w.b2; g.N = H; g.K = FF; g.resid = x2_c; g.y = y_c;
-            gemm_bf16_nt_kernel<EPI_RESID, 2><<<grid_s, blk_s, lds_s, st>>>(g);
-            ln_rows_kernel<<<dim3((unsigned)(Mc / 4)), dim3(256), 0, st>>>(y_c, s.nb, w.ln2g, w.ln2b, c.ln_eps, x_c, xb_c);
+    for (int li = 0; li < e->cfg.n_layers; ++li) {
+        const bool last = !f.mean && li == e->cfg.n_layers - 1;
+        switch (f.family) {
+        case FAM_SPLIT: HAC_TRY(last ? tail_split(e, f, li) : layer_split(e, f, li)); break;
+        case FAM_GEMM8: HAC_TRY(last ? tail_classic(e, f, li) : layer_gemm8(e, f, li)); break;
+        default: HAC_TRY(last ? tail_classic(e, f, li) : layer_classic(e, f, li));
         }
         HAC_HIP(hipGetLastError());
-        if (dump && dump->layer == li) return dump_state(li);
+        if (dump && dump->layer == li) return dump_state(e, f, *dump, li);
     }
-#undef HAC_GEMM
     HAC_TRY(prof_end(e, 0, st));
-    if (mean) {
-        // the stream after the last layer: un-normalized rows (gemm8: bf16 in xb; classic: fp32 in x) + statsF, as a next layer would read them
-        if (g8) HAC_TRY(pool_and_head<bf16>(e, xb, statsF, s, B, out_dev, st));
-        else HAC_TRY(pool_and_head<float>(e, x, statsF, s, B, out_dev, st));
-    } else {
-        // ANCE head on the compact <s> rows: projection (y_c is free again), then LayerNorm_768 and the per-sequence error flag
-        const int head_ns = B <= 64 ? 8 : CLS_NS;
-        cls_head_proj_kernel<<<dim3((unsigned)((B + CLS_SB - 1) / CLS_SB), H / head_ns), dim3(256), 0, st>>>(x_c, s, 1, B, e->wh, e->bh, y_c, head_ns);
-        cls_head_norm_kernel<<<dim3((unsigned)B), dim3(256), 0, st>>>(y_c, s, e->ng, e->nb, 1e-5f, out_dev);
-        HAC_HIP(hipGetLastError());
-    }
-    if (e->plan_attn_pipe && e->attn_pipe < 0 && !e->redo_pending) {
-        if (!fw_capturing) {
-            if (!e->h_redo) HAC_HIP(hipHostMalloc((void **)&e->h_redo, 64, hipHostMallocDefault));
-            if (!e->redo_ev) HAC_HIP(hipEventCreateWithFlags(&e->redo_ev, hipEventDisableTiming));
-            HAC_HIP(hipMemcpyAsync(e->h_redo, e->ws_redo.p, 64, hipMemcpyDeviceToHost, st));
-            HAC_HIP(hipEventRecord(e->redo_ev, st));
-            e->redo_pending = true;
-            e->redo_items = (long)B * NH;
-        }
-    }
-    e->plan_sub_batches += 1;
-    e->plan_rows += Mp;
-    e->plan_gemm = g8 ? "gemm8" : (big ? "classic256" : "classic128");
+    // mean: the stream after the last layer, un-normalized rows (gemm8: bf16 in xb; otherwise fp32 in x) + statsF, as a next layer would
+    // read them.  first: the ANCE head on the compact <s> rows (y_c is free again).
+    if (f.mean && f.family == FAM_GEMM8) HAC_TRY(pool_and_head<bf16>(e, f.xb, f.statsF, f.s, B, out_dev, st));
+    else if (f.mean) HAC_TRY(pool_and_head<float>(e, f.x, f.statsF, f.s, B, out_dev, st));
+    else HAC_TRY(launch_head(e, f.x_c, f.y_c, f.s, B, out_dev, st));
+    if (!split) HAC_TRY(redo_fetch(e, f, capturing));
+    plan_add(e, f);
     return HAC_OK;
 }
 
@@ -2233,11 +2264,29 @@ void drop_graphs(hac_encoder *e) {
 constexpr size_t GRAPH_MAX_SHAPES = 64;   // captured (B, L, options) shapes kept per encoder
 bool graph_eligible(const hac_encoder *e, int B, int L, hipStream_t st) {
     if (e->graph_mode == 0 || e->prof_mask != 0) return false;
-    const int L32 = (L + SEQ_ALIGN - 1) / SEQ_ALIGN * SEQ_ALIGN;
-    if ((long)B * L32 > GRAPH_MAX_ROWS || (long)B * L32 > e->max_tokens) return false;   // (beyond max_tokens the call is cut into sub-batches)
+    if ((long)B * pad_len(L) > GRAPH_MAX_ROWS || (long)B * pad_len(L) > e->max_tokens) return false;   // (beyond max_tokens the call is cut into sub-batches)
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return false;   // the caller captures: plain launches
     return true;
+}
+// captures the forward of ge's shape on the encoder's own stream, in place of what ge held
+template <typename IT>
+int graph_capture(hac_encoder *e, hac_encoder::GraphEntry &ge, const IT *gids, const IT *gmask, int B, int L, float *gout) {
+    if (ge.exec) graphs_quiesce(e);
+    if (ge.exec) (void)hipGraphExecDestroy(ge.exec);
+    if (ge.graph) (void)hipGraphDestroy(ge.graph);
+    ge.exec = nullptr;
+    ge.graph = nullptr;
+    HAC_HIP(hipStreamSynchronize(e->stream));
+    HAC_HIP(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
+    const int rc = run_forward<IT>(e, gids, gmask, B, L, gout, e->stream);
+    const hipError_t ce = hipStreamEndCapture(e->stream, &ge.graph);
+    if (rc != HAC_OK) return rc;
+    if (ce != hipSuccess || !ge.graph) return fail(HAC_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
+    HAC_HIP(hipGraphInstantiate(&ge.exec, ge.graph, nullptr, nullptr, 0));
+    ge.sig = ws_signature(e);
+    ge.plan = e->plan;
+    return HAC_OK;
 }
 template <typename IT>
 int forward_graph(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, float *out_dev, hipStream_t st) {
@@ -2257,54 +2306,21 @@ int forward_graph(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, f
     float *gout = (float *)e->ws_gout.p;
     HAC_HIP(hipMemcpyAsync(e->ws_gids.p, ids, n_in, hipMemcpyDeviceToDevice, st));
     HAC_HIP(hipMemcpyAsync(e->ws_gmask.p, mask, n_in, hipMemcpyDeviceToDevice, st));
-    e->plan_sub_batches = 1;
     if (ge.seen == 0) {
         // first call of this shape: plain launches through the private buffers -- sizes every workspace (no allocation may
         // happen inside a capture) and is a valid forward by itself
-        e->plan_rows = 0;
         HAC_TRY(run_forward<IT>(e, gids, gmask, B, L, gout, st));
         ge.seen = 1;
-        ge.gemm = e->plan_gemm;
-        ge.rows = e->plan_rows;
-        ge.ks_out = e->plan_ks_out;
-        ge.ks_down = e->plan_ks_down;
-        ge.attn_pipe = e->plan_attn_pipe;
-        e->plan_sub_batches = 1;
-        e->plan_graph = "eager-first";
+        e->plan.graph = "eager-first";
     } else {
-        if (!ge.exec || ge.sig != ws_signature(e)) {
-            // (a larger forward in between may have regrown a workspace: the captured launches hold the old pointers)
-            if (ge.exec) graphs_quiesce(e);
-            if (ge.exec) (void)hipGraphExecDestroy(ge.exec);
-            if (ge.graph) (void)hipGraphDestroy(ge.graph);
-            ge.exec = nullptr;
-            ge.graph = nullptr;
-            HAC_HIP(hipStreamSynchronize(e->stream));
-            HAC_HIP(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-            e->plan_rows = 0;
-            const int rc = run_forward<IT>(e, gids, gmask, B, L, gout, e->stream);
-            const hipError_t ce = hipStreamEndCapture(e->stream, &ge.graph);
-            e->plan_sub_batches = 1;
-            if (rc != HAC_OK) return rc;
-            if (ce != hipSuccess || !ge.graph) return fail(HAC_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
-            HAC_HIP(hipGraphInstantiate(&ge.exec, ge.graph, nullptr, nullptr, 0));
-            ge.sig = ws_signature(e);
-            ge.gemm = e->plan_gemm;
-            ge.rows = e->plan_rows;
-            ge.ks_out = e->plan_ks_out;
-            ge.ks_down = e->plan_ks_down;
-            ge.attn_pipe = e->plan_attn_pipe;
-        }
+        // (a larger forward in between may have regrown a workspace: the captured launches hold the old pointers)
+        if (!ge.exec || ge.sig != ws_signature(e)) HAC_TRY(graph_capture<IT>(e, ge, gids, gmask, B, L, gout));
         HAC_HIP(hipGraphLaunch(ge.exec, st));
         if (!e->graph_done) HAC_HIP(hipEventCreateWithFlags(&e->graph_done, hipEventDisableTiming));
         HAC_HIP(hipEventRecord(e->graph_done, st));
         e->graph_done_armed = true;
-        e->plan_gemm = ge.gemm;
-        e->plan_rows = ge.rows;
-        e->plan_ks_out = ge.ks_out;
-        e->plan_ks_down = ge.ks_down;
-        e->plan_attn_pipe = ge.attn_pipe;
-        e->plan_graph = "replay";
+        e->plan = ge.plan;
+        e->plan.graph = "replay";
     }
     HAC_HIP(hipMemcpyAsync(out_dev, gout, n_out, hipMemcpyDeviceToDevice, st));
     return HAC_OK;
@@ -2312,13 +2328,8 @@ int forward_graph(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, f
 
 template <typename IT>
 int forward_batched(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, float *out_dev, hipStream_t st) {
-    const int L32 = (L + SEQ_ALIGN - 1) / SEQ_ALIGN * SEQ_ALIGN;
-    e->plan_sub_batches = 0;
-    e->plan_rows = 0;
-    e->plan_graph = "off";
-    e->plan_precision = e->precision;
-    e->plan_pooling = e->pooling;
-    if (e->precision == 1) HAC_TRY(ensure_split_weights(e));
+    const int L32 = pad_len(L);
+    HAC_TRY(begin_call(e));
     if (graph_eligible(e, B, L, st)) return forward_graph<IT>(e, ids, mask, B, L, out_dev, st);
     if ((long)B * L32 <= e->max_tokens) return run_forward<IT>(e, ids, mask, B, L, out_dev, st);
     // More rows than one pass holds if every sequence were full length: size the sub-batches by the REAL padded
@@ -2360,6 +2371,77 @@ int forward_batched(hac_encoder *e, const IT *ids, const IT *mask, int B, int L,
     return HAC_OK;
 }
 
+// the packed bf16 weights of layer i, and their LayerNorm-folded forms for gemm8, from the checkpoint's fp32 tensors
+int finalize_layer(hac_encoder *e, int i) {
+    const std::string q = "roberta.encoder.layer." + std::to_string(i) + ".";
+    LayerW &l = e->layers[i];
+    float *wq, *wk, *wv, *bq, *bk, *bv, *t;
+    HAC_TRY(get_raw(e, q + "attention.self.query.weight", (size_t)H * H, &wq));
+    HAC_TRY(get_raw(e, q + "attention.self.key.weight", (size_t)H * H, &wk));
+    HAC_TRY(get_raw(e, q + "attention.self.value.weight", (size_t)H * H, &wv));
+    HAC_TRY(get_raw(e, q + "attention.self.query.bias", H, &bq));
+    HAC_TRY(get_raw(e, q + "attention.self.key.bias", H, &bk));
+    HAC_TRY(get_raw(e, q + "attention.self.value.bias", H, &bv));
+    HAC_HIP(hipMalloc((void **)&l.wqkv, (size_t)3 * H * H * sizeof(bf16)));
+    HAC_HIP(hipMalloc((void **)&l.bqkv, (size_t)3 * H * 4));
+    const float *ws[3] = {wq, wk, wv};
+    const float *bs[3] = {bq, bk, bv};
+    for (int j = 0; j < 3; ++j) {
+        f32_to_bf16_kernel<<<dim3((unsigned)(((size_t)H * H + 255) / 256)), dim3(256), 0, e->stream>>>(ws[j], l.wqkv + (size_t)j * H * H, (size_t)H * H);
+        HAC_HIP(hipMemcpyAsync(l.bqkv + j * H, bs[j], H * 4, hipMemcpyDeviceToDevice, e->stream));
+    }
+    HAC_TRY(get_raw(e, q + "attention.output.dense.weight", (size_t)H * H, &t));
+    HAC_TRY(to_bf16(e, t, (size_t)H * H, &l.wo));
+    HAC_TRY(get_raw(e, q + "attention.output.dense.bias", H, &l.bo));
+    HAC_TRY(get_raw(e, q + "attention.output.LayerNorm.weight", H, &l.ln1g));
+    HAC_TRY(get_raw(e, q + "attention.output.LayerNorm.bias", H, &l.ln1b));
+    HAC_TRY(get_raw(e, q + "intermediate.dense.weight", (size_t)FF * H, &t));
+    HAC_TRY(to_bf16(e, t, (size_t)FF * H, &l.w1));
+    HAC_TRY(get_raw(e, q + "intermediate.dense.bias", FF, &l.b1));
+    HAC_TRY(get_raw(e, q + "output.dense.weight", (size_t)H * FF, &t));
+    HAC_TRY(to_bf16(e, t, (size_t)H * FF, &l.w2));
+    HAC_TRY(get_raw(e, q + "output.dense.bias", H, &l.b2));
+    HAC_TRY(get_raw(e, q + "output.LayerNorm.weight", H, &l.ln2g));
+    HAC_TRY(get_raw(e, q + "output.LayerNorm.bias", H, &l.ln2b));
+    // large-batch path: fold the LayerNorm in front of QKV (the previous layer's output LayerNorm; layer 0 reads the
+    // already normalized embedding rows) and the one in front of FFN-up (this layer's attention LayerNorm)
+    HAC_HIP(hipMalloc((void **)&l.wqkv8, (size_t)3 * H * H * sizeof(bf16)));
+    HAC_HIP(hipMalloc((void **)&l.w18, (size_t)FF * H * sizeof(bf16)));
+    HAC_HIP(hipMalloc((void **)&l.fold, (size_t)(2 * 3 * H + 2 * FF) * 4));
+    const float *pg = i ? e->layers[i - 1].ln2g : nullptr, *pb = i ? e->layers[i - 1].ln2b : nullptr;
+    const float qscale = 0.125f * 1.44269504088896341f;   // softmax scale / ln 2: the attention kernel works in base 2
+    for (int j = 0; j < 3; ++j)
+        fold_ln_kernel<<<dim3(H), dim3(256), 0, e->stream>>>(ws[j], bs[j], pg, pb, H, j == 0 ? qscale : 1.0f, l.wqkv8 + (size_t)j * H * H,
+                                                             l.fold + j * H, l.fold + 3 * H + j * H);
+    HAC_TRY(get_raw(e, q + "intermediate.dense.weight", (size_t)FF * H, &t));
+    fold_ln_kernel<<<dim3(FF), dim3(256), 0, e->stream>>>(t, l.b1, l.ln1g, l.ln1b, H, 1.0f, l.w18, l.fold + 6 * H, l.fold + 6 * H + FF);
+    HAC_HIP(hipGetLastError());
+    return HAC_OK;
+}
+
+// every kernel launched with more than 64 KB of dynamic LDS
+void raise_lds_limits() {
+    (void)hipFuncSetAttribute((const void *)attention_kernel<8, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    (void)hipFuncSetAttribute((const void *)attention_kernel<16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+    (void)hipFuncSetAttribute((const void *)attention_stream_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
+    (void)hipFuncSetAttribute((const void *)attention_stream_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
+    (void)hipFuncSetAttribute((const void *)attention_pipe_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
+    (void)hipFuncSetAttribute((const void *)attention_pipe_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
+    (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_QKV, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
+    (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_RESID, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
+    (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_GELU, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
+    (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_QKV, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
+    (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_RESID, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
+    (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_GELU, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
+    (void)hipFuncSetAttribute((const void *)gemm_split_nt_kernel<EPI_QKV>, hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_GEMM_LDS);
+    (void)hipFuncSetAttribute((const void *)gemm_split_nt_kernel<EPI_RESID>, hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_GEMM_LDS);
+    (void)hipFuncSetAttribute((const void *)gemm_split_nt_kernel<EPI_GELU>, hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_GEMM_LDS);
+    (void)hipFuncSetAttribute((const void *)attention_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * ATS_STAGE);
+    (void)hipFuncSetAttribute((const void *)gemm8_kernel<EPI8_QKV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
+    (void)hipFuncSetAttribute((const void *)gemm8_kernel<EPI8_RESID, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
+    (void)hipFuncSetAttribute((const void *)gemm8_kernel<EPI8_GELU, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2384,32 +2466,11 @@ int hac_encoder_create(const hac_encoder_config *cfg, int device, hac_encoder **
         delete e;
         return fail(HAC_ERR_HIP, "hipStreamCreate failed");
     }
-    (void)hipFuncSetAttribute((const void *)attention_kernel<8, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void *)attention_kernel<16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    (void)hipFuncSetAttribute((const void *)attention_stream_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
-    (void)hipFuncSetAttribute((const void *)attention_stream_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    (void)hipFuncSetAttribute((const void *)attention_pipe_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
-    (void)hipFuncSetAttribute((const void *)attention_pipe_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_QKV, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
-    (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_RESID, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
-    (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_GELU, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
-    (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_QKV, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_RESID, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_GELU, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    (void)hipFuncSetAttribute((const void *)gemm_split_nt_kernel<EPI_QKV>, hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_GEMM_LDS);
-    (void)hipFuncSetAttribute((const void *)gemm_split_nt_kernel<EPI_RESID>, hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_GEMM_LDS);
-    (void)hipFuncSetAttribute((const void *)gemm_split_nt_kernel<EPI_GELU>, hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_GEMM_LDS);
-    (void)hipFuncSetAttribute((const void *)attention_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * ATS_STAGE);
-    (void)hipFuncSetAttribute((const void *)gemm8_kernel<EPI8_QKV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    (void)hipFuncSetAttribute((const void *)gemm8_kernel<EPI8_RESID, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    (void)hipFuncSetAttribute((const void *)gemm8_kernel<EPI8_GELU, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    if (const char *m = getenv("HAC_ENC_GEMM")) {   // classic | 8phase | auto
-        const std::string v(m);
-        if (v != "auto" && v != "classic" && v != "8phase") {
-            delete e;
-            return fail(HAC_ERR_INVALID, "HAC_ENC_GEMM = '%s': auto | classic | 8phase", m);
-        }
-        e->gemm_mode = v == "classic" ? 0 : (v == "8phase" ? 1 : -1);
+    raise_lds_limits();
+    const char *m = getenv("HAC_ENC_GEMM");
+    if (m && !parse_gemm_mode(m, &e->gemm_mode)) {
+        delete e;
+        return fail(HAC_ERR_INVALID, "HAC_ENC_GEMM = '%s': auto | classic | 8phase", m);
     }
     {
         hipDeviceProp_t prop;
@@ -2424,15 +2485,7 @@ void hac_encoder_destroy(hac_encoder *e) {
     DeviceGuard g(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (auto &kv : e->raw) (void)hipFree(kv.second);
-    for (auto &l : e->layers)
-        for (bf16 *p : {l.wqkv, l.wo, l.w1, l.w2, l.wqkv_lo, l.wo_lo, l.w1_lo, l.w2_lo})
-            if (p) (void)hipFree(p);
-    for (auto &l : e->layers) {
-        if (l.bqkv) (void)hipFree(l.bqkv);
-        if (l.wqkv8) (void)hipFree(l.wqkv8);
-        if (l.w18) (void)hipFree(l.w18);
-        if (l.fold) (void)hipFree(l.fold);
-    }
+    for (auto &l : e->layers) free_layer(l);
     drop_graphs(e);
     if (e->graph_done) (void)hipEventDestroy(e->graph_done);
     if (e->clk_ev) (void)hipEventDestroy(e->clk_ev);
@@ -2489,60 +2542,10 @@ int hac_encoder_finalize(hac_encoder *e) {
     HAC_TRY(get_raw(e, "embeddingHead.bias", H, &e->bh));
     HAC_TRY(get_raw(e, "norm.weight", H, &e->ng));
     HAC_TRY(get_raw(e, "norm.bias", H, &e->nb));
-    for (auto &l : e->layers) {
-        for (bf16 *pp : {l.wqkv, l.wo, l.w1, l.w2, l.wqkv8, l.w18, l.wqkv_lo, l.wo_lo, l.w1_lo, l.w2_lo})
-            if (pp) (void)hipFree(pp);
-        if (l.bqkv) (void)hipFree(l.bqkv);
-        if (l.fold) (void)hipFree(l.fold);
-    }
+    for (auto &l : e->layers) free_layer(l);
     e->layers.assign(c.n_layers, LayerW());
     e->split_weights = false;
-    for (int i = 0; i < c.n_layers; ++i) {
-        const std::string q = "roberta.encoder.layer." + std::to_string(i) + ".";
-        LayerW &l = e->layers[i];
-        float *wq, *wk, *wv, *bq, *bk, *bv, *t;
-        HAC_TRY(get_raw(e, q + "attention.self.query.weight", (size_t)H * H, &wq));
-        HAC_TRY(get_raw(e, q + "attention.self.key.weight", (size_t)H * H, &wk));
-        HAC_TRY(get_raw(e, q + "attention.self.value.weight", (size_t)H * H, &wv));
-        HAC_TRY(get_raw(e, q + "attention.self.query.bias", H, &bq));
-        HAC_TRY(get_raw(e, q + "attention.self.key.bias", H, &bk));
-        HAC_TRY(get_raw(e, q + "attention.self.value.bias", H, &bv));
-        HAC_HIP(hipMalloc((void **)&l.wqkv, (size_t)3 * H * H * sizeof(bf16)));
-        HAC_HIP(hipMalloc((void **)&l.bqkv, (size_t)3 * H * 4));
-        const float *ws[3] = {wq, wk, wv};
-        const float *bs[3] = {bq, bk, bv};
-        for (int j = 0; j < 3; ++j) {
-            f32_to_bf16_kernel<<<dim3((unsigned)(((size_t)H * H + 255) / 256)), dim3(256), 0, e->stream>>>(ws[j], l.wqkv + (size_t)j * H * H, (size_t)H * H);
-            HAC_HIP(hipMemcpyAsync(l.bqkv + j * H, bs[j], H * 4, hipMemcpyDeviceToDevice, e->stream));
-        }
-        HAC_TRY(get_raw(e, q + "attention.output.dense.weight", (size_t)H * H, &t));
-        HAC_TRY(to_bf16(e, t, (size_t)H * H, &l.wo));
-        HAC_TRY(get_raw(e, q + "attention.output.dense.bias", H, &l.bo));
-        HAC_TRY(get_raw(e, q + "attention.output.LayerNorm.weight", H, &l.ln1g));
-        HAC_TRY(get_raw(e, q + "attention.output.LayerNorm.bias", H, &l.ln1b));
-        HAC_TRY(get_raw(e, q + "intermediate.dense.weight", (size_t)FF * H, &t));
-        HAC_TRY(to_bf16(e, t, (size_t)FF * H, &l.w1));
-        HAC_TRY(get_raw(e, q + "intermediate.dense.bias", FF, &l.b1));
-        HAC_TRY(get_raw(e, q + "output.dense.weight", (size_t)H * FF, &t));
-        HAC_TRY(to_bf16(e, t, (size_t)H * FF, &l.w2));
-        HAC_TRY(get_raw(e, q + "output.dense.bias", H, &l.b2));
-        HAC_TRY(get_raw(e, q + "output.LayerNorm.weight", H, &l.ln2g));
-        HAC_TRY(get_raw(e, q + "output.LayerNorm.bias", H, &l.ln2b));
-        // large-batch path: fold the LayerNorm in front of QKV (the previous layer's output LayerNorm; layer 0 reads the
-        // already normalized embedding rows) and the one in front of FFN-up (this layer's attention LayerNorm)
-        HAC_HIP(hipMalloc((void **)&l.wqkv8, (size_t)3 * H * H * sizeof(bf16)));
-        HAC_HIP(hipMalloc((void **)&l.w18, (size_t)FF * H * sizeof(bf16)));
-        HAC_HIP(hipMalloc((void **)&l.fold, (size_t)(2 * 3 * H + 2 * FF) * 4));
-        const float *pg = i ? e->layers[i - 1].ln2g : nullptr, *pb = i ? e->layers[i - 1].ln2b : nullptr;
-        const float qscale = 0.125f * 1.44269504088896341f;   // softmax scale / ln 2: the attention kernel works in base 2
-        for (int j = 0; j < 3; ++j)
-            fold_ln_kernel<<<dim3(H), dim3(256), 0, e->stream>>>(ws[j], bs[j], pg, pb, H, j == 0 ? qscale : 1.0f, l.wqkv8 + (size_t)j * H * H,
-                                                                 l.fold + j * H, l.fold + 3 * H + j * H);
-        float *w1f;
-        HAC_TRY(get_raw(e, q + "intermediate.dense.weight", (size_t)FF * H, &w1f));
-        fold_ln_kernel<<<dim3(FF), dim3(256), 0, e->stream>>>(w1f, l.b1, l.ln1g, l.ln1b, H, 1.0f, l.w18, l.fold + 6 * H, l.fold + 6 * H + FF);
-        HAC_HIP(hipGetLastError());
-    }
+    for (int i = 0; i < c.n_layers; ++i) HAC_TRY(finalize_layer(e, i));
     HAC_HIP(hipStreamSynchronize(e->stream));
     e->finalized = true;
     return HAC_OK;
@@ -2608,7 +2611,7 @@ int hac_encoder_layer_state(hac_encoder *e, const int32_t *ids, const int32_t *m
         return fail(HAC_ERR_INVALID, "layer_state: layer %d outside [-1, %d]", layer, e->cfg.n_layers - 1);
     if (e->pooling == 0 && (layer < -1 || layer > e->cfg.n_layers - 2))
         return fail(HAC_ERR_INVALID, "layer_state: layer %d outside [-1, %d] (the last layer continues the <s> rows only)", layer, e->cfg.n_layers - 2);
-    const int L32 = (L + SEQ_ALIGN - 1) / SEQ_ALIGN * SEQ_ALIGN;
+    const int L32 = pad_len(L);
     if ((long)B * L32 > e->max_tokens) return fail(HAC_ERR_INVALID, "layer_state: %d x %d rows exceed one pass (max_tokens %ld)", B, L32, e->max_tokens);
     for (int b = 0; b < B; ++b) {   // (the forward reports such a sequence as a NaN embedding; there is no embedding here)
         int len = 0;
@@ -2630,12 +2633,7 @@ int hac_encoder_layer_state(hac_encoder *e, const int32_t *ids, const int32_t *m
     HAC_HIP(hipStreamSynchronize(e->stream));
     HAC_HIP(hipMemcpy(e->ws_ids.p, ids, n * 4, hipMemcpyHostToDevice));
     HAC_HIP(hipMemcpy(e->ws_mask.p, mask, n * 4, hipMemcpyHostToDevice));
-    e->plan_sub_batches = 0;
-    e->plan_rows = 0;
-    e->plan_graph = "off";   // never captured: plain launches of the forward's own kernels
-    e->plan_precision = e->precision;
-    e->plan_pooling = e->pooling;
-    if (e->precision == 1) HAC_TRY(ensure_split_weights(e));
+    HAC_TRY(begin_call(e));   // (never captured: plain launches of the forward's own kernels)
     const LayerDump dump{layer, d_rows, d_stats, norm_out ? d_norm : nullptr};
     HAC_TRY(run_forward<int>(e, (const int *)e->ws_ids.p, (const int *)e->ws_mask.p, B, L, nullptr, e->stream, 0, -1, 0, &dump));
     HAC_HIP(hipStreamSynchronize(e->stream));
@@ -2651,8 +2649,7 @@ int hac_encoder_set_option(hac_encoder *e, const char *name, const char *value) 
     // a value outside the documented set is an error, never a silent default (a mistyped value in a cross-check test would
     // otherwise exercise the wrong kernels and still pass)
     if (n == "gemm") {
-        if (v != "auto" && v != "classic" && v != "8phase") return fail(HAC_ERR_INVALID, "encoder option gemm = '%s': auto | classic | 8phase", value);
-        e->gemm_mode = v == "classic" ? 0 : (v == "8phase" ? 1 : -1);
+        if (!parse_gemm_mode(value, &e->gemm_mode)) return fail(HAC_ERR_INVALID, "encoder option gemm = '%s': auto | classic | 8phase", value);
     } else if (n == "precision") {
         if (v != "bf16" && v != "split") return fail(HAC_ERR_INVALID, "encoder option precision = '%s': bf16 | split", value);
         e->precision = v == "split" ? 1 : 0;
@@ -2700,10 +2697,11 @@ int hac_encoder_set_option(hac_encoder *e, const char *name, const char *value) 
 
 const char *hac_encoder_last_plan(hac_encoder *e) {
     if (!e) return "none";
-    const bool split = e->plan_precision == 1;   // (what the most recent forward ran, not what the option says now)
-    snprintf(e->last_plan, sizeof e->last_plan, "gemm=%s attn=%s sub_batches=%d rows=%ld graph=%s ksplit=%d/%d attn_form=%s%s%s", e->plan_gemm, e->attn_mode ? "twopass" : "stream",
-             e->plan_sub_batches, e->plan_rows, e->plan_graph, e->plan_ks_out, e->plan_ks_down,
-             split ? "split" : (e->attn_mode ? "twopass" : (e->plan_attn_pipe ? "woven" : "single")), split ? " precision=split" : "", e->plan_pooling == 1 ? " pool=mean" : "");
+    const Plan &p = e->plan;
+    const bool split = p.precision == 1;   // (what the most recent forward ran, not what the option says now)
+    snprintf(e->last_plan, sizeof e->last_plan, "gemm=%s attn=%s sub_batches=%d rows=%ld graph=%s ksplit=%d/%d attn_form=%s%s%s", p.gemm, e->attn_mode ? "twopass" : "stream",
+             p.sub_batches, p.rows, p.graph, p.ks_out, p.ks_down,
+             split ? "split" : (e->attn_mode ? "twopass" : (p.attn_pipe ? "woven" : "single")), split ? " precision=split" : "", p.pooling == 1 ? " pool=mean" : "");
     return e->last_plan;
 }
 

@@ -121,7 +121,7 @@ def ance_embed(sd, input_ids, attention_mask, family=None, eps=1e-5, pad_id=1, m
     """Embedding stage, fp64: LN(word[id] + type[0] + pos[HF position id]) of every token (mask: the prefix of valid tokens).
     Returns the state dict of ance_layer ({rows, mean, rstd, norm} as torch float64 over [B, L]); the rows are already
     normalized (mean 0, rstd 1, norm = rows).  family "classic": rows are fp32 (embed_ln_kernel, encoder.hip: ln768_store writes
-    x_f32 unrounded) -- modelled as exact; "gemm8": the rows are stored only as bf16 (ln768_store's x_bf; run_forward passes
+    x_f32 unrounded) -- modelled as exact; "gemm8": the rows are stored only as bf16 (ln768_store's x_bf; fwd_build passes
     x_f32 = nullptr on that path); "split": as classic (the pair of the rows is formed by the consumer).  mutate: "eps" (LayerNorm eps 1e-12) or "pos" (position ids one too high, the last one clamped to the table)."""
     ids = torch.as_tensor(np.asarray(input_ids), dtype=torch.long)
     mask = torch.as_tensor(np.asarray(attention_mask), dtype=torch.long)
@@ -322,7 +322,7 @@ def ance_tail(sd, i, x_in, attention_mask, family=None, n_heads=12, eps=1e-5, mu
     """The last encoder layer i and the ANCE head in fp64 from the state the layers before it left (x_in as for ance_layer;
     i = 0: ance_embed's state).  Returns the embeddings, float64 [B, H] (= ance_forward's output when family is None).
 
-    Only what the kernels compute (run_forward, `last`): keys and values of every row, the query of row 0 of each sequence,
+    Only what the kernels compute (encoder.hip tail_classic / tail_split): keys and values of every row, the query of row 0 of each sequence,
     its attention (cls_only), then out-projection, LayerNorm, FFN and LayerNorm on the gathered <s> rows, and the head.
       classic (and split, with its pair rounding): Q, K, V as in ance_layer;
       gemm8: K, V folded as in ance_layer; the <s> query in the same folded form, scale folded in, bf16 (cls_q_kernel);

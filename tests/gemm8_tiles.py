@@ -8,7 +8,7 @@ slot + per_xcd, ... -- `seq` counts a workgroup's tiles, my_tiles is how many it
 seam of the kernel (the DMA stream running on into the next tile, the RESID epilogue re-staging the next tile's first
 k-tiles, s_tile += per_xcd) happens between seq and seq + 1 of one workgroup.
 
-The launches of one encoder layer (encoder.hip run_forward), as (nx, n_groups, n_tile0):
+The launches of one encoder layer (encoder.hip layer_gemm8, and qkv_gemm8 from tail_classic for the last layer), as (nx, n_groups, n_tile0):
 
   class     launch                         nx  groups  tile0   first mt_all at which a workgroup of 256 takes a 2nd tile
   QKV       EPI8_QKV, N = 2304              9     1      0      25

@@ -25,7 +25,7 @@ has no rounded operand (E_emul = 0): its bound is LAYER_BOUNDS' 1.4e-7 = 2^-23 +
 for every recipe (a relative figure: the outlier gain scales kernel and reference alike).  No bound comes from what this file
 measures.
 
-The model's split-K choice (run_forward_split pick_ksplit) goes by the PADDED rows B x L32 of a call, not the packed rows: on a
+The model's split-K choice (encoder.hip pick_ksplit, with the split family's one workgroup slot per CU) goes by the PADDED rows B x L32 of a call, not the packed rows: on a
 256-CU part the 8 x 512 `edges` batch and SPLIT_EDGES run 1/1, L = 100 runs 2/3, 1 x 64 runs 3/6 and 4 x 512 runs 2/2
 (model_ksplit below mirrors the rule; every case asserts what ran from last_plan()).
 
@@ -45,7 +45,7 @@ Measured on MI355X, first run of this file (rel: embed / layer 0 / layer 1 / tai
   D peaked 1.080e-4 / 1.004e-4 / 8.50e-5 (2.13e-4 / 1.90e-4 / 1.35e-4); outlier 3.73e-5 / 1.89e-5 / 2.00e-5 (7.78e-5 / 3.61e-5 / 2.92e-5)
   E weakest separations: gelu_tanh 4.3 / 4.4 / 7.5 (std008), 1.9 / 1.9 / 2.9 (std012); logits 53 ... 163; key_chunk 461 ... 26936
 The kernels sit 1.1 ... 1.4 x above the emulation on the layers of every std-weight case (1.29 ... 1.33 on the four cells the bounds
-come from), at most 1.8 x anywhere (the outlier tail): no case here needed a margin of its own, and no defect of split.inc / run_forward_split showed.
+come from), at most 1.8 x anywhere (the outlier tail): no case here needed a margin of its own, and no defect of split.inc / the split layer bodies (layer_split, tail_split) showed.
 """
 import numpy as np
 import pytest
@@ -100,7 +100,7 @@ def encoder(recipe, depth):
 
 
 def model_ksplit(B, L, n_cu):
-    """run_forward_split's pick_ksplit for one sub-batch of B x L: "a/b" for out-proj (K = 768) and FFN-down (K = 3072)."""
+    """encoder.hip's pick_ksplit with the split family's slots (ksplit_slots: n_cu) for one sub-batch of B x L: "a/b" for out-proj (K = 768) and FFN-down (K = 3072)."""
     Mp = (B * ((L + 31) // 32 * 32) + 255) // 256 * 256
 
     def pick(KT, min_kt):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Development: forward time of small batches with the split-K of the two residual GEMMs pinned ("ksplit_pin" = "out/down"),
-every combination, interleaved rounds -- what the cost model in run_forward (pick_ksplit) is checked against.
+every combination, interleaved rounds -- what the cost model of encoder.hip's pick_ksplit is checked against.
   python tools/ks_sweep.py [BxL ...]"""
 import os
 import sys
