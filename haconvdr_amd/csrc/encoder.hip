@@ -63,11 +63,13 @@ struct SeqInfo {
     int *desc;    // [B][4] (16-byte aligned) the work list's entries in full: (len, len32, first row, sequence) -- one scalar load per item (attn_pipe.inc)
 };
 
-// one workgroup per sequence: len = sum(mask), prefix check, HF position ids
-//   pos = cumsum(id != pad) * (id != pad) + pad     (pad = 1)
+// one workgroup per sequence: len = sum(mask), prefix check, position ids by the model's rule (pos_rule, uniform over the launch)
+//   POS_ROBERTA: HF's pos = cumsum(id != pad) * (id != pad) + pad     (pad = 1)
+//   POS_BERT:    pos = t, whatever the ids are ([PAD] = 0 inside a sequence is an ordinary token; pad_id is not read)
+enum { POS_ROBERTA = 0, POS_BERT = 1 };
 template <typename IT>
 __global__ __launch_bounds__(512) void seq_prep_kernel(const IT *__restrict__ ids, const IT *__restrict__ mask, int L, SeqInfo s,
-                                                       int pad_id, int vocab) {
+                                                       int pad_id, int vocab, int pos_rule) {
     __shared__ int wsum[8];
     __shared__ int wlen[8];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -101,7 +103,7 @@ __global__ __launch_bounds__(512) void seq_prep_kernel(const IT *__restrict__ id
     }
     const int cum = sc + base;
     if (t < L) {
-        s.pos[(size_t)b * L + t] = np ? cum + pad_id : pad_id;
+        s.pos[(size_t)b * L + t] = pos_rule == POS_BERT ? t : (np ? cum + pad_id : pad_id);
         if ((m != 0) != (t < len)) atomicOr(s.err + b, 1);  // not a prefix mask
         if (t < len && !id_ok) atomicOr(s.err + b, 4);      // only attended tokens are looked up
     }
@@ -1460,7 +1462,7 @@ struct Plan {
     int sub_batches = 0;
     long rows = 0;
     const char *graph = "off";
-    int precision = 0, pooling = 0;
+    int precision = 0, pooling = 0, model = 0;
     int ks_out = 1, ks_down = 1;
     int attn_pipe = 0;                    // the layers used the woven attention form
 };
@@ -1484,6 +1486,7 @@ struct hac_encoder {
     size_t idstats_rows = 0;
     int precision = 0;                    // 0: bf16 operands; 1: split (hi + lo pairs, three MFMAs per product: split.inc)
     bool split_weights = false;           // the lo twins of the weights exist
+    int model = 0;                        // 0: roberta (roberta.* tensors, HF position rule, L <= max_pos - 2); 1: bert (bert.* tensors, pos = t, L <= max_pos)
     int pooling = 0;                      // 0: first (the <s> row, models.py:56); 1: mean (masked mean of the last layer's rows, models.py:57-61)
     GrowBuf ws_pool;                      // pooling = mean: [2][B][768] fp32, the pooled rows | the head's projection
     GrowBuf ws_xb_lo, ws_q_lo, ws_k_lo, ws_vt_lo, ws_ctx_lo, ws_h_lo, ws_cls_lo;   // the lo twins of the activations an MFMA reads
@@ -1547,6 +1550,11 @@ struct hac_encoder {
 namespace {
 
 int enc_fail_missing(const std::string &name) { return fail(HAC_ERR_INVALID, "encoder weight '%s' was never set", name.c_str()); }
+
+// the checkpoint's name prefix of the chosen model ("model" option): roberta.embeddings.*, bert.encoder.layer.N.*, ...
+const char *model_prefix(const hac_encoder *e) { return e->model == 1 ? "bert." : "roberta."; }
+// the longest L a forward takes: the HF RoBERTa rule reads position rows up to L + 1, BERT's rows up to L - 1
+int max_len(const hac_encoder *e) { return std::min(512, e->model == 1 ? e->cfg.max_pos : e->cfg.max_pos - 2); }
 
 int get_raw(hac_encoder *e, const std::string &name, size_t count, float **out) {
     auto it = e->raw.find(name);
@@ -1662,7 +1670,7 @@ int ensure_split_weights(hac_encoder *e) {
         f32_to_bf16_lo_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream>>>(src, dst, n);
     };
     for (int i = 0; i < e->cfg.n_layers; ++i) {
-        const std::string q = "roberta.encoder.layer." + std::to_string(i) + ".";
+        const std::string q = std::string(model_prefix(e)) + "encoder.layer." + std::to_string(i) + ".";
         LayerW &l = e->layers[i];
         float *t;
         if (!l.wqkv_lo) HAC_HIP(hipMalloc((void **)&l.wqkv_lo, (size_t)3 * H * H * sizeof(bf16)));
@@ -1693,6 +1701,7 @@ int begin_call(hac_encoder *e) {
     e->plan.graph = "off";
     e->plan.precision = e->precision;
     e->plan.pooling = e->pooling;
+    e->plan.model = e->model;
     return e->precision == 1 ? ensure_split_weights(e) : HAC_OK;
 }
 
@@ -1855,7 +1864,7 @@ int fwd_build(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, hipSt
     f.mean = e->pooling == 1;
     HAC_TRY(reserve_rows(e, f));
     HAC_TRY(seq_layout(e, B, L, f.s));
-    seq_prep_kernel<IT><<<dim3(B), dim3(512), 0, st>>>(ids, mask, L, f.s, c.pad_token_id, c.vocab);
+    seq_prep_kernel<IT><<<dim3(B), dim3(512), 0, st>>>(ids, mask, L, f.s, c.pad_token_id, c.vocab, e->model == 1 ? POS_BERT : POS_ROBERTA);
     seq_offsets_kernel<<<dim3(1), dim3(256), 0, st>>>(f.s, B);
     attn_order_kernel<<<dim3(1), dim3(256), 0, st>>>(f.s, B);
     f.total = f.s.off + B;
@@ -2297,7 +2306,8 @@ int forward_graph(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, f
     const uint64_t key = ((uint64_t)B << 40) | ((uint64_t)L << 24) | ((uint64_t)sizeof(IT) << 16) | ((uint64_t)(e->attn_mode & 1) << 8) |
                          ((uint64_t)((e->gemm_mode + 1) & 3) << 4) | ((uint64_t)(e->ksplit_mode & 1) << 12) |
                          ((uint64_t)(e->attn_qsplit & 1) << 13) | ((uint64_t)(e->g8_stagger & 1) << 14) | ((uint64_t)((e->attn_pipe + 1) & 3) << 15) |
-                         ((uint64_t)(e->precision & 1) << 20) | ((uint64_t)(e->pooling & 1) << 21);
+                         ((uint64_t)(e->precision & 1) << 20) | ((uint64_t)(e->pooling & 1) << 21) |
+                         ((uint64_t)(e->model & 1) << 22);   // (fixed once weights are set; keyed like every other option a captured forward depends on)
     // (a caller that pads every batch to its own longest sequence can show hundreds of shapes: the cache is bounded, and starting
     // over costs each live shape one plain forward and one capture)
     if (e->graphs.size() >= GRAPH_MAX_SHAPES && e->graphs.find(key) == e->graphs.end()) drop_graphs(e);
@@ -2337,7 +2347,7 @@ int forward_batched(hac_encoder *e, const IT *ids, const IT *mask, int B, int L,
     // max_tokens-row GEMMs instead of running them half empty.
     SeqInfo s;
     HAC_TRY(seq_layout(e, B, L, s));
-    seq_prep_kernel<IT><<<dim3(B), dim3(512), 0, st>>>(ids, mask, L, s, e->cfg.pad_token_id, e->cfg.vocab);
+    seq_prep_kernel<IT><<<dim3(B), dim3(512), 0, st>>>(ids, mask, L, s, e->cfg.pad_token_id, e->cfg.vocab, e->model == 1 ? POS_BERT : POS_ROBERTA);
     HAC_HIP(hipGetLastError());
     // the one host read-back of a large forward: B ints through pinned memory, on the caller's stream
     if (e->h_len_cap < (size_t)B) {
@@ -2373,7 +2383,7 @@ int forward_batched(hac_encoder *e, const IT *ids, const IT *mask, int B, int L,
 
 // the packed bf16 weights of layer i, and their LayerNorm-folded forms for gemm8, from the checkpoint's fp32 tensors
 int finalize_layer(hac_encoder *e, int i) {
-    const std::string q = "roberta.encoder.layer." + std::to_string(i) + ".";
+    const std::string q = std::string(model_prefix(e)) + "encoder.layer." + std::to_string(i) + ".";
     LayerW &l = e->layers[i];
     float *wq, *wk, *wv, *bq, *bk, *bv, *t;
     HAC_TRY(get_raw(e, q + "attention.self.query.weight", (size_t)H * H, &wq));
@@ -2532,7 +2542,7 @@ int hac_encoder_finalize(hac_encoder *e) {
     DeviceGuard g(e->device);
     drop_graphs(e);   // captured launches hold the old weights' pointers
     const hac_encoder_config &c = e->cfg;
-    const std::string p = "roberta.embeddings.";
+    const std::string p = std::string(model_prefix(e)) + "embeddings.";
     HAC_TRY(get_raw(e, p + "word_embeddings.weight", (size_t)c.vocab * H, &e->word));
     HAC_TRY(get_raw(e, p + "position_embeddings.weight", (size_t)c.max_pos * H, &e->posw));
     HAC_TRY(get_raw(e, p + "token_type_embeddings.weight", (size_t)c.type_vocab * H, &e->typew));
@@ -2555,8 +2565,9 @@ int hac_encoder_forward_device(hac_encoder *e, const void *ids_dev, const void *
                                float *out_dev, void *hip_stream) {
     if (!e) return fail(HAC_ERR_INVALID, "null encoder");
     if (!e->finalized) return fail(HAC_ERR_INVALID, "encoder weights not finalized (hac_encoder_finalize)");
-    if (B < 0 || L < 1 || L > 512 || L + 2 > e->cfg.max_pos || (B > 0 && (!ids_dev || !mask_dev || !out_dev)))
-        return fail(HAC_ERR_INVALID, "forward: bad arguments (B=%d, L=%d; L must be in [1, min(512, max_pos-2)])", B, L);
+    if (B < 0 || L < 1 || L > max_len(e) || (B > 0 && (!ids_dev || !mask_dev || !out_dev)))
+        return fail(HAC_ERR_INVALID, e->model == 1 ? "forward: bad arguments (B=%d, L=%d; L must be in [1, min(512, max_pos)] with model = bert)"
+                                                   : "forward: bad arguments (B=%d, L=%d; L must be in [1, min(512, max_pos-2)])", B, L);
     if (elem_bytes != 4 && elem_bytes != 8) return fail(HAC_ERR_INVALID, "forward: ids/mask must be int32 or int64");
     if (B == 0) return HAC_OK;
     DeviceGuard g(e->device);
@@ -2604,7 +2615,7 @@ int hac_encoder_layer_state(hac_encoder *e, const int32_t *ids, const int32_t *m
                             float *norm_out) {
     if (!e) return fail(HAC_ERR_INVALID, "null encoder");
     if (!e->finalized) return fail(HAC_ERR_INVALID, "encoder weights not finalized (hac_encoder_finalize)");
-    if (B < 1 || L < 1 || L > 512 || L + 2 > e->cfg.max_pos || !ids || !mask || !rows_out || !stats_out)
+    if (B < 1 || L < 1 || L > max_len(e) || !ids || !mask || !rows_out || !stats_out)
         return fail(HAC_ERR_INVALID, "layer_state: bad arguments (B=%d, L=%d)", B, L);
     // (pooling = mean runs the last layer on every row: its state exists and means what every other layer's does)
     if (e->pooling == 1 && (layer < -1 || layer > e->cfg.n_layers - 1))
@@ -2653,6 +2664,11 @@ int hac_encoder_set_option(hac_encoder *e, const char *name, const char *value) 
     } else if (n == "precision") {
         if (v != "bf16" && v != "split") return fail(HAC_ERR_INVALID, "encoder option precision = '%s': bf16 | split", value);
         e->precision = v == "split" ? 1 : 0;
+    } else if (n == "model") {
+        // (the tensor names, the position rule and the length bound follow it: chosen before the first tensor arrives, then fixed)
+        if (v != "roberta" && v != "bert") return fail(HAC_ERR_INVALID, "encoder option model = '%s': roberta | bert", value);
+        if (!e->raw.empty()) return fail(HAC_ERR_INVALID, "encoder option model = '%s': must be set before the first hac_encoder_set_weight", value);
+        e->model = v == "bert" ? 1 : 0;
     } else if (n == "pooling") {
         if (v != "first" && v != "mean") return fail(HAC_ERR_INVALID, "encoder option pooling = '%s': first | mean", value);
         e->pooling = v == "mean" ? 1 : 0;
@@ -2699,9 +2715,9 @@ const char *hac_encoder_last_plan(hac_encoder *e) {
     if (!e) return "none";
     const Plan &p = e->plan;
     const bool split = p.precision == 1;   // (what the most recent forward ran, not what the option says now)
-    snprintf(e->last_plan, sizeof e->last_plan, "gemm=%s attn=%s sub_batches=%d rows=%ld graph=%s ksplit=%d/%d attn_form=%s%s%s", p.gemm, e->attn_mode ? "twopass" : "stream",
+    snprintf(e->last_plan, sizeof e->last_plan, "gemm=%s attn=%s sub_batches=%d rows=%ld graph=%s ksplit=%d/%d attn_form=%s%s%s%s", p.gemm, e->attn_mode ? "twopass" : "stream",
              p.sub_batches, p.rows, p.graph, p.ks_out, p.ks_down,
-             split ? "split" : (e->attn_mode ? "twopass" : (p.attn_pipe ? "woven" : "single")), split ? " precision=split" : "", p.pooling == 1 ? " pool=mean" : "");
+             split ? "split" : (e->attn_mode ? "twopass" : (p.attn_pipe ? "woven" : "single")), split ? " precision=split" : "", p.pooling == 1 ? " pool=mean" : "", p.model == 1 ? " model=bert" : "");
     return e->last_plan;
 }
 

@@ -5,6 +5,8 @@ attention_mask)`` with integer tensors [B, L] (src/test_HAConvDR_topiocqa.py:211
 gen_doc_embeddings.py:110) and returns a float32 tensor [B, 768] on the same device
 (= src/models.py:44).  Weights use the checkpoint's own key names (``roberta.*``,
 ``embeddingHead.*``, ``norm.*``; ``classifier.*`` is ignored as in the reference's forward).
+``BERTEncoder`` is the same seam for the reference's ``BERT`` class (src/models.py:66-110, load_model's BERT_* types):
+``bert.*`` names, position ids arange(L), the same kernels behind the embedding stage.
 All arithmetic runs in the gfx950 HIP kernels of libhaconvdr.so; there is no CPU fallback.
 """
 import ctypes
@@ -26,6 +28,11 @@ def split_bf16(x):
 
 
 class ANCEEncoder:
+    MODEL = "roberta"            # the "model" option of the handle (include/haconvdr.h): tensor names, position rule, length bound
+    KEY_PREFIX = "roberta."      # the checkpoint's name prefix of the transformer's tensors
+    UNUSED_PREFIXES = ("classifier.",)          # present in the checkpoint, unused by forward (models.py:26)
+    CONFIG_DEFAULTS = {"ln_eps": 1e-5, "pad_token_id": 1}    # RobertaConfig's, where config.json is silent
+
     def __init__(self, n_layers=12, vocab=50265, max_pos=514, type_vocab=1, pad_token_id=1, ln_eps=1e-5, device=0, precision="bf16",
                  pooling="first"):
         self.device = int(device)
@@ -33,6 +40,8 @@ class ANCEEncoder:
         cfg = _lib.EncoderConfig(self.n_layers, 768, 12, 3072, int(vocab), int(max_pos), int(type_vocab), int(pad_token_id), float(ln_eps))
         self._h = ctypes.c_void_p()
         _lib.check(_lib.lib().hac_encoder_create(ctypes.byref(cfg), self.device, ctypes.byref(self._h)))
+        if self.MODEL != "roberta":  # before the first tensor: the names hac_encoder_finalize asks for follow it
+            self.set_option("model", self.MODEL)
         if precision != "bf16":     # "split": hi + lo bf16 operand pairs, three MFMAs per product (include/haconvdr.h, "precision")
             self.set_option("precision", precision)
         self._pooling = "first"
@@ -52,8 +61,8 @@ class ANCEEncoder:
         """sd: name -> float32 array / torch tensor with the reference checkpoint's names."""
         L = _lib.lib()
         for name, v in sd.items():
-            if name.startswith("classifier.") or name.endswith("position_ids"):
-                continue                       # present in the checkpoint, unused by ANCE.forward (models.py:26)
+            if name.startswith(self.UNUSED_PREFIXES) or name.endswith("position_ids"):
+                continue                       # present in the checkpoint, unused by forward (models.py:26, :72)
             a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
             a = np.ascontiguousarray(a, dtype=np.float32)
             _lib.check(L.hac_encoder_set_weight(self._h, name.encode(), a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), a.size))
@@ -62,11 +71,19 @@ class ANCEEncoder:
 
     @classmethod
     def from_state_dict(cls, sd, device=0, **kw):
-        n_layers = 1 + max(int(k.split(".")[3]) for k in sd if k.startswith("roberta.encoder.layer."))
-        vocab, _ = np.shape(sd["roberta.embeddings.word_embeddings.weight"])
-        max_pos, _ = np.shape(sd["roberta.embeddings.position_embeddings.weight"])
-        tv, _ = np.shape(sd["roberta.embeddings.token_type_embeddings.weight"])
+        p = cls.KEY_PREFIX
+        n_layers = cls._count_layers(sd)
+        vocab, _ = np.shape(sd[p + "embeddings.word_embeddings.weight"])
+        max_pos, _ = np.shape(sd[p + "embeddings.position_embeddings.weight"])
+        tv, _ = np.shape(sd[p + "embeddings.token_type_embeddings.weight"])
         return cls(n_layers=n_layers, vocab=vocab, max_pos=max_pos, type_vocab=tv, device=device, **kw).load_state_dict(sd)
+
+    @classmethod
+    def _count_layers(cls, sd):
+        layers = [int(k.split(".")[3]) for k in sd if k.startswith(cls.KEY_PREFIX + "encoder.layer.")]
+        if not layers or cls.KEY_PREFIX + "embeddings.word_embeddings.weight" not in sd:
+            raise ValueError(f"no {cls.KEY_PREFIX}* tensors in the state dict: not a checkpoint {cls.__name__} reads")
+        return 1 + max(layers)
 
     @classmethod
     def from_pretrained(cls, path, device=0, precision="bf16", pooling="first"):
@@ -91,22 +108,27 @@ class ANCEEncoder:
         if os.path.exists(cfg_path):
             with open(cfg_path) as f:
                 cfg = json.load(f)
-            n_layers = 1 + max(int(k.split(".")[3]) for k in sd if k.startswith("roberta.encoder.layer."))
-            vocab, hidden = sd["roberta.embeddings.word_embeddings.weight"].shape
+            if cls.MODEL != "roberta" and cfg.get("model_type", cls.MODEL) != cls.MODEL:
+                raise ValueError(f"{cfg_path}: model_type = {cfg['model_type']!r}; {cls.__name__} reads {cls.MODEL!r} checkpoints")
+            p = cls.KEY_PREFIX
+            n_layers = cls._count_layers(sd)
+            vocab, hidden = sd[p + "embeddings.word_embeddings.weight"].shape
             found = {"num_hidden_layers": n_layers, "hidden_size": hidden, "vocab_size": vocab,
-                     "max_position_embeddings": sd["roberta.embeddings.position_embeddings.weight"].shape[0],
-                     "type_vocab_size": sd["roberta.embeddings.token_type_embeddings.weight"].shape[0],
-                     "intermediate_size": sd["roberta.encoder.layer.0.intermediate.dense.weight"].shape[0]}
+                     "max_position_embeddings": sd[p + "embeddings.position_embeddings.weight"].shape[0],
+                     "type_vocab_size": sd[p + "embeddings.token_type_embeddings.weight"].shape[0],
+                     "intermediate_size": sd[p + "encoder.layer.0.intermediate.dense.weight"].shape[0]}
             for key, have in found.items():
                 if key in cfg and int(cfg[key]) != int(have):
                     raise ValueError(f"{cfg_path}: {key} = {cfg[key]} but the checkpoint's tensors say {have}")
             if int(cfg.get("num_attention_heads", 12)) != 12 or int(cfg.get("hidden_size", 768)) != 768 or int(cfg.get("intermediate_size", 3072)) != 3072:
-                raise ValueError(f"{cfg_path}: only the RoBERTa-base geometry of ANCE is built (hidden 768, 12 heads, FFN 3072)")
+                raise ValueError(f"{cfg_path}: only the base geometry is built (hidden 768, 12 heads, FFN 3072)")
             if cfg.get("hidden_act", "gelu") != "gelu":
                 raise ValueError(f"{cfg_path}: hidden_act = {cfg['hidden_act']!r}; the kernels implement erf GELU")
             if cfg.get("position_embedding_type", "absolute") != "absolute":
                 raise ValueError(f"{cfg_path}: position_embedding_type = {cfg['position_embedding_type']!r} is not supported")
-            kw = {"ln_eps": float(cfg.get("layer_norm_eps", 1e-5)), "pad_token_id": int(cfg.get("pad_token_id", 1))}
+            pad = cfg.get("pad_token_id")   # (may be null in a hand-written config)
+            kw = {"ln_eps": float(cfg.get("layer_norm_eps", cls.CONFIG_DEFAULTS["ln_eps"])),
+                  "pad_token_id": int(cls.CONFIG_DEFAULTS["pad_token_id"] if pad is None else pad)}
         return cls.from_state_dict(sd, device=device, precision=precision, pooling=pooling, **kw)
 
     # ---- forward -----------------------------------------------------------
@@ -182,7 +204,8 @@ class ANCEEncoder:
 
     def last_plan(self):
         """Kernel families of the most recent forward: "gemm=gemm8|classic256|classic128|split128 attn=... sub_batches=N rows=R ...",
-        with " precision=split" appended when it ran in split mode and " pool=mean" when it pooled the masked mean."""
+        with " precision=split" appended when it ran in split mode, " pool=mean" when it pooled the masked mean and " model=bert"
+        when the handle is a BERTEncoder."""
         return _lib.lib().hac_encoder_last_plan(self._h).decode()
 
     KERNEL_CLASSES = ("qkv", "attention", "out_proj", "ffn_up", "ffn_down", "layernorm")   # HAC_ENC_CLASS_* of include/haconvdr.h
@@ -225,3 +248,20 @@ class ANCEEncoder:
         n = ctypes.c_int()
         _lib.check(_lib.lib().hac_encoder_profile_drain_class(self._h, self.KERNEL_CLASSES.index(name), buf, cap, ctypes.byref(n)))
         return [float(buf[i]) for i in range(n.value)]
+
+
+class BERTEncoder(ANCEEncoder):
+    """The reference's ``BERT`` class (src/models.py:66-110; load_model's BERT_Query / BERT_Passage): the same head, pooling and
+    forward as ``ANCE`` over a ``BertModel``.  Checkpoint names are ``bert.*`` (``bert.pooler.*`` is unused by forward, like
+    ``classifier.*``), position ids are ``arange(L)`` whatever the token ids, so the 512-row table serves L = 512, row 0 of the
+    2-row token-type table is added (the reference never passes ``token_type_ids``) and the LayerNorm eps is BertConfig's
+    1e-12.  Behind the embedding stage it runs the kernels ANCEEncoder runs (the handle's "model" option, include/haconvdr.h)."""
+    MODEL = "bert"
+    KEY_PREFIX = "bert."
+    UNUSED_PREFIXES = ("classifier.", "bert.pooler.")
+    CONFIG_DEFAULTS = {"ln_eps": 1e-12, "pad_token_id": 0}    # BertConfig's
+
+    def __init__(self, n_layers=12, vocab=30522, max_pos=512, type_vocab=2, pad_token_id=0, ln_eps=1e-12, device=0, precision="bf16",
+                 pooling="first"):
+        super().__init__(n_layers=n_layers, vocab=vocab, max_pos=max_pos, type_vocab=type_vocab, pad_token_id=pad_token_id, ln_eps=ln_eps,
+                         device=device, precision=precision, pooling=pooling)

@@ -192,13 +192,20 @@ def encode_passages(model, passages, out_dir, per_gpu_eval_batch_size=250, n_gpu
 
 
 def load_model(model_type, model_path, device=0):
-    """Mirror of load_model(model_type, model_path) (src/models.py:112-140) for the ANCE types: returns
-    ``(tokenizer, model)``.  The tokenizer is the checkpoint's RobertaTokenizer when its vocabulary files are in the
-    directory, else None (the passage pipeline never uses it: it reads pre-tokenized records)."""
-    from .encoder import ANCEEncoder
-    if model_type not in ("ANCE_Query", "ANCE_Passage"):
-        raise ValueError("{} is not supported by the MI355X path (ANCE_Query / ANCE_Passage only)".format(model_type))
+    """Mirror of load_model(model_type, model_path) (src/models.py:112-136), both arms: returns ``(tokenizer, model)``.
+    ANCE_Query / ANCE_Passage give an ANCEEncoder, BERT_Query / BERT_Passage a BERTEncoder; any other type raises ValueError
+    as there, and so does a directory whose checkpoint is the other arm's.  The tokenizer is the checkpoint's
+    RobertaTokenizer / BertTokenizer when its vocabulary files are in the directory, else None (the passage pipeline never
+    uses it: it reads pre-tokenized records)."""
+    from .encoder import ANCEEncoder, BERTEncoder
     tokenizer = None
+    if model_type in ("BERT_Query", "BERT_Passage"):
+        if os.path.exists(os.path.join(model_path, "vocab.txt")):
+            from transformers import BertTokenizer
+            tokenizer = BertTokenizer.from_pretrained(model_path, do_lower_case=True)
+        return tokenizer, BERTEncoder.from_pretrained(model_path, device=device)
+    if model_type not in ("ANCE_Query", "ANCE_Passage"):
+        raise ValueError("{}: load_model knows ANCE_Query / ANCE_Passage / BERT_Query / BERT_Passage".format(model_type))
     if os.path.exists(os.path.join(model_path, "vocab.json")) and os.path.exists(os.path.join(model_path, "merges.txt")):
         from transformers import RobertaTokenizer
         tokenizer = RobertaTokenizer.from_pretrained(model_path, do_lower_case=True)

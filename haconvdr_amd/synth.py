@@ -122,10 +122,23 @@ def ance_state_dict(seed=0xA11CE, n_layers=12, hidden=768, ffn=3072, vocab=50265
     1−cos between different sequences' embeddings 1e-4 … 2e-3): parity asserts on such outputs cannot
     tell one sequence from another.  0.08 ("content-sensitive": attention logits of σ ≈ 5, different
     sequences ≥ 0.05 apart in 1−cos) is what the discriminative goldens use."""
+    return _encoder_state_dict("roberta.", seed, n_layers, hidden, ffn, vocab, max_pos, 1, rich, layer_matrix_std)
+
+
+def bert_state_dict(seed=0xBE27, n_layers=12, layer_matrix_std=0.02, rich=True, hidden=768, ffn=3072, vocab=30522, max_pos=512):
+    """``ance_state_dict``'s recipe under the names of the reference's ``BERT`` class (src/models.py:66-110): ``bert.*`` with a
+    2-row token-type table and bert-base-uncased's 30522 / 512 tables, plus ``embeddingHead.*`` / ``norm.*``.  Every tensor is
+    drawn from a stream seeded by its own name, so no tensor shares bits with ``ance_state_dict`` of the same seed.  The
+    tensors a checkpoint holds and the forward never reads (``bert.pooler.*``, ``classifier.*``, ``position_ids``) are not
+    generated."""
+    return _encoder_state_dict("bert.", seed, n_layers, hidden, ffn, vocab, max_pos, 2, rich, layer_matrix_std)
+
+
+def _encoder_state_dict(prefix, seed, n_layers, hidden, ffn, vocab, max_pos, type_vocab, rich, layer_matrix_std):
     sd = {}
 
     def mat(name, shape):
-        std = layer_matrix_std if name.startswith("roberta.encoder.layer.") else 0.02
+        std = layer_matrix_std if name.startswith(prefix + "encoder.layer.") else 0.02
         sd[name] = normal_fast(_name_seed(seed, name), shape, std)
 
     def vec(name, n, kind):
@@ -136,14 +149,14 @@ def ance_state_dict(seed=0xA11CE, n_layers=12, hidden=768, ffn=3072, vocab=50265
         else:
             sd[name] = normal_fast(_name_seed(seed, name), (n,), 0.05 if kind == "beta" else 0.02)
 
-    p = "roberta.embeddings."
+    p = prefix + "embeddings."
     mat(p + "word_embeddings.weight", (vocab, hidden))
     mat(p + "position_embeddings.weight", (max_pos, hidden))
-    mat(p + "token_type_embeddings.weight", (1, hidden))
+    mat(p + "token_type_embeddings.weight", (type_vocab, hidden))
     vec(p + "LayerNorm.weight", hidden, "gamma")
     vec(p + "LayerNorm.bias", hidden, "beta")
     for i in range(n_layers):
-        q = f"roberta.encoder.layer.{i}."
+        q = f"{prefix}encoder.layer.{i}."
         for nm in ("query", "key", "value"):
             mat(q + f"attention.self.{nm}.weight", (hidden, hidden))
             vec(q + f"attention.self.{nm}.bias", hidden, "bias")

@@ -199,7 +199,7 @@ typedef struct {
     int vocab;         /* 50265 */
     int max_pos;       /* 514 */
     int type_vocab;    /* 1 */
-    int pad_token_id;  /* 1: position ids are cumsum(id != pad)*(id != pad) + pad (HF RoBERTa) */
+    int pad_token_id;  /* 1: position ids are cumsum(id != pad)*(id != pad) + pad (HF RoBERTa); not read with "model" = "bert" (pos = t) */
     float ln_eps;      /* 1e-5 */
 } hac_encoder_config;
 
@@ -207,7 +207,8 @@ int hac_encoder_create(const hac_encoder_config *cfg, int device, hac_encoder **
 void hac_encoder_destroy(hac_encoder *enc);
 /* One tensor of the checkpoint, by its state-dict name (ANCE.from_pretrained keys, :170):
  * "roberta.embeddings.*", "roberta.encoder.layer.N.*", "embeddingHead.*", "norm.*"
- * ("classifier.*" exists in the checkpoint but is unused by forward: do not pass it).
+ * ("classifier.*" exists in the checkpoint but is unused by forward: do not pass it); with "model" = "bert" (hac_encoder_set_option)
+ * the first two are "bert.embeddings.*", "bert.encoder.layer.N.*".
  * data: host float32, copied before return. */
 int hac_encoder_set_weight(hac_encoder *enc, const char *name, const float *data, size_t count);
 /* Checks that every tensor is present and packs the GEMM weights to bf16. */
@@ -278,10 +279,22 @@ int hac_encoder_forward_device(hac_encoder *enc, const void *ids_dev, const void
  * the last layer's rows ("Pooling").  Family choice, "ksplit", "graph" (the mode is part of a captured
  * shape's key), "max_tokens" and the profiling classes work as in "first" (the pool kernel counts in HAC_ENC_CLASS_LN);
  * hac_encoder_last_plan appends " pool=mean"; hac_encoder_layer_state accepts the last layer, n_layers - 1, in this mode only.
- * A sequence the device flags is a NaN row in either mode.  Switching back to "first" restores the default path bit for bit. */
+ * A sequence the device flags is a NaN row in either mode.  Switching back to "first" restores the default path bit for bit.
+ *
+ * "model" = "roberta" (default) | "bert": which arm of the reference's load_model (src/models.py:112-136) the handle serves.
+ * Accepted until the first hac_encoder_set_weight; afterwards, and with any other value, HAC_ERR_INVALID.  "bert" is the
+ * reference's BERT class (src/models.py:66-110) over BertModel, base geometry: the tensors are "bert.embeddings.*" /
+ * "bert.encoder.layer.N.*" (+ the same "embeddingHead.*", "norm.*"; "bert.pooler.*" and "classifier.*" are unused by forward:
+ * do not pass them), and hac_encoder_finalize names the first tensor missing under the chosen model's names.  Position ids are
+ * pos = t for every token, whatever its id ([PAD] = 0 inside a sequence is an ordinary token; pad_token_id is not read), so
+ * the position table's max_pos rows serve L up to min(512, max_pos) -- "roberta" keeps HF's cumsum rule and its bound
+ * min(512, max_pos - 2).  Row 0 of the token-type table (type_vocab = 2) is added, as the reference never passes
+ * token_type_ids; ln_eps is the config's (1e-12).  The layer stack is the one kernel set in both models: every "gemm" family,
+ * "precision", "pooling", "graph" (the model is part of a captured shape's key), "max_tokens" and hac_encoder_layer_state
+ * work as described above.  hac_encoder_last_plan appends " model=bert" (nothing in "roberta"). */
 int hac_encoder_set_option(hac_encoder *enc, const char *name, const char *value);
 /* What the most recent forward ran: "gemm=gemm8|classic256|classic128 attn=stream|twopass sub_batches=N rows=R graph=off|eager-first|replay ksplit=S_out/S_down attn_form=woven|single|twopass"
- * (+ " precision=split" and / or " pool=mean" when the forward ran in those modes; tests and bench.py assert the kernel family they mean to check).  The GEMM family and, with the classic kernels, the tile
+ * (+ " precision=split", " pool=mean" and / or " model=bert" when the forward ran in those modes; tests and bench.py assert the kernel family they mean to check).  The GEMM family and, with the classic kernels, the tile
  * size are chosen once per call, from the rows of the whole batch: every sub-batch runs the same kernels. */
 const char *hac_encoder_last_plan(hac_encoder *enc);
 
