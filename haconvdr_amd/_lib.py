@@ -12,6 +12,8 @@ LIB_PATH = os.environ.get("HAC_LIBRARY_PATH") or os.path.join(_HERE, "csrc", "li
 _LIB = None
 
 HAC_MAX_K = 2048
+HAC_ERR_INVALID = 1    # include/haconvdr.h: a bad argument
+HAC_ERR_UNSUPPORTED = 4
 HAC_ERR_INTERNAL = 5   # include/haconvdr.h: the device detected a broken invariant of the library (never a hang, never wrong bits)
 
 
@@ -38,6 +40,11 @@ def _declare(L):
     L.hac_index_search_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, vp, vp, vp]
     L.hac_index_search_keys_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, ctypes.c_uint32, vp]
     L.hac_index_reset.argtypes = [vp]
+    L.hac_index_reconstruct.argtypes = [vp, i64, i64, c_f32p]
+    L.hac_index_reconstruct_ids.argtypes = [vp, ctypes.POINTER(i64), i64, c_f32p]
+    L.hac_index_reconstruct_device.argtypes = [vp, vp, i64, i64, vp, vp]
+    L.hac_index_score_ids.argtypes = [vp, c_f32p, i64, ctypes.POINTER(i64), i64, c_f32p]
+    L.hac_index_score_ids_device.argtypes = [vp, vp, i64, vp, i64, vp, vp]
     L.hac_index_ntotal.argtypes = [vp]
     L.hac_index_ntotal.restype = i64
     L.hac_index_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p]
@@ -73,7 +80,8 @@ def _declare(L):
     for name in ("hac_index_create", "hac_index_add", "hac_index_add_device", "hac_index_search",
                  "hac_index_search_device", "hac_index_search_keys_device", "hac_index_reset",
                  "hac_index_set_option", "hac_index_set_profiling", "hac_index_profile_drain", "hac_merge_keys_device",
-                 "hac_keys_to_results_device"):
+                 "hac_keys_to_results_device", "hac_index_reconstruct", "hac_index_reconstruct_ids", "hac_index_reconstruct_device",
+                 "hac_index_score_ids", "hac_index_score_ids_device"):
         getattr(L, name).restype = ctypes.c_int
 
 
@@ -83,6 +91,7 @@ EXPORTED_SYMBOLS = (
     "hac_index_add_device", "hac_index_search", "hac_index_search_device", "hac_index_search_keys_device",
     "hac_index_reset", "hac_index_ntotal", "hac_index_set_option", "hac_index_set_profiling", "hac_index_profile_drain", "hac_index_last_plan",
     "hac_index_last_status", "hac_merge_keys_device", "hac_keys_to_results_device",
+    "hac_index_reconstruct", "hac_index_reconstruct_ids", "hac_index_reconstruct_device", "hac_index_score_ids", "hac_index_score_ids_device",
     "hac_encoder_create", "hac_encoder_destroy", "hac_encoder_set_weight", "hac_encoder_finalize", "hac_encoder_forward",
     "hac_encoder_forward_device", "hac_encoder_set_option", "hac_encoder_last_plan", "hac_encoder_set_profiling", "hac_encoder_profile_drain",
     "hac_encoder_profile_drain_class", "hac_encoder_last_clock", "hac_encoder_attention_redo", "hac_encoder_layer_state",

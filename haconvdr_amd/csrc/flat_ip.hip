@@ -237,6 +237,141 @@ __global__ __launch_bounds__(256) void half_image_kernel(const float4 *__restric
     }
 }
 
+// ------------------------------------------------------------------ rows by id
+// Read-back of the rows (hac_index_reconstruct*) and canonical scores of named rows (hac_index_score_ids*).  Row ids are
+// positions of the one-device numbering: group = id / 64 of the segment table, lane = id % 64.  The fp32 tiles are always a
+// valid source; where a segment's row-major copy is current (rimg_tab[s] != null, see upload_segs) the by-id kernels read
+// the row contiguously from it.  Bits only move: no kernel here does arithmetic on a row it returns.
+__device__ __forceinline__ int seg_of_group(const SegDesc *__restrict__ segs, int nseg, u32 g) {
+    int s = 0;
+    while (s + 1 < nseg && g >= segs[s + 1].gstart) ++s;
+    return s;
+}
+// (segment index, pointer to the row's first 16-byte piece, distance between its pieces in 16-byte units)
+__device__ __forceinline__ gf4ptr row_pieces(const SegDesc *__restrict__ segs, const float4 *const *__restrict__ rimg_tab, int nseg,
+                                             long long id, int K4, size_t &stride) {
+    const u32 grp = (u32)(id / GROUP_ROWS), r = (u32)(id % GROUP_ROWS);
+    const int sg = seg_of_group(segs, nseg, grp);
+    const float4 *rimg = rimg_tab[sg];
+    stride = rimg ? 1 : GROUP_ROWS;
+    return rimg ? as_global(rimg) + ((size_t)(grp - segs[sg].gstart) * GROUP_ROWS + r) * K4
+                : as_global(segs[sg].ptr) + (size_t)(grp - segs[sg].gstart) * K4 * GROUP_ROWS + r;
+}
+
+// Rows [i0, i0 + n) -> out, row-major: tile_rows_kernel's padded LDS transpose run backwards.  One workgroup per group the
+// range touches (the first and the last may be partial, consecutive groups may lie in different segments): whole 1-KiB
+// chunks in (one per wave and load), 256 contiguous bytes per 16 lanes out.  untile_rows_kernel's direct form stores one
+// 16-byte piece per lane at a row stride, 64 lanes in 64 rows; it stays what it is for the once-per-index copy.
+__global__ __launch_bounds__(256) void untile_range_kernel(const SegDesc *__restrict__ segs, int nseg, long i0, long n, int K4,
+                                                           f4 *__restrict__ out) {
+    __shared__ f4 tile[16][65];
+    const int tid = threadIdx.x;
+    const long g = i0 / GROUP_ROWS + blockIdx.x;
+    const int sg = seg_of_group(segs, nseg, (u32)g);
+    const gf4ptr src = as_global(segs[sg].ptr) + (size_t)(g - segs[sg].gstart) * K4 * GROUP_ROWS;
+    const long r_lo = max(i0, g * GROUP_ROWS), r_hi = min(i0 + n, g * GROUP_ROWS + GROUP_ROWS);
+    for (int k4b = 0; k4b < K4; k4b += 16) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = tid + 256 * j;
+            const int c = i >> 6, r = i & 63;
+            if (k4b + c < K4) tile[c][r] = src[(size_t)(k4b + c) * GROUP_ROWS + r];   // (rows outside the range: inside the group's allocation, never stored)
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = tid + 256 * j;
+            const int r = i >> 4, c = i & 15;
+            const long dr = g * GROUP_ROWS + r;
+            if (dr >= r_lo && dr < r_hi && k4b + c < K4) out[(size_t)(dr - i0) * K4 + k4b + c] = tile[c][r];
+        }
+        __syncthreads();
+    }
+}
+
+// out[o] = row ids[o], o < n.  One wave per output row, ROWS_PER_WAVE rows in flight per wave (all their loads are issued
+// before the first store).  A row is K4 <= 256 pieces, lane l takes pieces l, l + 64, ...: consecutive 16 bytes out of the
+// row-major copy, or one piece per 1-KiB chunk out of the tiles (one useful piece per 64-byte sector, the price of T64).
+// An id outside [0, n_rows) gives a row of all-ones words and reads nothing.
+constexpr int ROWS_PER_WAVE = 4;
+__global__ __launch_bounds__(256) void rows_by_id_kernel(const SegDesc *__restrict__ segs, const float4 *const *__restrict__ rimg_tab, int nseg,
+                                                         const long long *__restrict__ ids, long n, long n_rows, int K4,
+                                                         f4 *__restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const long o0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * ROWS_PER_WAVE;
+    if (o0 >= n) return;
+    const float ones = __uint_as_float(0xFFFFFFFFu);
+    f4 v[ROWS_PER_WAVE][4];
+#pragma unroll
+    for (int u = 0; u < ROWS_PER_WAVE; ++u) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[u][j] = f4{ones, ones, ones, ones};
+        const long long idv = o0 + u < n ? ids[o0 + u] : -1ll;
+        // the id is the wave's: as a scalar, the segment lookup and the row's base address are scalar work
+        const long long id = ((long long)__builtin_amdgcn_readfirstlane((int)(idv >> 32)) << 32) | (long long)(u32)__builtin_amdgcn_readfirstlane((int)idv);
+        if (id >= 0 && id < n_rows) {
+            size_t stride;
+            const gf4ptr gp = row_pieces(segs, rimg_tab, nseg, id, K4, stride);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (lane + 64 * j < K4) v[u][j] = gp[(size_t)(lane + 64 * j) * stride];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < ROWS_PER_WAVE; ++u) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (o0 + u < n && lane + 64 * j < K4) out[(size_t)(o0 + u) * K4 + lane + 64 * j] = v[u][j];
+    }
+}
+
+// D[i][j] = canonical score of (q[i], row ids[i][j]): the k-ordered fmaf chain from 0 and make_key's "+ 0.0f", i.e. the
+// float a search returns for that pair on every route; -FLT_MAX for an id outside [0, n_rows).  NaN scores are returned as
+// they are (nothing is selected here, so nothing is dropped).  Workgroup = (query i, 256 consecutive j), the query row in
+// LDS, one thread per pair, eight pieces in flight.
+// The chain loop is a second copy of rescore_kernel's (scan_split.inc), not a shared __device__ function: that kernel's
+// register allocation (94 VGPRs, no scratch) is pinned by its place in the prefilter's tail and stays untouched by this file.
+__global__ __launch_bounds__(256) void score_ids_kernel(const SegDesc *__restrict__ segs, const float4 *const *__restrict__ rimg_tab, int nseg,
+                                                        const float *__restrict__ q, const long long *__restrict__ ids, long m,
+                                                        u32 blocks_per_q, long n_rows, int K4, float *__restrict__ D) {
+    __shared__ float qs[HAC_MAX_D];
+    const int tid = threadIdx.x;
+    const size_t qi = blockIdx.x / blocks_per_q;
+    const long j = (long)(blockIdx.x % blocks_per_q) * 256 + tid;
+    const int d = K4 * 4;
+    for (int i = tid; i < d; i += 256) qs[i] = q[qi * d + i];
+    __syncthreads();
+    if (j >= m) return;
+    const long long id = ids[qi * m + j];
+    float res = -FLT_MAX;
+    if (id >= 0 && id < n_rows) {
+        size_t stride;
+        const gf4ptr gp = row_pieces(segs, rimg_tab, nseg, id, K4, stride);
+        float s = 0.f;
+        f4 v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = gp[(size_t)i * stride];
+        for (int t = 0; t < K4; t += 8) {   // (d % 32 == 0: K4 is a multiple of 8)
+            f4 c[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) c[i] = v[i];
+            if (t + 8 < K4) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) v[i] = gp[(size_t)(t + 8 + i) * stride];
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                s = fmaf(c[i].x, qs[4 * (t + i) + 0], s);
+                s = fmaf(c[i].y, qs[4 * (t + i) + 1], s);
+                s = fmaf(c[i].z, qs[4 * (t + i) + 2], s);
+                s = fmaf(c[i].w, qs[4 * (t + i) + 3], s);
+            }
+        }
+        res = s + 0.0f;   // make_key: -0.0 -> +0.0
+    }
+    D[qi * m + j] = res;
+}
+
 // ------------------------------------------------------------------ scan kernel
 struct ScanArgs {
     const SegDesc *segs;
@@ -1201,7 +1336,7 @@ struct DeviceIndex {
         if (h_pin) (void)hipHostFree(h_pin);
         for (GrowBuf *b : {&ws_partial, &ws_pcnt, &ws_seedkeys, &ws_thr, &ws_thrglob, &ws_q, &ws_qt, &ws_keys, &ws_D, &ws_I, &ws_stage[0],
                            &ws_stage[1], &ws_err, &ws_norm, &ws_qsplit, &ws_delta, &ws_cand, &ws_akeys, &ws_fail, &ws_stat, &ws_fbidx[0], &ws_fbidx[1],
-                           &ws_fbq[0], &ws_fbq[1], &ws_fbkeys[0], &ws_fbkeys[1]})
+                           &ws_fbq[0], &ws_fbq[1], &ws_fbkeys[0], &ws_fbkeys[1], &ws_ids})
             b->release();
         if (h_fb) (void)hipHostFree(h_fb);
         if (h_err) (void)hipHostFree(h_err);
@@ -1535,10 +1670,10 @@ struct DeviceIndex {
         return HAC_OK;
     }
 
-    int add_host_rows(const float *x, int64_t n) {
-        DeviceGuard g(device);
-        const int64_t chunk_rows = std::max<int64_t>(GROUP_ROWS, (int64_t)(64u << 20) / (d * 4) / GROUP_ROWS * GROUP_ROWS);  // ~64 MiB
-        const size_t chunk_bytes = (size_t)chunk_rows * d * 4;
+    // rows per staging chunk of the host entry points that move rows (add, reconstruct): ~64 MiB
+    int64_t stage_rows() const { return std::max<int64_t>(GROUP_ROWS, (int64_t)(64u << 20) / (d * 4) / GROUP_ROWS * GROUP_ROWS); }
+    int stage_reserve() {
+        const size_t chunk_bytes = (size_t)stage_rows() * d * 4;
         if (h_stage_bytes < chunk_bytes) {
             for (int i = 0; i < 2; ++i) {
                 if (h_stage[i]) (void)hipHostFree(h_stage[i]);
@@ -1549,6 +1684,13 @@ struct DeviceIndex {
             h_stage_bytes = chunk_bytes;
         }
         for (int i = 0; i < 2; ++i) HAC_TRY(ws_stage[i].reserve(chunk_bytes));
+        return HAC_OK;
+    }
+
+    int add_host_rows(const float *x, int64_t n) {
+        DeviceGuard g(device);
+        const int64_t chunk_rows = stage_rows();
+        HAC_TRY(stage_reserve());
         int64_t done = 0;
         int slot = 0;
         bool used[2] = {false, false};
@@ -1608,6 +1750,128 @@ struct DeviceIndex {
         return HAC_OK;
     }
     int nseg_live = 0;
+
+    // ---- rows by id (hac_index_reconstruct* / hac_index_score_ids*): enqueue on `st` and return.  The only wait is the
+    // segment table's upload after an add / reset / a changed image, which the first search pays too; nothing is allocated,
+    // read back or written to the status ring, so once the table is up these calls can be captured into a graph.
+    static int check_out_ptr(const void *p, const char *what) {
+        if (((uintptr_t)p & 15) != 0) return fail(HAC_ERR_INVALID, "%s: device pointer must be 16-byte aligned", what);
+        return HAC_OK;
+    }
+    int rows_range_device(int64_t i0, int64_t n, float *out_dev, hipStream_t st) {
+        if (i0 < 0 || n < 0 || i0 > ntotal || n > ntotal - i0)
+            return fail(HAC_ERR_INVALID, "reconstruct: rows [%lld, %lld + %lld) are not inside [0, %lld]", (long long)i0, (long long)i0, (long long)n, (long long)ntotal);
+        if (n == 0) return HAC_OK;
+        HAC_TRY(check_out_ptr(out_dev, "reconstruct"));
+        HAC_TRY(upload_segs(st));
+        const long g_lo = (long)(i0 / GROUP_ROWS), g_hi = (long)((i0 + n + GROUP_ROWS - 1) / GROUP_ROWS);
+        untile_range_kernel<<<dim3((unsigned)(g_hi - g_lo)), dim3(256), 0, st>>>(d_segs, nseg_live, (long)i0, (long)n, K4, reinterpret_cast<f4 *>(out_dev));
+        HAC_HIP(hipGetLastError());
+        return HAC_OK;
+    }
+    int rows_ids_device(const int64_t *ids_dev, int64_t n, float *out_dev, hipStream_t st) {
+        if (n == 0) return HAC_OK;
+        if (n > (int64_t)0x7FFFFFFF * (4 * ROWS_PER_WAVE)) return fail(HAC_ERR_UNSUPPORTED, "reconstruct: %lld ids in one call exceed the grid", (long long)n);
+        HAC_TRY(check_out_ptr(out_dev, "reconstruct"));
+        HAC_TRY(upload_segs(st));
+        const int64_t per_wg = 4 * ROWS_PER_WAVE;
+        rows_by_id_kernel<<<dim3((unsigned)((n + per_wg - 1) / per_wg)), dim3(256), 0, st>>>(d_segs, d_rimg, nseg_live, (const long long *)ids_dev, (long)n,
+                                                                                           (long)ntotal, K4, reinterpret_cast<f4 *>(out_dev));
+        HAC_HIP(hipGetLastError());
+        return HAC_OK;
+    }
+    int score_ids_device(const float *q_dev, int64_t nq, const int64_t *ids_dev, int64_t m, float *D_dev, hipStream_t st) {
+        if (nq == 0 || m == 0) return HAC_OK;
+        const int64_t bpq = (m + 255) / 256;
+        if (bpq > 0x7FFFFFFF / nq) return fail(HAC_ERR_UNSUPPORTED, "score_ids: %lld x %lld pairs in one call exceed the grid", (long long)nq, (long long)m);
+        HAC_TRY(check_out_ptr(q_dev, "score_ids"));
+        HAC_TRY(upload_segs(st));
+        score_ids_kernel<<<dim3((unsigned)(nq * bpq)), dim3(256), 0, st>>>(d_segs, d_rimg, nseg_live, q_dev, (const long long *)ids_dev, (long)m, (u32)bpq,
+                                                                          (long)ntotal, K4, D_dev);
+        HAC_HIP(hipGetLastError());
+        return HAC_OK;
+    }
+
+    // Host forms over this shard's rows, synchronous, on the index's own stream, staged through the add's 64-MiB buffers in
+    // chunks (the whole of a 25M-row index is 77 GB: it never exists on the device a second time).
+    // ids != null: out row pos[i] (or i) = row ids[i], local numbering, < 0 = all-ones; ids == null: the rows [i0, i0 + n).
+    GrowBuf ws_ids;
+    int read_rows_host(const int64_t *ids, const int64_t *pos, int64_t i0, int64_t n, float *out) {
+        if (n == 0) return HAC_OK;
+        DeviceGuard g(device);
+        if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", device);
+        const int64_t chunk_rows = stage_rows();
+        const size_t row_bytes = (size_t)d * 4;
+        HAC_TRY(stage_reserve());
+        if (ids) {
+            HAC_TRY(ws_ids.reserve((size_t)std::min(chunk_rows, n) * 8));
+            HAC_TRY(pin_reserve((size_t)std::min(chunk_rows, n) * 8));
+        }
+        HAC_HIP(hipStreamSynchronize(stream));
+        for (int64_t done = 0; done < n; done += chunk_rows) {
+            const int64_t m = std::min(chunk_rows, n - done);
+            if (ids) {
+                std::memcpy(h_pin, ids + done, (size_t)m * 8);
+                HAC_HIP(hipMemcpyAsync(ws_ids.p, h_pin, (size_t)m * 8, hipMemcpyHostToDevice, stream));
+                HAC_TRY(rows_ids_device((const int64_t *)ws_ids.p, m, (float *)ws_stage[0].p, stream));
+            } else {
+                HAC_TRY(rows_range_device(i0 + done, m, (float *)ws_stage[0].p, stream));
+            }
+            HAC_HIP(hipMemcpyAsync(h_stage[0], ws_stage[0].p, (size_t)m * row_bytes, hipMemcpyDeviceToHost, stream));
+            HAC_HIP(hipStreamSynchronize(stream));
+            const char *src = static_cast<const char *>(h_stage[0]);
+            if (pos) {
+                for (int64_t i = 0; i < m; ++i) std::memcpy(out + (size_t)pos[done + i] * d, src + (size_t)i * row_bytes, row_bytes);
+            } else {
+                std::memcpy(out + (size_t)done * d, src, (size_t)m * row_bytes);
+            }
+        }
+        return HAC_OK;
+    }
+    // D[i][j] = score(q[i], row ids[i][j]) for the pairs this shard owns: local ids, -1 = a padding slot (-FLT_MAX), with
+    // `skip` (several devices) ids == skip name another shard's rows and leave D[i][j] alone.  Chunked over queries and, for
+    // very long lists, over j, so that one chunk's queries, ids and scores fit ~64 MiB.
+    int score_ids_host(const float *q, int64_t nq, const int64_t *ids, int64_t m, float *D, bool has_skip, int64_t skip) {
+        if (nq == 0 || m == 0) return HAC_OK;
+        DeviceGuard g(device);
+        if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", device);
+        const size_t budget = (size_t)64 << 20;
+        const int64_t MC = std::min<int64_t>(m, 1 << 20);
+        const int64_t QC = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(budget / ((size_t)MC * 12 + (size_t)d * 4))));
+        const size_t qb = (size_t)QC * d * 4, ib = (size_t)QC * MC * 8, db = (size_t)QC * MC * 4;
+        HAC_TRY(ws_q.reserve(qb));
+        HAC_TRY(ws_ids.reserve(ib));
+        HAC_TRY(ws_D.reserve(db));
+        HAC_TRY(pin_reserve(qb + ib + db));
+        HAC_HIP(hipStreamSynchronize(stream));
+        char *hq = static_cast<char *>(h_pin), *hi = hq + qb, *hd = hi + ib;
+        for (int64_t q0 = 0; q0 < nq; q0 += QC) {
+            const int64_t nqc = std::min(QC, nq - q0);
+            std::memcpy(hq, q + (size_t)q0 * d, (size_t)nqc * d * 4);
+            HAC_HIP(hipMemcpyAsync(ws_q.p, hq, (size_t)nqc * d * 4, hipMemcpyHostToDevice, stream));
+            for (int64_t j0 = 0; j0 < m; j0 += MC) {
+                const int64_t mc = std::min(MC, m - j0);
+                for (int64_t i = 0; i < nqc; ++i) std::memcpy(hi + (size_t)i * mc * 8, ids + (size_t)(q0 + i) * m + j0, (size_t)mc * 8);
+                HAC_HIP(hipMemcpyAsync(ws_ids.p, hi, (size_t)nqc * mc * 8, hipMemcpyHostToDevice, stream));
+                HAC_TRY(score_ids_device((const float *)ws_q.p, nqc, (const int64_t *)ws_ids.p, mc, (float *)ws_D.p, stream));
+                HAC_HIP(hipMemcpyAsync(hd, ws_D.p, (size_t)nqc * mc * 4, hipMemcpyDeviceToHost, stream));
+                HAC_HIP(hipStreamSynchronize(stream));
+                const float *res = reinterpret_cast<const float *>(hd);
+                for (int64_t i = 0; i < nqc; ++i) {
+                    float *Dr = D + (size_t)(q0 + i) * m + j0;
+                    if (!has_skip) {
+                        std::memcpy(Dr, res + (size_t)i * mc, (size_t)mc * 4);
+                    } else {
+                        const int64_t *ir = ids + (size_t)(q0 + i) * m + j0;
+                        for (int64_t j = 0; j < mc; ++j)
+                            if (ir[j] != skip) Dr[j] = res[(size_t)i * mc + j];
+                    }
+                }
+            }
+        }
+        return HAC_OK;
+    }
+
     char last_plan[320] = "none";
     // a device-decided prefilter search leaves its fallback count and err / bound on the device: plan() completes the text
     char plan_head[200] = "";
@@ -2534,6 +2798,152 @@ int hac_index_search(hac_index *idx, const float *q, int64_t nq, int k, float *D
     }
     if (rc_all != HAC_OK) return fail(rc_all, "%s", msg_all.c_str());
     return HAC_OK;
+}
+
+}  // extern "C"
+
+// ---- rows by id: reconstruct / score_ids -----------------------------------------------------------------------------
+namespace {
+// global row id -> (shard, shard-local row): the inverse of remap_positions_kernel, on the host.  One device: the identity.
+struct RowLocator {
+    struct Span {
+        int64_t global0, count, local0;
+        int shard;
+    };
+    std::vector<Span> spans;   // every shard's share of every add(), by first global row
+    explicit RowLocator(const hac_index *idx) {
+        if (idx->shards.size() < 2) return;
+        for (size_t s = 0; s < idx->spans.size(); ++s)
+            for (const SpanDesc &sp : idx->spans[s]) spans.push_back(Span{(int64_t)sp.global0, (int64_t)sp.count, (int64_t)sp.local0, (int)s});
+        std::sort(spans.begin(), spans.end(), [](const Span &a, const Span &b) { return a.global0 < b.global0; });
+    }
+    // id in [0, ntotal)
+    void locate(int64_t id, int &shard, int64_t &local) const {
+        if (spans.empty()) {
+            shard = 0;
+            local = id;
+            return;
+        }
+        size_t lo = 0, hi = spans.size() - 1;   // last span with global0 <= id
+        while (lo < hi) {
+            const size_t mid = (lo + hi + 1) >> 1;
+            if (spans[mid].global0 <= id) lo = mid;
+            else hi = mid - 1;
+        }
+        shard = spans[lo].shard;
+        local = spans[lo].local0 + (id - spans[lo].global0);
+    }
+};
+
+// the first id outside [-1, ntotal): the host entry points refuse it (the *_device ones cannot look)
+int check_host_ids(const char *what, const int64_t *ids, int64_t count, int64_t ntotal) {
+    for (int64_t i = 0; i < count; ++i)
+        if (ids[i] < -1 || ids[i] >= ntotal)
+            return fail(HAC_ERR_INVALID, "%s: id %lld at position %lld is outside [0, %lld) (-1 = a padding slot)", what, (long long)ids[i], (long long)i,
+                        (long long)ntotal);
+    return HAC_OK;
+}
+
+// fn(shard) on every shard, one host thread per device as hac_index_search runs them; the first failure is reported
+template <class F>
+int for_each_shard(hac_index *idx, F fn) {
+    const int S = (int)idx->shards.size();
+    if (S == 1) return fn(0);
+    std::vector<int> rcs(S, HAC_OK);
+    std::vector<std::string> msgs(S);
+    std::vector<std::thread> pool;
+    for (int si = 1; si < S; ++si)
+        pool.emplace_back([&, si] {
+            rcs[si] = fn(si);
+            if (rcs[si] != HAC_OK) msgs[si] = last_error_slot();
+        });
+    rcs[0] = fn(0);
+    if (rcs[0] != HAC_OK) msgs[0] = last_error_slot();
+    for (auto &t : pool) t.join();
+    for (int si = 0; si < S; ++si)
+        if (rcs[si] != HAC_OK) return fail(rcs[si], "shard %d (device %d): %s", si, idx->shards[si]->device, msgs[si].c_str());
+    return HAC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int hac_index_reconstruct_ids(hac_index *idx, const int64_t *ids, int64_t n, float *out) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    if (n < 0 || (n > 0 && (!ids || !out))) return fail(HAC_ERR_INVALID, "reconstruct: bad arguments");
+    if (n == 0) return HAC_OK;
+    HAC_TRY(check_host_ids("reconstruct", ids, n, idx->ntotal));
+    const int S = (int)idx->shards.size();
+    if (S == 1) return idx->shards[0]->read_rows_host(ids, nullptr, 0, n, out);
+    const RowLocator loc(idx);
+    std::vector<std::vector<int64_t>> local(S), pos(S);
+    for (int64_t i = 0; i < n; ++i) {
+        int sh = 0;
+        int64_t l = -1;   // (a padding slot: shard 0 writes its all-ones row)
+        if (ids[i] >= 0) loc.locate(ids[i], sh, l);
+        local[sh].push_back(l);
+        pos[sh].push_back(i);
+    }
+    return for_each_shard(idx, [&](int si) { return idx->shards[si]->read_rows_host(local[si].data(), pos[si].data(), 0, (int64_t)local[si].size(), out); });
+}
+
+int hac_index_reconstruct(hac_index *idx, int64_t i0, int64_t n, float *out) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    if (i0 < 0 || n < 0 || i0 > idx->ntotal || n > idx->ntotal - i0)
+        return fail(HAC_ERR_INVALID, "reconstruct: rows [%lld, %lld + %lld) are not inside [0, %lld]", (long long)i0, (long long)i0, (long long)n,
+                    (long long)idx->ntotal);
+    if (n == 0) return HAC_OK;
+    if (!out) return fail(HAC_ERR_INVALID, "reconstruct: bad arguments");
+    if (idx->shards.size() == 1) return idx->shards[0]->read_rows_host(nullptr, nullptr, i0, n, out);
+    // several devices: consecutive rows alternate between the shards with every add(); the range goes by id, a chunk at a time
+    const int64_t chunk = idx->shards[0]->stage_rows();
+    std::vector<int64_t> ids;
+    for (int64_t done = 0; done < n; done += chunk) {
+        const int64_t m = std::min(chunk, n - done);
+        ids.resize((size_t)m);
+        for (int64_t i = 0; i < m; ++i) ids[(size_t)i] = i0 + done + i;
+        HAC_TRY(hac_index_reconstruct_ids(idx, ids.data(), m, out + (size_t)done * idx->d));
+    }
+    return HAC_OK;
+}
+
+int hac_index_reconstruct_device(hac_index *idx, const int64_t *ids_dev, int64_t i0, int64_t n, float *out_dev, void *hip_stream) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    if (idx->shards.size() != 1) return fail(HAC_ERR_UNSUPPORTED, "reconstruct_device needs a single-device index");
+    if (n < 0 || (n > 0 && !out_dev)) return fail(HAC_ERR_INVALID, "reconstruct_device: bad arguments");
+    DeviceIndex *s = idx->shards[0];
+    DeviceGuard g(s->device);
+    if (ids_dev) return s->rows_ids_device(ids_dev, n, out_dev, (hipStream_t)hip_stream);
+    return s->rows_range_device(i0, n, out_dev, (hipStream_t)hip_stream);
+}
+
+int hac_index_score_ids(hac_index *idx, const float *q, int64_t nq, const int64_t *ids, int64_t m, float *D) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q || !ids || !D))) return fail(HAC_ERR_INVALID, "score_ids: bad arguments");
+    if (nq == 0 || m == 0) return HAC_OK;
+    HAC_TRY(check_host_ids("score_ids", ids, nq * m, idx->ntotal));
+    const int S = (int)idx->shards.size();
+    if (S == 1) return idx->shards[0]->score_ids_host(q, nq, ids, m, D, false, 0);
+    // every shard scores the pairs whose row it holds (padding slots: shard 0) and leaves the others' slots of D alone
+    const RowLocator loc(idx);
+    constexpr int64_t NOT_MINE = -2;
+    std::vector<std::vector<int64_t>> local(S, std::vector<int64_t>((size_t)(nq * m), NOT_MINE));
+    for (int64_t i = 0; i < nq * m; ++i) {
+        int sh = 0;
+        int64_t l = -1;
+        if (ids[i] >= 0) loc.locate(ids[i], sh, l);
+        local[sh][(size_t)i] = l;
+    }
+    return for_each_shard(idx, [&](int si) { return idx->shards[si]->score_ids_host(q, nq, local[si].data(), m, D, true, NOT_MINE); });
+}
+
+int hac_index_score_ids_device(hac_index *idx, const float *q_dev, int64_t nq, const int64_t *ids_dev, int64_t m, float *D_dev, void *hip_stream) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    if (idx->shards.size() != 1) return fail(HAC_ERR_UNSUPPORTED, "score_ids_device needs a single-device index");
+    if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q_dev || !ids_dev || !D_dev))) return fail(HAC_ERR_INVALID, "score_ids_device: bad arguments");
+    DeviceIndex *s = idx->shards[0];
+    DeviceGuard g(s->device);
+    return s->score_ids_device(q_dev, nq, ids_dev, m, D_dev, (hipStream_t)hip_stream);
 }
 
 int hac_index_last_status(hac_index *idx) {

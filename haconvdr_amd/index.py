@@ -31,6 +31,79 @@ def _keep_alive(t, stream):
     t.record_stream(stream)
 
 
+# ---- argument checks of the rows-by-id calls: no handle needed, a mistake raises ValueError before the library is called
+def _as_ids(ids, ndim, what):
+    """ids -> contiguous int64 ndarray of `ndim` dimensions; integers only (a float id is a mistake, not a row)."""
+    a = np.asarray(ids)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"{what}: ids must be integers, got dtype {a.dtype}")
+    if a.ndim != ndim:
+        raise ValueError(f"{what}: ids must have {ndim} dimension(s), got shape {a.shape}")
+    if a.dtype == np.uint64 and a.size and int(a.max()) > np.iinfo(np.int64).max:
+        raise ValueError(f"{what}: id {int(a.max())} does not fit int64")
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def _as_range(i0, n, what):
+    """(i0, n) of reconstruct_n as python ints; n may be None (= up to ntotal, resolved by the caller)."""
+    for name, v in (("i0", i0), ("n", n)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+            raise ValueError(f"{what}: {name} must be an integer, got {v!r}")
+    return int(i0), (None if n is None else int(n))
+
+
+def _as_queries(q, d, what):
+    a = np.asarray(q)
+    if a.dtype.kind not in "fiu" or a.ndim != 2 or a.shape[1] != d:
+        raise ValueError(f"{what} expects [nq, {d}] float32, got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _score_args(q, ids, d):
+    """(q float32 [nq, d], ids int64 [nq, m]) of score_ids."""
+    q = _as_queries(q, d, "score_ids")
+    ids = _as_ids(ids, 2, "score_ids")
+    if ids.shape[0] != q.shape[0]:
+        raise ValueError(f"score_ids: {q.shape[0]} queries but ids of shape {ids.shape} (one list per query)")
+    return q, ids
+
+
+def _as_k(k, what):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= _lib.HAC_MAX_K:
+        raise ValueError(f"{what}: k must be an integer in [1, {_lib.HAC_MAX_K}], got {k!r}")
+    return int(k)
+
+
+def _ids_tensor(ids, ndim, what):
+    import torch
+    if not isinstance(ids, torch.Tensor) or not ids.is_cuda:
+        raise ValueError(f"{what}: ids must be a CUDA tensor")
+    if ids.dtype != torch.int64:
+        raise ValueError(f"{what}: ids must be int64, got {ids.dtype}")
+    if ids.dim() != ndim:
+        raise ValueError(f"{what}: ids must have {ndim} dimension(s), got shape {tuple(ids.shape)}")
+    return ids.contiguous()
+
+
+def _queries_tensor(q, d, what):
+    import torch
+    if not isinstance(q, torch.Tensor) or not q.is_cuda:
+        raise ValueError(f"{what}: q must be a CUDA tensor")
+    if not q.dtype.is_floating_point or q.dim() != 2 or q.shape[1] != d:
+        raise ValueError(f"{what} expects [nq, {d}] float32, got {q.dtype} {tuple(q.shape)}")
+    return q.contiguous().float()
+
+
+def _score_args_tensor(q, ids, d):
+    q = _queries_tensor(q, d, "score_ids_tensor")
+    ids = _ids_tensor(ids, 2, "score_ids_tensor")
+    if ids.shape[0] != q.shape[0]:
+        raise ValueError(f"score_ids_tensor: {q.shape[0]} queries but ids of shape {tuple(ids.shape)} (one list per query)")
+    if ids.device != q.device:
+        raise ValueError(f"score_ids_tensor: q on {q.device} but ids on {ids.device}")
+    return q, ids
+
+
 class FlatIPIndex:
     """faiss.IndexFlatIP(d) drop-in: exact fp32 inner product, results ordered by
     (score desc, row asc), padded with -FLT_MAX / -1.
@@ -81,6 +154,45 @@ class FlatIPIndex:
     def ntotal(self):
         return int(_lib.lib().hac_index_ntotal(self._h))
 
+    # ---- the faiss read-back calls and exact scores of named rows (include/haconvdr.h, "rows by id") -------------
+    def reconstruct_n(self, i0=0, n=None):
+        """index.reconstruct_n(i0, n) -> float32 [n, d], the rows as they were added, bit for bit (n=None: up to ntotal)."""
+        i0, n = _as_range(i0, n, "reconstruct_n")
+        if n is None:
+            n = self.ntotal - i0
+        out = np.empty((max(n, 0), self.d), np.float32)
+        _lib.check(_lib.lib().hac_index_reconstruct(self._h, i0, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        return out
+
+    def reconstruct_batch(self, ids):
+        """index.reconstruct_batch(ids): int64 [n] -> float32 [n, d].  An id of -1 (a padding slot of a search) gives a row
+        of all-ones words, the NaN faiss writes there; any other id outside [0, ntotal) raises HacError."""
+        ids = _as_ids(ids, 1, "reconstruct_batch")
+        out = np.empty((ids.shape[0], self.d), np.float32)
+        _lib.check(_lib.lib().hac_index_reconstruct_ids(self._h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ids.shape[0],
+                                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        return out
+
+    def reconstruct(self, i):
+        """index.reconstruct(i) -> float32 [d]."""
+        return self.reconstruct_batch(_as_ids(i, 0, "reconstruct").reshape(1))[0]
+
+    def search_and_reconstruct(self, q, k):
+        """D, I, R = index.search_and_reconstruct(q, k): R float32 [nq, k, d] holds the rows I names (all-ones where I is -1)."""
+        q = _as_queries(q, self.d, "search_and_reconstruct")
+        D, I = self.search(q, _as_k(k, "search_and_reconstruct"))
+        return D, I, self.reconstruct_batch(I.reshape(-1)).reshape(I.shape[0], I.shape[1], self.d)
+
+    def score_ids(self, q, ids):
+        """Exact scores of named rows: q float32 [nq, d], ids int64 [nq, m] -> float32 [nq, m], the canonical score of every
+        (q[i], row ids[i, j]) -- the bits a search returns for that pair.  -1 scores -FLT_MAX; NaN scores stay NaN."""
+        q, ids = _score_args(q, ids, self.d)
+        D = np.empty(ids.shape, np.float32)
+        _lib.check(_lib.lib().hac_index_score_ids(self._h, q.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), q.shape[0],
+                                                  ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ids.shape[1],
+                                                  D.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        return D
+
     # ---- device-resident variants (torch tensors on the index's GPU) -------
     def add_tensor(self, x, stream=None):
         """x: torch float32 CUDA tensor [n, d], contiguous.  Enqueued on ``stream`` (default: torch's current
@@ -119,6 +231,45 @@ class FlatIPIndex:
         for t in (q, keys):
             _keep_alive(t, stream)
         return keys
+
+    def reconstruct_tensor(self, ids=None, i0=0, n=None, stream=None):
+        """ids: int64 CUDA tensor [n] -> float32 CUDA [n, d]; ids=None: the rows [i0, i0 + n) (n=None: up to ntotal).
+        Enqueued on ``stream`` (default: torch's current stream), no host sync.  Any id outside [0, ntotal), -1 included,
+        gives a row of all-ones words and no error."""
+        import torch
+        if ids is None:
+            i0, n = _as_range(i0, n, "reconstruct_tensor")
+            if n is None:
+                n = self.ntotal - i0
+            idp = ctypes.c_void_p()
+            dev = torch.device("cuda", self.devices[0])
+        else:
+            ids = _ids_tensor(ids, 1, "reconstruct_tensor")
+            i0, n, idp, dev = 0, ids.shape[0], ctypes.c_void_p(ids.data_ptr()), ids.device
+        out = torch.empty((max(n, 0), self.d), dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().hac_index_reconstruct_device(self._h, idp, i0, n, ctypes.c_void_p(out.data_ptr()), _stream_ptr(stream)))
+        for t in (ids, out):
+            if t is not None:
+                _keep_alive(t, stream)
+        return out
+
+    def score_ids_tensor(self, q, ids, stream=None):
+        """q: float32 CUDA [nq, d], ids: int64 CUDA [nq, m] -> float32 CUDA [nq, m]; no host sync.  Any id outside
+        [0, ntotal), -1 included, scores -FLT_MAX."""
+        import torch
+        q, ids = _score_args_tensor(q, ids, self.d)
+        D = torch.empty(tuple(ids.shape), dtype=torch.float32, device=q.device)
+        _lib.check(_lib.lib().hac_index_score_ids_device(self._h, ctypes.c_void_p(q.data_ptr()), q.shape[0], ctypes.c_void_p(ids.data_ptr()),
+                                                         ids.shape[1], ctypes.c_void_p(D.data_ptr()), _stream_ptr(stream)))
+        for t in (q, ids, D):
+            _keep_alive(t, stream)
+        return D
+
+    def search_and_reconstruct_tensor(self, q, k, stream=None):
+        """search_tensor, then reconstruct_tensor on its I, on one stream -> (D [nq,k], I [nq,k], R [nq,k,d])."""
+        q = _queries_tensor(q, self.d, "search_and_reconstruct_tensor")
+        D, I = self.search_tensor(q, _as_k(k, "search_and_reconstruct_tensor"), stream=stream)
+        return D, I, self.reconstruct_tensor(I.reshape(-1), stream=stream).reshape(I.shape[0], I.shape[1], self.d)
 
     def set_option(self, name, value):
         """Tuning / test switch of this handle (include/haconvdr.h: hac_index_set_option), e.g.

@@ -160,7 +160,9 @@ class ResidentCorpus:
         if not ids:
             raise ValueError("no passage block could be loaded")
         self.dev = torch.device("cuda", self.index.devices[0])
-        self.id_map = torch.from_numpy(np.concatenate(ids)).to(self.dev)
+        self._ids = np.concatenate(ids)                       # row -> external passage id
+        self.id_map = torch.from_numpy(self._ids).to(self.dev)
+        self._lookup = None
 
     @property
     def ntotal(self):
@@ -173,3 +175,36 @@ class ResidentCorpus:
             np.ascontiguousarray(query_embeddings, dtype=np.float32))
         D, I = self.index.search_tensor(q.to(self.dev), topN, id_map=self.id_map)
         return D.cpu().numpy().astype(np.float64), I.cpu().numpy()
+
+    # ---- the seam of a re-ranker: rows and exact scores by EXTERNAL passage id --------------------------------------
+    def rows_of(self, passage_ids):
+        """External passage ids (any shape) -> rows of the index, int64 of the same shape; -1 where no block holds the id.
+        The lookup (the block id arrays sorted once, on the host) is built by the first call; an id that several rows
+        carry resolves to the first of them."""
+        if self._lookup is None:
+            order = np.argsort(self._ids, kind="stable")
+            self._lookup = (self._ids[order], order.astype(np.int64))
+        pid = np.asarray(passage_ids)
+        if pid.dtype.kind not in "iu":
+            raise ValueError(f"rows_of: passage ids must be integers, got dtype {pid.dtype}")
+        pid = pid.astype(np.int64)
+        sorted_ids, order = self._lookup
+        if len(sorted_ids) == 0:
+            return np.full(pid.shape, -1, np.int64)
+        at = np.minimum(np.searchsorted(sorted_ids, pid, side="left"), len(sorted_ids) - 1)
+        return np.where(sorted_ids[at] == pid, order[at], -1).astype(np.int64)
+
+    def score(self, query_embeddings, passage_ids):
+        """Exact scores of named passages -- dense re-ranking of another system's run (a BM25 top-1000, the gold passages):
+        query_embeddings float32 [nq,768], passage_ids int64 [nq,m] -> float64 [nq,m], the score search() gives that pair;
+        -FLT_MAX where the passage is in no block."""
+        import torch
+        q = query_embeddings.cpu().numpy() if isinstance(query_embeddings, torch.Tensor) else query_embeddings
+        pid = np.asarray(passage_ids)
+        if pid.ndim != 2:
+            raise ValueError(f"score: passage_ids must be [nq, m], got shape {pid.shape}")
+        return self.index.score_ids(q, self.rows_of(pid)).astype(np.float64)
+
+    def reconstruct(self, passage_ids):
+        """passage_ids int64 [n] -> float32 [n,768], the embeddings as the blocks hold them (all-ones words for an absent id)."""
+        return self.index.reconstruct_batch(self.rows_of(passage_ids))

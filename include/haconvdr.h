@@ -132,6 +132,51 @@ int hac_index_search_keys_device(hac_index *idx, const float *q_dev, int64_t nq,
 int hac_index_reset(hac_index *idx);
 /* index.ntotal */
 int64_t hac_index_ntotal(const hac_index *idx);
+/* ---- rows by id: the faiss read-back calls, and exact scores of named rows --------------------------------------------
+ * Row ids are the index's own numbering: insertion order since the last reset(), over the whole index whatever the number
+ * of devices, int64.  After reset() and a smaller add() the old content is unreachable: ids >= the new ntotal are outside.
+ *
+ * Reconstruct returns the float32 row exactly as it was added, bit for bit (NaN payloads, +-Inf, -0.0 and denormals
+ * included): add() only moves bits into the tiles and these calls only move them back.  The fp16 image is never a source;
+ * a segment's row-major rescoring copy ("rescore_rows") is where it is current, the tiles otherwise -- same bits.
+ *
+ * Score by id: D[i][j] is the canonical score of (q[i], row ids[i][j]): the k-ordered fp32 chain acc = fmaf(x[k], q[k], acc),
+ * k = 0..d-1 from acc = 0, followed by the "+ 0.0f" every search applies when it packs a key.  So score_ids(q, I) of any
+ * search result reproduces that search's D bit for bit, on every route.  This is not a top-k: nothing is dropped, and a NaN
+ * score is returned as NaN.
+ *
+ * Ids outside [0, ntotal):
+ *   *_device entry points  any such id (-1 included): no error, nothing is read out of bounds; reconstruct writes a row of
+ *                          all-ones words (0xFFFFFFFF per float, the NaN faiss's search_and_reconstruct writes for a -1
+ *                          label), score writes -FLT_MAX (the padding score of search);
+ *   host entry points      -1: the same outputs; any other id outside: HAC_ERR_INVALID, the message names the first
+ *                          offending id and its position.
+ * A range [i0, i0 + n) that is not inside [0, ntotal] is HAC_ERR_INVALID.  n == 0 / nq == 0 / m == 0 are HAC_OK and touch
+ * nothing.
+ *
+ * Host variants are synchronous, run on the index's own stream and work on a multi-device index (ids are translated to
+ * (shard, local row) on the host, every shard gathers its share on a host thread of its own); rows and scores are staged
+ * through a bounded (~64 MiB) device workspace in chunks.  *_device variants take a single-device index
+ * (HAC_ERR_UNSUPPORTED otherwise) and 16-byte aligned q_dev / out_dev (HAC_ERR_INVALID otherwise); they enqueue on the
+ * caller's stream and return, never read back, take no slot of the status ring and need no workspace; they synchronize at
+ * most once, for the segment-table upload that the first search after an add / reset also does, and can be captured into
+ * a HIP graph once that table is up (run one call outside the capture first).
+ *
+ * Out of scope: haconvdr_amd.sharded.ShardedSearcher (one process per GPU: reading a row another rank holds would need a
+ * collective); faiss's range_search and remove_ids; and nothing here changes how search routes or what it returns. */
+/* index.reconstruct_n(i0, n): host float32 [n, d]. */
+int hac_index_reconstruct(hac_index *idx, int64_t i0, int64_t n, float *out);
+/* index.reconstruct(i) / index.reconstruct_batch(ids): ids host int64 [n]; out host float32 [n, d]. */
+int hac_index_reconstruct_ids(hac_index *idx, const int64_t *ids, int64_t n, float *out);
+/* Device form of both (and the second half of index.search_and_reconstruct: pass a search's I): ids_dev int64 [n], or
+ * NULL for the range [i0, i0 + n) (i0 is not read when ids_dev is given); out_dev float32 [n, d]. */
+int hac_index_reconstruct_device(hac_index *idx, const int64_t *ids_dev, int64_t i0, int64_t n, float *out_dev, void *hip_stream);
+/* Exact scores of named rows -- what IndexFlatIP users compute as (q[i] * index.reconstruct_batch(ids[i])).sum(-1), in the
+ * canonical order: q host float32 [nq, d]; ids host int64 [nq, m]; D host float32 [nq, m]. */
+int hac_index_score_ids(hac_index *idx, const float *q, int64_t nq, const int64_t *ids, int64_t m, float *D);
+int hac_index_score_ids_device(hac_index *idx, const float *q_dev, int64_t nq, const int64_t *ids_dev, int64_t m, float *D_dev,
+                               void *hip_stream);
+
 /* Device-detected failures of searches enqueued so far (the host entry points report them themselves; the *_device entry
  * points cannot, they never read back).  Waits for the index's own streams only: synchronize YOUR stream first, then call
  * this.  Returns HAC_OK, or HAC_ERR_INTERNAL with the details in hac_last_error(); reading clears the device's error word
