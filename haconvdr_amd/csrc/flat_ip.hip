@@ -27,6 +27,7 @@
 #include <algorithm>
 #include <type_traits>
 #include <cfloat>
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -1087,6 +1088,19 @@ u32 next_pow2(u32 v) {
 
 #include "scan_split.inc"
 
+// Every instantiation of the two templated scan kernels, once: init raises each one's dynamic-LDS limit from these tables and
+// the launches look their kernel up in them, so an instantiation that is launched is one whose limit was raised.
+struct ScanqEntry { int NT, W; void (*fn)(ScanArgs); };
+#define SCANQ_ENTRY(NT, W) {NT, W, scanq_kernel<NT, W>}
+const ScanqEntry SCANQ_TABLE[] = {SCANQ_ENTRY(1, 4), SCANQ_ENTRY(2, 4), SCANQ_ENTRY(3, 4), SCANQ_ENTRY(4, 4),
+                                  SCANQ_ENTRY(1, 8), SCANQ_ENTRY(2, 8), SCANQ_ENTRY(3, 8), SCANQ_ENTRY(4, 8)};
+#undef SCANQ_ENTRY
+struct ScanhEntry { int terms; bool seeding; int qt_act; void (*fn)(ScanArgs, SplitArgs); };   // seeding: the MAXIMA form
+#define SCANH_ENTRY(TERMS, SEEDING, QT_ACT) {TERMS, SEEDING, QT_ACT, scanh_kernel<TERMS, SEEDING, QT_ACT>}
+const ScanhEntry SCANH_TABLE[] = {SCANH_ENTRY(1, false, 16), SCANH_ENTRY(3, false, 16), SCANH_ENTRY(1, true, 16), SCANH_ENTRY(3, true, 16),
+                                  SCANH_ENTRY(1, false, 8),  SCANH_ENTRY(1, true, 8),   SCANH_ENTRY(1, false, 4), SCANH_ENTRY(1, true, 4)};
+#undef SCANH_ENTRY
+
 // ------------------------------------------------------------------ one-device index
 struct Segment {
     float4 *buf = nullptr;   // cap_rows * d fp32 (T64 tiles)
@@ -1165,10 +1179,19 @@ struct DeviceIndex {
         if (const char *e = getenv("HAC_SCANQ_WAVES")) tune.scanq_waves = e[0] == '4' ? 4 : 8;
         if (getenv("HAC_SCAN_NO_P8")) tune.no_p8 = true;
     }
+    // v as one whole decimal integer in [lo, hi]
+    static bool parse_int(const std::string &v, long lo, long hi, long &out) {
+        char *end = nullptr;
+        const long t = strtol(v.c_str(), &end, 10);
+        if (v.empty() || *end || t < lo || t > hi) return false;
+        out = t;
+        return true;
+    }
     // a value outside the documented set is an error, never a silent default (a mistyped value in a cross-check test
     // would otherwise exercise the wrong kernels and still pass)
     int set_option(const char *name, const char *value) {
         const std::string n(name), v(value ? value : "");
+        long t = 0;
         auto one_of = [&](std::initializer_list<const char *> allowed) {
             for (const char *a : allowed)
                 if (v == a) return true;
@@ -1217,19 +1240,13 @@ struct DeviceIndex {
             if (!one_of({"0", "1", "auto"})) return HAC_ERR_INVALID;
             tune.rescore_rows = v == "0" ? 0 : (v == "1" ? 1 : -1);
         } else if (n == "debug_oom") {
-            char *end = nullptr;
-            const long t = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || t < 0 || t > 1000) return fail(HAC_ERR_INVALID, "index option debug_oom = '%s': an integer 0..1000", v.c_str());
+            if (!parse_int(v, 0, 1000, t)) return fail(HAC_ERR_INVALID, "index option debug_oom = '%s': an integer 0..1000", v.c_str());
             tune.debug_oom = (int)t;
         } else if (n == "debug_max_pass") {
-            char *end = nullptr;
-            const long t = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || t < 0 || t > 1000000) return fail(HAC_ERR_INVALID, "index option debug_max_pass = '%s': an integer >= 0", v.c_str());
+            if (!parse_int(v, 0, 1000000, t)) return fail(HAC_ERR_INVALID, "index option debug_max_pass = '%s': an integer >= 0", v.c_str());
             tune.debug_max_pass = (int)t;
         } else if (n == "seed_groups_max") {
-            char *end = nullptr;
-            const long t = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || t < 0) return fail(HAC_ERR_INVALID, "index option seed_groups_max = '%s': an integer >= 0 (0 = 14 sqrt(groups))", v.c_str());
+            if (!parse_int(v, 0, LONG_MAX, t)) return fail(HAC_ERR_INVALID, "index option seed_groups_max = '%s': an integer >= 0 (0 = 14 sqrt(groups))", v.c_str());
             tune.seed_groups_max = t <= 0 ? 0 : (int)std::max<long>(768, std::min<long>(t, 1 << 30));
         } else {
             return fail(HAC_ERR_INVALID, "unknown index option '%s'", name);
@@ -1243,31 +1260,44 @@ struct DeviceIndex {
     u32 *h_err = nullptr;      // pinned copy
 
     GrowBuf ws_fbidx[2], ws_fbq[2], ws_fbkeys[2];   // per cascade level: failed queries, their matrix, their keys
-    u32 *h_fb = nullptr;       // pinned: [0] failed queries, [1] max |s~ - s| / delta (float bits), [2..] flags / indices
-    size_t h_fb_words = 0;
+    PinBuf h_fb;               // u32 words: [0] failed queries, [1] max |s~ - s| / delta (float bits), [2..] flags / indices
     long split_searches = 0, split_fallback_queries = 0;
-    void *h_stage[2] = {nullptr, nullptr};
-    size_t h_stage_bytes = 0;
+    PinBuf h_stage[2];
     // Small host<->device traffic (queries, results, segment table) always goes through
     // pinned memory: pageable hipMemcpyAsync is not reliably stream-ordered on this stack.
-    void *h_pin = nullptr;
-    size_t h_pin_bytes = 0;
+    PinBuf h_pin;
     SegDesc *h_segs = nullptr;
-    int pin_reserve(size_t bytes) {
-        if (bytes <= h_pin_bytes) return HAC_OK;
-        if (h_pin) (void)hipHostFree(h_pin);
-        h_pin = nullptr;
-        h_pin_bytes = 0;
-        hipError_t e = hipHostMalloc(&h_pin, bytes + bytes / 4, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(HAC_ERR_OOM, "hipHostMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-        h_pin_bytes = bytes + bytes / 4;
-        return HAC_OK;
-    }
+    int pin_reserve(size_t bytes) { return bytes <= h_pin.cap ? HAC_OK : h_pin.reserve(bytes + bytes / 4, bytes); }
     hipEvent_t stage_ev[2] = {nullptr, nullptr};
     // profiling: one hipEvent pair per search around the main scan kernel, on the launch stream
     bool profiling = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
     size_t ev_used = 0;
+    // (a failure between the two leaves ev_used where it was: the pair is recorded over by the next timed scan)
+    int prof_begin(hipStream_t st) {
+        if (!profiling) return HAC_OK;
+        if (ev_used == ev_pool.size()) {
+            hipEvent_t a0, a1;
+            HAC_HIP(hipEventCreate(&a0));
+            HAC_HIP(hipEventCreate(&a1));
+            ev_pool.emplace_back(a0, a1);
+        }
+        HAC_HIP(hipEventRecord(ev_pool[ev_used].first, st));
+        return HAC_OK;
+    }
+    int prof_end(hipStream_t st) {
+        if (!profiling) return HAC_OK;
+        HAC_HIP(hipEventRecord(ev_pool[ev_used].second, st));
+        ++ev_used;
+        return HAC_OK;
+    }
+    // the scans of a prefilter search's fallback are not among its timed kernels: profiling is off while one of these lives
+    struct Untimed {
+        bool &flag;
+        const bool was;
+        explicit Untimed(bool &f) : flag(f), was(f) { flag = false; }
+        ~Untimed() { flag = was; }
+    };
 
     int init(int d_, int device_) {
         d = d_;
@@ -1305,16 +1335,9 @@ struct DeviceIndex {
                                         (int)LDS_LIMIT));
             HAC_HIP(hipFuncSetAttribute((const void *)merge_keys_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)(64 * 1024)));
-            const void *fq[] = {(const void *)scanq_kernel<1, 4>, (const void *)scanq_kernel<2, 4>, (const void *)scanq_kernel<3, 4>,
-                                (const void *)scanq_kernel<4, 4>, (const void *)scanq_kernel<1, 8>, (const void *)scanq_kernel<2, 8>,
-                                (const void *)scanq_kernel<3, 8>, (const void *)scanq_kernel<4, 8>};
-            for (const void *f : fq) HAC_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
+            for (const ScanqEntry &e : SCANQ_TABLE) HAC_HIP(hipFuncSetAttribute((const void *)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             HAC_HIP(hipFuncSetAttribute((const void *)sample_scores_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(64 * 1024)));
-            const void *fh[] = {(const void *)scanh_kernel<1, false>, (const void *)scanh_kernel<3, false>,
-                                (const void *)scanh_kernel<1, true>, (const void *)scanh_kernel<3, true>,
-                                (const void *)scanh_kernel<1, false, 8>, (const void *)scanh_kernel<1, true, 8>,
-                                (const void *)scanh_kernel<1, false, 4>, (const void *)scanh_kernel<1, true, 4>};
-            for (const void *f : fh) HAC_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
+            for (const ScanhEntry &e : SCANH_TABLE) HAC_HIP(hipFuncSetAttribute((const void *)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             attr_done[device] = true;
         }
         return HAC_OK;
@@ -1333,20 +1356,17 @@ struct DeviceIndex {
         if (h_segs) (void)hipHostFree(h_segs);
         if (d_rimg) (void)hipFree(d_rimg);
         if (h_rimg) (void)hipHostFree(h_rimg);
-        if (h_pin) (void)hipHostFree(h_pin);
+        for (PinBuf *b : {&h_pin, &h_fb, &h_stage[0], &h_stage[1]}) b->release();
         for (GrowBuf *b : {&ws_partial, &ws_pcnt, &ws_seedkeys, &ws_thr, &ws_thrglob, &ws_q, &ws_qt, &ws_keys, &ws_D, &ws_I, &ws_stage[0],
                            &ws_stage[1], &ws_err, &ws_norm, &ws_qsplit, &ws_delta, &ws_cand, &ws_akeys, &ws_fail, &ws_stat, &ws_fbidx[0], &ws_fbidx[1],
                            &ws_fbq[0], &ws_fbq[1], &ws_fbkeys[0], &ws_fbkeys[1], &ws_ids})
             b->release();
-        if (h_fb) (void)hipHostFree(h_fb);
         if (h_err) (void)hipHostFree(h_err);
         if (h_plan) (void)hipHostFree(h_plan);
         for (hipEvent_t ev : ev_plan)
             if (ev) (void)hipEventDestroy(ev);
-        for (int i = 0; i < 2; ++i) {
-            if (h_stage[i]) (void)hipHostFree(h_stage[i]);
-            if (stage_ev[i]) (void)hipEventDestroy(stage_ev[i]);
-        }
+        for (hipEvent_t ev : stage_ev)
+            if (ev) (void)hipEventDestroy(ev);
         for (auto &e : ev_pool) {
             (void)hipEventDestroy(e.first);
             (void)hipEventDestroy(e.second);
@@ -1674,15 +1694,7 @@ struct DeviceIndex {
     int64_t stage_rows() const { return std::max<int64_t>(GROUP_ROWS, (int64_t)(64u << 20) / (d * 4) / GROUP_ROWS * GROUP_ROWS); }
     int stage_reserve() {
         const size_t chunk_bytes = (size_t)stage_rows() * d * 4;
-        if (h_stage_bytes < chunk_bytes) {
-            for (int i = 0; i < 2; ++i) {
-                if (h_stage[i]) (void)hipHostFree(h_stage[i]);
-                h_stage[i] = nullptr;
-                hipError_t e = hipHostMalloc(&h_stage[i], chunk_bytes, hipHostMallocDefault);
-                if (e != hipSuccess) return fail(HAC_ERR_OOM, "hipHostMalloc(%zu) failed: %s", chunk_bytes, hipGetErrorString(e));
-            }
-            h_stage_bytes = chunk_bytes;
-        }
+        for (int i = 0; i < 2; ++i) HAC_TRY(h_stage[i].reserve(chunk_bytes));
         for (int i = 0; i < 2; ++i) HAC_TRY(ws_stage[i].reserve(chunk_bytes));
         return HAC_OK;
     }
@@ -1700,7 +1712,7 @@ struct DeviceIndex {
             {   // pageable -> pinned staging: one core copies ~12 GB/s, the link takes ~50: split the chunk over a few threads
                 const size_t bytes = (size_t)m * d * 4;
                 const char *src = reinterpret_cast<const char *>(x + (size_t)done * d);
-                char *dst = static_cast<char *>(h_stage[slot]);
+                char *dst = static_cast<char *>(h_stage[slot].p);
                 const int nt = bytes >= (8u << 20) ? 4 : 1;
                 const size_t part = (bytes / nt + 4095) & ~(size_t)4095;
                 std::vector<std::thread> pool;
@@ -1711,7 +1723,7 @@ struct DeviceIndex {
                 std::memcpy(dst, src, std::min(bytes, part));
                 for (auto &th : pool) th.join();
             }
-            HAC_HIP(hipMemcpyAsync(ws_stage[slot].p, h_stage[slot], (size_t)m * d * 4, hipMemcpyHostToDevice, stream));
+            HAC_HIP(hipMemcpyAsync(ws_stage[slot].p, h_stage[slot].p, (size_t)m * d * 4, hipMemcpyHostToDevice, stream));
             // one new segment per add() at most: size it for everything that is left
             HAC_TRY(add_device_rows((const float *)ws_stage[slot].p, m, stream, n - done));
             HAC_HIP(hipEventRecord(stage_ev[slot], stream));
@@ -1811,15 +1823,15 @@ struct DeviceIndex {
         for (int64_t done = 0; done < n; done += chunk_rows) {
             const int64_t m = std::min(chunk_rows, n - done);
             if (ids) {
-                std::memcpy(h_pin, ids + done, (size_t)m * 8);
-                HAC_HIP(hipMemcpyAsync(ws_ids.p, h_pin, (size_t)m * 8, hipMemcpyHostToDevice, stream));
+                std::memcpy(h_pin.p, ids + done, (size_t)m * 8);
+                HAC_HIP(hipMemcpyAsync(ws_ids.p, h_pin.p, (size_t)m * 8, hipMemcpyHostToDevice, stream));
                 HAC_TRY(rows_ids_device((const int64_t *)ws_ids.p, m, (float *)ws_stage[0].p, stream));
             } else {
                 HAC_TRY(rows_range_device(i0 + done, m, (float *)ws_stage[0].p, stream));
             }
-            HAC_HIP(hipMemcpyAsync(h_stage[0], ws_stage[0].p, (size_t)m * row_bytes, hipMemcpyDeviceToHost, stream));
+            HAC_HIP(hipMemcpyAsync(h_stage[0].p, ws_stage[0].p, (size_t)m * row_bytes, hipMemcpyDeviceToHost, stream));
             HAC_HIP(hipStreamSynchronize(stream));
-            const char *src = static_cast<const char *>(h_stage[0]);
+            const char *src = static_cast<const char *>(h_stage[0].p);
             if (pos) {
                 for (int64_t i = 0; i < m; ++i) std::memcpy(out + (size_t)pos[done + i] * d, src + (size_t)i * row_bytes, row_bytes);
             } else {
@@ -1844,7 +1856,7 @@ struct DeviceIndex {
         HAC_TRY(ws_D.reserve(db));
         HAC_TRY(pin_reserve(qb + ib + db));
         HAC_HIP(hipStreamSynchronize(stream));
-        char *hq = static_cast<char *>(h_pin), *hi = hq + qb, *hd = hi + ib;
+        char *hq = static_cast<char *>(h_pin.p), *hi = hq + qb, *hd = hi + ib;
         for (int64_t q0 = 0; q0 < nq; q0 += QC) {
             const int64_t nqc = std::min(QC, nq - q0);
             std::memcpy(hq, q + (size_t)q0 * d, (size_t)nqc * d * 4);
@@ -1951,12 +1963,12 @@ struct DeviceIndex {
 
     static size_t scanq_lds(int NQ, int C) { return (size_t)NQ * (2 * 16 * 16 + (size_t)C * 8 + 8) + 16; }
 
-    int make_plan(int64_t nq, int k, u32 n_items, Plan &pl, bool want16 = false) const {
+    int make_plan(int64_t nq, int k, u32 n_items, Plan &pl) const {
         pl.kind = 0;
         pl.NT = 0;
         pl.W = SCAN_WAVES;
         // many queries: GEMM-shaped kernel, NQ = 32*NT queries per workgroup
-        if (nq > 16 && K4 % 16 == 0 && !want16 && !tune.force_scan16) {
+        if (nq > 16 && K4 % 16 == 0 && !tune.force_scan16) {
             const int C2 = (int)std::max<u32>(32u, next_pow2((u32)k + 1u));
             int best_nt = 0;
             int64_t best_pad = 0;
@@ -2002,28 +2014,26 @@ struct DeviceIndex {
         return HAC_OK;
     }
 
-    template <int NT, int W>
-    static void launch_scanq(const ScanArgs &a, int P, int n_qtiles, size_t lds, hipStream_t st) {
-        scanq_kernel<NT, W><<<dim3((unsigned)P, (unsigned)n_qtiles), dim3(W * 64), lds, st>>>(a);
-    }
-
-    int run_scan(const Plan &pl, const float *q_dev, int64_t nq, int k, u32 g_first, u32 g_step, u32 n_items,
-                 const float *thr_init, u32 pos_base, int P, hipStream_t st, bool timed, const int *nq_dev = nullptr, bool cleared = false) {
-        ScanArgs a;
-        a.nq_dev = nq_dev;
+    // the fields every scan launch shares (the rest zero)
+    ScanArgs scan_args(const float *q_dev, int64_t nq) const {
+        ScanArgs a{};
         a.segs = d_segs;
         a.nseg = nseg_live;
         a.q = reinterpret_cast<const float4 *>(q_dev);
-        a.qt = reinterpret_cast<const float4 *>(ws_qt.p);
         a.nq = (int)nq;
         a.K4 = K4;
+        a.n_rows = (long)ntotal;
+        return a;
+    }
+    int run_scan(const Plan &pl, const float *q_dev, int64_t nq, int k, u32 G, const float *thr_init, u32 pos_base, hipStream_t st, const int *nq_dev, bool cleared) {
+        ScanArgs a = scan_args(q_dev, nq);
+        a.nq_dev = nq_dev;
+        a.qt = reinterpret_cast<const float4 *>(ws_qt.p);
         a.k = k;
         a.C = pl.C;
         a.QT = pl.QT;
-        a.n_rows = (long)ntotal;
-        a.g_first = g_first;
-        a.g_step = g_step;
-        a.n_items = n_items;
+        a.g_step = 1;
+        a.n_items = G;
         a.thr_init = thr_init;
         a.thr_glob = thrglob();
         a.partial = (u64 *)ws_partial.p;
@@ -2033,47 +2043,26 @@ struct DeviceIndex {
             HAC_HIP(hipMemsetAsync(ws_pcnt.p, 0, (size_t)nq * 4, st));
             HAC_TRY(clear_thrglob((size_t)pl.n_qtiles * pl.QT, st));
         }
-        if (timed) {
-            if (ev_used == ev_pool.size()) {
-                hipEvent_t a0, a1;
-                HAC_HIP(hipEventCreate(&a0));
-                HAC_HIP(hipEventCreate(&a1));
-                ev_pool.emplace_back(a0, a1);
-            }
-            HAC_HIP(hipEventRecord(ev_pool[ev_used].first, st));
-        }
+        HAC_TRY(prof_begin(st));
         if (pl.kind == 0) {
-            scan16_kernel<<<dim3((unsigned)P, (unsigned)pl.n_qtiles), dim3(SCAN_WAVES * 64), pl.lds_scan, st>>>(a);
+            scan16_kernel<<<dim3((unsigned)pl.P, (unsigned)pl.n_qtiles), dim3(SCAN_WAVES * 64), pl.lds_scan, st>>>(a);
         } else {
-            const int key = pl.NT * 10 + pl.W;
-            switch (key) {
-                case 14: launch_scanq<1, 4>(a, P, pl.n_qtiles, pl.lds_scan, st); break;
-                case 24: launch_scanq<2, 4>(a, P, pl.n_qtiles, pl.lds_scan, st); break;
-                case 34: launch_scanq<3, 4>(a, P, pl.n_qtiles, pl.lds_scan, st); break;
-                case 44: launch_scanq<4, 4>(a, P, pl.n_qtiles, pl.lds_scan, st); break;
-                case 18: launch_scanq<1, 8>(a, P, pl.n_qtiles, pl.lds_scan, st); break;
-                case 28: launch_scanq<2, 8>(a, P, pl.n_qtiles, pl.lds_scan, st); break;
-                case 38: launch_scanq<3, 8>(a, P, pl.n_qtiles, pl.lds_scan, st); break;
-                case 48: launch_scanq<4, 8>(a, P, pl.n_qtiles, pl.lds_scan, st); break;
-                default: return fail(HAC_ERR_UNSUPPORTED, "internal: no scanq<%d,%d>", pl.NT, pl.W);
-            }
+            void (*fn)(ScanArgs) = nullptr;
+            for (const ScanqEntry &e : SCANQ_TABLE)
+                if (e.NT == pl.NT && e.W == pl.W) fn = e.fn;
+            if (!fn) return fail(HAC_ERR_UNSUPPORTED, "internal: no scanq<%d,%d>", pl.NT, pl.W);
+            fn<<<dim3((unsigned)pl.P, (unsigned)pl.n_qtiles), dim3(pl.W * 64), pl.lds_scan, st>>>(a);
         }
         HAC_HIP(hipGetLastError());
-        if (timed) {
-            HAC_HIP(hipEventRecord(ev_pool[ev_used].second, st));
-            ++ev_used;
-        }
-        return HAC_OK;
+        return prof_end(st);
     }
 
-    // keys_out: device u64 [nq][k]; the exact fp32 kernels only.  nq_dev (optional): the number of queries present lives on
+    // keys_out: device u64 [nq][k]; the exact fp32 kernels only (arguments: checked by search_keys).  nq_dev (optional): the number of queries present lives on
     // the device and nq is the capacity everything is sized for (the prefilter's device-decided fallback): no threshold
     // seeding (fewer launches on a path that is empty in the common case), the scan's workgroups are shared among the live
     // query tiles (vgrid), and rows of keys_out beyond *nq_dev are left alone.
     int search_keys_exact(const float *q_dev, int64_t nq, int k, u64 *keys_out, u32 pos_base, hipStream_t st, const int *nq_dev = nullptr, bool cleared = false) {
         if (nq == 0) return HAC_OK;
-        if (((uintptr_t)q_dev & 15) != 0) return fail(HAC_ERR_INVALID, "search: query pointer must be 16-byte aligned");
-        if ((uint64_t)pos_base + (uint64_t)ntotal > 0xFFFFFFFFull) return fail(HAC_ERR_UNSUPPORTED, "row positions exceed 32 bits");
         if (ntotal == 0) {
             HAC_HIP(hipMemsetAsync(keys_out, 0, (size_t)nq * k * 8, st));
             return HAC_OK;
@@ -2102,13 +2091,7 @@ struct DeviceIndex {
             const u32 S = 4u * n_sample;                             // four maxima per sample group
             HAC_TRY(ws_seedkeys.reserve((size_t)nq * S * 4));        // group maxima [nq][S]
             HAC_TRY(ws_thr.reserve((size_t)nq * 4));
-            ScanArgs a{};
-            a.segs = d_segs;
-            a.nseg = nseg_live;
-            a.q = reinterpret_cast<const float4 *>(q_dev);
-            a.nq = (int)nq;
-            a.K4 = K4;
-            a.n_rows = (long)ntotal;
+            ScanArgs a = scan_args(q_dev, nq);
             a.g_first = 0;
             a.g_step = G / n_sample;
             a.n_items = n_sample;
@@ -2120,16 +2103,16 @@ struct DeviceIndex {
             HAC_HIP(hipGetLastError());
             thr_init = (const float *)ws_thr.p;
         }
-        if (nq_dev) {
-            // (the caller's plan stays: this is its fallback)
-        } else if (pl.kind == 1)
-            snprintf(last_plan, sizeof last_plan, "scanq_kernel<NT=%d,W=%d> grid=(%d,%d) NQ=%d C=%d lds=%zu seed=%d", pl.NT, pl.W, pl.P,
-                     pl.n_qtiles, pl.QT, pl.C, pl.lds_scan, thr_init ? 1 : 0);
-        else
-            snprintf(last_plan, sizeof last_plan, "scan16_kernel<W=%d> grid=(%d,%d) QT=%d C=%d lds=%zu seed=%d", SCAN_WAVES, pl.P,
-                     pl.n_qtiles, pl.QT, pl.C, pl.lds_scan, thr_init ? 1 : 0);
-        if (!nq_dev) plan_text_slot = -1;   // (last_plan is this search's text; older device-decided searches still deliver their counts)
-        HAC_TRY(run_scan(pl, q_dev, nq, k, 0, 1, G, thr_init, pos_base, pl.P, st, profiling, nq_dev, cleared));
+        if (!nq_dev) {   // (a device-decided fallback: the caller's plan stays)
+            if (pl.kind == 1)
+                snprintf(last_plan, sizeof last_plan, "scanq_kernel<NT=%d,W=%d> grid=(%d,%d) NQ=%d C=%d lds=%zu seed=%d", pl.NT, pl.W, pl.P,
+                         pl.n_qtiles, pl.QT, pl.C, pl.lds_scan, thr_init ? 1 : 0);
+            else
+                snprintf(last_plan, sizeof last_plan, "scan16_kernel<W=%d> grid=(%d,%d) QT=%d C=%d lds=%zu seed=%d", SCAN_WAVES, pl.P,
+                         pl.n_qtiles, pl.QT, pl.C, pl.lds_scan, thr_init ? 1 : 0);
+            plan_text_slot = -1;   // (last_plan is this search's text; older device-decided searches still deliver their counts)
+        }
+        HAC_TRY(run_scan(pl, q_dev, nq, k, G, thr_init, pos_base, st, nq_dev, cleared));
         // the workgroups' survivors sit densely per query: radix select of the k best, one sort of k keys
         const int np2 = (int)next_pow2((u32)k);
         select_keys_kernel<<<dim3((unsigned)nq), dim3(256), (size_t)np2 * 8, st>>>((const u64 *)ws_partial.p, (size_t)pl.P * k,
@@ -2190,17 +2173,6 @@ struct DeviceIndex {
         return light_searches_since_add++ >= LIGHT_SEARCHES_BEFORE_IMAGE;
     }
 
-    int fb_reserve(size_t words) {
-        if (words <= h_fb_words) return HAC_OK;
-        if (h_fb) (void)hipHostFree(h_fb);
-        h_fb = nullptr;
-        h_fb_words = 0;
-        hipError_t e = hipHostMalloc((void **)&h_fb, words * 4 * 2, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(HAC_ERR_OOM, "hipHostMalloc(%zu) failed: %s", words * 8, hipGetErrorString(e));
-        h_fb_words = words * 2;
-        return HAC_OK;
-    }
-
     // Cascade: one fp16 product per score (|s~ - s| ~ 1.2e-3 |q||x| proven) decides every query whose candidate
     // list it can certify; if many fail, three products (hi/lo split, ~2.8e-4 |q||x|, three times the MFMA work)
     // retry those; whatever is left goes to the exact fp32 kernels.  level 0 -> terms 1, level 1 -> terms 3.
@@ -2208,274 +2180,320 @@ struct DeviceIndex {
     // Queries go through in chunks of at most 1024 (four 256-query tiles x 64 row streams fill the chip): the
     // rescoring of chunk c (HBM gathers, no matrix work) runs on a second stream under the scan of chunk c+1.
     static constexpr int64_t SPLIT_CHUNK = 1024;
-    int search_keys_split(const float *q_dev, int64_t nq, int k, u64 *keys_out, u32 pos_base, hipStream_t st, int level = 0,
-                          bool device_decides = false) {
+    // where a chunk of n queries runs and how its scan is cut
+    struct ChunkGeom {
+        int n_qtiles, qt_act, n_pass;
+        long P, pstride;
+        u32 round_groups, GA, bounds[MAX_PASSES + 1];
+        bool seeded;
+    };
+    // One prefilter search (one cascade level): the call's arguments, the rest filled once by split_begin, carried through the stages below.
+    struct SplitCtx {
+        const float *q_dev;
+        int64_t nq;
+        int k;
+        u64 *keys_out;
+        u32 pos_base;
+        hipStream_t st;
+        int level;
+        int terms = 1;
+        size_t lds = 0;
+        u32 G = 0;
+        int64_t chunk = 0;
+        ScanArgs a{};    // the chunk-independent fields; the stages fill in the rest per chunk and pass
+        SplitArgs sp{};
+        int n_chunks = 0;
+        ChunkGeom last{};   // the last chunk's: what the plan text says
+    };
+    ChunkGeom chunk_geometry(int64_t n, u32 G, int terms) const {
+        ChunkGeom g;
+        g.n_qtiles = (int)((n + SH_NQ - 1) / SH_NQ);
+        long P = std::max<long>(1, n_cu / g.n_qtiles);
+        if (P >= 8) P = P / 8 * 8;  // same-row workgroups of different query tiles share an XCD (L2)
+        g.P = std::max<long>(1, std::min<long>(P, (G + SH_GPR - 1) / SH_GPR));
+        g.pstride = (long)g.P * SPLIT_K2 * MAX_PASSES;   // a workgroup flushes at most K2 survivors per query and pass
+        // one tile of at most 128 / 64 real queries: the instantiations without the empty 16-query tiles' matrix work (scanh_kernel, QT_ACT)
+        const bool few = terms == 1 && g.n_qtiles == 1 && !tune.no_halfq;
+        g.qt_act = few && n <= SH_NQ / 4 ? 4 : few && n <= SH_NQ / 2 ? 8 : 16;
+        g.round_groups = (u32)g.P * SH_GPR;
+        // (a scan that will be cut into passes refreshes its thresholds after ~6k groups anyway: 1024 groups of seeding do)
+        u32 probe_bounds[MAX_PASSES + 1];
+        const bool multipass = scan_passes(G, g.round_groups, true, probe_bounds) > 1;
+        const u32 seed_cap = tune.seed_groups_max > 0 ? (u32)tune.seed_groups_max : multipass ? 1024u : (u32)(14.0 * std::sqrt((double)G));
+        g.GA = std::min<u32>(G, (std::max<u32>(std::min<u32>(G / 16u, seed_cap), 768u) + g.round_groups - 1u) / g.round_groups * g.round_groups);
+        g.seeded = (size_t)4 * g.GA >= (size_t)SPLIT_K2;
+        g.n_pass = scan_passes(G, g.round_groups, g.seeded, g.bounds);
+        return g;
+    }
+    float *delta_of(int64_t off) const { return (float *)ws_delta.p + off; }
+    u64 *akeys_of(int64_t off) const { return (u64 *)ws_akeys.p + (size_t)off * SPLIT_K2; }
+
+    // the images and the segment table current, the workspaces of every chunk reserved, the argument templates filled
+    int split_begin(SplitCtx &c) {
         const int K2 = SPLIT_K2, C2 = SPLIT_C2;
-        const int terms = level == 0 ? tune.split_terms : 3;   // split_terms = 3: tests pin the first level
+        const int64_t nq = c.nq;
+        hipStream_t st = c.st;
+        c.terms = c.level == 0 ? tune.split_terms : 3;         // split_terms = 3: tests pin the first level
         plan_collect(false);                                   // an earlier device-decided search nobody asked about
         HAC_TRY(ensure_half_image(st));
         HAC_TRY(ensure_row_image(st));
         HAC_TRY(upload_segs(st));
-        const u32 G = (u32)((ntotal + GROUP_ROWS - 1) / GROUP_ROWS);
-        const int64_t chunk = std::min<int64_t>(nq, SPLIT_CHUNK);
-        const int n_qtiles_max = (int)((chunk + SH_NQ - 1) / SH_NQ);
-        const size_t lds = terms == 3 ? ShCfg<3>::LDS : ShCfg<1>::LDS;
+        c.G = (u32)((ntotal + GROUP_ROWS - 1) / GROUP_ROWS);
+        c.chunk = std::min<int64_t>(nq, SPLIT_CHUNK);
+        const int n_qtiles_max = (int)((c.chunk + SH_NQ - 1) / SH_NQ);
+        c.lds = c.terms == 3 ? ShCfg<3>::LDS : ShCfg<1>::LDS;
         long Pmax = std::max<long>(1, n_cu);
-        HAC_TRY(ws_qsplit.reserve((size_t)n_qtiles_max * SH_NQ * d * 2 * (terms == 3 ? 2 : 1)));
+        HAC_TRY(ws_qsplit.reserve((size_t)n_qtiles_max * SH_NQ * d * 2 * (c.terms == 3 ? 2 : 1)));
         HAC_TRY(ws_delta.reserve((size_t)(nq + SH_NQ) * 4));
         HAC_TRY(ws_cand.reserve((size_t)Pmax * SH_NQ * C2 * 8));          // P * n_qtiles <= n_cu workgroups
         // (n queries of a chunk in ceil(n / SH_NQ) tiles with P <= n_cu / tiles row streams each: n * P <= SH_NQ * n_cu)
-        HAC_TRY(ws_partial.reserve((size_t)std::min<int64_t>(chunk, SH_NQ) * Pmax * K2 * 8 * MAX_PASSES));
-        HAC_TRY(ws_pcnt.reserve((size_t)chunk * 4));
+        HAC_TRY(ws_partial.reserve((size_t)std::min<int64_t>(c.chunk, SH_NQ) * Pmax * K2 * 8 * MAX_PASSES));
+        HAC_TRY(ws_pcnt.reserve((size_t)c.chunk * 4));
         HAC_TRY(ws_thrglob.reserve(((size_t)n_qtiles_max * SH_NQ + THR_CTL_WORDS) * 4));
         HAC_TRY(ws_akeys.reserve((size_t)nq * K2 * 8));
         HAC_TRY(ws_fail.reserve((size_t)nq * 4));
         HAC_TRY(ws_stat.reserve(16));
-        HAC_TRY(ws_thr.reserve((size_t)chunk * 4));
-        HAC_TRY(fb_reserve((size_t)nq + 8));
+        HAC_TRY(ws_thr.reserve((size_t)c.chunk * 4));
+        if (((size_t)nq + 8) * 4 > h_fb.cap) HAC_TRY(h_fb.reserve(((size_t)nq + 8) * 8));   // (twice the need)
         // (ws_stat: cleared by the first chunk's split_queries_kernel)
 
-        ScanArgs a{};
-        a.segs = d_segs;
-        a.nseg = nseg_live;
-        a.K4 = K4;
-        a.n_rows = (long)ntotal;
-        a.pos_base = pos_base;
-        a.k = K2;
-        a.g_first = 0;
-        a.g_step = 1;
-        a.thr_glob = thrglob();
-        a.partial = (u64 *)ws_partial.p;
-        a.partial_cnt = (u32 *)ws_pcnt.p;
-        SplitArgs sp{};
-        sp.qsplit = (const u32x4 *)ws_qsplit.p;
-        sp.cand = (u64 *)ws_cand.p;
-        sp.C2 = C2;
-        sp.K2 = K2;
-        sp.thr_is_approx = 1;
-        long P_last = 0;
-        int n_qtiles_last = 0, seeded = 0, n_chunks = 0, passes_last = 1;
-        int qt_act_last = 16;
-        for (int64_t off = 0; off < nq; off += chunk, ++n_chunks) {
-            const int64_t n = std::min<int64_t>(chunk, nq - off);
-            const float *qc = q_dev + (size_t)off * d;
-            const int n_qtiles = (int)((n + SH_NQ - 1) / SH_NQ);
-            const int64_t nq_pad = (int64_t)n_qtiles * SH_NQ;
-            long P = std::max<long>(1, n_cu / n_qtiles);
-            if (P >= 8) P = P / 8 * 8;  // same-row workgroups of different query tiles share an XCD (L2)
-            P = std::max<long>(1, std::min<long>(P, (G + SH_GPR - 1) / SH_GPR));
-            const long pstride = (long)P * K2 * MAX_PASSES;   // a workgroup flushes at most K2 survivors per query and pass
-            float *delta_c = (float *)ws_delta.p + off;
-            u64 *akeys_c = (u64 *)ws_akeys.p + (size_t)off * K2;
-            split_queries_kernel<<<dim3((unsigned)nq_pad), dim3(192), 0, st>>>(reinterpret_cast<const float4 *>(qc), (int)n, K4, terms,
-                                                                              (const u32 *)ws_norm.p, (h16 *)ws_qsplit.p, delta_c, (u32 *)ws_pcnt.p,
-                                                                              (u32 *)ws_thrglob.p, (u32)std::max(0, tune.debug_max_pass),
-                                                                              off == 0 ? (u32 *)ws_stat.p : nullptr);
+        c.a = scan_args(nullptr, 0);   // (q, nq: per chunk)
+        c.a.pos_base = c.pos_base;
+        c.a.k = K2;
+        c.a.g_step = 1;
+        c.a.thr_glob = thrglob();
+        c.a.partial = (u64 *)ws_partial.p;
+        c.a.partial_cnt = (u32 *)ws_pcnt.p;
+        c.sp.qsplit = (const u32x4 *)ws_qsplit.p;
+        c.sp.cand = (u64 *)ws_cand.p;
+        c.sp.C2 = C2;
+        c.sp.K2 = K2;
+        c.sp.thr_is_approx = 1;
+        return HAC_OK;
+    }
+
+    int launch_scanh(const SplitCtx &c, const ChunkGeom &g, bool seeding) {
+        void (*fn)(ScanArgs, SplitArgs) = nullptr;
+        for (const ScanhEntry &e : SCANH_TABLE)
+            if (e.terms == c.terms && e.seeding == seeding && e.qt_act == g.qt_act) fn = e.fn;
+        if (!fn) return fail(HAC_ERR_UNSUPPORTED, "internal: no scanh<%d,%d,%d>", c.terms, (int)seeding, g.qt_act);
+        fn<<<dim3((unsigned)g.P, (unsigned)g.n_qtiles), dim3(SH_W * 64), c.lds, c.st>>>(c.a, c.sp);
+        HAC_HIP(hipGetLastError());
+        return HAC_OK;
+    }
+
+    // the chunk's queries split, the seeding pass and its thresholds, the passes with a threshold refresh between them: all on st
+    int scan_chunk(SplitCtx &c, const ChunkGeom &g, int64_t off, int64_t n) {
+        const int K2 = SPLIT_K2;
+        hipStream_t st = c.st;
+        ScanArgs &a = c.a;
+        SplitArgs &sp = c.sp;
+        const float *qc = c.q_dev + (size_t)off * d;
+        split_queries_kernel<<<dim3((unsigned)((int64_t)g.n_qtiles * SH_NQ)), dim3(192), 0, st>>>(
+            reinterpret_cast<const float4 *>(qc), (int)n, K4, c.terms, (const u32 *)ws_norm.p, (h16 *)ws_qsplit.p, delta_of(off), (u32 *)ws_pcnt.p,
+            (u32 *)ws_thrglob.p, (u32)std::max(0, tune.debug_max_pass), off == 0 ? (u32 *)ws_stat.p : nullptr);
+        HAC_HIP(hipGetLastError());
+        a.q = reinterpret_cast<const float4 *>(qc);
+        a.nq = (int)n;
+        sp.delta = delta_of(off);
+        sp.pstride = g.pstride;
+        // (ws_pcnt, the thresholds and their control words: cleared by split_queries_kernel)
+        HAC_TRY(prof_begin(st));
+        // Seeding pass: the head of the corpus is scored once just for its per-quarter maxima; their K2-th largest
+        // opens the real pass over ALL rows with thresholds that only ~K2 * G / GA rows per query pass.  Without sharp
+        // opening thresholds list compactions (sorts) cost as much as half the MFMA work; the seeding pass itself (and
+        // the selection over its 4 GA maxima per query) costs in proportion to GA: a sixteenth of the corpus up to
+        // 1M rows, then ~14 sqrt(G) groups (measured optimum at 6.75M / 10M / 25M rows: 4.1k / 5.1k / 10k groups;
+        // a sixteenth of 25M rows cost 1.5 ms more per 1000-query search, 2k groups 11 ms more).
+        if (g.seeded) {
+            const u32 S = 4u * g.GA;
+            HAC_TRY(ws_seedkeys.reserve((size_t)c.chunk * S * 4));
+            a.n_items = g.GA;
+            a.thr_init = nullptr;
+            sp.maxima = (float *)ws_seedkeys.p;
+            HAC_TRY(launch_scanh(c, g, true));
+            kth_select_kernel<<<dim3((unsigned)n), dim3(256), 0, st>>>((const float *)ws_seedkeys.p, S, K2, (float *)ws_thr.p);
             HAC_HIP(hipGetLastError());
-            a.q = reinterpret_cast<const float4 *>(qc);
-            a.nq = (int)n;
-            sp.delta = delta_c;
-            sp.pstride = pstride;
-            // (ws_pcnt, the thresholds and their control words: cleared by split_queries_kernel)
-            if (profiling) {
-                if (ev_used == ev_pool.size()) {
-                    hipEvent_t a0, a1;
-                    HAC_HIP(hipEventCreate(&a0));
-                    HAC_HIP(hipEventCreate(&a1));
-                    ev_pool.emplace_back(a0, a1);
-                }
-                HAC_HIP(hipEventRecord(ev_pool[ev_used].first, st));
-            }
-            // Seeding pass: the head of the corpus is scored once just for its per-quarter maxima; their K2-th largest
-            // opens the real pass over ALL rows with thresholds that only ~K2 * G / GA rows per query pass.  Without sharp
-            // opening thresholds list compactions (sorts) cost as much as half the MFMA work; the seeding pass itself (and
-            // the selection over its 4 GA maxima per query) costs in proportion to GA: a sixteenth of the corpus up to
-            // 1M rows, then ~14 sqrt(G) groups (measured optimum at 6.75M / 10M / 25M rows: 4.1k / 5.1k / 10k groups;
-            // a sixteenth of 25M rows cost 1.5 ms more per 1000-query search, 2k groups 11 ms more).
-            const dim3 grid((unsigned)P, (unsigned)n_qtiles), blk(SH_W * 64);
-            // one tile of at most 128 / 64 real queries: the instantiations without the empty 16-query tiles' matrix work (scanh_kernel, QT_ACT)
-            const bool few = terms == 1 && n_qtiles == 1 && !tune.no_halfq;
-            const int qt_act = few && n <= SH_NQ / 4 ? 4 : few && n <= SH_NQ / 2 ? 8 : 16;
-            const u32 round_groups = (u32)P * SH_GPR;
-            // (a scan that will be cut into passes refreshes its thresholds after ~6k groups anyway: 1024 groups of seeding do)
-            u32 probe_bounds[MAX_PASSES + 1];
-            const bool multipass = scan_passes(G, round_groups, true, probe_bounds) > 1;
-            const u32 seed_cap = tune.seed_groups_max > 0 ? (u32)tune.seed_groups_max : multipass ? 1024u : (u32)(14.0 * std::sqrt((double)G));
-            u32 GA = std::min<u32>(G, (std::max<u32>(std::min<u32>(G / 16u, seed_cap), 768u) + round_groups - 1u) / round_groups * round_groups);
-            const float *thr_init = nullptr;
-            if ((size_t)4 * GA >= (size_t)K2) {
-                const u32 S = 4u * GA;
-                HAC_TRY(ws_seedkeys.reserve((size_t)chunk * S * 4));
-                a.n_items = GA;
-                a.thr_init = nullptr;
-                sp.maxima = (float *)ws_seedkeys.p;
-                if (terms == 3) scanh_kernel<3, true><<<grid, blk, lds, st>>>(a, sp);
-                else if (qt_act == 4) scanh_kernel<1, true, 4><<<grid, blk, lds, st>>>(a, sp);
-                else if (qt_act == 8) scanh_kernel<1, true, 8><<<grid, blk, lds, st>>>(a, sp);
-                else scanh_kernel<1, true><<<grid, blk, lds, st>>>(a, sp);
-                HAC_HIP(hipGetLastError());
-                kth_select_kernel<<<dim3((unsigned)n), dim3(256), 0, st>>>((const float *)ws_seedkeys.p, S, K2, (float *)ws_thr.p);
-                HAC_HIP(hipGetLastError());
-                thr_init = (const float *)ws_thr.p;
-            }
-            // The scan itself, in up to three passes over consecutive row ranges (big corpora, seeded thresholds).  A workgroup's own
-            // lists never reach their compaction mark (~100 candidates per query and row stream over a whole 25M-row scan), so
-            // within one launch the seeded threshold is all a query ever has: 0.07 % of the pairs pass it where K2 / rows would
-            // do, and parking + appending those candidates is ~12 % of the kernel.  Between passes the K2-th best s~ of everything
-            // found SO FAR (all row streams together: select_keys_kernel over the survivors flushed by the passes before) is a
-            // valid, much sharper bound: after 8 % of the rows ~3x fewer pairs pass, after 30 % ~8x fewer.
-            u32 bounds[MAX_PASSES + 1];
-            const int n_pass = scan_passes(G, round_groups, thr_init != nullptr, bounds);
-            a.thr_init = thr_init;
-            for (int ps = 0; ps < n_pass; ++ps) {
-                a.g_first = bounds[ps];
-                a.n_items = bounds[ps + 1] - bounds[ps];
-                if (terms == 3) scanh_kernel<3, false><<<grid, blk, lds, st>>>(a, sp);
-                else if (qt_act == 4) scanh_kernel<1, false, 4><<<grid, blk, lds, st>>>(a, sp);
-                else if (qt_act == 8) scanh_kernel<1, false, 8><<<grid, blk, lds, st>>>(a, sp);
-                else scanh_kernel<1, false><<<grid, blk, lds, st>>>(a, sp);
-                HAC_HIP(hipGetLastError());
-                if (ps + 1 < n_pass) {   // refresh: ws_thr[q] = max(ws_thr[q], K2-th best s~ so far)
-                    select_keys_kernel<<<dim3((unsigned)n), dim3(256), (size_t)K2 * 8, st>>>((const u64 *)ws_partial.p, (size_t)pstride,
-                                                                                             (const u32 *)ws_pcnt.p, (u32)pstride, K2, K2, nullptr, (float *)ws_thr.p,
-                                                                                             nullptr, 0, 0, 1, nullptr, nullptr, true);
-                    HAC_HIP(hipGetLastError());
-                }
-            }
-            a.g_first = 0;
-            passes_last = n_pass;
-            qt_act_last = qt_act;
-            if (profiling) {
-                HAC_HIP(hipEventRecord(ev_pool[ev_used].second, st));
-                ++ev_used;
-            }
-            // exact top-K2 by approximate score over all workgroups' survivors
-            select_keys_kernel<<<dim3((unsigned)n), dim3(256), (size_t)K2 * 8, st>>>((const u64 *)ws_partial.p, (size_t)pstride,
-                                                                                     (const u32 *)ws_pcnt.p, (u32)pstride, K2, K2, akeys_c, nullptr,
-                                                                                     nullptr, 0, 0, 1, thrglob(), (u32 *)ws_err.p);
-            HAC_HIP(hipGetLastError());
-            // rescoring + certificate of this chunk on the second stream (reads only akeys, delta, the queries and
-            // the corpus; everything the next chunk's scan reuses is already consumed)
-            HAC_HIP(hipEventRecord(ev_chunk[n_chunks & 1], st));
-            HAC_HIP(hipStreamWaitEvent(stream2, ev_chunk[n_chunks & 1], 0));
-            rescore_kernel<<<dim3((unsigned)n), dim3(256), 0, stream2>>>(a, d_rimg, akeys_c, delta_c, K2, k, keys_out + (size_t)off * k,
-                                                                        (u32 *)ws_fail.p + off, (u32 *)ws_stat.p);
-            HAC_HIP(hipGetLastError());
-            P_last = P;
-            n_qtiles_last = n_qtiles;
-            seeded = thr_init ? 1 : 0;
         }
-        HAC_HIP(hipEventRecord(ev_tail, stream2));
-        HAC_HIP(hipStreamWaitEvent(st, ev_tail, 0));
-        if (device_decides) {
-            // No read-back: the failed queries (none, in the common case) are compacted into a list, searched again by the
-            // exact fp32 kernels and scattered back into place, every launch sized for all nq and cut down on the device by
-            // the count the certificates left in ws_stat[0].  The stream is never synchronized; the plan text (fallback
-            // count, err / bound) is completed when hac_index_last_plan asks for it.
-            GrowBuf &fbidx = ws_fbidx[0], &fbq = ws_fbq[0], &fbkeys = ws_fbkeys[0];
-            const int n_fchunks = (int)((nq + QUERY_CHUNK - 1) / QUERY_CHUNK);
-            HAC_TRY(fbidx.reserve(((size_t)nq + n_fchunks) * 4));
-            HAC_TRY(fbq.reserve((size_t)nq * d * 4));
-            HAC_TRY(fbkeys.reserve((size_t)nq * k * 8));
-            int *chunk_cnt = (int *)fbidx.p + nq;
-            compact_failed_kernel<<<dim3(1), dim3(256), 0, st>>>((const u32 *)ws_fail.p, (int)nq, (int *)fbidx.p, chunk_cnt, n_fchunks, (int)QUERY_CHUNK);
-            HAC_HIP(hipGetLastError());
-            const int *nf_dev = (const int *)ws_stat.p;
-            // (the first fallback chunk's survivor counts and thresholds are cleared by gather_rows_kernel: sized from that chunk's plan)
-            Plan pl0;
-            const int64_t n0 = std::min<int64_t>(QUERY_CHUNK, nq);
-            HAC_TRY(make_plan(n0, k, G, pl0));
-            const int n_thr0 = pl0.n_qtiles * pl0.QT + THR_CTL_WORDS;
-            HAC_TRY(ws_pcnt.reserve((size_t)n0 * 4));
-            HAC_TRY(ws_thrglob.reserve((size_t)n_thr0 * 4));
-            gather_rows_kernel<<<dim3((unsigned)((std::max<long>((long)nq * K4, n_thr0) + 255) / 256)), dim3(256), 0, st>>>(
-                reinterpret_cast<const float4 *>(q_dev), (const int *)fbidx.p, (int)nq, K4, (float4 *)fbq.p, nf_dev, (u32 *)ws_pcnt.p, (int)n0,
-                (u32 *)ws_thrglob.p, n_thr0, (u32)std::max(0, tune.debug_max_pass));
-            HAC_HIP(hipGetLastError());
-            const bool prof = profiling;
-            profiling = false;   // timed kernels of a search: the prefilter's scans
-            int rc = HAC_OK;
-            for (int c = 0; c < n_fchunks && rc == HAC_OK; ++c) {
-                const int64_t off = (int64_t)c * QUERY_CHUNK, n = std::min<int64_t>(QUERY_CHUNK, nq - off);
-                rc = search_keys_exact((const float *)fbq.p + (size_t)off * d, n, k, (u64 *)fbkeys.p + (size_t)off * k, pos_base, st, chunk_cnt + c, c == 0);
+        // The scan itself, in up to three passes over consecutive row ranges (big corpora, seeded thresholds).  A workgroup's own
+        // lists never reach their compaction mark (~100 candidates per query and row stream over a whole 25M-row scan), so
+        // within one launch the seeded threshold is all a query ever has: 0.07 % of the pairs pass it where K2 / rows would
+        // do, and parking + appending those candidates is ~12 % of the kernel.  Between passes the K2-th best s~ of everything
+        // found SO FAR (all row streams together: select_keys_kernel over the survivors flushed by the passes before) is a
+        // valid, much sharper bound: after 8 % of the rows ~3x fewer pairs pass, after 30 % ~8x fewer.
+        a.thr_init = g.seeded ? (const float *)ws_thr.p : nullptr;
+        for (int ps = 0; ps < g.n_pass; ++ps) {
+            a.g_first = g.bounds[ps];
+            a.n_items = g.bounds[ps + 1] - g.bounds[ps];
+            HAC_TRY(launch_scanh(c, g, false));
+            if (ps + 1 < g.n_pass) {   // refresh: ws_thr[q] = max(ws_thr[q], K2-th best s~ so far)
+                select_keys_kernel<<<dim3((unsigned)n), dim3(256), (size_t)K2 * 8, st>>>(
+                    (const u64 *)ws_partial.p, (size_t)g.pstride, (const u32 *)ws_pcnt.p, (u32)g.pstride, K2, K2, nullptr, (float *)ws_thr.p, nullptr, 0, 0, 1, nullptr, nullptr, true);
+                HAC_HIP(hipGetLastError());
             }
-            profiling = prof;
-            HAC_TRY(rc);
-            scatter_keys_kernel<<<dim3((unsigned)(((long)nq * k + 255) / 256)), dim3(256), 0, st>>>((const u64 *)fbkeys.p, (const int *)fbidx.p,
-                                                                                                  (int)nq, k, keys_out, nf_dev);
-            HAC_HIP(hipGetLastError());
-            ++split_searches;
-            snprintf(plan_head, sizeof plan_head, "split: scanh_kernel<%d> grid=(%ld,%d) NQ=%d K2=%d chunks=%d lds=%zu seed=%d passes=%d rescore=%s%s", terms, P_last,
-                     n_qtiles_last, SH_NQ, K2, n_chunks, lds, seeded, passes_last, rescore_from(), qt_act_last == 8 ? " tiles=half" : qt_act_last == 4 ? " tiles=quarter" : "");
-            snprintf(last_plan, sizeof last_plan, "%s fallback=device-side/%lld", plan_head, (long long)nq);
-            // (a search that is being captured takes no slot: every replay would write the slot's pinned words again, under whichever
-            // live search owns the slot by then)
-            const int slot = stream_is_capturing(st) ? -1 : plan_slot();
-            if (slot < 0) {
-                snprintf(last_plan, sizeof last_plan, "%s fallback=device-side/%lld (status not collected)", plan_head, (long long)nq);
-                plan_text_slot = -1;
-                return HAC_OK;
+        }
+        a.g_first = 0;
+        return prof_end(st);
+    }
+
+    // the chunk's K2 candidates per query selected on st, handed over to stream2, rescored and certified there
+    int select_and_rescore(SplitCtx &c, const ChunkGeom &g, int64_t off, int64_t n) {
+        const int K2 = SPLIT_K2;
+        // exact top-K2 by approximate score over all workgroups' survivors
+        select_keys_kernel<<<dim3((unsigned)n), dim3(256), (size_t)K2 * 8, c.st>>>(
+            (const u64 *)ws_partial.p, (size_t)g.pstride, (const u32 *)ws_pcnt.p, (u32)g.pstride, K2, K2, akeys_of(off), nullptr, nullptr, 0, 0, 1, thrglob(), (u32 *)ws_err.p);
+        HAC_HIP(hipGetLastError());
+        // rescoring + certificate of this chunk on the second stream (reads only akeys, delta, the queries and
+        // the corpus; everything the next chunk's scan reuses is already consumed)
+        HAC_HIP(hipEventRecord(ev_chunk[c.n_chunks & 1], c.st));
+        HAC_HIP(hipStreamWaitEvent(stream2, ev_chunk[c.n_chunks & 1], 0));
+        rescore_kernel<<<dim3((unsigned)n), dim3(256), 0, stream2>>>(c.a, d_rimg, akeys_of(off), delta_of(off), K2, c.k, c.keys_out + (size_t)off * c.k,
+                                                                    (u32 *)ws_fail.p + off, (u32 *)ws_stat.p);
+        HAC_HIP(hipGetLastError());
+        c.last = g;
+        return HAC_OK;
+    }
+
+    // the part of the plan text that every form of a prefilter search starts with
+    void split_plan_head(char *out, size_t size, const SplitCtx &c) const {
+        snprintf(out, size, "split: scanh_kernel<%d> grid=(%ld,%d) NQ=%d K2=%d chunks=%d lds=%zu seed=%d passes=%d rescore=%s%s", c.terms, c.last.P,
+                 c.last.n_qtiles, SH_NQ, SPLIT_K2, c.n_chunks, c.lds, c.last.seeded ? 1 : 0, c.last.n_pass, rescore_from(),
+                 c.last.qt_act == 8 ? " tiles=half" : c.last.qt_act == 4 ? " tiles=quarter" : "");
+    }
+
+    // No read-back: the failed queries (none, in the common case) are compacted into a list, searched again by the
+    // exact fp32 kernels and scattered back into place, every launch sized for all nq and cut down on the device by
+    // the count the certificates left in ws_stat[0].  The stream is never synchronized; the plan text (fallback
+    // count, err / bound) is completed when hac_index_last_plan asks for it.
+    int fallback_device(const SplitCtx &c) {
+        const int64_t nq = c.nq;
+        const int k = c.k;
+        hipStream_t st = c.st;
+        GrowBuf &fbidx = ws_fbidx[0], &fbq = ws_fbq[0], &fbkeys = ws_fbkeys[0];
+        const int n_fchunks = (int)((nq + QUERY_CHUNK - 1) / QUERY_CHUNK);
+        HAC_TRY(fbidx.reserve(((size_t)nq + n_fchunks) * 4));
+        HAC_TRY(fbq.reserve((size_t)nq * d * 4));
+        HAC_TRY(fbkeys.reserve((size_t)nq * k * 8));
+        int *chunk_cnt = (int *)fbidx.p + nq;
+        compact_failed_kernel<<<dim3(1), dim3(256), 0, st>>>((const u32 *)ws_fail.p, (int)nq, (int *)fbidx.p, chunk_cnt, n_fchunks, (int)QUERY_CHUNK);
+        HAC_HIP(hipGetLastError());
+        const int *nf_dev = (const int *)ws_stat.p;
+        // (the first fallback chunk's survivor counts and thresholds are cleared by gather_rows_kernel: sized from that chunk's plan)
+        Plan pl0;
+        const int64_t n0 = std::min<int64_t>(QUERY_CHUNK, nq);
+        HAC_TRY(make_plan(n0, k, c.G, pl0));
+        const int n_thr0 = pl0.n_qtiles * pl0.QT + THR_CTL_WORDS;
+        HAC_TRY(ws_pcnt.reserve((size_t)n0 * 4));
+        HAC_TRY(ws_thrglob.reserve((size_t)n_thr0 * 4));
+        gather_rows_kernel<<<dim3((unsigned)((std::max<long>((long)nq * K4, n_thr0) + 255) / 256)), dim3(256), 0, st>>>(
+            reinterpret_cast<const float4 *>(c.q_dev), (const int *)fbidx.p, (int)nq, K4, (float4 *)fbq.p, nf_dev, (u32 *)ws_pcnt.p, (int)n0,
+            (u32 *)ws_thrglob.p, n_thr0, (u32)std::max(0, tune.debug_max_pass));
+        HAC_HIP(hipGetLastError());
+        {
+            Untimed untimed(profiling);   // timed kernels of a search: the prefilter's scans
+            for (int fc = 0; fc < n_fchunks; ++fc) {
+                const int64_t off = (int64_t)fc * QUERY_CHUNK, n = std::min<int64_t>(QUERY_CHUNK, nq - off);
+                HAC_TRY(search_keys_exact((const float *)fbq.p + (size_t)off * d, n, k, (u64 *)fbkeys.p + (size_t)off * k, c.pos_base, st, chunk_cnt + fc, fc == 0));
             }
-            HAC_HIP(hipMemcpyAsync(h_plan + 2 * slot, ws_stat.p, 8, hipMemcpyDeviceToHost, st));
-            HAC_HIP(hipEventRecord(ev_plan[slot], st));
-            slot_pending[slot] = true;
-            slot_nq[slot] = nq;
-            plan_text_slot = slot;
+        }
+        scatter_keys_kernel<<<dim3((unsigned)(((long)nq * k + 255) / 256)), dim3(256), 0, st>>>((const u64 *)fbkeys.p, (const int *)fbidx.p, (int)nq, k, c.keys_out, nf_dev);
+        HAC_HIP(hipGetLastError());
+        ++split_searches;
+        split_plan_head(plan_head, sizeof plan_head, c);
+        snprintf(last_plan, sizeof last_plan, "%s fallback=device-side/%lld", plan_head, (long long)nq);
+        // (a search that is being captured takes no slot: every replay would write the slot's pinned words again, under whichever
+        // live search owns the slot by then)
+        const int slot = stream_is_capturing(st) ? -1 : plan_slot();
+        if (slot < 0) {
+            snprintf(last_plan, sizeof last_plan, "%s fallback=device-side/%lld (status not collected)", plan_head, (long long)nq);
+            plan_text_slot = -1;
             return HAC_OK;
         }
-        HAC_HIP(hipMemcpyAsync(h_fb, ws_stat.p, 8, hipMemcpyDeviceToHost, st));
+        HAC_HIP(hipMemcpyAsync(h_plan + 2 * slot, ws_stat.p, 8, hipMemcpyDeviceToHost, st));
+        HAC_HIP(hipEventRecord(ev_plan[slot], st));
+        slot_pending[slot] = true;
+        slot_nq[slot] = nq;
+        plan_text_slot = slot;
+        return HAC_OK;
+    }
+
+    // the status read back; the queries that failed gathered, decided by the next level and scattered back into place
+    int fallback_host(const SplitCtx &c) {
+        const int64_t nq = c.nq;
+        const int k = c.k;
+        hipStream_t st = c.st;
+        u32 *fb = (u32 *)h_fb.p;
+        HAC_HIP(hipMemcpyAsync(fb, ws_stat.p, 8, hipMemcpyDeviceToHost, st));
         HAC_HIP(hipStreamSynchronize(st));
-        const u32 nfail = h_fb[0];
+        const u32 nfail = fb[0];
         float maxratio;
-        std::memcpy(&maxratio, &h_fb[1], 4);
-        if (level == 0) ++split_searches;
-        char plan_here[sizeof last_plan];
-        snprintf(plan_here, sizeof plan_here, "split: scanh_kernel<%d> grid=(%ld,%d) NQ=%d K2=%d chunks=%d lds=%zu seed=%d passes=%d rescore=%s%s fallback=%u/%lld err/bound=%.3g",
-                 terms, P_last, n_qtiles_last, SH_NQ, K2, n_chunks, lds, seeded, passes_last, rescore_from(), qt_act_last == 8 ? " tiles=half" : qt_act_last == 4 ? " tiles=quarter" : "", nfail, (long long)nq, (double)maxratio);
+        std::memcpy(&maxratio, &fb[1], 4);
+        if (c.level == 0) ++split_searches;
+        char head[sizeof last_plan], plan_here[sizeof last_plan];
+        split_plan_head(head, sizeof head, c);
+        snprintf(plan_here, sizeof plan_here, "%s fallback=%u/%lld err/bound=%.3g", head, nfail, (long long)nq, (double)maxratio);
         std::memcpy(last_plan, plan_here, sizeof last_plan);
         plan_text_slot = -1;
         if (nfail == 0) return HAC_OK;
 
         // certificate failed for some queries: the next level decides those
-        HAC_HIP(hipMemcpyAsync(h_fb + 8, ws_fail.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+        HAC_HIP(hipMemcpyAsync(fb + 8, ws_fail.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
         HAC_HIP(hipStreamSynchronize(st));
         std::vector<int> idx;
         idx.reserve(nfail);
         for (int64_t i = 0; i < nq; ++i)
-            if (h_fb[8 + i]) idx.push_back((int)i);
+            if (fb[8 + i]) idx.push_back((int)i);
         const int nf = (int)idx.size();
-        std::memcpy(h_fb + 8, idx.data(), (size_t)nf * 4);
-        GrowBuf &fbidx = ws_fbidx[level & 1], &fbq = ws_fbq[level & 1], &fbkeys = ws_fbkeys[level & 1];
+        std::memcpy(fb + 8, idx.data(), (size_t)nf * 4);
+        GrowBuf &fbidx = ws_fbidx[c.level & 1], &fbq = ws_fbq[c.level & 1], &fbkeys = ws_fbkeys[c.level & 1];
         HAC_TRY(fbidx.reserve((size_t)nf * 4));
         HAC_TRY(fbq.reserve((size_t)nf * d * 4));
         HAC_TRY(fbkeys.reserve((size_t)nf * k * 8));
-        HAC_HIP(hipMemcpyAsync(fbidx.p, h_fb + 8, (size_t)nf * 4, hipMemcpyHostToDevice, st));
+        HAC_HIP(hipMemcpyAsync(fbidx.p, fb + 8, (size_t)nf * 4, hipMemcpyHostToDevice, st));
         gather_rows_kernel<<<dim3((unsigned)(((long)nf * K4 + 255) / 256)), dim3(256), 0, st>>>(
-            reinterpret_cast<const float4 *>(q_dev), (const int *)fbidx.p, nf, K4, (float4 *)fbq.p);
+            reinterpret_cast<const float4 *>(c.q_dev), (const int *)fbidx.p, nf, K4, (float4 *)fbq.p);
         HAC_HIP(hipGetLastError());
         HAC_HIP(hipStreamSynchronize(st));   // h_fb is reused by the next level
-        const bool prof = profiling;
-        profiling = false;   // timed kernels of a search: the first level's scans
         int rc;
-        if (terms == 1 && nf >= 64) {
-            rc = search_keys_split((const float *)fbq.p, nf, k, (u64 *)fbkeys.p, pos_base, st, 1);
-            char both[sizeof last_plan];
-            snprintf(both, sizeof both, "%.160s ; then %.130s", plan_here, last_plan + 7);
-            std::memcpy(plan_here, both, sizeof plan_here);
-        } else {
-            split_fallback_queries += nf;
-            rc = search_keys_exact((const float *)fbq.p, nf, k, (u64 *)fbkeys.p, pos_base, st);
+        {
+            Untimed untimed(profiling);   // timed kernels of a search: the first level's scans
+            if (c.terms == 1 && nf >= 64) {
+                rc = search_keys_split((const float *)fbq.p, nf, k, (u64 *)fbkeys.p, c.pos_base, st, 1);
+                char both[sizeof last_plan];
+                snprintf(both, sizeof both, "%.160s ; then %.130s", plan_here, last_plan + 7);
+                std::memcpy(plan_here, both, sizeof plan_here);
+            } else {
+                split_fallback_queries += nf;
+                rc = search_keys_exact((const float *)fbq.p, nf, k, (u64 *)fbkeys.p, c.pos_base, st);
+            }
         }
-        profiling = prof;
         std::memcpy(last_plan, plan_here, sizeof last_plan);
         HAC_TRY(rc);
-        scatter_keys_kernel<<<dim3((unsigned)(((long)nf * k + 255) / 256)), dim3(256), 0, st>>>((const u64 *)fbkeys.p,
-                                                                                              (const int *)fbidx.p, nf, k, keys_out);
+        scatter_keys_kernel<<<dim3((unsigned)(((long)nf * k + 255) / 256)), dim3(256), 0, st>>>((const u64 *)fbkeys.p, (const int *)fbidx.p, nf, k, c.keys_out);
         HAC_HIP(hipGetLastError());
         HAC_HIP(hipStreamSynchronize(st));
         return HAC_OK;
     }
 
+    int search_keys_split(const float *q_dev, int64_t nq, int k, u64 *keys_out, u32 pos_base, hipStream_t st, int level = 0, bool device_decides = false) {
+        SplitCtx c{q_dev, nq, k, keys_out, pos_base, st, level};
+        HAC_TRY(split_begin(c));
+        for (int64_t off = 0; off < nq; off += c.chunk, ++c.n_chunks) {
+            const int64_t n = std::min<int64_t>(c.chunk, nq - off);
+            const ChunkGeom g = chunk_geometry(n, c.G, c.terms);
+            HAC_TRY(scan_chunk(c, g, off, n));
+            HAC_TRY(select_and_rescore(c, g, off, n));
+        }
+        HAC_HIP(hipEventRecord(ev_tail, stream2));
+        HAC_HIP(hipStreamWaitEvent(st, ev_tail, 0));
+        return device_decides ? fallback_device(c) : fallback_host(c);
+    }
+
+    int check_search_args(const float *q_dev, u32 pos_base) const {
+        if (((uintptr_t)q_dev & 15) != 0) return fail(HAC_ERR_INVALID, "search: query pointer must be 16-byte aligned");
+        if ((uint64_t)pos_base + (uint64_t)ntotal > 0xFFFFFFFFull) return fail(HAC_ERR_UNSUPPORTED, "row positions exceed 32 bits");
+        return HAC_OK;
+    }
     // keys_out: device u64 [nq][k], canonical (score desc, row asc) keys of the k best rows per query.
     // Large query sets (the reference searches a whole test set per block: 2.5k - 16k queries) go through
     // in chunks: 512 inside the prefilter (search_keys_split), 1024 for the exact kernels (16 query tiles x 16
@@ -2484,10 +2502,7 @@ struct DeviceIndex {
     // device_entry: the call came through a *_device entry point, which must not synchronize the caller's stream: the
     // prefilter's certificates are then read by the device (option split_decide pins either way for tests)
     int search_keys(const float *q_dev, int64_t nq, int k, u64 *keys_out, u32 pos_base, hipStream_t st, bool device_entry = false) {
-        if (nq > 0 && ntotal > 0) {
-            if (((uintptr_t)q_dev & 15) != 0) return fail(HAC_ERR_INVALID, "search: query pointer must be 16-byte aligned");
-            if ((uint64_t)pos_base + (uint64_t)ntotal > 0xFFFFFFFFull) return fail(HAC_ERR_UNSUPPORTED, "row positions exceed 32 bits");
-        }
+        if (nq > 0) HAC_TRY(check_search_args(q_dev, pos_base));
         if (nq > 0 && ntotal > 0 && decide_prefilter(nq, k, stream_is_capturing(st)) && !(tune.split < 0 && half_image_unavailable)) {
             const int rc_img = ensure_half_image(st);
             if (rc_img == HAC_OK) return search_keys_split(q_dev, nq, k, keys_out, pos_base, st, 0, tune.split_decide < 0 ? device_entry : tune.split_decide == 1);
@@ -2497,10 +2512,9 @@ struct DeviceIndex {
             drop_half_images();
             half_image_unavailable = true;
         }
-        for (int64_t off = 0; off < nq || off == 0; off += QUERY_CHUNK) {
+        for (int64_t off = 0; off < nq; off += QUERY_CHUNK) {
             const int64_t n = std::min<int64_t>(QUERY_CHUNK, nq - off);
             HAC_TRY(search_keys_exact(q_dev + (size_t)off * d, n, k, keys_out + (size_t)off * k, pos_base, st));
-            if (nq == 0) break;
         }
         return HAC_OK;
     }
@@ -2536,6 +2550,55 @@ struct hac_index {
     std::vector<GrowBuf> ws_spans;
     std::vector<char> spans_dirty;
 };
+
+namespace {
+// the one shard of a single-device index, for the entry points that have no multi-device form (what: theirs, for the message)
+int single_shard(hac_index *idx, const char *what, DeviceIndex *&s) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    if (idx->shards.size() != 1) return fail(HAC_ERR_UNSUPPORTED, "%s needs a single-device index", what);
+    s = idx->shards[0];
+    return HAC_OK;
+}
+
+// fn(shard) on every shard; with several devices one host thread per shard drives its device (a prefilter search reads a status word back:
+// in sequence the devices would take turns).  The first failure is reported, its message carried back to the caller's error slot.
+template <class F>
+int for_each_shard(hac_index *idx, F fn) {
+    const int S = (int)idx->shards.size();
+    if (S == 1) return fn(0);
+    std::vector<int> rcs(S, HAC_OK);
+    std::vector<std::string> msgs(S);
+    std::vector<std::thread> pool;
+    for (int si = 1; si < S; ++si)
+        pool.emplace_back([&, si] {
+            rcs[si] = fn(si);
+            if (rcs[si] != HAC_OK) msgs[si] = last_error_slot();
+        });
+    rcs[0] = fn(0);
+    if (rcs[0] != HAC_OK) msgs[0] = last_error_slot();
+    for (auto &t : pool) t.join();
+    for (int si = 0; si < S; ++si)
+        if (rcs[si] != HAC_OK) return fail(rcs[si], "shard %d (device %d): %s", si, idx->shards[si]->device, msgs[si].c_str());
+    return HAC_OK;
+}
+
+// fn(shard) on every shard in turn, each on its device: every shard's error word is read and cleared, the first failure is the one reported
+template <class F>
+int first_shard_error(hac_index *idx, F fn) {
+    int rc_all = HAC_OK;
+    std::string msg_all;
+    for (auto *s : idx->shards) {
+        DeviceGuard g(s->device);
+        const int rc = fn(s);
+        if (rc != HAC_OK && rc_all == HAC_OK) {
+            rc_all = rc;
+            msg_all = last_error_slot();
+        }
+    }
+    if (rc_all != HAC_OK) return fail(rc_all, "%s", msg_all.c_str());
+    return HAC_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -2616,11 +2679,10 @@ int hac_index_add(hac_index *idx, const float *x, int64_t n) {
 }
 
 int hac_index_add_device(hac_index *idx, const float *x_dev, int64_t n, void *hip_stream) {
-    if (!idx) return fail(HAC_ERR_INVALID, "null index");
-    if (idx->shards.size() != 1) return fail(HAC_ERR_UNSUPPORTED, "add_device needs a single-device index");
+    DeviceIndex *s = nullptr;
+    HAC_TRY(single_shard(idx, "add_device", s));
     if (n < 0 || (n > 0 && !x_dev)) return fail(HAC_ERR_INVALID, "add_device: bad arguments");
     if (n == 0) return HAC_OK;
-    DeviceIndex *s = idx->shards[0];
     DeviceGuard g(s->device);
     HAC_TRY(s->add_device_rows(x_dev, n, (hipStream_t)hip_stream));
     idx->ntotal += n;
@@ -2642,11 +2704,10 @@ int64_t hac_index_ntotal(const hac_index *idx) { return idx ? idx->ntotal : -1; 
 
 int hac_index_search_keys_device(hac_index *idx, const float *q_dev, int64_t nq, int k, uint64_t *keys_dev,
                                  uint32_t pos_base, void *hip_stream) {
-    if (!idx) return fail(HAC_ERR_INVALID, "null index");
-    if (idx->shards.size() != 1) return fail(HAC_ERR_UNSUPPORTED, "search_keys_device needs a single-device index");
+    DeviceIndex *s = nullptr;
+    HAC_TRY(single_shard(idx, "search_keys_device", s));
     HAC_TRY(check_k(k));
     if (nq < 0 || (nq > 0 && (!q_dev || !keys_dev))) return fail(HAC_ERR_INVALID, "search: bad arguments");
-    DeviceIndex *s = idx->shards[0];
     DeviceGuard g(s->device);
     return s->search_keys(q_dev, nq, k, (u64 *)keys_dev, pos_base, (hipStream_t)hip_stream, true);
 }
@@ -2686,12 +2747,11 @@ int hac_merge_keys_device(int device, const uint64_t *lists_dev, int n_lists, in
 
 int hac_index_search_device(hac_index *idx, const float *q_dev, int64_t nq, int k, float *D_dev, int64_t *I_dev,
                             const int64_t *id_map_dev, void *hip_stream) {
-    if (!idx) return fail(HAC_ERR_INVALID, "null index");
-    if (idx->shards.size() != 1) return fail(HAC_ERR_UNSUPPORTED, "search_device needs a single-device index");
+    DeviceIndex *s = nullptr;
+    HAC_TRY(single_shard(idx, "search_device", s));
     HAC_TRY(check_k(k));
     if (nq < 0 || (nq > 0 && (!q_dev || !D_dev || !I_dev))) return fail(HAC_ERR_INVALID, "search: bad arguments");
     if (nq == 0) return HAC_OK;
-    DeviceIndex *s = idx->shards[0];
     DeviceGuard g(s->device);
     HAC_TRY(s->ws_keys.reserve((size_t)nq * k * 8));
     HAC_TRY(s->search_keys(q_dev, nq, k, (u64 *)s->ws_keys.p, 0u, (hipStream_t)hip_stream, true));
@@ -2712,9 +2772,7 @@ int hac_index_search(hac_index *idx, const float *q, int64_t nq, int k, float *D
         HAC_TRY(idx->ws_lists.reserve((size_t)S * nq * k * 8));
         HAC_TRY(idx->ws_out.reserve((size_t)nq * k * 8));
     }
-    // Every shard searches its own rows on its own stream.  With several devices one host thread per shard drives
-    // its device (the prefilter path reads a status word back per search: in sequence the devices would take turns);
-    // a thread's failure message is carried back to the caller's error slot.
+    // every shard searches its own rows on its own stream (for_each_shard)
     auto search_shard = [&](int si) -> int {
         DeviceIndex *s = idx->shards[si];
         DeviceGuard g(s->device);
@@ -2723,8 +2781,8 @@ int hac_index_search(hac_index *idx, const float *q, int64_t nq, int k, float *D
         HAC_TRY(s->ws_keys.reserve((size_t)nq * k * 8));
         HAC_TRY(s->pin_reserve(std::max(qbytes, (size_t)nq * k * 12)));
         HAC_HIP(hipStreamSynchronize(s->stream));
-        std::memcpy(s->h_pin, q, qbytes);
-        HAC_HIP(hipMemcpyAsync(s->ws_q.p, s->h_pin, qbytes, hipMemcpyHostToDevice, s->stream));
+        std::memcpy(s->h_pin.p, q, qbytes);
+        HAC_HIP(hipMemcpyAsync(s->ws_q.p, s->h_pin.p, qbytes, hipMemcpyHostToDevice, s->stream));
         HAC_TRY(s->search_keys((const float *)s->ws_q.p, nq, k, (u64 *)s->ws_keys.p, 0u, s->stream));
         HAC_HIP(hipMemcpyAsync(s->h_err, s->ws_err.p, 8, hipMemcpyDeviceToHost, s->stream));   // checked after the final wait
         if (S > 1) {   // shard-local rows -> insertion-order positions of the whole index
@@ -2745,23 +2803,7 @@ int hac_index_search(hac_index *idx, const float *q, int64_t nq, int k, float *D
         }
         return HAC_OK;
     };
-    if (S == 1) {
-        HAC_TRY(search_shard(0));
-    } else {
-        std::vector<int> rcs(S, HAC_OK);
-        std::vector<std::string> msgs(S);
-        std::vector<std::thread> pool;
-        for (int si = 1; si < S; ++si)
-            pool.emplace_back([&, si] {
-                rcs[si] = search_shard(si);
-                if (rcs[si] != HAC_OK) msgs[si] = last_error_slot();
-            });
-        rcs[0] = search_shard(0);
-        if (rcs[0] != HAC_OK) msgs[0] = last_error_slot();
-        for (auto &t : pool) t.join();
-        for (int si = 0; si < S; ++si)
-            if (rcs[si] != HAC_OK) return fail(rcs[si], "shard %d (device %d): %s", si, idx->shards[si]->device, msgs[si].c_str());
-    }
+    HAC_TRY(for_each_shard(idx, search_shard));
     DeviceGuard g0(s0->device);
     const uint64_t *final_keys = (const uint64_t *)s0->ws_keys.p;
     if (S > 1) {
@@ -2778,7 +2820,7 @@ int hac_index_search(hac_index *idx, const float *q, int64_t nq, int k, float *D
     HAC_TRY(s0->ws_D.reserve((size_t)nq * k * 4));
     HAC_TRY(s0->ws_I.reserve((size_t)nq * k * 8));
     HAC_TRY(hac_keys_to_results_device(s0->device, final_keys, nq * k, nullptr, (float *)s0->ws_D.p, (int64_t *)s0->ws_I.p, s0->stream));
-    char *hp = (char *)s0->h_pin;
+    char *hp = (char *)s0->h_pin.p;
     HAC_HIP(hipMemcpyAsync(hp, s0->ws_I.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s0->stream));
     HAC_HIP(hipMemcpyAsync(hp + (size_t)nq * k * 8, s0->ws_D.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s0->stream));
     HAC_HIP(hipStreamSynchronize(s0->stream));
@@ -2786,18 +2828,7 @@ int hac_index_search(hac_index *idx, const float *q, int64_t nq, int k, float *D
     std::memcpy(D, hp + (size_t)nq * k * 8, (size_t)nq * k * 4);
     // a scan workgroup that ran into its pass bound: the results are delivered (the affected lists EMPTY), the call says so
     // (every shard's words are read and cleared before returning: a word left set would be blamed on a later search)
-    int rc_all = HAC_OK;
-    std::string msg_all;
-    for (auto *s : idx->shards) {
-        DeviceGuard gs(s->device);
-        const int rc = s->check_err(s->stream);
-        if (rc != HAC_OK && rc_all == HAC_OK) {
-            rc_all = rc;
-            msg_all = last_error_slot();
-        }
-    }
-    if (rc_all != HAC_OK) return fail(rc_all, "%s", msg_all.c_str());
-    return HAC_OK;
+    return first_shard_error(idx, [](DeviceIndex *s) { return s->check_err(s->stream); });
 }
 
 }  // extern "C"
@@ -2844,26 +2875,6 @@ int check_host_ids(const char *what, const int64_t *ids, int64_t count, int64_t 
     return HAC_OK;
 }
 
-// fn(shard) on every shard, one host thread per device as hac_index_search runs them; the first failure is reported
-template <class F>
-int for_each_shard(hac_index *idx, F fn) {
-    const int S = (int)idx->shards.size();
-    if (S == 1) return fn(0);
-    std::vector<int> rcs(S, HAC_OK);
-    std::vector<std::string> msgs(S);
-    std::vector<std::thread> pool;
-    for (int si = 1; si < S; ++si)
-        pool.emplace_back([&, si] {
-            rcs[si] = fn(si);
-            if (rcs[si] != HAC_OK) msgs[si] = last_error_slot();
-        });
-    rcs[0] = fn(0);
-    if (rcs[0] != HAC_OK) msgs[0] = last_error_slot();
-    for (auto &t : pool) t.join();
-    for (int si = 0; si < S; ++si)
-        if (rcs[si] != HAC_OK) return fail(rcs[si], "shard %d (device %d): %s", si, idx->shards[si]->device, msgs[si].c_str());
-    return HAC_OK;
-}
 }  // namespace
 
 extern "C" {
@@ -2908,10 +2919,9 @@ int hac_index_reconstruct(hac_index *idx, int64_t i0, int64_t n, float *out) {
 }
 
 int hac_index_reconstruct_device(hac_index *idx, const int64_t *ids_dev, int64_t i0, int64_t n, float *out_dev, void *hip_stream) {
-    if (!idx) return fail(HAC_ERR_INVALID, "null index");
-    if (idx->shards.size() != 1) return fail(HAC_ERR_UNSUPPORTED, "reconstruct_device needs a single-device index");
+    DeviceIndex *s = nullptr;
+    HAC_TRY(single_shard(idx, "reconstruct_device", s));
     if (n < 0 || (n > 0 && !out_dev)) return fail(HAC_ERR_INVALID, "reconstruct_device: bad arguments");
-    DeviceIndex *s = idx->shards[0];
     DeviceGuard g(s->device);
     if (ids_dev) return s->rows_ids_device(ids_dev, n, out_dev, (hipStream_t)hip_stream);
     return s->rows_range_device(i0, n, out_dev, (hipStream_t)hip_stream);
@@ -2938,10 +2948,9 @@ int hac_index_score_ids(hac_index *idx, const float *q, int64_t nq, const int64_
 }
 
 int hac_index_score_ids_device(hac_index *idx, const float *q_dev, int64_t nq, const int64_t *ids_dev, int64_t m, float *D_dev, void *hip_stream) {
-    if (!idx) return fail(HAC_ERR_INVALID, "null index");
-    if (idx->shards.size() != 1) return fail(HAC_ERR_UNSUPPORTED, "score_ids_device needs a single-device index");
+    DeviceIndex *s = nullptr;
+    HAC_TRY(single_shard(idx, "score_ids_device", s));
     if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q_dev || !ids_dev || !D_dev))) return fail(HAC_ERR_INVALID, "score_ids_device: bad arguments");
-    DeviceIndex *s = idx->shards[0];
     DeviceGuard g(s->device);
     return s->score_ids_device(q_dev, nq, ids_dev, m, D_dev, (hipStream_t)hip_stream);
 }
@@ -2952,18 +2961,7 @@ int hac_index_last_status(hac_index *idx) {
         DeviceGuard g(s->device);
         if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", s->device);
     }
-    int rc_all = HAC_OK;
-    std::string msg_all;
-    for (auto *s : idx->shards) {   // every shard's word is read and cleared, the first failure is the one reported
-        DeviceGuard g(s->device);
-        const int rc = s->fetch_err(s->stream);
-        if (rc != HAC_OK && rc_all == HAC_OK) {
-            rc_all = rc;
-            msg_all = last_error_slot();
-        }
-    }
-    if (rc_all != HAC_OK) return fail(rc_all, "%s", msg_all.c_str());
-    return HAC_OK;
+    return first_shard_error(idx, [](DeviceIndex *s) { return s->fetch_err(s->stream); });
 }
 
 int hac_index_set_option(hac_index *idx, const char *name, const char *value) {

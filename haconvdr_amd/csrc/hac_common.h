@@ -86,4 +86,27 @@ struct GrowBuf {
     }
 };
 
+// pinned host buffer that only ever grows, to exactly the size asked for (how far ahead to grow is the caller's rule;
+// needed: the size a failure names when the caller asked for more than it needs)
+struct PinBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    int reserve(size_t bytes, size_t needed = 0) {
+        if (bytes <= cap) return HAC_OK;
+        release();
+        hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            p = nullptr;
+            return fail(HAC_ERR_OOM, "hipHostMalloc(%zu) failed: %s", needed ? needed : bytes, hipGetErrorString(e));
+        }
+        cap = bytes;
+        return HAC_OK;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
 }  // namespace hac
