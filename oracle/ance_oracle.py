@@ -75,6 +75,7 @@ def ance_forward(sd, input_ids, attention_mask, n_layers=None, n_heads=12, eps=1
 # One stage at a time, fp64, with the HIP kernels' bf16 rounding points (tests/test_encoder_layers_gpu.py: teacher-forced parity)
 
 LAYER_MUTATIONS = ("eps", "logits", "key_plus", "key_minus", "bias", "gelu_tanh")   # what ance_layer(mutate=...) knows
+ATTN_MUTATIONS = ("logits", "key_plus", "key_minus", "key_next", "top_key", "head_next", "block_stale")   # ance_attention's, local
 CHUNK_MUTATIONS = ("key_chunk",)      # of the split attention kernel's 64-key chunk loop (tests/test_encoder_precision_shapes_gpu.py)
 EMBED_MUTATIONS = ("eps", "pos")                                                    # what ance_embed(mutate=...) knows
 LOG2E = 1.4426950408889634
@@ -191,31 +192,97 @@ def _project(sd, i, nm, x, mean, rstd, xn, g_in, b_in, family, n_heads, mutate=N
     return R((A @ R(Wf).T + bias) * c) if nm == "query" else R(A @ R(Wf).T + bias)
 
 
-def _attend(Qs, K, V, n, n_heads, family, attn, mutate=None):
+def _attend(Qs, K, V, n, n_heads, family, attn, mutate=None, nxt=None):
     """Attention context [nq, H] of the query rows Qs [nq, H] (base 2, _project) of one sequence of n valid rows over its
-    keys and values K, V [>= n, H]: the arithmetic of ance_layer's docstring (mutations "logits", "key_plus", "key_minus")."""
+    keys and values K, V [>= n, H]: the arithmetic of ance_layer's docstring (mutations "logits", "key_plus", "key_minus";
+    ance_attention's: "key_next" with nxt = (k, v), one more key row [H] each, "top_key", "head_next", "block_stale")."""
     R = _rounding(family)
     nq, H = Qs.shape
     dh = H // n_heads
     nk = min(K.shape[0], n + 1) if mutate == "key_plus" else (max(1, n - 1) if mutate == "key_minus" else n)
     if mutate == "key_chunk":
         nk = min(K.shape[0], (n + 63) // 64 * 64)
+    K, V = K[:nk], V[:nk]
+    if mutate == "key_next":
+        K, V, nk = torch.cat([K, nxt[0][None]]), torch.cat([V, nxt[1][None]]), nk + 1
     qh = Qs.reshape(nq, n_heads, dh).transpose(0, 1)
-    kh = K[:nk].reshape(nk, n_heads, dh).transpose(0, 1)
-    vh = V[:nk].reshape(nk, n_heads, dh).transpose(0, 1)
+    kh = K.reshape(nk, n_heads, dh).transpose(0, 1)
+    vh = V.reshape(nk, n_heads, dh).transpose(0, 1)
+    if mutate == "head_next":
+        vh = vh.roll(-1, 0)
     lg = qh @ kh.transpose(-1, -2)                                         # base-2 logits
     if mutate == "logits":
         lg = lg * 1.01
+    if mutate == "top_key" and nk > 1:                                     # (weight exactly 0, and out of every maximum)
+        lg = lg.masked_fill(F.one_hot(lg.argmax(-1), nk).bool(), -1e30)
     if family and attn == "stream":
         mb = _window_reference(lg)                                         # [heads, nq, blocks]
         mk = mb.repeat_interleave(32, -1)[..., :nk]                        # the reference in force at each key's block
         P = torch.exp2(lg - mb[..., -1:])
         Pr = R(torch.exp2(lg - mk)) * torch.exp2(mk - mb[..., -1:])
+        if mutate == "block_stale":                                        # l and O of the earlier blocks never rescaled
+            P = torch.exp2(lg - mk)
+            Pr = R(P)
     else:
         P = torch.exp2(lg - lg.max(-1, keepdim=True).values)
         Pr = R(P)
     o = (Pr @ vh) / P.sum(-1, keepdim=True)
     return R(o).transpose(0, 1).reshape(nq, H)
+
+
+def ance_qkv(sd, i, x_in, family=None, n_heads=12):
+    """(Q, K, V) of layer i, float64 [B, L, H] as the family stores them (_project), from the state x_in of ance_layer."""
+    x, mean, rstd, g_in, b_in, xn = _layer_input(sd, i, x_in)
+    return tuple(_project(sd, i, nm, x, mean, rstd, xn, g_in, b_in, family, n_heads) for nm in ("query", "key", "value"))
+
+
+def attention_moves(qkv, attention_mask, n_heads=12):
+    """bool [B, L, heads]: the (row, head) slices whose streaming softmax reference moves at a key block after the first
+    (_window_reference) -- the only ones that "block_stale" changes."""
+    Q, K, _ = qkv
+    B, L, H = Q.shape
+    lens = torch.as_tensor(np.asarray(attention_mask), dtype=torch.long).sum(1).tolist()
+    out = torch.zeros(B, L, n_heads, dtype=torch.bool)
+    for s, n in enumerate(lens):
+        lg = Q[s, :n].reshape(n, n_heads, -1).transpose(0, 1) @ K[s, :n].reshape(n, n_heads, -1).transpose(0, 1).transpose(-1, -2)
+        mb = _window_reference(lg)
+        out[s, :n] = (mb[..., 1:] != mb[..., :-1]).any(-1).transpose(0, 1)
+    return out
+
+
+def ance_attention(sd, i, x_in, attention_mask, family=None, attn="stream", mutate=None, where=None, n_heads=12, qkv=None):
+    """Layer i's attention context alone, float64 [B, L, H] (zeros beyond each sequence's length): ance_layer's Q, K, V and
+    attend step on the state x_in, nothing behind them (tests/attn_probe.py observes it through a transparent layer).
+    qkv: ance_qkv's result for the same (sd, i, x_in, family), to share it among calls.
+
+    mutate (ATTN_MUTATIONS), applied in the slices where = {(b, t, h)} only (None: in every slice): "logits" / "key_plus" /
+    "key_minus" as in ance_layer, and
+      "key_next"    the row also attends the first row of the next sequence of the batch ((b + 1) % B) with that row's own K
+                    and V: what a kernel over packed rows reads one past a sequence's end;
+      "top_key"     the key with the row's largest logit is dropped (lengths > 1);
+      "head_next"   V of head (h + 1) % n_heads;
+      "block_stale" (family set, attn = "stream") when the softmax reference moves at a key block, the sum and the context
+                    of the blocks before it are not rescaled (a no-op in the rows of which attention_moves says False)."""
+    assert family in FAMILIES and attn in ("stream", "twopass") and (mutate is None or mutate in ATTN_MUTATIONS), (family, attn, mutate)
+    assert mutate != "block_stale" or (family and attn == "stream"), (family, attn)
+    lens = torch.as_tensor(np.asarray(attention_mask), dtype=torch.long).sum(1).tolist()
+    Q, K, V = qkv if qkv is not None else ance_qkv(sd, i, x_in, family, n_heads)
+    B, L, H = Q.shape
+    dh = H // n_heads
+    ctx = torch.zeros(B, L, H, dtype=torch.float64)
+    for s, n in enumerate(lens):
+        nxt = (K[(s + 1) % B, 0], V[(s + 1) % B, 0])
+        if mutate is None or where is not None:
+            ctx[s, :n] = _attend(Q[s, :n], K[s], V[s], n, n_heads, family, attn)
+        else:
+            ctx[s, :n] = _attend(Q[s, :n], K[s], V[s], n, n_heads, family, attn, mutate, nxt)
+        rows = sorted({t for b, t, _ in where if b == s}) if (mutate and where is not None) else []
+        if rows:
+            mut = _attend(Q[s, rows], K[s], V[s], n, n_heads, family, attn, mutate, nxt)
+            for b, t, h in where:
+                if b == s:
+                    ctx[s, t, h * dh:(h + 1) * dh] = mut[rows.index(t), h * dh:(h + 1) * dh]
+    return ctx
 
 
 def ance_layer(sd, i, x_in, attention_mask, family=None, n_heads=12, eps=1e-5, mutate=None, attn="stream"):
