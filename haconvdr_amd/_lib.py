@@ -56,6 +56,9 @@ def _declare(L):
     L.hac_index_last_plan.restype = ctypes.c_char_p
     L.hac_merge_keys_device.argtypes = [ctypes.c_int, vp, ctypes.c_int, i64, ctypes.c_int, vp, vp]
     L.hac_keys_to_results_device.argtypes = [ctypes.c_int, vp, i64, vp, vp, vp, vp]
+    L.hac_filter_keys_device.argtypes = [ctypes.c_int, vp, i64, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp]
+    L.hac_index_search_excluding.argtypes = [vp, c_f32p, i64, ctypes.c_int, ctypes.POINTER(i64), ctypes.c_int, c_f32p, ctypes.POINTER(i64)]
+    L.hac_index_search_excluding_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp]
     L.hac_encoder_create.argtypes = [vp, ctypes.c_int, ctypes.POINTER(vp)]
     L.hac_encoder_destroy.argtypes = [vp]
     L.hac_encoder_destroy.restype = None
@@ -81,7 +84,8 @@ def _declare(L):
                  "hac_index_search_device", "hac_index_search_keys_device", "hac_index_reset",
                  "hac_index_set_option", "hac_index_set_profiling", "hac_index_profile_drain", "hac_merge_keys_device",
                  "hac_keys_to_results_device", "hac_index_reconstruct", "hac_index_reconstruct_ids", "hac_index_reconstruct_device",
-                 "hac_index_score_ids", "hac_index_score_ids_device"):
+                 "hac_index_score_ids", "hac_index_score_ids_device", "hac_filter_keys_device", "hac_index_search_excluding",
+                 "hac_index_search_excluding_device"):
         getattr(L, name).restype = ctypes.c_int
 
 
@@ -90,7 +94,8 @@ EXPORTED_SYMBOLS = (
     "hac_last_error", "hac_version", "hac_index_create", "hac_index_destroy", "hac_index_add",
     "hac_index_add_device", "hac_index_search", "hac_index_search_device", "hac_index_search_keys_device",
     "hac_index_reset", "hac_index_ntotal", "hac_index_set_option", "hac_index_set_profiling", "hac_index_profile_drain", "hac_index_last_plan",
-    "hac_index_last_status", "hac_merge_keys_device", "hac_keys_to_results_device",
+    "hac_index_last_status", "hac_merge_keys_device", "hac_keys_to_results_device", "hac_filter_keys_device",
+    "hac_index_search_excluding", "hac_index_search_excluding_device",
     "hac_index_reconstruct", "hac_index_reconstruct_ids", "hac_index_reconstruct_device", "hac_index_score_ids", "hac_index_score_ids_device",
     "hac_encoder_create", "hac_encoder_destroy", "hac_encoder_set_weight", "hac_encoder_finalize", "hac_encoder_forward",
     "hac_encoder_forward_device", "hac_encoder_set_option", "hac_encoder_last_plan", "hac_encoder_set_profiling", "hac_encoder_profile_drain",

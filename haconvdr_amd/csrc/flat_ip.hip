@@ -95,8 +95,9 @@ __device__ __forceinline__ gf4ptr as_global(const float4 *p) { return (gf4ptr)(p
 
 __device__ __forceinline__ void lds_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); }
 
-// In-LDS bitonic sort, descending, by ONE wave.  buf has capacity >= next_pow2(n).
-__device__ void wave_sort_desc(u64 *buf, u32 n, int lane) {
+// In-LDS bitonic sort, descending, by ONE wave.  buf has capacity >= next_pow2(n).  T: u64 keys, or u32 words (filter_keys_kernel).
+template <class T>
+__device__ void wave_sort_desc(T *buf, u32 n, int lane) {
     u32 np2 = 1;
     while (np2 < n) np2 <<= 1;
     for (u32 i = n + lane; i < np2; i += 64) buf[i] = 0;
@@ -107,7 +108,7 @@ __device__ void wave_sort_desc(u64 *buf, u32 n, int lane) {
                 u32 lo = 2 * t - (t & (stride - 1));
                 u32 hi = lo + stride;
                 bool desc = (lo & size) == 0;
-                u64 a = buf[lo], b = buf[hi];
+                T a = buf[lo], b = buf[hi];
                 if ((a < b) == desc) {
                     buf[lo] = b;
                     buf[hi] = a;
@@ -1055,6 +1056,52 @@ __global__ void keys_to_results_kernel(const u64 *__restrict__ keys, long n, con
         D[i] = ord2f((u32)(key >> 32));
         I[i] = id_map ? id_map[pos] : (long long)pos;
     }
+}
+
+// Per query: the first kout keys of a sorted list of kin whose position is not among the query's e excluded positions, in
+// their order, the rest of the output row 0.  One wave (= one workgroup) per query.  The exclusions that can match at all
+// (0 <= value <= 0xFFFFFFFF; anything else is padding) go to LDS as the low key word they would carry, 0xFFFFFFFF - position,
+// and are sorted there; the keys are then walked in chunks of 64, a lane per key: binary search, ballot, popcount prefix =
+// destination.  No atomics: the output is a pure function of the inputs.  out must not alias in (the row strides differ).
+// Dynamic LDS: next_pow2(max(e, 1)) u32 words.
+__global__ __launch_bounds__(64) void filter_keys_kernel(const u64 *__restrict__ in, int kin, const long long *__restrict__ excl, int e,
+                                                         int kout, u64 *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u32 *ex = reinterpret_cast<u32 *>(smem);
+    const int lane = threadIdx.x;
+    const size_t q = blockIdx.x;
+    const u64 below = (1ull << lane) - 1ull;   // the lanes before this one
+    u32 m = 0;                                 // exclusions kept
+    for (int base = 0; base < e; base += 64) {
+        const int i = base + lane;
+        const long long v = i < e ? excl[q * (size_t)e + i] : -1ll;
+        const bool valid = v >= 0 && v <= 0xFFFFFFFFll;
+        const u64 vote = __ballot(valid);
+        if (valid) ex[m + (u32)__popcll(vote & below)] = 0xFFFFFFFFu - (u32)v;
+        m += (u32)__popcll(vote);
+    }
+    lds_fence();
+    if (m > 1) wave_sort_desc(ex, m, lane);
+    const u64 *src = in + q * (size_t)kin;
+    u64 *dst = out + q * (size_t)kout;
+    u32 written = 0;
+    for (int base = 0; base < kin && written < (u32)kout; base += 64) {
+        const int i = base + lane;
+        const u64 key = i < kin ? src[i] : 0ull;
+        const u32 w = (u32)key;
+        u32 lo = 0, hi = m;                    // first index of the descending list whose word is <= w
+        while (lo < hi) {
+            const u32 mid = (lo + hi) >> 1;
+            if (ex[mid] > w) lo = mid + 1;
+            else hi = mid;
+        }
+        const bool keep = key != 0ull && !(lo < m && ex[lo] == w);
+        const u64 vote = __ballot(keep);
+        const u32 at = written + (u32)__popcll(vote & below);
+        if (keep && at < (u32)kout) dst[at] = key;
+        written += (u32)__popcll(vote);
+    }
+    for (u32 i = min(written, (u32)kout) + lane; i < (u32)kout; i += 64) dst[i] = 0ull;
 }
 
 // In-process multi-device index: a shard numbers its rows densely in the order it received them, while the
@@ -2531,6 +2578,13 @@ int check_k(int k) {
     return HAC_OK;
 }
 
+// search_excluding: the search itself runs at k + e
+int check_k_e(int k, int e) {
+    if (k < 1 || e < 0 || (long)k + e > HAC_MAX_K)
+        return fail(HAC_ERR_INVALID, "search_excluding: k=%d, e=%d: needs k >= 1, e >= 0 and k + e <= %d (the search runs at k + e)", k, e, HAC_MAX_K);
+    return HAC_OK;
+}
+
 }  // namespace
 }  // namespace hac
 
@@ -2545,6 +2599,7 @@ struct hac_index {
     int64_t ntotal = 0;
     // multi-device merge workspace lives on shard 0
     GrowBuf ws_lists, ws_out;
+    GrowBuf ws_excl;   // hac_index_search_excluding: the host's exclusion lists, on shard 0
     // n_dev > 1: per shard, its share of every add() (see remap_positions_kernel)
     std::vector<std::vector<SpanDesc>> spans;
     std::vector<GrowBuf> ws_spans;
@@ -2641,6 +2696,7 @@ void hac_index_destroy(hac_index *idx) {
         DeviceGuard g(idx->shards[0]->device);
         idx->ws_lists.release();
         idx->ws_out.release();
+        idx->ws_excl.release();
     }
     for (size_t i = 0; i < idx->shards.size(); ++i) {
         if (i < idx->ws_spans.size()) {
@@ -2745,6 +2801,22 @@ int hac_merge_keys_device(int device, const uint64_t *lists_dev, int n_lists, in
     return HAC_OK;
 }
 
+int hac_filter_keys_device(int device, const uint64_t *keys_dev, int64_t nq, int kin, const int64_t *excl_pos_dev, int e, int kout,
+                           uint64_t *out_dev, void *hip_stream) {
+    if (kin < 1 || kin > HAC_MAX_K || kout < 1 || kout > kin || e < 0 || e >= HAC_MAX_K)
+        return fail(HAC_ERR_INVALID, "filter_keys: kin=%d, kout=%d, e=%d: needs 1 <= kout <= kin <= %d and 0 <= e < %d", kin, kout, e, HAC_MAX_K,
+                    HAC_MAX_K);
+    if (nq < 0 || (nq > 0 && (!keys_dev || !out_dev || (e > 0 && !excl_pos_dev)))) return fail(HAC_ERR_INVALID, "filter_keys: bad arguments");
+    if (nq == 0) return HAC_OK;
+    if ((const uint64_t *)out_dev == keys_dev) return fail(HAC_ERR_INVALID, "filter_keys: out must not alias the input keys");
+    DeviceGuard g(device);
+    if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", device);
+    filter_keys_kernel<<<dim3((unsigned)nq), dim3(64), (size_t)next_pow2((u32)std::max(e, 1)) * 4, (hipStream_t)hip_stream>>>(
+        (const u64 *)keys_dev, kin, (const long long *)excl_pos_dev, e, kout, (u64 *)out_dev);
+    HAC_HIP(hipGetLastError());
+    return HAC_OK;
+}
+
 int hac_index_search_device(hac_index *idx, const float *q_dev, int64_t nq, int k, float *D_dev, int64_t *I_dev,
                             const int64_t *id_map_dev, void *hip_stream) {
     DeviceIndex *s = nullptr;
@@ -2758,19 +2830,41 @@ int hac_index_search_device(hac_index *idx, const float *q_dev, int64_t nq, int 
     return hac_keys_to_results_device(s->device, (const uint64_t *)s->ws_keys.p, nq * k, id_map_dev, D_dev, I_dev, hip_stream);
 }
 
-int hac_index_search(hac_index *idx, const float *q, int64_t nq, int k, float *D, int64_t *I) {
-    if (!idx) return fail(HAC_ERR_INVALID, "null index");
-    HAC_TRY(check_k(k));
-    if (nq < 0 || (nq > 0 && (!q || !D || !I))) return fail(HAC_ERR_INVALID, "search: bad arguments");
+// The top-k of (rows minus E), |E| <= e, lies inside the top-(k + e) of the rows, in the same order: search k + e keys, filter.
+int hac_index_search_excluding_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const int64_t *excl_dev, int e, float *D_dev,
+                                      int64_t *I_dev, const int64_t *id_map_dev, void *hip_stream) {
+    DeviceIndex *s = nullptr;
+    HAC_TRY(single_shard(idx, "search_excluding_device", s));
+    HAC_TRY(check_k_e(k, e));
+    if (e == 0) return hac_index_search_device(idx, q_dev, nq, k, D_dev, I_dev, id_map_dev, hip_stream);
+    if (nq < 0 || (nq > 0 && (!q_dev || !excl_dev || !D_dev || !I_dev))) return fail(HAC_ERR_INVALID, "search_excluding: bad arguments");
     if (nq == 0) return HAC_OK;
+    DeviceGuard g(s->device);
+    const int kq = k + e;
+    HAC_TRY(s->ws_keys.reserve((size_t)nq * kq * 8));
+    HAC_TRY(idx->ws_out.reserve((size_t)nq * k * 8));
+    HAC_TRY(s->search_keys(q_dev, nq, kq, (u64 *)s->ws_keys.p, 0u, (hipStream_t)hip_stream, true));
+    // (row ids are the positions the keys carry, pos_base = 0; an id outside [0, ntotal) is padding or names no key)
+    HAC_TRY(hac_filter_keys_device(s->device, (const uint64_t *)s->ws_keys.p, nq, kq, excl_dev, e, k, (uint64_t *)idx->ws_out.p, hip_stream));
+    return hac_keys_to_results_device(s->device, (const uint64_t *)idx->ws_out.p, nq * k, id_map_dev, D_dev, I_dev, hip_stream);
+}
+
+}  // extern "C"
+
+namespace {
+// The host driver of hac_index_search (e == 0: kq == k, no filter) and hac_index_search_excluding (the shards search, are
+// remapped and merged at kq = k + e; the merged lists are filtered down to k on shard 0).  Arguments checked by the callers.
+int search_host(hac_index *idx, const float *q, int64_t nq, int k, const int64_t *excl, int e, float *D, int64_t *I) {
+    const int kq = k + e;
     const int S = (int)idx->shards.size();
-    const size_t qbytes = (size_t)nq * idx->d * 4;
+    const size_t qbytes = (size_t)nq * idx->d * 4, ebytes = (size_t)nq * e * 8;
     // each shard searches its rows; positions are global (shard base + local row)
     DeviceIndex *s0 = idx->shards[0];
     {
         DeviceGuard g0(s0->device);
-        HAC_TRY(idx->ws_lists.reserve((size_t)S * nq * k * 8));
-        HAC_TRY(idx->ws_out.reserve((size_t)nq * k * 8));
+        HAC_TRY(idx->ws_lists.reserve((size_t)S * nq * kq * 8));
+        HAC_TRY(idx->ws_out.reserve((size_t)nq * kq * 8));
+        if (e) HAC_TRY(idx->ws_excl.reserve(ebytes));
     }
     // every shard searches its own rows on its own stream (for_each_shard)
     auto search_shard = [&](int si) -> int {
@@ -2778,12 +2872,17 @@ int hac_index_search(hac_index *idx, const float *q, int64_t nq, int k, float *D
         DeviceGuard g(s->device);
         if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", s->device);
         HAC_TRY(s->ws_q.reserve(qbytes));
-        HAC_TRY(s->ws_keys.reserve((size_t)nq * k * 8));
-        HAC_TRY(s->pin_reserve(std::max(qbytes, (size_t)nq * k * 12)));
+        HAC_TRY(s->ws_keys.reserve((size_t)nq * kq * 8));
+        const size_t xbytes = si == 0 ? ebytes : 0;   // the exclusion lists travel behind shard 0's queries
+        HAC_TRY(s->pin_reserve(std::max(qbytes + xbytes, (size_t)nq * k * 12)));
         HAC_HIP(hipStreamSynchronize(s->stream));
         std::memcpy(s->h_pin.p, q, qbytes);
         HAC_HIP(hipMemcpyAsync(s->ws_q.p, s->h_pin.p, qbytes, hipMemcpyHostToDevice, s->stream));
-        HAC_TRY(s->search_keys((const float *)s->ws_q.p, nq, k, (u64 *)s->ws_keys.p, 0u, s->stream));
+        if (xbytes) {
+            std::memcpy((char *)s->h_pin.p + qbytes, excl, xbytes);
+            HAC_HIP(hipMemcpyAsync(idx->ws_excl.p, (char *)s->h_pin.p + qbytes, xbytes, hipMemcpyHostToDevice, s->stream));
+        }
+        HAC_TRY(s->search_keys((const float *)s->ws_q.p, nq, kq, (u64 *)s->ws_keys.p, 0u, s->stream));
         HAC_HIP(hipMemcpyAsync(s->h_err, s->ws_err.p, 8, hipMemcpyDeviceToHost, s->stream));   // checked after the final wait
         if (S > 1) {   // shard-local rows -> insertion-order positions of the whole index
             const std::vector<SpanDesc> &sp = idx->spans[si];
@@ -2794,7 +2893,7 @@ int hac_index_search(hac_index *idx, const float *q, int64_t nq, int k, float *D
                     HAC_HIP(hipMemcpy(idx->ws_spans[si].p, sp.data(), sp.size() * sizeof(SpanDesc), hipMemcpyHostToDevice));
                     idx->spans_dirty[si] = 0;
                 }
-                const long nk = (long)nq * k;
+                const long nk = (long)nq * kq;
                 remap_positions_kernel<<<dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s->stream>>>(
                     (u64 *)s->ws_keys.p, nk, (const SpanDesc *)idx->ws_spans[si].p, (int)sp.size());
                 HAC_HIP(hipGetLastError());
@@ -2811,11 +2910,16 @@ int hac_index_search(hac_index *idx, const float *q, int64_t nq, int k, float *D
         // streams are non-blocking, a legacy-stream D2D copy would not be ordered with them)
         for (int si = 0; si < S; ++si) {
             DeviceIndex *s = idx->shards[si];
-            HAC_HIP(hipMemcpyAsync((char *)idx->ws_lists.p + (size_t)si * nq * k * 8, s->ws_keys.p, (size_t)nq * k * 8,
+            HAC_HIP(hipMemcpyAsync((char *)idx->ws_lists.p + (size_t)si * nq * kq * 8, s->ws_keys.p, (size_t)nq * kq * 8,
                                    hipMemcpyDeviceToDevice, s0->stream));
         }
-        HAC_TRY(hac_merge_keys_device(s0->device, (const uint64_t *)idx->ws_lists.p, S, nq, k, (uint64_t *)idx->ws_out.p, s0->stream));
+        HAC_TRY(hac_merge_keys_device(s0->device, (const uint64_t *)idx->ws_lists.p, S, nq, kq, (uint64_t *)idx->ws_out.p, s0->stream));
         final_keys = (const uint64_t *)idx->ws_out.p;
+    }
+    if (e) {   // the kq best of all rows -> the k best of (rows minus the query's excluded rows); the merge's input slabs are free by now
+        uint64_t *filtered = (uint64_t *)(S > 1 ? idx->ws_lists.p : idx->ws_out.p);
+        HAC_TRY(hac_filter_keys_device(s0->device, final_keys, nq, kq, (const int64_t *)idx->ws_excl.p, e, k, filtered, s0->stream));
+        final_keys = filtered;
     }
     HAC_TRY(s0->ws_D.reserve((size_t)nq * k * 4));
     HAC_TRY(s0->ws_I.reserve((size_t)nq * k * 8));
@@ -2829,6 +2933,29 @@ int hac_index_search(hac_index *idx, const float *q, int64_t nq, int k, float *D
     // a scan workgroup that ran into its pass bound: the results are delivered (the affected lists EMPTY), the call says so
     // (every shard's words are read and cleared before returning: a word left set would be blamed on a later search)
     return first_shard_error(idx, [](DeviceIndex *s) { return s->check_err(s->stream); });
+}
+}  // namespace
+
+extern "C" {
+
+int hac_index_search(hac_index *idx, const float *q, int64_t nq, int k, float *D, int64_t *I) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    HAC_TRY(check_k(k));
+    if (nq < 0 || (nq > 0 && (!q || !D || !I))) return fail(HAC_ERR_INVALID, "search: bad arguments");
+    if (nq == 0) return HAC_OK;
+    return search_host(idx, q, nq, k, nullptr, 0, D, I);
+}
+
+int hac_index_search_excluding(hac_index *idx, const float *q, int64_t nq, int k, const int64_t *excl, int e, float *D, int64_t *I) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    HAC_TRY(check_k_e(k, e));
+    if (nq < 0 || (nq > 0 && (!q || !D || !I || (e > 0 && !excl)))) return fail(HAC_ERR_INVALID, "search_excluding: bad arguments");
+    if (nq == 0) return HAC_OK;
+    for (int64_t i = 0; i < nq * e; ++i)   // -1 is padding; any other id outside the index is the caller's mistake
+        if (excl[i] < -1 || excl[i] >= idx->ntotal)
+            return fail(HAC_ERR_INVALID, "search_excluding: id %lld at (query %lld, column %lld) is outside [0, %lld) (-1 = padding)",
+                        (long long)excl[i], (long long)(i / e), (long long)(i % e), (long long)idx->ntotal);
+    return search_host(idx, q, nq, k, excl, e, D, I);
 }
 
 }  // extern "C"

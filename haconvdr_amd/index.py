@@ -104,6 +104,47 @@ def _score_args_tensor(q, ids, d):
     return q, ids
 
 
+def _check_exclude_shape(nq, k, shape, what):
+    if shape[0] != nq:
+        raise ValueError(f"{what}: {nq} queries but exclude of shape {tuple(shape)} (one list per query)")
+    if k + shape[1] > _lib.HAC_MAX_K:
+        raise ValueError(f"{what}: k + e = {k} + {shape[1]} exceeds {_lib.HAC_MAX_K} (the search runs at k + e)")
+
+
+def _exclude_args(q, k, exclude, d, what="search_excluding"):
+    """(q float32 [nq, d], k, exclude int64 [nq, e]) of search_excluding."""
+    q = _as_queries(q, d, what)
+    k = _as_k(k, what)
+    exclude = _as_ids(exclude, 2, what)
+    _check_exclude_shape(q.shape[0], k, exclude.shape, what)
+    return q, k, exclude
+
+
+def _exclude_args_tensor(q, k, exclude, d, what="search_excluding_tensor"):
+    q = _queries_tensor(q, d, what)
+    k = _as_k(k, what)
+    exclude = _ids_tensor(exclude, 2, what)
+    _check_exclude_shape(q.shape[0], k, exclude.shape, what)
+    if exclude.device != q.device:
+        raise ValueError(f"{what}: q on {q.device} but exclude on {exclude.device}")
+    return q, k, exclude
+
+
+def _filter_args(keys, exclude_pos, k, what="filter_keys"):
+    """(keys int64 CUDA [nq, kin], exclude_pos int64 CUDA [nq, e], k in [1, kin]) of filter_keys."""
+    keys = _ids_tensor(keys, 2, what)
+    exclude_pos = _ids_tensor(exclude_pos, 2, what)
+    k = _as_k(k, what)
+    if keys.shape[1] > _lib.HAC_MAX_K or k > keys.shape[1]:
+        raise ValueError(f"{what}: needs k = {k} <= kin = {keys.shape[1]} <= {_lib.HAC_MAX_K}")
+    if exclude_pos.shape[0] != keys.shape[0] or exclude_pos.shape[1] >= _lib.HAC_MAX_K:
+        raise ValueError(f"{what}: keys of shape {tuple(keys.shape)} but exclude_pos of shape {tuple(exclude_pos.shape)} "
+                         f"(one list of fewer than {_lib.HAC_MAX_K} positions per query)")
+    if exclude_pos.device != keys.device:
+        raise ValueError(f"{what}: keys on {keys.device} but exclude_pos on {exclude_pos.device}")
+    return keys, exclude_pos, k
+
+
 class FlatIPIndex:
     """faiss.IndexFlatIP(d) drop-in: exact fp32 inner product, results ordered by
     (score desc, row asc), padded with -FLT_MAX / -1.
@@ -145,6 +186,19 @@ class FlatIPIndex:
         _lib.check(_lib.lib().hac_index_search(self._h, q.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), q.shape[0], k,
                                                D.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                                I.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return D, I
+
+    def search_excluding(self, q, k, exclude):
+        """search(q, k) over (rows minus the query's excluded rows): exclude int64 [nq, e] row ids, -1 = padding, duplicates
+        allowed; any other id outside [0, ntotal) raises HacError.  The search runs at k + e <= HAC_MAX_K (include/haconvdr.h);
+        faiss: SearchParameters(sel=IDSelectorNot(IDSelectorBatch(ids))), one selector per query."""
+        q, k, exclude = _exclude_args(q, k, exclude, self.d)
+        D = np.empty((q.shape[0], k), np.float32)
+        I = np.empty((q.shape[0], k), np.int64)
+        _lib.check(_lib.lib().hac_index_search_excluding(self._h, q.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), q.shape[0], k,
+                                                         exclude.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), exclude.shape[1],
+                                                         D.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                                         I.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         return D, I
 
     def reset(self):
@@ -217,6 +271,22 @@ class FlatIPIndex:
                                                       ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()), mp,
                                                       _stream_ptr(stream)))
         for t in (q, D, I):
+            _keep_alive(t, stream)
+        return D, I
+
+    def search_excluding_tensor(self, q, k, exclude, id_map=None, stream=None):
+        """search_tensor over (rows minus the query's excluded rows): exclude int64 CUDA [nq, e] ROW ids (not id_map's), any id
+        outside [0, ntotal) is ignored.  No host sync; capturable after one call of the largest (nq, k + e)."""
+        import torch
+        q, k, exclude = _exclude_args_tensor(q, k, exclude, self.d)
+        D = torch.empty((q.shape[0], k), dtype=torch.float32, device=q.device)
+        I = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
+        mp = ctypes.c_void_p(id_map.data_ptr()) if id_map is not None else ctypes.c_void_p()
+        _lib.check(_lib.lib().hac_index_search_excluding_device(self._h, ctypes.c_void_p(q.data_ptr()), q.shape[0], k,
+                                                                ctypes.c_void_p(exclude.data_ptr()), exclude.shape[1],
+                                                                ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()), mp,
+                                                                _stream_ptr(stream)))
+        for t in (q, exclude, D, I):
             _keep_alive(t, stream)
         return D, I
 
@@ -304,6 +374,20 @@ def merge_keys(lists, stream=None):
     out = torch.empty((nq, k), dtype=torch.int64, device=lists.device)
     _lib.check(_lib.lib().hac_merge_keys_device(lists.device.index or 0, ctypes.c_void_p(lists.data_ptr()), L, nq, k,
                                                 ctypes.c_void_p(out.data_ptr()), _stream_ptr(stream)))
+    return out
+
+
+def filter_keys(keys, exclude_pos, k, stream=None):
+    """keys [nq, kin] sorted per-query lists, exclude_pos int64 CUDA [nq, e] global positions (< 0 or > 0xFFFFFFFF = padding)
+    -> [nq, k]: each query's first k keys whose position is not excluded, in order, the rest 0."""
+    import torch
+    keys, exclude_pos, k = _filter_args(keys, exclude_pos, k)
+    out = torch.empty((keys.shape[0], k), dtype=torch.int64, device=keys.device)
+    _lib.check(_lib.lib().hac_filter_keys_device(keys.device.index or 0, ctypes.c_void_p(keys.data_ptr()), keys.shape[0], keys.shape[1],
+                                                 ctypes.c_void_p(exclude_pos.data_ptr()), exclude_pos.shape[1], k,
+                                                 ctypes.c_void_p(out.data_ptr()), _stream_ptr(stream)))
+    for t in (keys, exclude_pos, out):
+        _keep_alive(t, stream)
     return out
 
 

@@ -143,6 +143,31 @@ def search_one_by_one(args, passage_embeddings_dir, index, query_embeddings, top
     return merged_D, merged_I
 
 
+def rows_carrying(sorted_ids, order, exclude):
+    """External ids int64 [nq, e] (-1 = padding) -> int64 [nq, w]: per query EVERY row that carries one of its ids (an id two
+    blocks hold names two rows), in the order of the ids, padded with -1 to the widest list (w = 0 when no id is held).
+    (sorted_ids, order): the row -> id array sorted ascending and the rows in that order.  An id no row carries adds nothing."""
+    pid = np.asarray(exclude)
+    if pid.dtype.kind not in "iu":
+        raise ValueError(f"exclude: passage ids must be integers, got dtype {pid.dtype}")
+    if pid.ndim != 2:
+        raise ValueError(f"exclude must be [nq, e], got shape {pid.shape}")
+    pid = pid.astype(np.int64)
+    lo = np.searchsorted(sorted_ids, pid, side="left")
+    cnt = np.where(pid == -1, 0, np.searchsorted(sorted_ids, pid, side="right") - lo)
+    per_query = cnt.sum(axis=1)
+    out = np.full((pid.shape[0], int(per_query.max()) if pid.shape[0] else 0), -1, np.int64)
+    cnt, lo = cnt.reshape(-1), lo.reshape(-1)
+    total = int(cnt.sum())
+    if total:
+        first = np.cumsum(cnt) - cnt                                          # of each (query, id) run, in the flat output
+        within = np.arange(total) - np.repeat(first, cnt)
+        query = np.repeat(np.repeat(np.arange(pid.shape[0]), pid.shape[1]), cnt)
+        col = np.arange(total) - np.repeat(np.cumsum(per_query) - per_query, per_query)
+        out[query, col] = order[np.repeat(lo, cnt) + within]
+    return out
+
+
 class ResidentCorpus:
     """All passage blocks of a directory resident in HBM, searched many times (the reference reloads
     every block for every evaluation run, :77-123).  Same result contract as search_one_by_one."""
@@ -168,12 +193,26 @@ class ResidentCorpus:
     def ntotal(self):
         return self.index.ntotal
 
-    def search(self, query_embeddings, topN):
-        """query_embeddings: float32 [nq,768] (numpy or CUDA tensor) -> (D float64 [nq,topN], I int64 [nq,topN])."""
+    def _id_lookup(self):
+        """(ids sorted ascending, their rows): built once, on the host, by the first call that needs it."""
+        if self._lookup is None:
+            order = np.argsort(self._ids, kind="stable")
+            self._lookup = (self._ids[order], order.astype(np.int64))
+        return self._lookup
+
+    def search(self, query_embeddings, topN, exclude=None):
+        """query_embeddings: float32 [nq,768] (numpy or CUDA tensor) -> (D float64 [nq,topN], I int64 [nq,topN]).
+        exclude: optional int64 [nq, e] EXTERNAL passage ids (-1 = padding) the query must not get back -- its gold passages
+        when mining hard negatives, what a conversation has already shown; every row that carries such an id is left out, an
+        id no block holds is ignored, and the list is still filled to topN (the search runs at topN + the widest row list)."""
         import torch
         q = query_embeddings if isinstance(query_embeddings, torch.Tensor) else torch.from_numpy(
             np.ascontiguousarray(query_embeddings, dtype=np.float32))
-        D, I = self.index.search_tensor(q.to(self.dev), topN, id_map=self.id_map)
+        if exclude is None:
+            D, I = self.index.search_tensor(q.to(self.dev), topN, id_map=self.id_map)
+        else:
+            rows = rows_carrying(*self._id_lookup(), exclude)
+            D, I = self.index.search_excluding_tensor(q.to(self.dev), topN, torch.from_numpy(rows).to(self.dev), id_map=self.id_map)
         return D.cpu().numpy().astype(np.float64), I.cpu().numpy()
 
     # ---- the seam of a re-ranker: rows and exact scores by EXTERNAL passage id --------------------------------------
@@ -181,14 +220,11 @@ class ResidentCorpus:
         """External passage ids (any shape) -> rows of the index, int64 of the same shape; -1 where no block holds the id.
         The lookup (the block id arrays sorted once, on the host) is built by the first call; an id that several rows
         carry resolves to the first of them."""
-        if self._lookup is None:
-            order = np.argsort(self._ids, kind="stable")
-            self._lookup = (self._ids[order], order.astype(np.int64))
         pid = np.asarray(passage_ids)
         if pid.dtype.kind not in "iu":
             raise ValueError(f"rows_of: passage ids must be integers, got dtype {pid.dtype}")
         pid = pid.astype(np.int64)
-        sorted_ids, order = self._lookup
+        sorted_ids, order = self._id_lookup()
         if len(sorted_ids) == 0:
             return np.full(pid.shape, -1, np.int64)
         at = np.minimum(np.searchsorted(sorted_ids, pid, side="left"), len(sorted_ids) - 1)

@@ -26,11 +26,17 @@ class ShardedSearcher:
     local_keys(q, k, pos_base) -> int64(uint64 bits) tensor [nq, k]   (default: the HIP index)
     merge(lists [R, nq, k])    -> [nq, k]                              (default: HIP merge kernel)
     to_results(keys, id_map)   -> (D, I)                               (default: HIP kernel)
-    The three hooks exist so that the distributed plumbing can be exercised on CPU with
+    filter(keys [nq, k + e], exclude [nq, e], k) -> [nq, k]            (default: HIP filter kernel)
+    The four hooks exist so that the distributed plumbing can be exercised on CPU with
     gloo and a test double; the product path always uses the HIP defaults.
+
+    exclude (optional, int64 [nq, e], on the keys' device): per query, GLOBAL positions (shard_base + local row) that must
+    not be returned, identical on every rank; < 0 is padding.  Every rank then searches k + e, the all-gather and the merge
+    run at k + e, and the merged lists are filtered down to k: the top-k of (corpus minus E) lies inside the top-(k + |E|)
+    of the corpus, in the same order.  exclude=None is the path above, unchanged; the filter hook is not called.
     """
 
-    def __init__(self, index, shard_base, group=None, id_map=None, local_keys=None, merge=None, to_results=None):
+    def __init__(self, index, shard_base, group=None, id_map=None, local_keys=None, merge=None, to_results=None, filter=None):
         from . import index as _index
         self.index = index
         self.shard_base = int(shard_base)
@@ -39,8 +45,13 @@ class ShardedSearcher:
         self._local_keys = local_keys or (lambda q, k, base: index.search_keys_tensor(q, k, pos_base=base))
         self._merge = merge or _index.merge_keys
         self._to_results = to_results or _index.keys_to_results
+        self._filter = filter or _index.filter_keys
 
-    def search_keys(self, q, k):
+    def search_keys(self, q, k, exclude=None):
+        if exclude is not None:
+            if exclude.dim() != 2 or exclude.shape[0] != q.shape[0]:
+                raise ValueError(f"exclude must be [nq, e] with nq = {q.shape[0]}, got shape {tuple(exclude.shape)}")
+            return self._filter(self.search_keys(q, k + exclude.shape[1]), exclude, k)
         keys = self._local_keys(q, k, self.shard_base)
         if not dist.is_initialized():
             return keys                                   # a single process holding the whole corpus
@@ -50,5 +61,5 @@ class ShardedSearcher:
         dist.all_gather_into_tensor(gathered, keys.contiguous(), group=self.group)
         return self._merge(gathered.view(world, nq, k))
 
-    def search(self, q, k):
-        return self._to_results(self.search_keys(q, k), self.id_map)
+    def search(self, q, k, exclude=None):
+        return self._to_results(self.search_keys(q, k, exclude), self.id_map)

@@ -128,6 +128,37 @@ int hac_index_search_device(hac_index *idx, const float *q_dev, int64_t nq, int 
 int hac_index_search_keys_device(hac_index *idx, const float *q_dev, int64_t nq, int k,
                                  uint64_t *keys_dev, uint32_t pos_base, void *hip_stream);
 
+/* ---- search with per-query excluded rows --------------------------------------------------------------------------------
+ * The search contract above over (rows minus the query's excluded rows): canonical fp32 fma-chain score, order (score desc,
+ * row asc), NaN scores never returned, short lists padded -FLT_MAX / -1.  faiss users know it as
+ * SearchParameters(sel=IDSelectorNot(IDSelectorBatch(ids))), here with one id list per query: a query's gold passages when
+ * mining dense hard negatives, the passages a conversation has already shown.
+ *
+ * excl: int64 [nq, e] row ids of the index (its own numbering, as in "rows by id" below -- not id_map's external ids); -1 is
+ * padding, duplicates are allowed.  With e == 0, or lists that name no row of the query's top-(k + e), the result equals
+ * hac_index_search*'s bit for bit.
+ *
+ * How: for an exclusion set E, |E| <= e, the top-k of (rows minus E) is contained in the top-(k + e) of the rows, in the same
+ * order.  The call therefore searches k' = k + e keys with the kernels of search and filters the sorted key lists on the
+ * device (hac_filter_keys_device) before they become (D, I).  Consequences:
+ *   - k >= 1, e >= 0 and k + e <= HAC_MAX_K, otherwise HAC_ERR_INVALID (the message names k, e and the ceiling);
+ *   - every route decision of search is made for k', not k: the half-precision prefilter needs k + e <= 192, and a k' that
+ *     does not fit the LDS candidate buffers fails as it does for search, naming k';
+ *   - the cost is that of a search at k' plus one pass over nq * k' keys.
+ *
+ * Ids outside [0, ntotal), as for the rows-by-id calls: the *_device entry point ignores them (it cannot look); the host entry
+ * point ignores -1 and returns HAC_ERR_INVALID for any other, naming the first offending id and its (query, column).
+ *
+ * Host variant: synchronous, works on a multi-device index (the shards search k' keys, which are remapped and merged at k'
+ * exactly as in hac_index_search; the filter then runs once, on the first device); status words of the scans are reported as
+ * hac_index_search reports them.  Device variant: single-device index (HAC_ERR_UNSUPPORTED otherwise); enqueues on hip_stream,
+ * never reads back; the k' keys and the filtered keys live in workspaces of the index, which grow by the rule above: run one
+ * call of the largest (nq, k + e) before capturing it into a HIP graph; id_map_dev fuses the remap of the RESULT as in
+ * hac_index_search_device.  nq == 0 is HAC_OK and touches nothing. */
+int hac_index_search_excluding(hac_index *idx, const float *q, int64_t nq, int k, const int64_t *excl, int e, float *D, int64_t *I);
+int hac_index_search_excluding_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const int64_t *excl_dev, int e,
+                                      float *D_dev, int64_t *I_dev, const int64_t *id_map_dev, void *hip_stream);
+
 /* index.reset() — src/test_HAConvDR_topiocqa.py:122.  Keeps allocations for reuse. */
 int hac_index_reset(hac_index *idx);
 /* index.ntotal */
@@ -230,6 +261,15 @@ int hac_merge_keys_device(int device, const uint64_t *lists_dev, int n_lists, in
 int hac_keys_to_results_device(int device, const uint64_t *keys_dev, int64_t n_keys,
                                const int64_t *id_map_dev, float *D_dev, int64_t *I_dev,
                                void *hip_stream);
+
+/* Per query, the first kout keys of a sorted list whose position is not excluded.  keys_dev: uint64 [nq, kin], every row sorted
+ * descending, 0 = empty slot (what hac_index_search_keys_device and hac_merge_keys_device write); excl_pos_dev: int64 [nq, e]
+ * GLOBAL positions, pos_base + row, the numbering the keys carry (may be NULL when e == 0) -- a value < 0 or > 0xFFFFFFFF is
+ * padding and matches nothing, duplicates are allowed; out_dev: uint64 [nq, kout], the surviving keys in their order, then 0.
+ * 1 <= kout <= kin <= HAC_MAX_K, 0 <= e < HAC_MAX_K, out_dev must not alias keys_dev (the row strides differ): otherwise
+ * HAC_ERR_INVALID.  One launch on hip_stream, no atomics: the output is a pure function of the inputs.  nq == 0 is HAC_OK. */
+int hac_filter_keys_device(int device, const uint64_t *keys_dev, int64_t nq, int kin, const int64_t *excl_pos_dev, int e, int kout,
+                           uint64_t *out_dev, void *hip_stream);
 
 /* ----------------------------------------------------------------- encoder */
 /* model(input_ids, attention_mask) -> float32 [B,768]: ANCE.forward, src/models.py:39-64
