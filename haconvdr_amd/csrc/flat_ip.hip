@@ -1134,6 +1134,7 @@ u32 next_pow2(u32 v) {
 }
 
 #include "scan_split.inc"
+#include "rank.inc"
 
 // Every instantiation of the two templated scan kernels, once: init raises each one's dynamic-LDS limit from these tables and
 // the launches look their kernel up in them, so an instantiation that is launched is one whose limit was raised.
@@ -1385,6 +1386,7 @@ struct DeviceIndex {
             for (const ScanqEntry &e : SCANQ_TABLE) HAC_HIP(hipFuncSetAttribute((const void *)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             HAC_HIP(hipFuncSetAttribute((const void *)sample_scores_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(64 * 1024)));
             for (const ScanhEntry &e : SCANH_TABLE) HAC_HIP(hipFuncSetAttribute((const void *)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
+            HAC_HIP(hipFuncSetAttribute((const void *)count_ahead_kernel<RANK_MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             attr_done[device] = true;
         }
         return HAC_OK;
@@ -1406,7 +1408,7 @@ struct DeviceIndex {
         for (PinBuf *b : {&h_pin, &h_fb, &h_stage[0], &h_stage[1]}) b->release();
         for (GrowBuf *b : {&ws_partial, &ws_pcnt, &ws_seedkeys, &ws_thr, &ws_thrglob, &ws_q, &ws_qt, &ws_keys, &ws_D, &ws_I, &ws_stage[0],
                            &ws_stage[1], &ws_err, &ws_norm, &ws_qsplit, &ws_delta, &ws_cand, &ws_akeys, &ws_fail, &ws_stat, &ws_fbidx[0], &ws_fbidx[1],
-                           &ws_fbq[0], &ws_fbq[1], &ws_fbkeys[0], &ws_fbkeys[1], &ws_ids})
+                           &ws_fbq[0], &ws_fbq[1], &ws_fbkeys[0], &ws_fbkeys[1], &ws_ids, &ws_rank})
             b->release();
         if (h_err) (void)hipHostFree(h_err);
         if (h_plan) (void)hipHostFree(h_plan);
@@ -1926,6 +1928,106 @@ struct DeviceIndex {
                             if (ir[j] != skip) Dr[j] = res[(size_t)i * mc + j];
                     }
                 }
+            }
+        }
+        return HAC_OK;
+    }
+
+    // ---- rank of named rows (rank.inc; hac_index_rank_ids*, hac_index_count_ahead_device): enqueue on `st` and return.
+    // Like the rows-by-id calls: nothing is read back and no slot of the status ring is taken; the only wait is the segment
+    // table's upload after an add / reset.  Unlike them these need a workspace (the counters and, for rank_ids, the
+    // reference scores: nq * m * 12 bytes), which grows by the rule of the search workspaces.
+    GrowBuf ws_rank;
+    static int check_rank_size(const char *what, int64_t nq, int64_t m) {
+        if (m > ((int64_t)1 << 40) / nq) return fail(HAC_ERR_UNSUPPORTED, "%s: %lld x %lld pairs in one call exceed the workspace", what, (long long)nq, (long long)m);
+        return HAC_OK;
+    }
+    u64 *rank_counters() const { return (u64 *)ws_rank.p; }
+    float *rank_scores(int64_t nq, int64_t m) const { return (float *)((u64 *)ws_rank.p + (size_t)nq * m); }
+    // out[i][j] = count_ahead(q[i], ref_score[i][j], ref_bound[i][j]) over this index's rows, or -1 (rank_finish_kernel)
+    int count_ahead_device(const char *what, const float *q_dev, int64_t nq, const float *ref_score_dev, const int64_t *ref_bound_dev, bool bounds_are_ids,
+                           int64_t m, int64_t *out_dev, hipStream_t st) {
+        if (nq == 0 || m == 0) return HAC_OK;
+        HAC_TRY(check_rank_size(what, nq, m));
+        HAC_TRY(check_out_ptr(q_dev, what));
+        HAC_TRY(ws_rank.reserve((size_t)nq * m * 12));
+        HAC_TRY(upload_segs(st));
+        HAC_HIP(hipMemsetAsync(rank_counters(), 0, (size_t)nq * m * 8, st));
+        const u32 G = (u32)((ntotal + GROUP_ROWS - 1) / GROUP_ROWS);
+        const int64_t chunks = (m + RANK_MT - 1) / RANK_MT;
+        // queries in chunks of QUERY_CHUNK, as the exact search takes them; grid.x as make_plan sizes scan16's for the same rows and queries
+        for (int64_t off = 0; off < nq && G > 0; off += QUERY_CHUNK) {
+            const int64_t n = std::min<int64_t>(QUERY_CHUNK, nq - off);
+            ScanArgs a = scan_args(q_dev + (size_t)off * d, n);
+            a.QT = (int)std::min<int64_t>(16, n);
+            a.n_items = G;
+            const int T = (int)((n + a.QT - 1) / a.QT);
+            const size_t lds = rank_lds(K4, a.QT, RANK_MT);
+            // resident workgroups per CU: LDS-limited like scan16's, and 3 by the kernel's registers (144 of 512 per SIMD, one wave of a workgroup each)
+            const int per_cu = std::max(1, std::min<int>((int)std::min<size_t>(LDS_LIMIT / lds, 32 / SCAN_WAVES), 3));
+            long P = std::max<long>(1, (long)n_cu * per_cu / T);
+            if (P >= 8 && !tune.no_p8) P = P / 8 * 8;
+            P = std::max<long>(1, std::min<long>(P, (G + SCAN_WAVES - 1) / SCAN_WAVES));
+            RankArgs ra{ref_score_dev + (size_t)off * m, (const long long *)ref_bound_dev + (size_t)off * m, rank_counters() + (size_t)off * m, (long)m, 0u};
+            for (int64_t c0 = 0; c0 < chunks; c0 += 65535) {
+                ra.chunk0 = (u32)c0;
+                const unsigned nz = (unsigned)std::min<int64_t>(65535, chunks - c0);
+                count_ahead_kernel<RANK_MT><<<dim3((unsigned)P, (unsigned)T, nz), dim3(SCAN_WAVES * 64), lds, st>>>(a, ra);
+                HAC_HIP(hipGetLastError());
+            }
+            snprintf(last_plan, sizeof last_plan, "count_ahead_kernel<MT=%d> grid=(%ld,%d) QT=%d chunks=%lld lds=%zu", RANK_MT, P, T, a.QT, (long long)chunks, lds);
+            plan_text_slot = -1;
+        }
+        const int64_t total = nq * m;
+        rank_finish_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(rank_counters(), ref_score_dev, (const long long *)ref_bound_dev, bounds_are_ids,
+                                                                                       (long)total, (long)ntotal, (long long *)out_dev);
+        HAC_HIP(hipGetLastError());
+        return HAC_OK;
+    }
+    // rank[i][j] = count_ahead(q[i], score_ids(q[i], ids[i][j]), ids[i][j]): score_ids_kernel into the workspace, the counters, the finish
+    int rank_ids_device(const float *q_dev, int64_t nq, const int64_t *ids_dev, int64_t m, int64_t *rank_dev, hipStream_t st) {
+        if (nq == 0 || m == 0) return HAC_OK;
+        HAC_TRY(check_rank_size("rank_ids", nq, m));
+        HAC_TRY(ws_rank.reserve((size_t)nq * m * 12));
+        HAC_TRY(score_ids_device(q_dev, nq, ids_dev, m, rank_scores(nq, m), st));
+        return count_ahead_device("rank_ids", q_dev, nq, rank_scores(nq, m), ids_dev, true, m, rank_dev, st);
+    }
+    // Host form over this shard's rows, synchronous, on the index's own stream, staged like score_ids_host.  ref_score == null:
+    // rank_ids (ids: local row ids, -1 = padding); otherwise count_ahead with ids as the bounds (what a shard of a multi-device
+    // index is asked: the scores come from the shard that owns the row).
+    int rank_host(const float *q, int64_t nq, const int64_t *ids, const float *ref_score, int64_t m, int64_t *out) {
+        if (nq == 0 || m == 0) return HAC_OK;
+        DeviceGuard g(device);
+        if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", device);
+        const size_t budget = (size_t)64 << 20;
+        const int64_t MC = std::min<int64_t>(m, 1 << 20);
+        const int64_t QC = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(budget / ((size_t)MC * 20 + (size_t)d * 4))));
+        const size_t qb = (size_t)QC * d * 4, ib = (size_t)QC * MC * 8, sb = (size_t)QC * MC * 4, ob = (size_t)QC * MC * 8;
+        HAC_TRY(ws_q.reserve(qb));
+        HAC_TRY(ws_ids.reserve(ib));
+        HAC_TRY(ws_D.reserve(sb));
+        HAC_TRY(ws_I.reserve(ob));
+        HAC_TRY(pin_reserve(qb + ib + ob + sb));
+        HAC_HIP(hipStreamSynchronize(stream));
+        char *hq = static_cast<char *>(h_pin.p), *hi = hq + qb, *ho = hi + ib, *hs = ho + ob;
+        for (int64_t q0 = 0; q0 < nq; q0 += QC) {
+            const int64_t nqc = std::min(QC, nq - q0);
+            std::memcpy(hq, q + (size_t)q0 * d, (size_t)nqc * d * 4);
+            HAC_HIP(hipMemcpyAsync(ws_q.p, hq, (size_t)nqc * d * 4, hipMemcpyHostToDevice, stream));
+            for (int64_t j0 = 0; j0 < m; j0 += MC) {
+                const int64_t mc = std::min(MC, m - j0);
+                for (int64_t i = 0; i < nqc; ++i) std::memcpy(hi + (size_t)i * mc * 8, ids + (size_t)(q0 + i) * m + j0, (size_t)mc * 8);
+                HAC_HIP(hipMemcpyAsync(ws_ids.p, hi, (size_t)nqc * mc * 8, hipMemcpyHostToDevice, stream));
+                if (ref_score) {
+                    for (int64_t i = 0; i < nqc; ++i) std::memcpy(hs + (size_t)i * mc * 4, ref_score + (size_t)(q0 + i) * m + j0, (size_t)mc * 4);
+                    HAC_HIP(hipMemcpyAsync(ws_D.p, hs, (size_t)nqc * mc * 4, hipMemcpyHostToDevice, stream));
+                    HAC_TRY(count_ahead_device("count_ahead", (const float *)ws_q.p, nqc, (const float *)ws_D.p, (const int64_t *)ws_ids.p, false, mc, (int64_t *)ws_I.p, stream));
+                } else {
+                    HAC_TRY(rank_ids_device((const float *)ws_q.p, nqc, (const int64_t *)ws_ids.p, mc, (int64_t *)ws_I.p, stream));
+                }
+                HAC_HIP(hipMemcpyAsync(ho, ws_I.p, (size_t)nqc * mc * 8, hipMemcpyDeviceToHost, stream));
+                HAC_HIP(hipStreamSynchronize(stream));
+                for (int64_t i = 0; i < nqc; ++i) std::memcpy(out + (size_t)(q0 + i) * m + j0, ho + (size_t)i * mc * 8, (size_t)mc * 8);
             }
         }
         return HAC_OK;
@@ -3080,6 +3182,62 @@ int hac_index_score_ids_device(hac_index *idx, const float *q_dev, int64_t nq, c
     if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q_dev || !ids_dev || !D_dev))) return fail(HAC_ERR_INVALID, "score_ids_device: bad arguments");
     DeviceGuard g(s->device);
     return s->score_ids_device(q_dev, nq, ids_dev, m, D_dev, (hipStream_t)hip_stream);
+}
+
+// ---- rank of named rows ------------------------------------------------------------------------------------------------
+int hac_index_count_ahead_device(hac_index *idx, const float *q_dev, int64_t nq, const float *ref_score_dev, const int64_t *ref_bound_dev, int64_t m,
+                                 int64_t *count_dev, void *hip_stream) {
+    DeviceIndex *s = nullptr;
+    HAC_TRY(single_shard(idx, "count_ahead_device", s));
+    if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q_dev || !ref_score_dev || !ref_bound_dev || !count_dev))) return fail(HAC_ERR_INVALID, "count_ahead_device: bad arguments");
+    DeviceGuard g(s->device);
+    return s->count_ahead_device("count_ahead_device", q_dev, nq, ref_score_dev, ref_bound_dev, false, m, count_dev, (hipStream_t)hip_stream);
+}
+
+int hac_index_rank_ids_device(hac_index *idx, const float *q_dev, int64_t nq, const int64_t *ids_dev, int64_t m, int64_t *rank_dev, void *hip_stream) {
+    DeviceIndex *s = nullptr;
+    HAC_TRY(single_shard(idx, "rank_ids_device", s));
+    if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q_dev || !ids_dev || !rank_dev))) return fail(HAC_ERR_INVALID, "rank_ids_device: bad arguments");
+    DeviceGuard g(s->device);
+    return s->rank_ids_device(q_dev, nq, ids_dev, m, rank_dev, (hipStream_t)hip_stream);
+}
+
+int hac_index_rank_ids(hac_index *idx, const float *q, int64_t nq, const int64_t *ids, int64_t m, int64_t *rank) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q || !ids || !rank))) return fail(HAC_ERR_INVALID, "rank_ids: bad arguments");
+    if (nq == 0 || m == 0) return HAC_OK;
+    if (check_host_ids("rank_ids", ids, nq * m, idx->ntotal) != HAC_OK) {   // (the message again, with the id's place in the [nq, m] matrix)
+        for (int64_t i = 0; i < nq * m; ++i)
+            if (ids[i] < -1 || ids[i] >= idx->ntotal)
+                return fail(HAC_ERR_INVALID, "rank_ids: id %lld at (query %lld, column %lld) is outside [0, %lld) (-1 = a padding slot)", (long long)ids[i],
+                            (long long)(i / m), (long long)(i % m), (long long)idx->ntotal);
+    }
+    const int S = (int)idx->shards.size();
+    if (S == 1) return idx->shards[0]->rank_host(q, nq, ids, nullptr, m, rank);
+    // Several devices.  The reference scores come from the shard that owns the row (the multi-shard score_ids path); every shard
+    // then counts its own rows ahead of (score, bound), the bound translated into its numbering: b_s(id) = the number of the
+    // shard's rows with a global id below id, summed over its spans.  A shard's local order preserves the global order, so a tie
+    // still breaks by global row; the counts of the shards add up.
+    const size_t total = (size_t)(nq * m);
+    std::vector<float> scores(total);
+    HAC_TRY(hac_index_score_ids(idx, q, nq, ids, m, scores.data()));
+    std::vector<std::vector<int64_t>> bounds(S, std::vector<int64_t>(total)), part(S, std::vector<int64_t>(total));
+    for (int si = 0; si < S; ++si)
+        for (size_t i = 0; i < total; ++i) {
+            int64_t b = -1;
+            if (ids[i] >= 0) {
+                b = 0;
+                for (const SpanDesc &sp : idx->spans[si]) b += std::min<int64_t>(std::max<int64_t>(ids[i] - (int64_t)sp.global0, 0), (int64_t)sp.count);
+            }
+            bounds[si][i] = b;
+        }
+    HAC_TRY(for_each_shard(idx, [&](int si) { return idx->shards[si]->rank_host(q, nq, bounds[si].data(), scores.data(), m, part[si].data()); }));
+    for (size_t i = 0; i < total; ++i) {
+        int64_t sum = 0;
+        for (int si = 0; si < S; ++si) sum = (sum < 0 || part[si][i] < 0) ? -1 : sum + part[si][i];   // (-1: padding or a NaN score, on every shard alike)
+        rank[i] = sum;
+    }
+    return HAC_OK;
 }
 
 int hac_index_last_status(hac_index *idx) {

@@ -104,6 +104,40 @@ def _score_args_tensor(q, ids, d):
     return q, ids
 
 
+def _rank_args(q, ids, d):
+    """(q float32 [nq, d], ids int64 [nq, m]) of rank_ids."""
+    q = _as_queries(q, d, "rank_ids")
+    ids = _as_ids(ids, 2, "rank_ids")
+    if ids.shape[0] != q.shape[0]:
+        raise ValueError(f"rank_ids: {q.shape[0]} queries but ids of shape {ids.shape} (one list per query)")
+    return q, ids
+
+
+def _rank_args_tensor(q, ids, d, what="rank_ids_tensor"):
+    q = _queries_tensor(q, d, what)
+    ids = _ids_tensor(ids, 2, what)
+    if ids.shape[0] != q.shape[0]:
+        raise ValueError(f"{what}: {q.shape[0]} queries but ids of shape {tuple(ids.shape)} (one list per query)")
+    if ids.device != q.device:
+        raise ValueError(f"{what}: q on {q.device} but ids on {ids.device}")
+    return q, ids
+
+
+def _count_args_tensor(q, ref_scores, ref_bounds, d, what="count_ahead_tensor"):
+    """(q float32 CUDA [nq, d], ref_scores float32 CUDA [nq, m], ref_bounds int64 CUDA [nq, m]) of count_ahead_tensor."""
+    import torch
+    q, ref_bounds = _rank_args_tensor(q, ref_bounds, d, what)
+    if not isinstance(ref_scores, torch.Tensor) or not ref_scores.is_cuda:
+        raise ValueError(f"{what}: ref_scores must be a CUDA tensor")
+    if ref_scores.dtype != torch.float32:
+        raise ValueError(f"{what}: ref_scores must be float32 (the bits a search returns), got {ref_scores.dtype}")
+    if tuple(ref_scores.shape) != tuple(ref_bounds.shape):
+        raise ValueError(f"{what}: ref_scores of shape {tuple(ref_scores.shape)} but ref_bounds of shape {tuple(ref_bounds.shape)}")
+    if ref_scores.device != q.device:
+        raise ValueError(f"{what}: q on {q.device} but ref_scores on {ref_scores.device}")
+    return q, ref_scores.contiguous(), ref_bounds
+
+
 def _check_exclude_shape(nq, k, shape, what):
     if shape[0] != nq:
         raise ValueError(f"{what}: {nq} queries but exclude of shape {tuple(shape)} (one list per query)")
@@ -247,6 +281,18 @@ class FlatIPIndex:
                                                   D.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
         return D
 
+    def rank_ids(self, q, ids):
+        """Exact corpus rank of named rows: q float32 [nq, d], ids int64 [nq, m] -> int64 [nq, m], the 0-based position row
+        ids[i, j] takes in an unbounded search of q[i] (order: score desc, row asc) -- no ceiling at HAC_MAX_K, and
+        rank_ids(q, I)[i, j] == j for the I of any search.  -1 for the id -1 and for a row whose score is NaN (no search
+        returns it); any other id outside [0, ntotal) raises HacError.  One pass over the rows per (16 queries, 8 ids)."""
+        q, ids = _rank_args(q, ids, self.d)
+        R = np.empty(ids.shape, np.int64)
+        _lib.check(_lib.lib().hac_index_rank_ids(self._h, q.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), q.shape[0],
+                                                 ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ids.shape[1],
+                                                 R.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return R
+
     # ---- device-resident variants (torch tensors on the index's GPU) -------
     def add_tensor(self, x, stream=None):
         """x: torch float32 CUDA tensor [n, d], contiguous.  Enqueued on ``stream`` (default: torch's current
@@ -334,6 +380,33 @@ class FlatIPIndex:
         for t in (q, ids, D):
             _keep_alive(t, stream)
         return D
+
+    def rank_ids_tensor(self, q, ids, stream=None):
+        """q: float32 CUDA [nq, d], ids: int64 CUDA [nq, m] -> int64 CUDA [nq, m], rank_ids without a host sync.  Any id outside
+        [0, ntotal), -1 included, ranks -1.  Capturable after one call of the largest (nq, m)."""
+        import torch
+        q, ids = _rank_args_tensor(q, ids, self.d)
+        R = torch.empty(tuple(ids.shape), dtype=torch.int64, device=q.device)
+        _lib.check(_lib.lib().hac_index_rank_ids_device(self._h, ctypes.c_void_p(q.data_ptr()), q.shape[0], ctypes.c_void_p(ids.data_ptr()),
+                                                        ids.shape[1], ctypes.c_void_p(R.data_ptr()), _stream_ptr(stream)))
+        for t in (q, ids, R):
+            _keep_alive(t, stream)
+        return R
+
+    def count_ahead_tensor(self, q, ref_scores, ref_bounds, stream=None):
+        """The primitive behind rank_ids, the one corpus shards add up: per (query i, slot j) the number of this index's rows r
+        whose score is not NaN and beats (ref_scores[i, j], ref_bounds[i, j]): s > s_ref, or s == s_ref and r < bound.
+        q float32 CUDA [nq, d], ref_scores float32 CUDA [nq, m], ref_bounds int64 CUDA [nq, m] -> int64 CUDA [nq, m]; -1 for a
+        NaN reference score or a negative bound; a bound above ntotal behaves like ntotal.  No host sync."""
+        import torch
+        q, ref_scores, ref_bounds = _count_args_tensor(q, ref_scores, ref_bounds, self.d)
+        C = torch.empty(tuple(ref_bounds.shape), dtype=torch.int64, device=q.device)
+        _lib.check(_lib.lib().hac_index_count_ahead_device(self._h, ctypes.c_void_p(q.data_ptr()), q.shape[0], ctypes.c_void_p(ref_scores.data_ptr()),
+                                                           ctypes.c_void_p(ref_bounds.data_ptr()), ref_bounds.shape[1],
+                                                           ctypes.c_void_p(C.data_ptr()), _stream_ptr(stream)))
+        for t in (q, ref_scores, ref_bounds, C):
+            _keep_alive(t, stream)
+        return C
 
     def search_and_reconstruct_tensor(self, q, k, stream=None):
         """search_tensor, then reconstruct_tensor on its I, on one stream -> (D [nq,k], I [nq,k], R [nq,k,d])."""

@@ -241,6 +241,19 @@ class ResidentCorpus:
             raise ValueError(f"score: passage_ids must be [nq, m], got shape {pid.shape}")
         return self.index.score_ids(q, self.rows_of(pid)).astype(np.float64)
 
+    def rank(self, query_embeddings, passage_ids):
+        """Exact corpus rank of named passages: query_embeddings float32 [nq,768], passage_ids int64 [nq,m] EXTERNAL ids ->
+        int64 [nq,m], the 0-based position search() of unbounded depth would give the passage's row; -1 where no block holds
+        the id (or the row's score is NaN).  The rank is over ROWS, not over de-duplicated passage ids: an id several rows
+        carry resolves to the first of them (rows_of), and the other rows that carry it count as rows in front or behind like
+        any other -- the TREC writer's per-query de-duplication (trec.output_test_res) is not applied."""
+        import torch
+        q = query_embeddings.cpu().numpy() if isinstance(query_embeddings, torch.Tensor) else query_embeddings
+        pid = np.asarray(passage_ids)
+        if pid.ndim != 2:
+            raise ValueError(f"rank: passage_ids must be [nq, m], got shape {pid.shape}")
+        return self.index.rank_ids(q, self.rows_of(pid))
+
     def reconstruct(self, passage_ids):
         """passage_ids int64 [n] -> float32 [n,768], the embeddings as the blocks hold them (all-ones words for an absent id)."""
         return self.index.reconstruct_batch(self.rows_of(passage_ids))

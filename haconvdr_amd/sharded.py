@@ -27,8 +27,11 @@ class ShardedSearcher:
     merge(lists [R, nq, k])    -> [nq, k]                              (default: HIP merge kernel)
     to_results(keys, id_map)   -> (D, I)                               (default: HIP kernel)
     filter(keys [nq, k + e], exclude [nq, e], k) -> [nq, k]            (default: HIP filter kernel)
-    The four hooks exist so that the distributed plumbing can be exercised on CPU with
+    local_scores(q, local_ids [nq, m]) -> float32 [nq, m]              (default: index.score_ids_tensor)
+    count_ahead(q, ref_scores, ref_bounds [nq, m]) -> int64 [nq, m]    (default: index.count_ahead_tensor)
+    The six hooks exist so that the distributed plumbing can be exercised on CPU with
     gloo and a test double; the product path always uses the HIP defaults.
+    n_local: rows this rank holds (default: index.ntotal when rank() is called).
 
     exclude (optional, int64 [nq, e], on the keys' device): per query, GLOBAL positions (shard_base + local row) that must
     not be returned, identical on every rank; < 0 is padding.  Every rank then searches k + e, the all-gather and the merge
@@ -36,7 +39,8 @@ class ShardedSearcher:
     of the corpus, in the same order.  exclude=None is the path above, unchanged; the filter hook is not called.
     """
 
-    def __init__(self, index, shard_base, group=None, id_map=None, local_keys=None, merge=None, to_results=None, filter=None):
+    def __init__(self, index, shard_base, group=None, id_map=None, local_keys=None, merge=None, to_results=None, filter=None,
+                 local_scores=None, count_ahead=None, n_local=None):
         from . import index as _index
         self.index = index
         self.shard_base = int(shard_base)
@@ -46,6 +50,9 @@ class ShardedSearcher:
         self._merge = merge or _index.merge_keys
         self._to_results = to_results or _index.keys_to_results
         self._filter = filter or _index.filter_keys
+        self._local_scores = local_scores or (lambda q, ids: index.score_ids_tensor(q, ids))
+        self._count_ahead = count_ahead or (lambda q, s, b: index.count_ahead_tensor(q, s, b))
+        self._n_local = n_local
 
     def search_keys(self, q, k, exclude=None):
         if exclude is not None:
@@ -63,3 +70,39 @@ class ShardedSearcher:
 
     def search(self, q, k, exclude=None):
         return self._to_results(self.search_keys(q, k, exclude), self.id_map)
+
+    def rank(self, q, ids):
+        """Exact rank of named rows over the whole sharded corpus: ids int64 [nq, m] GLOBAL positions (shard_base + local row),
+        identical on every rank, < 0 is padding -> int64 [nq, m] on every rank, the 0-based position the row takes in an unbounded
+        search of q[i]; -1 for padding, a position no rank holds, and a row whose score is NaN.
+
+        The rank that holds a row scores it (every other rank contributes -inf) and one all_reduce(MAX) hands the score to
+        everyone; next to it travels a flag word (1 = somebody holds the row, 3 = and its score is NaN: a NaN does not survive a
+        MAX reliably, so it goes through as a flag and the score as -inf).  Every rank then counts its own rows ahead of (score,
+        clamp(id - shard_base, 0, n_local)) -- a shard's local order is the global order, so score ties still break by global
+        position -- and one all_reduce(SUM) adds the counts.  Two collectives of [nq, m] words, no rows moved."""
+        if ids.dim() != 2 or ids.shape[0] != q.shape[0]:
+            raise ValueError(f"ids must be [nq, m] with nq = {q.shape[0]}, got shape {tuple(ids.shape)}")
+        if ids.dtype != torch.int64:
+            raise ValueError(f"ids must be int64, got {ids.dtype}")
+        n_local = int(self.index.ntotal if self._n_local is None else self._n_local)
+        local = ids - self.shard_base
+        mine = (ids >= 0) & (local >= 0) & (local < n_local)
+        neg_inf = float("-inf")
+        if ids.numel() == 0:
+            return torch.empty_like(ids)
+        s = self._local_scores(q, torch.where(mine, local, torch.full_like(local, -1)))
+        nan = mine & torch.isnan(s)
+        score = torch.where(mine & ~nan, s, torch.full_like(s, neg_inf))
+        flags = mine.to(torch.int32) + 2 * nan.to(torch.int32)
+        distributed = dist.is_initialized()
+        if distributed:
+            dist.all_reduce(score, op=dist.ReduceOp.MAX, group=self.group)
+            dist.all_reduce(flags, op=dist.ReduceOp.MAX, group=self.group)      # (at most one rank holds a row: MAX is that rank's word)
+        ranked = flags == 1
+        score = torch.where(flags == 3, torch.full_like(score, float("nan")), score)
+        counts = self._count_ahead(q, score.contiguous(), local.clamp(0, n_local).contiguous())
+        counts = torch.where(ranked, counts, torch.zeros_like(counts))
+        if distributed:
+            dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.group)
+        return torch.where(ranked, counts, torch.full_like(counts, -1))

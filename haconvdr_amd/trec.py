@@ -116,6 +116,38 @@ def print_trec_res(run_file, qrel_file, rel_threshold=1):
     return res
 
 
+def metrics_from_ranks(ranks, ks=(10, 100), cutoff=None):
+    """MRR and Recall@k straight from exact ranks (FlatIPIndex.rank_ids, ResidentCorpus.rank, ShardedSearcher.rank): no run
+    file, no top-N list, and a gold passage beyond the list is a rank like any other.  ranks: int64 [nq, m], row i the
+    0-based ranks of query i's relevant passages, -1 = padding or an unranked passage.  Same units as print_trec_res: percent,
+    rounded to 5 places, averaged over the queries.  recip_rank = 1 / (1 + the best rank), 0 if none is ranked; recall_k =
+    passages with rank < k / the row's relevant passages, which are the slots that are not -1 (a -1 slot is never counted as
+    relevant: a judged passage the corpus does not hold has to be counted by the caller).  cutoff=N treats ranks >= N as
+    unranked -- they still count as relevant -- which reproduces the figures of a run file written at top_n = N.  A query
+    without any relevant slot scores 0, as in print_trec_res.
+    Returns {"MRR", "Recall@<k>" for k in ks}.  Not here: NDCG (needs the graded gains) and a mirror of the reference's
+    improve_judge (test_PRJ_*.py), which compares exactly these reciprocal ranks between two query forms."""
+    r = np.asarray(ranks)
+    if r.dtype.kind not in "iu" or r.ndim != 2:
+        raise ValueError(f"metrics_from_ranks: ranks must be an integer [nq, m] array, got {r.dtype} {r.shape}")
+    r = r.astype(np.int64)
+    relevant = r >= 0
+    found = relevant if cutoff is None else relevant & (r < int(cutoff))
+    n_rel = relevant.sum(axis=1)
+    nq = r.shape[0]
+
+    def avg(v):                                                # (print_trec_res's own arithmetic: python floats, summed in query order)
+        v = [float(t) for t in v]
+        return round(sum(v) / len(v) * 100, 5) if v else 0.0
+    best = np.where(found, r, np.iinfo(np.int64).max).min(axis=1) if r.shape[1] else np.full(nq, np.iinfo(np.int64).max)
+    has = found.any(axis=1) if r.shape[1] else np.zeros(nq, bool)
+    res = {"MRR": avg(np.where(has, 1.0 / (np.where(has, best, 0) + 1.0), 0.0))}
+    for k in ks:
+        hit = (found & (r < int(k))).sum(axis=1)
+        res[f"Recall@{int(k)}"] = avg(np.where(n_rel > 0, hit / np.maximum(n_rel, 1), 0.0))
+    return res
+
+
 def gen_metric_score_and_save(args, index, query_embeddings, query_embedding2id, evaluate=None):
     """Mirror of gen_metric_score_and_save(args, index, Q, ids) (:355-372)."""
     from .search import search_one_by_one

@@ -193,8 +193,9 @@ int64_t hac_index_ntotal(const hac_index *idx);
  * most once, for the segment-table upload that the first search after an add / reset also does, and can be captured into
  * a HIP graph once that table is up (run one call outside the capture first).
  *
- * Out of scope: haconvdr_amd.sharded.ShardedSearcher (one process per GPU: reading a row another rank holds would need a
- * collective); faiss's range_search and remove_ids; and nothing here changes how search routes or what it returns. */
+ * Out of scope: reconstruct through haconvdr_amd.sharded.ShardedSearcher (one process per GPU: reading a row another rank
+ * holds would need a collective; its rank() below needs only two all-reduces of [nq, m] words); faiss's range_search and
+ * remove_ids; and nothing here changes how search routes or what it returns. */
 /* index.reconstruct_n(i0, n): host float32 [n, d]. */
 int hac_index_reconstruct(hac_index *idx, int64_t i0, int64_t n, float *out);
 /* index.reconstruct(i) / index.reconstruct_batch(ids): ids host int64 [n]; out host float32 [n, d]. */
@@ -207,6 +208,44 @@ int hac_index_reconstruct_device(hac_index *idx, const int64_t *ids_dev, int64_t
 int hac_index_score_ids(hac_index *idx, const float *q, int64_t nq, const int64_t *ids, int64_t m, float *D);
 int hac_index_score_ids_device(hac_index *idx, const float *q_dev, int64_t nq, const int64_t *ids_dev, int64_t m, float *D_dev,
                                void *hip_stream);
+
+/* ---- rank of named rows: at what position does the WHOLE corpus put this row for this query? ---------------------------
+ * Every other question the index answers is bounded by HAC_MAX_K; this one is not.  One definition, for a query q, a
+ * reference score s_ref and a bound b (an int64 row number in the numbering of the rows being counted):
+ *   count_ahead(q, s_ref, b) = #{ rows r in [0, ntotal) : s(q, r) is not NaN and (s(q, r) > s_ref or (s(q, r) == s_ref and r < b)) }
+ * with s the canonical score above (the k-ordered fmaf chain and the "+ 0.0f" of a packed key) and float comparisons: -0.0
+ * == +0.0, +-Inf are ordinary scores.  That is "key(s, r) > key(s_ref, b)" over the rows a search can return.  A NaN s_ref
+ * gives -1, a b below 0 gives -1, a b above ntotal behaves like ntotal.
+ *   rank_ids(q, ids)[i][j] = count_ahead(q[i], score_ids(q[i], ids[i][j]), ids[i][j])
+ * is the 0-based position row ids[i][j] takes in an unbounded search of q[i]: for D, I = search(q, k) on any route,
+ * rank_ids(q, I)[i][j] == j wherever I[i][j] >= 0.  It is -1 for the id -1 and for a row whose own score is NaN (no search
+ * ever returns it).  Ids outside [0, ntotal) follow the rows-by-id rule: *_device entry points give -1 and no error, the
+ * host entry point ignores -1 and returns HAC_ERR_INVALID for any other, naming the first offending id and its (query, column).
+ *
+ * How: score_ids gives the reference; count_ahead_kernel (csrc/rank.inc) then streams the rows once in the shape of
+ * scan16_kernel -- same tiles, same bit-exact MFMA chain -- and counts in its epilogue; integer sums, no candidate lists,
+ * no thresholds, so no pass bound and nothing for the status word; the result is a pure function of the inputs.  Rows behind
+ * ntotal (zeros, or stale rows after reset() and a smaller add()) and NaN scores never count.
+ * Cost: the corpus is read once per (tile of 16 queries, chunk of 8 references): ceil(nq / 16) * ceil(m / 8) passes at the
+ * exact scan's stream rate, whatever the ranks turn out to be.  Typical m is 1..4 (a query's gold passages): one pass per 16
+ * queries.  A GEMM-shaped many-query form (scanq's query staging) does not exist yet.  Nothing here changes how search routes
+ * or what it returns.
+ *
+ * *_device entry points: single-device index (HAC_ERR_UNSUPPORTED otherwise), 16-byte aligned q_dev; they enqueue on
+ * hip_stream, never read back and take no slot of the status ring.  Their workspace (counters and reference scores, nq * m * 12
+ * bytes) grows by the rule of the search workspaces: run one call of the largest (nq, m) before capturing into a HIP graph.
+ * nq == 0 or m == 0 is HAC_OK and touches nothing.  hac_index_last_plan afterwards reads
+ * "count_ahead_kernel<MT=8> grid=(P,T) QT=.. chunks=.. lds=..".
+ * count_ahead is the primitive shards add up: ref_score_dev float32 [nq, m], ref_bound_dev int64 [nq, m], count_dev int64
+ * [nq, m] over THIS index's rows (haconvdr_amd.sharded: the owner's score, bounds clamp(id - shard_base, 0, n_local), a sum).
+ * Host rank_ids: synchronous, on the index's own stream, staged in chunks like score_ids; on a multi-device index the scores
+ * come from the shard that owns the row, every shard counts its rows on a host thread of its own ahead of (score, the bound
+ * translated into its numbering) and the host adds the counts. */
+int hac_index_count_ahead_device(hac_index *idx, const float *q_dev, int64_t nq, const float *ref_score_dev, const int64_t *ref_bound_dev,
+                                 int64_t m, int64_t *count_dev, void *hip_stream);
+int hac_index_rank_ids(hac_index *idx, const float *q, int64_t nq, const int64_t *ids, int64_t m, int64_t *rank);
+int hac_index_rank_ids_device(hac_index *idx, const float *q_dev, int64_t nq, const int64_t *ids_dev, int64_t m, int64_t *rank_dev,
+                              void *hip_stream);
 
 /* Device-detected failures of searches enqueued so far (the host entry points report them themselves; the *_device entry
  * points cannot, they never read back).  Waits for the index's own streams only: synchronize YOUR stream first, then call
