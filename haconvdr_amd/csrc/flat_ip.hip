@@ -31,6 +31,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <numeric>
 #include <thread>
 #include <vector>
 
@@ -1812,226 +1813,7 @@ struct DeviceIndex {
     }
     int nseg_live = 0;
 
-    // ---- rows by id (hac_index_reconstruct* / hac_index_score_ids*): enqueue on `st` and return.  The only wait is the
-    // segment table's upload after an add / reset / a changed image, which the first search pays too; nothing is allocated,
-    // read back or written to the status ring, so once the table is up these calls can be captured into a graph.
-    static int check_out_ptr(const void *p, const char *what) {
-        if (((uintptr_t)p & 15) != 0) return fail(HAC_ERR_INVALID, "%s: device pointer must be 16-byte aligned", what);
-        return HAC_OK;
-    }
-    int rows_range_device(int64_t i0, int64_t n, float *out_dev, hipStream_t st) {
-        if (i0 < 0 || n < 0 || i0 > ntotal || n > ntotal - i0)
-            return fail(HAC_ERR_INVALID, "reconstruct: rows [%lld, %lld + %lld) are not inside [0, %lld]", (long long)i0, (long long)i0, (long long)n, (long long)ntotal);
-        if (n == 0) return HAC_OK;
-        HAC_TRY(check_out_ptr(out_dev, "reconstruct"));
-        HAC_TRY(upload_segs(st));
-        const long g_lo = (long)(i0 / GROUP_ROWS), g_hi = (long)((i0 + n + GROUP_ROWS - 1) / GROUP_ROWS);
-        untile_range_kernel<<<dim3((unsigned)(g_hi - g_lo)), dim3(256), 0, st>>>(d_segs, nseg_live, (long)i0, (long)n, K4, reinterpret_cast<f4 *>(out_dev));
-        HAC_HIP(hipGetLastError());
-        return HAC_OK;
-    }
-    int rows_ids_device(const int64_t *ids_dev, int64_t n, float *out_dev, hipStream_t st) {
-        if (n == 0) return HAC_OK;
-        if (n > (int64_t)0x7FFFFFFF * (4 * ROWS_PER_WAVE)) return fail(HAC_ERR_UNSUPPORTED, "reconstruct: %lld ids in one call exceed the grid", (long long)n);
-        HAC_TRY(check_out_ptr(out_dev, "reconstruct"));
-        HAC_TRY(upload_segs(st));
-        const int64_t per_wg = 4 * ROWS_PER_WAVE;
-        rows_by_id_kernel<<<dim3((unsigned)((n + per_wg - 1) / per_wg)), dim3(256), 0, st>>>(d_segs, d_rimg, nseg_live, (const long long *)ids_dev, (long)n,
-                                                                                           (long)ntotal, K4, reinterpret_cast<f4 *>(out_dev));
-        HAC_HIP(hipGetLastError());
-        return HAC_OK;
-    }
-    int score_ids_device(const float *q_dev, int64_t nq, const int64_t *ids_dev, int64_t m, float *D_dev, hipStream_t st) {
-        if (nq == 0 || m == 0) return HAC_OK;
-        const int64_t bpq = (m + 255) / 256;
-        if (bpq > 0x7FFFFFFF / nq) return fail(HAC_ERR_UNSUPPORTED, "score_ids: %lld x %lld pairs in one call exceed the grid", (long long)nq, (long long)m);
-        HAC_TRY(check_out_ptr(q_dev, "score_ids"));
-        HAC_TRY(upload_segs(st));
-        score_ids_kernel<<<dim3((unsigned)(nq * bpq)), dim3(256), 0, st>>>(d_segs, d_rimg, nseg_live, q_dev, (const long long *)ids_dev, (long)m, (u32)bpq,
-                                                                          (long)ntotal, K4, D_dev);
-        HAC_HIP(hipGetLastError());
-        return HAC_OK;
-    }
-
-    // Host forms over this shard's rows, synchronous, on the index's own stream, staged through the add's 64-MiB buffers in
-    // chunks (the whole of a 25M-row index is 77 GB: it never exists on the device a second time).
-    // ids != null: out row pos[i] (or i) = row ids[i], local numbering, < 0 = all-ones; ids == null: the rows [i0, i0 + n).
-    GrowBuf ws_ids;
-    int read_rows_host(const int64_t *ids, const int64_t *pos, int64_t i0, int64_t n, float *out) {
-        if (n == 0) return HAC_OK;
-        DeviceGuard g(device);
-        if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", device);
-        const int64_t chunk_rows = stage_rows();
-        const size_t row_bytes = (size_t)d * 4;
-        HAC_TRY(stage_reserve());
-        if (ids) {
-            HAC_TRY(ws_ids.reserve((size_t)std::min(chunk_rows, n) * 8));
-            HAC_TRY(pin_reserve((size_t)std::min(chunk_rows, n) * 8));
-        }
-        HAC_HIP(hipStreamSynchronize(stream));
-        for (int64_t done = 0; done < n; done += chunk_rows) {
-            const int64_t m = std::min(chunk_rows, n - done);
-            if (ids) {
-                std::memcpy(h_pin.p, ids + done, (size_t)m * 8);
-                HAC_HIP(hipMemcpyAsync(ws_ids.p, h_pin.p, (size_t)m * 8, hipMemcpyHostToDevice, stream));
-                HAC_TRY(rows_ids_device((const int64_t *)ws_ids.p, m, (float *)ws_stage[0].p, stream));
-            } else {
-                HAC_TRY(rows_range_device(i0 + done, m, (float *)ws_stage[0].p, stream));
-            }
-            HAC_HIP(hipMemcpyAsync(h_stage[0].p, ws_stage[0].p, (size_t)m * row_bytes, hipMemcpyDeviceToHost, stream));
-            HAC_HIP(hipStreamSynchronize(stream));
-            const char *src = static_cast<const char *>(h_stage[0].p);
-            if (pos) {
-                for (int64_t i = 0; i < m; ++i) std::memcpy(out + (size_t)pos[done + i] * d, src + (size_t)i * row_bytes, row_bytes);
-            } else {
-                std::memcpy(out + (size_t)done * d, src, (size_t)m * row_bytes);
-            }
-        }
-        return HAC_OK;
-    }
-    // D[i][j] = score(q[i], row ids[i][j]) for the pairs this shard owns: local ids, -1 = a padding slot (-FLT_MAX), with
-    // `skip` (several devices) ids == skip name another shard's rows and leave D[i][j] alone.  Chunked over queries and, for
-    // very long lists, over j, so that one chunk's queries, ids and scores fit ~64 MiB.
-    int score_ids_host(const float *q, int64_t nq, const int64_t *ids, int64_t m, float *D, bool has_skip, int64_t skip) {
-        if (nq == 0 || m == 0) return HAC_OK;
-        DeviceGuard g(device);
-        if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", device);
-        const size_t budget = (size_t)64 << 20;
-        const int64_t MC = std::min<int64_t>(m, 1 << 20);
-        const int64_t QC = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(budget / ((size_t)MC * 12 + (size_t)d * 4))));
-        const size_t qb = (size_t)QC * d * 4, ib = (size_t)QC * MC * 8, db = (size_t)QC * MC * 4;
-        HAC_TRY(ws_q.reserve(qb));
-        HAC_TRY(ws_ids.reserve(ib));
-        HAC_TRY(ws_D.reserve(db));
-        HAC_TRY(pin_reserve(qb + ib + db));
-        HAC_HIP(hipStreamSynchronize(stream));
-        char *hq = static_cast<char *>(h_pin.p), *hi = hq + qb, *hd = hi + ib;
-        for (int64_t q0 = 0; q0 < nq; q0 += QC) {
-            const int64_t nqc = std::min(QC, nq - q0);
-            std::memcpy(hq, q + (size_t)q0 * d, (size_t)nqc * d * 4);
-            HAC_HIP(hipMemcpyAsync(ws_q.p, hq, (size_t)nqc * d * 4, hipMemcpyHostToDevice, stream));
-            for (int64_t j0 = 0; j0 < m; j0 += MC) {
-                const int64_t mc = std::min(MC, m - j0);
-                for (int64_t i = 0; i < nqc; ++i) std::memcpy(hi + (size_t)i * mc * 8, ids + (size_t)(q0 + i) * m + j0, (size_t)mc * 8);
-                HAC_HIP(hipMemcpyAsync(ws_ids.p, hi, (size_t)nqc * mc * 8, hipMemcpyHostToDevice, stream));
-                HAC_TRY(score_ids_device((const float *)ws_q.p, nqc, (const int64_t *)ws_ids.p, mc, (float *)ws_D.p, stream));
-                HAC_HIP(hipMemcpyAsync(hd, ws_D.p, (size_t)nqc * mc * 4, hipMemcpyDeviceToHost, stream));
-                HAC_HIP(hipStreamSynchronize(stream));
-                const float *res = reinterpret_cast<const float *>(hd);
-                for (int64_t i = 0; i < nqc; ++i) {
-                    float *Dr = D + (size_t)(q0 + i) * m + j0;
-                    if (!has_skip) {
-                        std::memcpy(Dr, res + (size_t)i * mc, (size_t)mc * 4);
-                    } else {
-                        const int64_t *ir = ids + (size_t)(q0 + i) * m + j0;
-                        for (int64_t j = 0; j < mc; ++j)
-                            if (ir[j] != skip) Dr[j] = res[(size_t)i * mc + j];
-                    }
-                }
-            }
-        }
-        return HAC_OK;
-    }
-
-    // ---- rank of named rows (rank.inc; hac_index_rank_ids*, hac_index_count_ahead_device): enqueue on `st` and return.
-    // Like the rows-by-id calls: nothing is read back and no slot of the status ring is taken; the only wait is the segment
-    // table's upload after an add / reset.  Unlike them these need a workspace (the counters and, for rank_ids, the
-    // reference scores: nq * m * 12 bytes), which grows by the rule of the search workspaces.
-    GrowBuf ws_rank;
-    static int check_rank_size(const char *what, int64_t nq, int64_t m) {
-        if (m > ((int64_t)1 << 40) / nq) return fail(HAC_ERR_UNSUPPORTED, "%s: %lld x %lld pairs in one call exceed the workspace", what, (long long)nq, (long long)m);
-        return HAC_OK;
-    }
-    u64 *rank_counters() const { return (u64 *)ws_rank.p; }
-    float *rank_scores(int64_t nq, int64_t m) const { return (float *)((u64 *)ws_rank.p + (size_t)nq * m); }
-    // out[i][j] = count_ahead(q[i], ref_score[i][j], ref_bound[i][j]) over this index's rows, or -1 (rank_finish_kernel)
-    int count_ahead_device(const char *what, const float *q_dev, int64_t nq, const float *ref_score_dev, const int64_t *ref_bound_dev, bool bounds_are_ids,
-                           int64_t m, int64_t *out_dev, hipStream_t st) {
-        if (nq == 0 || m == 0) return HAC_OK;
-        HAC_TRY(check_rank_size(what, nq, m));
-        HAC_TRY(check_out_ptr(q_dev, what));
-        HAC_TRY(ws_rank.reserve((size_t)nq * m * 12));
-        HAC_TRY(upload_segs(st));
-        HAC_HIP(hipMemsetAsync(rank_counters(), 0, (size_t)nq * m * 8, st));
-        const u32 G = (u32)((ntotal + GROUP_ROWS - 1) / GROUP_ROWS);
-        const int64_t chunks = (m + RANK_MT - 1) / RANK_MT;
-        // queries in chunks of QUERY_CHUNK, as the exact search takes them; grid.x as make_plan sizes scan16's for the same rows and queries
-        for (int64_t off = 0; off < nq && G > 0; off += QUERY_CHUNK) {
-            const int64_t n = std::min<int64_t>(QUERY_CHUNK, nq - off);
-            ScanArgs a = scan_args(q_dev + (size_t)off * d, n);
-            a.QT = (int)std::min<int64_t>(16, n);
-            a.n_items = G;
-            const int T = (int)((n + a.QT - 1) / a.QT);
-            const size_t lds = rank_lds(K4, a.QT, RANK_MT);
-            // resident workgroups per CU: LDS-limited like scan16's, and 3 by the kernel's registers (144 of 512 per SIMD, one wave of a workgroup each)
-            const int per_cu = std::max(1, std::min<int>((int)std::min<size_t>(LDS_LIMIT / lds, 32 / SCAN_WAVES), 3));
-            long P = std::max<long>(1, (long)n_cu * per_cu / T);
-            if (P >= 8 && !tune.no_p8) P = P / 8 * 8;
-            P = std::max<long>(1, std::min<long>(P, (G + SCAN_WAVES - 1) / SCAN_WAVES));
-            RankArgs ra{ref_score_dev + (size_t)off * m, (const long long *)ref_bound_dev + (size_t)off * m, rank_counters() + (size_t)off * m, (long)m, 0u};
-            for (int64_t c0 = 0; c0 < chunks; c0 += 65535) {
-                ra.chunk0 = (u32)c0;
-                const unsigned nz = (unsigned)std::min<int64_t>(65535, chunks - c0);
-                count_ahead_kernel<RANK_MT><<<dim3((unsigned)P, (unsigned)T, nz), dim3(SCAN_WAVES * 64), lds, st>>>(a, ra);
-                HAC_HIP(hipGetLastError());
-            }
-            snprintf(last_plan, sizeof last_plan, "count_ahead_kernel<MT=%d> grid=(%ld,%d) QT=%d chunks=%lld lds=%zu", RANK_MT, P, T, a.QT, (long long)chunks, lds);
-            plan_text_slot = -1;
-        }
-        const int64_t total = nq * m;
-        rank_finish_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(rank_counters(), ref_score_dev, (const long long *)ref_bound_dev, bounds_are_ids,
-                                                                                       (long)total, (long)ntotal, (long long *)out_dev);
-        HAC_HIP(hipGetLastError());
-        return HAC_OK;
-    }
-    // rank[i][j] = count_ahead(q[i], score_ids(q[i], ids[i][j]), ids[i][j]): score_ids_kernel into the workspace, the counters, the finish
-    int rank_ids_device(const float *q_dev, int64_t nq, const int64_t *ids_dev, int64_t m, int64_t *rank_dev, hipStream_t st) {
-        if (nq == 0 || m == 0) return HAC_OK;
-        HAC_TRY(check_rank_size("rank_ids", nq, m));
-        HAC_TRY(ws_rank.reserve((size_t)nq * m * 12));
-        HAC_TRY(score_ids_device(q_dev, nq, ids_dev, m, rank_scores(nq, m), st));
-        return count_ahead_device("rank_ids", q_dev, nq, rank_scores(nq, m), ids_dev, true, m, rank_dev, st);
-    }
-    // Host form over this shard's rows, synchronous, on the index's own stream, staged like score_ids_host.  ref_score == null:
-    // rank_ids (ids: local row ids, -1 = padding); otherwise count_ahead with ids as the bounds (what a shard of a multi-device
-    // index is asked: the scores come from the shard that owns the row).
-    int rank_host(const float *q, int64_t nq, const int64_t *ids, const float *ref_score, int64_t m, int64_t *out) {
-        if (nq == 0 || m == 0) return HAC_OK;
-        DeviceGuard g(device);
-        if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", device);
-        const size_t budget = (size_t)64 << 20;
-        const int64_t MC = std::min<int64_t>(m, 1 << 20);
-        const int64_t QC = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(budget / ((size_t)MC * 20 + (size_t)d * 4))));
-        const size_t qb = (size_t)QC * d * 4, ib = (size_t)QC * MC * 8, sb = (size_t)QC * MC * 4, ob = (size_t)QC * MC * 8;
-        HAC_TRY(ws_q.reserve(qb));
-        HAC_TRY(ws_ids.reserve(ib));
-        HAC_TRY(ws_D.reserve(sb));
-        HAC_TRY(ws_I.reserve(ob));
-        HAC_TRY(pin_reserve(qb + ib + ob + sb));
-        HAC_HIP(hipStreamSynchronize(stream));
-        char *hq = static_cast<char *>(h_pin.p), *hi = hq + qb, *ho = hi + ib, *hs = ho + ob;
-        for (int64_t q0 = 0; q0 < nq; q0 += QC) {
-            const int64_t nqc = std::min(QC, nq - q0);
-            std::memcpy(hq, q + (size_t)q0 * d, (size_t)nqc * d * 4);
-            HAC_HIP(hipMemcpyAsync(ws_q.p, hq, (size_t)nqc * d * 4, hipMemcpyHostToDevice, stream));
-            for (int64_t j0 = 0; j0 < m; j0 += MC) {
-                const int64_t mc = std::min(MC, m - j0);
-                for (int64_t i = 0; i < nqc; ++i) std::memcpy(hi + (size_t)i * mc * 8, ids + (size_t)(q0 + i) * m + j0, (size_t)mc * 8);
-                HAC_HIP(hipMemcpyAsync(ws_ids.p, hi, (size_t)nqc * mc * 8, hipMemcpyHostToDevice, stream));
-                if (ref_score) {
-                    for (int64_t i = 0; i < nqc; ++i) std::memcpy(hs + (size_t)i * mc * 4, ref_score + (size_t)(q0 + i) * m + j0, (size_t)mc * 4);
-                    HAC_HIP(hipMemcpyAsync(ws_D.p, hs, (size_t)nqc * mc * 4, hipMemcpyHostToDevice, stream));
-                    HAC_TRY(count_ahead_device("count_ahead", (const float *)ws_q.p, nqc, (const float *)ws_D.p, (const int64_t *)ws_ids.p, false, mc, (int64_t *)ws_I.p, stream));
-                } else {
-                    HAC_TRY(rank_ids_device((const float *)ws_q.p, nqc, (const int64_t *)ws_ids.p, mc, (int64_t *)ws_I.p, stream));
-                }
-                HAC_HIP(hipMemcpyAsync(ho, ws_I.p, (size_t)nqc * mc * 8, hipMemcpyDeviceToHost, stream));
-                HAC_HIP(hipStreamSynchronize(stream));
-                for (int64_t i = 0; i < nqc; ++i) std::memcpy(out + (size_t)(q0 + i) * m + j0, ho + (size_t)i * mc * 8, (size_t)mc * 8);
-            }
-        }
-        return HAC_OK;
-    }
+    GrowBuf ws_ids, ws_rank;   // the by-id calls (rows_host.inc): a chunk's ids; the rank calls' counters and reference scores
 
     char last_plan[320] = "none";
     // a device-decided prefilter search leaves its fallback count and err / bound on the device: plan() completes the text
@@ -2709,12 +2491,14 @@ struct hac_index {
 };
 
 namespace {
-// the one shard of a single-device index, for the entry points that have no multi-device form (what: theirs, for the message)
-int single_shard(hac_index *idx, const char *what, DeviceIndex *&s) {
+// fn(the one shard of a single-device index), on its device: the entry points that have no multi-device form (what: theirs, for
+// the message); fn checks the rest of the arguments
+template <class F>
+int on_single_shard(hac_index *idx, const char *what, F fn) {
     if (!idx) return fail(HAC_ERR_INVALID, "null index");
     if (idx->shards.size() != 1) return fail(HAC_ERR_UNSUPPORTED, "%s needs a single-device index", what);
-    s = idx->shards[0];
-    return HAC_OK;
+    DeviceGuard g(idx->shards[0]->device);
+    return fn(*idx->shards[0]);
 }
 
 // fn(shard) on every shard; with several devices one host thread per shard drives its device (a prefilter search reads a status word back:
@@ -2756,6 +2540,8 @@ int first_shard_error(hac_index *idx, F fn) {
     return HAC_OK;
 }
 }  // namespace
+
+#include "rows_host.inc"
 
 extern "C" {
 
@@ -2837,14 +2623,13 @@ int hac_index_add(hac_index *idx, const float *x, int64_t n) {
 }
 
 int hac_index_add_device(hac_index *idx, const float *x_dev, int64_t n, void *hip_stream) {
-    DeviceIndex *s = nullptr;
-    HAC_TRY(single_shard(idx, "add_device", s));
-    if (n < 0 || (n > 0 && !x_dev)) return fail(HAC_ERR_INVALID, "add_device: bad arguments");
-    if (n == 0) return HAC_OK;
-    DeviceGuard g(s->device);
-    HAC_TRY(s->add_device_rows(x_dev, n, (hipStream_t)hip_stream));
-    idx->ntotal += n;
-    return HAC_OK;
+    return on_single_shard(idx, "add_device", [&](DeviceIndex &s) -> int {
+        if (n < 0 || (n > 0 && !x_dev)) return fail(HAC_ERR_INVALID, "add_device: bad arguments");
+        if (n == 0) return HAC_OK;
+        HAC_TRY(s.add_device_rows(x_dev, n, (hipStream_t)hip_stream));
+        idx->ntotal += n;
+        return HAC_OK;
+    });
 }
 
 int hac_index_reset(hac_index *idx) {
@@ -2862,12 +2647,11 @@ int64_t hac_index_ntotal(const hac_index *idx) { return idx ? idx->ntotal : -1; 
 
 int hac_index_search_keys_device(hac_index *idx, const float *q_dev, int64_t nq, int k, uint64_t *keys_dev,
                                  uint32_t pos_base, void *hip_stream) {
-    DeviceIndex *s = nullptr;
-    HAC_TRY(single_shard(idx, "search_keys_device", s));
-    HAC_TRY(check_k(k));
-    if (nq < 0 || (nq > 0 && (!q_dev || !keys_dev))) return fail(HAC_ERR_INVALID, "search: bad arguments");
-    DeviceGuard g(s->device);
-    return s->search_keys(q_dev, nq, k, (u64 *)keys_dev, pos_base, (hipStream_t)hip_stream, true);
+    return on_single_shard(idx, "search_keys_device", [&](DeviceIndex &s) -> int {
+        HAC_TRY(check_k(k));
+        if (nq < 0 || (nq > 0 && (!q_dev || !keys_dev))) return fail(HAC_ERR_INVALID, "search: bad arguments");
+        return s.search_keys(q_dev, nq, k, (u64 *)keys_dev, pos_base, (hipStream_t)hip_stream, true);
+    });
 }
 
 int hac_keys_to_results_device(int device, const uint64_t *keys_dev, int64_t n_keys, const int64_t *id_map_dev,
@@ -2921,34 +2705,32 @@ int hac_filter_keys_device(int device, const uint64_t *keys_dev, int64_t nq, int
 
 int hac_index_search_device(hac_index *idx, const float *q_dev, int64_t nq, int k, float *D_dev, int64_t *I_dev,
                             const int64_t *id_map_dev, void *hip_stream) {
-    DeviceIndex *s = nullptr;
-    HAC_TRY(single_shard(idx, "search_device", s));
-    HAC_TRY(check_k(k));
-    if (nq < 0 || (nq > 0 && (!q_dev || !D_dev || !I_dev))) return fail(HAC_ERR_INVALID, "search: bad arguments");
-    if (nq == 0) return HAC_OK;
-    DeviceGuard g(s->device);
-    HAC_TRY(s->ws_keys.reserve((size_t)nq * k * 8));
-    HAC_TRY(s->search_keys(q_dev, nq, k, (u64 *)s->ws_keys.p, 0u, (hipStream_t)hip_stream, true));
-    return hac_keys_to_results_device(s->device, (const uint64_t *)s->ws_keys.p, nq * k, id_map_dev, D_dev, I_dev, hip_stream);
+    return on_single_shard(idx, "search_device", [&](DeviceIndex &s) -> int {
+        HAC_TRY(check_k(k));
+        if (nq < 0 || (nq > 0 && (!q_dev || !D_dev || !I_dev))) return fail(HAC_ERR_INVALID, "search: bad arguments");
+        if (nq == 0) return HAC_OK;
+        HAC_TRY(s.ws_keys.reserve((size_t)nq * k * 8));
+        HAC_TRY(s.search_keys(q_dev, nq, k, (u64 *)s.ws_keys.p, 0u, (hipStream_t)hip_stream, true));
+        return hac_keys_to_results_device(s.device, (const uint64_t *)s.ws_keys.p, nq * k, id_map_dev, D_dev, I_dev, hip_stream);
+    });
 }
 
 // The top-k of (rows minus E), |E| <= e, lies inside the top-(k + e) of the rows, in the same order: search k + e keys, filter.
 int hac_index_search_excluding_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const int64_t *excl_dev, int e, float *D_dev,
                                       int64_t *I_dev, const int64_t *id_map_dev, void *hip_stream) {
-    DeviceIndex *s = nullptr;
-    HAC_TRY(single_shard(idx, "search_excluding_device", s));
-    HAC_TRY(check_k_e(k, e));
-    if (e == 0) return hac_index_search_device(idx, q_dev, nq, k, D_dev, I_dev, id_map_dev, hip_stream);
-    if (nq < 0 || (nq > 0 && (!q_dev || !excl_dev || !D_dev || !I_dev))) return fail(HAC_ERR_INVALID, "search_excluding: bad arguments");
-    if (nq == 0) return HAC_OK;
-    DeviceGuard g(s->device);
-    const int kq = k + e;
-    HAC_TRY(s->ws_keys.reserve((size_t)nq * kq * 8));
-    HAC_TRY(idx->ws_out.reserve((size_t)nq * k * 8));
-    HAC_TRY(s->search_keys(q_dev, nq, kq, (u64 *)s->ws_keys.p, 0u, (hipStream_t)hip_stream, true));
-    // (row ids are the positions the keys carry, pos_base = 0; an id outside [0, ntotal) is padding or names no key)
-    HAC_TRY(hac_filter_keys_device(s->device, (const uint64_t *)s->ws_keys.p, nq, kq, excl_dev, e, k, (uint64_t *)idx->ws_out.p, hip_stream));
-    return hac_keys_to_results_device(s->device, (const uint64_t *)idx->ws_out.p, nq * k, id_map_dev, D_dev, I_dev, hip_stream);
+    return on_single_shard(idx, "search_excluding_device", [&](DeviceIndex &s) -> int {
+        HAC_TRY(check_k_e(k, e));
+        if (e == 0) return hac_index_search_device(idx, q_dev, nq, k, D_dev, I_dev, id_map_dev, hip_stream);
+        if (nq < 0 || (nq > 0 && (!q_dev || !excl_dev || !D_dev || !I_dev))) return fail(HAC_ERR_INVALID, "search_excluding: bad arguments");
+        if (nq == 0) return HAC_OK;
+        const int kq = k + e;
+        HAC_TRY(s.ws_keys.reserve((size_t)nq * kq * 8));
+        HAC_TRY(idx->ws_out.reserve((size_t)nq * k * 8));
+        HAC_TRY(s.search_keys(q_dev, nq, kq, (u64 *)s.ws_keys.p, 0u, (hipStream_t)hip_stream, true));
+        // (row ids are the positions the keys carry, pos_base = 0; an id outside [0, ntotal) is padding or names no key)
+        HAC_TRY(hac_filter_keys_device(s.device, (const uint64_t *)s.ws_keys.p, nq, kq, excl_dev, e, k, (uint64_t *)idx->ws_out.p, hip_stream));
+        return hac_keys_to_results_device(s.device, (const uint64_t *)idx->ws_out.p, nq * k, id_map_dev, D_dev, I_dev, hip_stream);
+    });
 }
 
 }  // extern "C"
@@ -3053,192 +2835,13 @@ int hac_index_search_excluding(hac_index *idx, const float *q, int64_t nq, int k
     HAC_TRY(check_k_e(k, e));
     if (nq < 0 || (nq > 0 && (!q || !D || !I || (e > 0 && !excl)))) return fail(HAC_ERR_INVALID, "search_excluding: bad arguments");
     if (nq == 0) return HAC_OK;
-    for (int64_t i = 0; i < nq * e; ++i)   // -1 is padding; any other id outside the index is the caller's mistake
-        if (excl[i] < -1 || excl[i] >= idx->ntotal)
-            return fail(HAC_ERR_INVALID, "search_excluding: id %lld at (query %lld, column %lld) is outside [0, %lld) (-1 = padding)",
-                        (long long)excl[i], (long long)(i / e), (long long)(i % e), (long long)idx->ntotal);
+    HAC_TRY(check_host_ids("search_excluding", excl, nq, e, idx->ntotal, IdPlace::QUERY_COLUMN, "padding"));   // (-1 is padding; any other id outside the index is the caller's mistake)
     return search_host(idx, q, nq, k, excl, e, D, I);
 }
 
 }  // extern "C"
 
-// ---- rows by id: reconstruct / score_ids -----------------------------------------------------------------------------
-namespace {
-// global row id -> (shard, shard-local row): the inverse of remap_positions_kernel, on the host.  One device: the identity.
-struct RowLocator {
-    struct Span {
-        int64_t global0, count, local0;
-        int shard;
-    };
-    std::vector<Span> spans;   // every shard's share of every add(), by first global row
-    explicit RowLocator(const hac_index *idx) {
-        if (idx->shards.size() < 2) return;
-        for (size_t s = 0; s < idx->spans.size(); ++s)
-            for (const SpanDesc &sp : idx->spans[s]) spans.push_back(Span{(int64_t)sp.global0, (int64_t)sp.count, (int64_t)sp.local0, (int)s});
-        std::sort(spans.begin(), spans.end(), [](const Span &a, const Span &b) { return a.global0 < b.global0; });
-    }
-    // id in [0, ntotal)
-    void locate(int64_t id, int &shard, int64_t &local) const {
-        if (spans.empty()) {
-            shard = 0;
-            local = id;
-            return;
-        }
-        size_t lo = 0, hi = spans.size() - 1;   // last span with global0 <= id
-        while (lo < hi) {
-            const size_t mid = (lo + hi + 1) >> 1;
-            if (spans[mid].global0 <= id) lo = mid;
-            else hi = mid - 1;
-        }
-        shard = spans[lo].shard;
-        local = spans[lo].local0 + (id - spans[lo].global0);
-    }
-};
-
-// the first id outside [-1, ntotal): the host entry points refuse it (the *_device ones cannot look)
-int check_host_ids(const char *what, const int64_t *ids, int64_t count, int64_t ntotal) {
-    for (int64_t i = 0; i < count; ++i)
-        if (ids[i] < -1 || ids[i] >= ntotal)
-            return fail(HAC_ERR_INVALID, "%s: id %lld at position %lld is outside [0, %lld) (-1 = a padding slot)", what, (long long)ids[i], (long long)i,
-                        (long long)ntotal);
-    return HAC_OK;
-}
-
-}  // namespace
-
 extern "C" {
-
-int hac_index_reconstruct_ids(hac_index *idx, const int64_t *ids, int64_t n, float *out) {
-    if (!idx) return fail(HAC_ERR_INVALID, "null index");
-    if (n < 0 || (n > 0 && (!ids || !out))) return fail(HAC_ERR_INVALID, "reconstruct: bad arguments");
-    if (n == 0) return HAC_OK;
-    HAC_TRY(check_host_ids("reconstruct", ids, n, idx->ntotal));
-    const int S = (int)idx->shards.size();
-    if (S == 1) return idx->shards[0]->read_rows_host(ids, nullptr, 0, n, out);
-    const RowLocator loc(idx);
-    std::vector<std::vector<int64_t>> local(S), pos(S);
-    for (int64_t i = 0; i < n; ++i) {
-        int sh = 0;
-        int64_t l = -1;   // (a padding slot: shard 0 writes its all-ones row)
-        if (ids[i] >= 0) loc.locate(ids[i], sh, l);
-        local[sh].push_back(l);
-        pos[sh].push_back(i);
-    }
-    return for_each_shard(idx, [&](int si) { return idx->shards[si]->read_rows_host(local[si].data(), pos[si].data(), 0, (int64_t)local[si].size(), out); });
-}
-
-int hac_index_reconstruct(hac_index *idx, int64_t i0, int64_t n, float *out) {
-    if (!idx) return fail(HAC_ERR_INVALID, "null index");
-    if (i0 < 0 || n < 0 || i0 > idx->ntotal || n > idx->ntotal - i0)
-        return fail(HAC_ERR_INVALID, "reconstruct: rows [%lld, %lld + %lld) are not inside [0, %lld]", (long long)i0, (long long)i0, (long long)n,
-                    (long long)idx->ntotal);
-    if (n == 0) return HAC_OK;
-    if (!out) return fail(HAC_ERR_INVALID, "reconstruct: bad arguments");
-    if (idx->shards.size() == 1) return idx->shards[0]->read_rows_host(nullptr, nullptr, i0, n, out);
-    // several devices: consecutive rows alternate between the shards with every add(); the range goes by id, a chunk at a time
-    const int64_t chunk = idx->shards[0]->stage_rows();
-    std::vector<int64_t> ids;
-    for (int64_t done = 0; done < n; done += chunk) {
-        const int64_t m = std::min(chunk, n - done);
-        ids.resize((size_t)m);
-        for (int64_t i = 0; i < m; ++i) ids[(size_t)i] = i0 + done + i;
-        HAC_TRY(hac_index_reconstruct_ids(idx, ids.data(), m, out + (size_t)done * idx->d));
-    }
-    return HAC_OK;
-}
-
-int hac_index_reconstruct_device(hac_index *idx, const int64_t *ids_dev, int64_t i0, int64_t n, float *out_dev, void *hip_stream) {
-    DeviceIndex *s = nullptr;
-    HAC_TRY(single_shard(idx, "reconstruct_device", s));
-    if (n < 0 || (n > 0 && !out_dev)) return fail(HAC_ERR_INVALID, "reconstruct_device: bad arguments");
-    DeviceGuard g(s->device);
-    if (ids_dev) return s->rows_ids_device(ids_dev, n, out_dev, (hipStream_t)hip_stream);
-    return s->rows_range_device(i0, n, out_dev, (hipStream_t)hip_stream);
-}
-
-int hac_index_score_ids(hac_index *idx, const float *q, int64_t nq, const int64_t *ids, int64_t m, float *D) {
-    if (!idx) return fail(HAC_ERR_INVALID, "null index");
-    if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q || !ids || !D))) return fail(HAC_ERR_INVALID, "score_ids: bad arguments");
-    if (nq == 0 || m == 0) return HAC_OK;
-    HAC_TRY(check_host_ids("score_ids", ids, nq * m, idx->ntotal));
-    const int S = (int)idx->shards.size();
-    if (S == 1) return idx->shards[0]->score_ids_host(q, nq, ids, m, D, false, 0);
-    // every shard scores the pairs whose row it holds (padding slots: shard 0) and leaves the others' slots of D alone
-    const RowLocator loc(idx);
-    constexpr int64_t NOT_MINE = -2;
-    std::vector<std::vector<int64_t>> local(S, std::vector<int64_t>((size_t)(nq * m), NOT_MINE));
-    for (int64_t i = 0; i < nq * m; ++i) {
-        int sh = 0;
-        int64_t l = -1;
-        if (ids[i] >= 0) loc.locate(ids[i], sh, l);
-        local[sh][(size_t)i] = l;
-    }
-    return for_each_shard(idx, [&](int si) { return idx->shards[si]->score_ids_host(q, nq, local[si].data(), m, D, true, NOT_MINE); });
-}
-
-int hac_index_score_ids_device(hac_index *idx, const float *q_dev, int64_t nq, const int64_t *ids_dev, int64_t m, float *D_dev, void *hip_stream) {
-    DeviceIndex *s = nullptr;
-    HAC_TRY(single_shard(idx, "score_ids_device", s));
-    if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q_dev || !ids_dev || !D_dev))) return fail(HAC_ERR_INVALID, "score_ids_device: bad arguments");
-    DeviceGuard g(s->device);
-    return s->score_ids_device(q_dev, nq, ids_dev, m, D_dev, (hipStream_t)hip_stream);
-}
-
-// ---- rank of named rows ------------------------------------------------------------------------------------------------
-int hac_index_count_ahead_device(hac_index *idx, const float *q_dev, int64_t nq, const float *ref_score_dev, const int64_t *ref_bound_dev, int64_t m,
-                                 int64_t *count_dev, void *hip_stream) {
-    DeviceIndex *s = nullptr;
-    HAC_TRY(single_shard(idx, "count_ahead_device", s));
-    if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q_dev || !ref_score_dev || !ref_bound_dev || !count_dev))) return fail(HAC_ERR_INVALID, "count_ahead_device: bad arguments");
-    DeviceGuard g(s->device);
-    return s->count_ahead_device("count_ahead_device", q_dev, nq, ref_score_dev, ref_bound_dev, false, m, count_dev, (hipStream_t)hip_stream);
-}
-
-int hac_index_rank_ids_device(hac_index *idx, const float *q_dev, int64_t nq, const int64_t *ids_dev, int64_t m, int64_t *rank_dev, void *hip_stream) {
-    DeviceIndex *s = nullptr;
-    HAC_TRY(single_shard(idx, "rank_ids_device", s));
-    if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q_dev || !ids_dev || !rank_dev))) return fail(HAC_ERR_INVALID, "rank_ids_device: bad arguments");
-    DeviceGuard g(s->device);
-    return s->rank_ids_device(q_dev, nq, ids_dev, m, rank_dev, (hipStream_t)hip_stream);
-}
-
-int hac_index_rank_ids(hac_index *idx, const float *q, int64_t nq, const int64_t *ids, int64_t m, int64_t *rank) {
-    if (!idx) return fail(HAC_ERR_INVALID, "null index");
-    if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q || !ids || !rank))) return fail(HAC_ERR_INVALID, "rank_ids: bad arguments");
-    if (nq == 0 || m == 0) return HAC_OK;
-    if (check_host_ids("rank_ids", ids, nq * m, idx->ntotal) != HAC_OK) {   // (the message again, with the id's place in the [nq, m] matrix)
-        for (int64_t i = 0; i < nq * m; ++i)
-            if (ids[i] < -1 || ids[i] >= idx->ntotal)
-                return fail(HAC_ERR_INVALID, "rank_ids: id %lld at (query %lld, column %lld) is outside [0, %lld) (-1 = a padding slot)", (long long)ids[i],
-                            (long long)(i / m), (long long)(i % m), (long long)idx->ntotal);
-    }
-    const int S = (int)idx->shards.size();
-    if (S == 1) return idx->shards[0]->rank_host(q, nq, ids, nullptr, m, rank);
-    // Several devices.  The reference scores come from the shard that owns the row (the multi-shard score_ids path); every shard
-    // then counts its own rows ahead of (score, bound), the bound translated into its numbering: b_s(id) = the number of the
-    // shard's rows with a global id below id, summed over its spans.  A shard's local order preserves the global order, so a tie
-    // still breaks by global row; the counts of the shards add up.
-    const size_t total = (size_t)(nq * m);
-    std::vector<float> scores(total);
-    HAC_TRY(hac_index_score_ids(idx, q, nq, ids, m, scores.data()));
-    std::vector<std::vector<int64_t>> bounds(S, std::vector<int64_t>(total)), part(S, std::vector<int64_t>(total));
-    for (int si = 0; si < S; ++si)
-        for (size_t i = 0; i < total; ++i) {
-            int64_t b = -1;
-            if (ids[i] >= 0) {
-                b = 0;
-                for (const SpanDesc &sp : idx->spans[si]) b += std::min<int64_t>(std::max<int64_t>(ids[i] - (int64_t)sp.global0, 0), (int64_t)sp.count);
-            }
-            bounds[si][i] = b;
-        }
-    HAC_TRY(for_each_shard(idx, [&](int si) { return idx->shards[si]->rank_host(q, nq, bounds[si].data(), scores.data(), m, part[si].data()); }));
-    for (size_t i = 0; i < total; ++i) {
-        int64_t sum = 0;
-        for (int si = 0; si < S; ++si) sum = (sum < 0 || part[si][i] < 0) ? -1 : sum + part[si][i];   // (-1: padding or a NaN score, on every shard alike)
-        rank[i] = sum;
-    }
-    return HAC_OK;
-}
 
 int hac_index_last_status(hac_index *idx) {
     if (!idx) return fail(HAC_ERR_INVALID, "null index");

@@ -1,0 +1,392 @@
+// Rows by id and their rank (hac_index_reconstruct*, hac_index_score_ids*, hac_index_rank_ids*, hac_index_count_ahead_device):
+// everything between the C ABI and the kernels of flat_ip.hip ("rows by id") and rank.inc.  Included by flat_ip.hip behind
+// hac_index; free functions over one shard (DeviceIndex &), which lends its segment table, its stream, its pinned slab, its
+// staging buffers and the workspaces ws_q / ws_ids / ws_D / ws_I / ws_rank -- nothing of the search state.
+namespace {
+
+// ---- device forms: enqueue on `st` and return.  The only wait is the segment table's upload after an add / reset / a changed
+// image, which the first search pays too; nothing is read back or written to the status ring, so once the table is up (and,
+// for the rank calls, the workspace of the largest shape exists) these calls can be captured into a graph.
+int check_dev_ptr(const void *p, const char *what) {
+    if (((uintptr_t)p & 15) != 0) return fail(HAC_ERR_INVALID, "%s: device pointer must be 16-byte aligned", what);
+    return HAC_OK;
+}
+int rows_range_device(DeviceIndex &x, int64_t i0, int64_t n, float *out_dev, hipStream_t st) {
+    if (i0 < 0 || n < 0 || i0 > x.ntotal || n > x.ntotal - i0)
+        return fail(HAC_ERR_INVALID, "reconstruct: rows [%lld, %lld + %lld) are not inside [0, %lld]", (long long)i0, (long long)i0, (long long)n, (long long)x.ntotal);
+    if (n == 0) return HAC_OK;
+    HAC_TRY(check_dev_ptr(out_dev, "reconstruct"));
+    HAC_TRY(x.upload_segs(st));
+    const long g_lo = (long)(i0 / GROUP_ROWS), g_hi = (long)((i0 + n + GROUP_ROWS - 1) / GROUP_ROWS);
+    untile_range_kernel<<<dim3((unsigned)(g_hi - g_lo)), dim3(256), 0, st>>>(x.d_segs, x.nseg_live, (long)i0, (long)n, x.K4, reinterpret_cast<f4 *>(out_dev));
+    HAC_HIP(hipGetLastError());
+    return HAC_OK;
+}
+int rows_ids_device(DeviceIndex &x, const int64_t *ids_dev, int64_t n, float *out_dev, hipStream_t st) {
+    if (n == 0) return HAC_OK;
+    if (n > (int64_t)0x7FFFFFFF * (4 * ROWS_PER_WAVE)) return fail(HAC_ERR_UNSUPPORTED, "reconstruct: %lld ids in one call exceed the grid", (long long)n);
+    HAC_TRY(check_dev_ptr(out_dev, "reconstruct"));
+    HAC_TRY(x.upload_segs(st));
+    const int64_t per_wg = 4 * ROWS_PER_WAVE;
+    rows_by_id_kernel<<<dim3((unsigned)((n + per_wg - 1) / per_wg)), dim3(256), 0, st>>>(x.d_segs, x.d_rimg, x.nseg_live, (const long long *)ids_dev, (long)n,
+                                                                                       (long)x.ntotal, x.K4, reinterpret_cast<f4 *>(out_dev));
+    HAC_HIP(hipGetLastError());
+    return HAC_OK;
+}
+int score_ids_device(DeviceIndex &x, const float *q_dev, int64_t nq, const int64_t *ids_dev, int64_t m, float *D_dev, hipStream_t st) {
+    if (nq == 0 || m == 0) return HAC_OK;
+    const int64_t bpq = (m + 255) / 256;
+    if (bpq > 0x7FFFFFFF / nq) return fail(HAC_ERR_UNSUPPORTED, "score_ids: %lld x %lld pairs in one call exceed the grid", (long long)nq, (long long)m);
+    HAC_TRY(check_dev_ptr(q_dev, "score_ids"));
+    HAC_TRY(x.upload_segs(st));
+    score_ids_kernel<<<dim3((unsigned)(nq * bpq)), dim3(256), 0, st>>>(x.d_segs, x.d_rimg, x.nseg_live, q_dev, (const long long *)ids_dev, (long)m, (u32)bpq,
+                                                                      (long)x.ntotal, x.K4, D_dev);
+    HAC_HIP(hipGetLastError());
+    return HAC_OK;
+}
+
+// The rank calls need a workspace (the counters and, for rank_ids, the reference scores: nq * m * 12 bytes), which grows by
+// the rule of the search workspaces.
+int check_rank_size(const char *what, int64_t nq, int64_t m) {
+    if (m > ((int64_t)1 << 40) / nq) return fail(HAC_ERR_UNSUPPORTED, "%s: %lld x %lld pairs in one call exceed the workspace", what, (long long)nq, (long long)m);
+    return HAC_OK;
+}
+u64 *rank_counters(const DeviceIndex &x) { return (u64 *)x.ws_rank.p; }
+float *rank_scores(const DeviceIndex &x, int64_t nq, int64_t m) { return (float *)((u64 *)x.ws_rank.p + (size_t)nq * m); }
+// out[i][j] = count_ahead(q[i], ref_score[i][j], ref_bound[i][j]) over this shard's rows, or -1 (rank_finish_kernel)
+int count_ahead_device(DeviceIndex &x, const char *what, const float *q_dev, int64_t nq, const float *ref_score_dev, const int64_t *ref_bound_dev,
+                       bool bounds_are_ids, int64_t m, int64_t *out_dev, hipStream_t st) {
+    if (nq == 0 || m == 0) return HAC_OK;
+    HAC_TRY(check_rank_size(what, nq, m));
+    HAC_TRY(check_dev_ptr(q_dev, what));
+    HAC_TRY(x.ws_rank.reserve((size_t)nq * m * 12));
+    HAC_TRY(x.upload_segs(st));
+    HAC_HIP(hipMemsetAsync(rank_counters(x), 0, (size_t)nq * m * 8, st));
+    const u32 G = (u32)((x.ntotal + GROUP_ROWS - 1) / GROUP_ROWS);
+    const int64_t chunks = (m + RANK_MT - 1) / RANK_MT;
+    // queries in chunks of QUERY_CHUNK, as the exact search takes them; grid.x as make_plan sizes scan16's for the same rows and queries
+    for (int64_t off = 0; off < nq && G > 0; off += DeviceIndex::QUERY_CHUNK) {
+        const int64_t n = std::min<int64_t>(DeviceIndex::QUERY_CHUNK, nq - off);
+        ScanArgs a = x.scan_args(q_dev + (size_t)off * x.d, n);
+        a.QT = (int)std::min<int64_t>(16, n);
+        a.n_items = G;
+        const int T = (int)((n + a.QT - 1) / a.QT);
+        const size_t lds = rank_lds(x.K4, a.QT, RANK_MT);
+        // resident workgroups per CU: LDS-limited like scan16's, and 3 by the kernel's registers (144 of 512 per SIMD, one wave of a workgroup each)
+        const int per_cu = std::max(1, std::min<int>((int)std::min<size_t>(LDS_LIMIT / lds, 32 / SCAN_WAVES), 3));
+        long P = std::max<long>(1, (long)x.n_cu * per_cu / T);
+        if (P >= 8 && !x.tune.no_p8) P = P / 8 * 8;
+        P = std::max<long>(1, std::min<long>(P, (G + SCAN_WAVES - 1) / SCAN_WAVES));
+        RankArgs ra{ref_score_dev + (size_t)off * m, (const long long *)ref_bound_dev + (size_t)off * m, rank_counters(x) + (size_t)off * m, (long)m, 0u};
+        for (int64_t c0 = 0; c0 < chunks; c0 += 65535) {
+            ra.chunk0 = (u32)c0;
+            const unsigned nz = (unsigned)std::min<int64_t>(65535, chunks - c0);
+            count_ahead_kernel<RANK_MT><<<dim3((unsigned)P, (unsigned)T, nz), dim3(SCAN_WAVES * 64), lds, st>>>(a, ra);
+            HAC_HIP(hipGetLastError());
+        }
+        snprintf(x.last_plan, sizeof x.last_plan, "count_ahead_kernel<MT=%d> grid=(%ld,%d) QT=%d chunks=%lld lds=%zu", RANK_MT, P, T, a.QT, (long long)chunks, lds);
+        x.plan_text_slot = -1;
+    }
+    const int64_t total = nq * m;
+    rank_finish_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(rank_counters(x), ref_score_dev, (const long long *)ref_bound_dev, bounds_are_ids,
+                                                                                   (long)total, (long)x.ntotal, (long long *)out_dev);
+    HAC_HIP(hipGetLastError());
+    return HAC_OK;
+}
+// rank[i][j] = count_ahead(q[i], score_ids(q[i], ids[i][j]), ids[i][j]): score_ids_kernel into the workspace, the counters, the finish
+int rank_ids_device(DeviceIndex &x, const float *q_dev, int64_t nq, const int64_t *ids_dev, int64_t m, int64_t *rank_dev, hipStream_t st) {
+    if (nq == 0 || m == 0) return HAC_OK;
+    HAC_TRY(check_rank_size("rank_ids", nq, m));
+    HAC_TRY(x.ws_rank.reserve((size_t)nq * m * 12));
+    HAC_TRY(score_ids_device(x, q_dev, nq, ids_dev, m, rank_scores(x, nq, m), st));
+    return count_ahead_device(x, "rank_ids", q_dev, nq, rank_scores(x, nq, m), ids_dev, true, m, rank_dev, st);
+}
+
+// ---- host forms over one shard's rows: synchronous, on the shard's own stream, one chunk in flight.  They run on
+// for_each_shard's threads, so they touch the shard's own buffers only and write disjoint slots of the caller's output.
+// `bytes` of the shard's pinned slab, free to be written: it may still be the source of an earlier copy on the shard's stream.
+int pin_slab(DeviceIndex &x, size_t bytes, char *&slab) {
+    HAC_TRY(x.pin_reserve(bytes));
+    HAC_HIP(hipStreamSynchronize(x.stream));
+    slab = static_cast<char *>(x.h_pin.p);
+    return HAC_OK;
+}
+
+// Rows, staged through the add's 64-MiB buffers a chunk at a time (the whole of a 25M-row index is 77 GB: it never exists on
+// the device a second time).  ids != null: out row pos[i] (or i) = row ids[i], local numbering, < 0 = all-ones; ids == null:
+// the rows [i0, i0 + n).
+int read_rows_host(DeviceIndex &x, const int64_t *ids, const int64_t *pos, int64_t i0, int64_t n, float *out) {
+    if (n == 0) return HAC_OK;
+    DeviceGuard g(x.device);
+    if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", x.device);
+    const int64_t chunk_rows = x.stage_rows();
+    const size_t row_bytes = (size_t)x.d * 4, id_bytes = ids ? (size_t)std::min(chunk_rows, n) * 8 : 0;
+    HAC_TRY(x.stage_reserve());
+    HAC_TRY(x.ws_ids.reserve(id_bytes));
+    char *hi = nullptr;
+    HAC_TRY(pin_slab(x, id_bytes, hi));
+    for (int64_t done = 0; done < n; done += chunk_rows) {
+        const int64_t m = std::min(chunk_rows, n - done);
+        if (ids) {
+            std::memcpy(hi, ids + done, (size_t)m * 8);
+            HAC_HIP(hipMemcpyAsync(x.ws_ids.p, hi, (size_t)m * 8, hipMemcpyHostToDevice, x.stream));
+            HAC_TRY(rows_ids_device(x, (const int64_t *)x.ws_ids.p, m, (float *)x.ws_stage[0].p, x.stream));
+        } else {
+            HAC_TRY(rows_range_device(x, i0 + done, m, (float *)x.ws_stage[0].p, x.stream));
+        }
+        HAC_HIP(hipMemcpyAsync(x.h_stage[0].p, x.ws_stage[0].p, (size_t)m * row_bytes, hipMemcpyDeviceToHost, x.stream));
+        HAC_HIP(hipStreamSynchronize(x.stream));
+        const char *src = static_cast<const char *>(x.h_stage[0].p);
+        if (pos) {
+            for (int64_t i = 0; i < m; ++i) std::memcpy(out + (size_t)pos[done + i] * x.d, src + (size_t)i * row_bytes, row_bytes);
+        } else {
+            std::memcpy(out + (size_t)done * x.d, src, (size_t)m * row_bytes);
+        }
+    }
+    return HAC_OK;
+}
+
+// One input plane of a host matrix [nq][m] of (query, row) pairs: `width` bytes per pair, staged into `dev`.  host == null: the
+// device form fills the plane itself; it still counts towards the chunk's size.
+struct PairPlane { const void *host; size_t width; GrowBuf *dev; };
+// out[i][j] = what launch(nqc, mc) leaves in out_dev for the pair (q[i], planes[.][i][j]), for all of a host matrix: chunked over
+// the queries and, for very long lists, over j, so that one chunk's queries, planes and results fit ~64 MiB (QC x MC pairs,
+// MC = min(m, 2^20)).  launch enqueues the device form on the shard's stream: queries in ws_q, planes and results [nqc][mc].
+// planes[0] holds the ids; with has_skip, pairs whose id == skip are another shard's and their slots of `out` are left alone.
+template <class Out, size_t NP, class Launch>
+int pair_matrix_host(DeviceIndex &x, const float *q, int64_t nq, int64_t m, const PairPlane (&planes)[NP], Out *out, GrowBuf &out_dev, bool has_skip,
+                     int64_t skip, Launch launch) {
+    if (nq == 0 || m == 0) return HAC_OK;
+    DeviceGuard g(x.device);
+    if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", x.device);
+    size_t pair_bytes = sizeof(Out);
+    for (const PairPlane &p : planes) pair_bytes += p.width;
+    const size_t budget = (size_t)64 << 20, q_bytes = (size_t)x.d * 4;
+    const int64_t MC = std::min<int64_t>(m, 1 << 20);
+    const int64_t QC = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(budget / ((size_t)MC * pair_bytes + q_bytes))));
+    const size_t pairs = (size_t)QC * MC;
+    HAC_TRY(x.ws_q.reserve(QC * q_bytes));
+    for (const PairPlane &p : planes) HAC_TRY(p.dev->reserve(pairs * p.width));
+    HAC_TRY(out_dev.reserve(pairs * sizeof(Out)));
+    char *hq = nullptr, *hp[NP];   // the slab: queries, results, planes
+    HAC_TRY(pin_slab(x, QC * q_bytes + pairs * pair_bytes, hq));
+    Out *res = reinterpret_cast<Out *>(hq + QC * q_bytes);
+    hp[0] = reinterpret_cast<char *>(res + pairs);
+    for (size_t p = 1; p < NP; ++p) hp[p] = hp[p - 1] + pairs * planes[p - 1].width;
+    const int64_t *ids = static_cast<const int64_t *>(planes[0].host);
+    for (int64_t q0 = 0; q0 < nq; q0 += QC) {
+        const int64_t nqc = std::min(QC, nq - q0);
+        std::memcpy(hq, q + (size_t)q0 * x.d, nqc * q_bytes);
+        HAC_HIP(hipMemcpyAsync(x.ws_q.p, hq, nqc * q_bytes, hipMemcpyHostToDevice, x.stream));
+        for (int64_t j0 = 0; j0 < m; j0 += MC) {
+            const int64_t mc = std::min(MC, m - j0);
+            const size_t first = (size_t)q0 * m + j0;   // the chunk's first pair in the caller's matrices
+            for (size_t p = 0; p < NP; ++p) {
+                if (!planes[p].host) continue;
+                const size_t w = planes[p].width;
+                const char *src = static_cast<const char *>(planes[p].host) + first * w;
+                for (int64_t i = 0; i < nqc; ++i) std::memcpy(hp[p] + (size_t)i * mc * w, src + (size_t)i * m * w, (size_t)mc * w);
+                HAC_HIP(hipMemcpyAsync(planes[p].dev->p, hp[p], (size_t)nqc * mc * w, hipMemcpyHostToDevice, x.stream));
+            }
+            HAC_TRY(launch(nqc, mc));
+            HAC_HIP(hipMemcpyAsync(res, out_dev.p, (size_t)nqc * mc * sizeof(Out), hipMemcpyDeviceToHost, x.stream));
+            HAC_HIP(hipStreamSynchronize(x.stream));
+            for (int64_t i = 0; i < nqc; ++i) {
+                Out *dst = out + first + (size_t)i * m;
+                const Out *r = res + (size_t)i * mc;
+                if (!has_skip) {
+                    std::memcpy(dst, r, (size_t)mc * sizeof(Out));
+                } else {
+                    const int64_t *ir = ids + first + (size_t)i * m;
+                    for (int64_t j = 0; j < mc; ++j)
+                        if (ir[j] != skip) dst[j] = r[j];
+                }
+            }
+        }
+    }
+    return HAC_OK;
+}
+// D[i][j] = score(q[i], row ids[i][j]) for the pairs this shard owns: local ids, -1 = a padding slot (-FLT_MAX); 12 bytes per pair
+int score_ids_host(DeviceIndex &x, const float *q, int64_t nq, const int64_t *ids, int64_t m, float *D, bool has_skip, int64_t skip) {
+    const PairPlane planes[] = {{ids, 8, &x.ws_ids}};
+    return pair_matrix_host(x, q, nq, m, planes, D, x.ws_D, has_skip, skip, [&](int64_t nqc, int64_t mc) {
+        return score_ids_device(x, (const float *)x.ws_q.p, nqc, (const int64_t *)x.ws_ids.p, mc, (float *)x.ws_D.p, x.stream);
+    });
+}
+// ref_score == null: rank_ids (ids: local row ids, -1 = padding); otherwise count_ahead with ids as the bounds (what a shard of a
+// multi-device index is asked: the scores come from the shard that owns the row).  20 bytes per pair either way.
+int rank_host(DeviceIndex &x, const float *q, int64_t nq, const int64_t *ids, const float *ref_score, int64_t m, int64_t *out) {
+    const PairPlane planes[] = {{ids, 8, &x.ws_ids}, {ref_score, 4, &x.ws_D}};
+    return pair_matrix_host(x, q, nq, m, planes, out, x.ws_I, false, 0, [&](int64_t nqc, int64_t mc) {
+        const float *qd = (const float *)x.ws_q.p;
+        const int64_t *id = (const int64_t *)x.ws_ids.p;
+        if (ref_score) return count_ahead_device(x, "count_ahead", qd, nqc, (const float *)x.ws_D.p, id, false, mc, (int64_t *)x.ws_I.p, x.stream);
+        return rank_ids_device(x, qd, nqc, id, mc, (int64_t *)x.ws_I.p, x.stream);
+    });
+}
+
+// ---- the caller's ids.  The first id outside [-1, ntotal) of a host matrix [rows][cols]: the host entry points refuse it (the
+// *_device ones cannot look).  `where` words its place: flat ("position %lld") or by (query, column); `pad` words what -1 is.
+enum class IdPlace { FLAT, QUERY_COLUMN };
+int check_host_ids(const char *what, const int64_t *ids, int64_t rows, int64_t cols, int64_t ntotal, IdPlace where, const char *pad = "a padding slot") {
+    for (int64_t i = 0; i < rows * cols; ++i) {
+        if (ids[i] >= -1 && ids[i] < ntotal) continue;
+        char place[80];
+        if (where == IdPlace::FLAT) snprintf(place, sizeof place, "position %lld", (long long)i);
+        else snprintf(place, sizeof place, "(query %lld, column %lld)", (long long)(i / cols), (long long)(i % cols));
+        return fail(HAC_ERR_INVALID, "%s: id %lld at %s is outside [0, %lld) (-1 = %s)", what, (long long)ids[i], place, (long long)ntotal, pad);
+    }
+    return HAC_OK;
+}
+
+// Global row id -> (shard, shard-local row) on an index of several devices: the inverse of remap_positions_kernel, on the host.
+// Every shard's share of every add() is a span; by first global row the spans tile [0, ntotal).
+struct RowLocator {
+    struct Span { int64_t global0, count, local0; int shard; };
+    int S;
+    std::vector<Span> spans;
+    std::vector<int64_t> before;   // [span][shard]: that shard's rows in the spans in front of this one
+    explicit RowLocator(const hac_index *idx) : S((int)idx->shards.size()) {
+        for (int s = 0; s < S; ++s)
+            for (const SpanDesc &sp : idx->spans[s]) spans.push_back(Span{(int64_t)sp.global0, (int64_t)sp.count, (int64_t)sp.local0, s});
+        std::sort(spans.begin(), spans.end(), [](const Span &a, const Span &b) { return a.global0 < b.global0; });
+        std::vector<int64_t> rows(S, 0);
+        for (const Span &sp : spans) {
+            before.insert(before.end(), rows.begin(), rows.end());
+            rows[sp.shard] += sp.count;
+        }
+    }
+    // The one pass over the caller's (checked) ids: per id the span that holds it, -1 for a padding slot.
+    std::vector<int32_t> locate(const int64_t *ids, size_t count) const {
+        std::vector<int32_t> at(count, -1);
+        const auto starts_behind = [](int64_t id, const Span &sp) { return id < sp.global0; };
+        for (size_t i = 0; i < count; ++i)   // the last span with global0 <= id
+            if (ids[i] >= 0) at[i] = (int32_t)(std::upper_bound(spans.begin(), spans.end(), ids[i], starts_behind) - spans.begin()) - 1;
+        return at;
+    }
+    // of an id and its span: the shard that holds the row (a padding slot: shard 0, which writes the all-ones row / -FLT_MAX) ...
+    int shard(int32_t at) const { return at < 0 ? 0 : spans[at].shard; }
+    // ... its row there (-1: padding) ...
+    int64_t local(int32_t at, int64_t id) const { return at < 0 ? -1 : spans[at].local0 + (id - spans[at].global0); }
+    // ... and b_s(id), the number of shard s's rows with a global id below id: the row itself on its own shard (a shard's local
+    // order is the global order), the rows of the spans in front on the others
+    int64_t rows_below(int32_t at, int64_t id, int s) const { return at < 0 ? -1 : s == spans[at].shard ? local(at, id) : before[(size_t)at * S + s]; }
+};
+
+// several devices: every shard scores the pairs whose row it holds (padding slots: shard 0) and leaves the others' slots of D alone
+int score_ids_shards(hac_index *idx, const RowLocator &loc, const std::vector<int32_t> &at, const float *q, int64_t nq, const int64_t *ids, int64_t m, float *D) {
+    constexpr int64_t NOT_MINE = -2;
+    std::vector<std::vector<int64_t>> local(loc.S, std::vector<int64_t>(at.size(), NOT_MINE));
+    for (size_t i = 0; i < at.size(); ++i) local[loc.shard(at[i])][i] = loc.local(at[i], ids[i]);
+    return for_each_shard(idx, [&](int si) { return score_ids_host(*idx->shards[si], q, nq, local[si].data(), m, D, true, NOT_MINE); });
+}
+}  // namespace
+
+extern "C" {
+
+int hac_index_reconstruct_ids(hac_index *idx, const int64_t *ids, int64_t n, float *out) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    if (n < 0 || (n > 0 && (!ids || !out))) return fail(HAC_ERR_INVALID, "reconstruct: bad arguments");
+    if (n == 0) return HAC_OK;
+    HAC_TRY(check_host_ids("reconstruct", ids, 1, n, idx->ntotal, IdPlace::FLAT));
+    const int S = (int)idx->shards.size();
+    if (S == 1) return read_rows_host(*idx->shards[0], ids, nullptr, 0, n, out);
+    const RowLocator loc(idx);
+    const std::vector<int32_t> at = loc.locate(ids, (size_t)n);
+    std::vector<std::vector<int64_t>> local(S), pos(S);
+    for (int64_t i = 0; i < n; ++i) {
+        const int sh = loc.shard(at[i]);
+        local[sh].push_back(loc.local(at[i], ids[i]));
+        pos[sh].push_back(i);
+    }
+    return for_each_shard(idx, [&](int si) { return read_rows_host(*idx->shards[si], local[si].data(), pos[si].data(), 0, (int64_t)local[si].size(), out); });
+}
+
+int hac_index_reconstruct(hac_index *idx, int64_t i0, int64_t n, float *out) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    if (i0 < 0 || n < 0 || i0 > idx->ntotal || n > idx->ntotal - i0)
+        return fail(HAC_ERR_INVALID, "reconstruct: rows [%lld, %lld + %lld) are not inside [0, %lld]", (long long)i0, (long long)i0, (long long)n,
+                    (long long)idx->ntotal);
+    if (n == 0) return HAC_OK;
+    if (!out) return fail(HAC_ERR_INVALID, "reconstruct: bad arguments");
+    if (idx->shards.size() == 1) return read_rows_host(*idx->shards[0], nullptr, nullptr, i0, n, out);
+    // several devices: consecutive rows alternate between the shards with every add(); the range goes by id, a chunk at a time
+    const int64_t chunk = idx->shards[0]->stage_rows();
+    std::vector<int64_t> ids((size_t)std::min(chunk, n));
+    for (int64_t done = 0; done < n; done += chunk) {
+        const int64_t m = std::min(chunk, n - done);
+        std::iota(ids.begin(), ids.begin() + m, i0 + done);
+        HAC_TRY(hac_index_reconstruct_ids(idx, ids.data(), m, out + (size_t)done * idx->d));
+    }
+    return HAC_OK;
+}
+
+int hac_index_reconstruct_device(hac_index *idx, const int64_t *ids_dev, int64_t i0, int64_t n, float *out_dev, void *hip_stream) {
+    return on_single_shard(idx, "reconstruct_device", [&](DeviceIndex &s) -> int {
+        if (n < 0 || (n > 0 && !out_dev)) return fail(HAC_ERR_INVALID, "reconstruct_device: bad arguments");
+        if (ids_dev) return rows_ids_device(s, ids_dev, n, out_dev, (hipStream_t)hip_stream);
+        return rows_range_device(s, i0, n, out_dev, (hipStream_t)hip_stream);
+    });
+}
+
+int hac_index_score_ids(hac_index *idx, const float *q, int64_t nq, const int64_t *ids, int64_t m, float *D) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q || !ids || !D))) return fail(HAC_ERR_INVALID, "score_ids: bad arguments");
+    if (nq == 0 || m == 0) return HAC_OK;
+    HAC_TRY(check_host_ids("score_ids", ids, nq, m, idx->ntotal, IdPlace::FLAT));
+    if (idx->shards.size() == 1) return score_ids_host(*idx->shards[0], q, nq, ids, m, D, false, 0);
+    const RowLocator loc(idx);
+    return score_ids_shards(idx, loc, loc.locate(ids, (size_t)(nq * m)), q, nq, ids, m, D);
+}
+
+int hac_index_score_ids_device(hac_index *idx, const float *q_dev, int64_t nq, const int64_t *ids_dev, int64_t m, float *D_dev, void *hip_stream) {
+    return on_single_shard(idx, "score_ids_device", [&](DeviceIndex &s) -> int {
+        if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q_dev || !ids_dev || !D_dev))) return fail(HAC_ERR_INVALID, "score_ids_device: bad arguments");
+        return score_ids_device(s, q_dev, nq, ids_dev, m, D_dev, (hipStream_t)hip_stream);
+    });
+}
+
+int hac_index_count_ahead_device(hac_index *idx, const float *q_dev, int64_t nq, const float *ref_score_dev, const int64_t *ref_bound_dev, int64_t m,
+                                 int64_t *count_dev, void *hip_stream) {
+    return on_single_shard(idx, "count_ahead_device", [&](DeviceIndex &s) -> int {
+        if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q_dev || !ref_score_dev || !ref_bound_dev || !count_dev)))
+            return fail(HAC_ERR_INVALID, "count_ahead_device: bad arguments");
+        return count_ahead_device(s, "count_ahead_device", q_dev, nq, ref_score_dev, ref_bound_dev, false, m, count_dev, (hipStream_t)hip_stream);
+    });
+}
+
+int hac_index_rank_ids_device(hac_index *idx, const float *q_dev, int64_t nq, const int64_t *ids_dev, int64_t m, int64_t *rank_dev, void *hip_stream) {
+    return on_single_shard(idx, "rank_ids_device", [&](DeviceIndex &s) -> int {
+        if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q_dev || !ids_dev || !rank_dev))) return fail(HAC_ERR_INVALID, "rank_ids_device: bad arguments");
+        return rank_ids_device(s, q_dev, nq, ids_dev, m, rank_dev, (hipStream_t)hip_stream);
+    });
+}
+
+int hac_index_rank_ids(hac_index *idx, const float *q, int64_t nq, const int64_t *ids, int64_t m, int64_t *rank) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q || !ids || !rank))) return fail(HAC_ERR_INVALID, "rank_ids: bad arguments");
+    if (nq == 0 || m == 0) return HAC_OK;
+    HAC_TRY(check_host_ids("rank_ids", ids, nq, m, idx->ntotal, IdPlace::QUERY_COLUMN));
+    const int S = (int)idx->shards.size();
+    if (S == 1) return rank_host(*idx->shards[0], q, nq, ids, nullptr, m, rank);
+    // Several devices.  The reference scores come from the shard that owns the row (score_ids_shards); every shard then counts
+    // its own rows ahead of (score, bound), the bound translated into its numbering (RowLocator::rows_below).  A shard's local
+    // order preserves the global order, so a tie still breaks by global row; the counts of the shards add up.
+    const size_t total = (size_t)(nq * m);
+    const RowLocator loc(idx);
+    const std::vector<int32_t> at = loc.locate(ids, total);
+    std::vector<float> scores(total);
+    HAC_TRY(score_ids_shards(idx, loc, at, q, nq, ids, m, scores.data()));
+    std::vector<std::vector<int64_t>> bounds(S, std::vector<int64_t>(total)), part(S, std::vector<int64_t>(total));
+    for (int si = 0; si < S; ++si)
+        for (size_t i = 0; i < total; ++i) bounds[si][i] = loc.rows_below(at[i], ids[i], si);
+    HAC_TRY(for_each_shard(idx, [&](int si) { return rank_host(*idx->shards[si], q, nq, bounds[si].data(), scores.data(), m, part[si].data()); }));
+    for (size_t i = 0; i < total; ++i) {
+        int64_t sum = 0;
+        for (int si = 0; si < S; ++si) sum = (sum < 0 || part[si][i] < 0) ? -1 : sum + part[si][i];   // (-1: padding or a NaN score, on every shard alike)
+        rank[i] = sum;
+    }
+    return HAC_OK;
+}
+
+}  // extern "C"

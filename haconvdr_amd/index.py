@@ -20,15 +20,39 @@ def _stream_ptr(stream):
     return ctypes.c_void_p(getattr(stream, "cuda_stream", stream))
 
 
-def _keep_alive(t, stream):
-    """The kernels read ``t`` asynchronously on ``stream`` (a torch stream, a raw hipStream_t or None = the
+def _keep_alive(stream, *tensors):
+    """The kernels read the tensors asynchronously on ``stream`` (a torch stream, a raw hipStream_t or None = the
     current stream): tell the caching allocator, or it may hand the memory out again too early."""
     import torch
     if stream is None:
         stream = torch.cuda.current_stream()
     elif not hasattr(stream, "cuda_stream"):
         stream = torch.cuda.ExternalStream(int(stream))
-    t.record_stream(stream)
+    for t in tensors:
+        t.record_stream(stream)
+
+
+# ---- the pointers the C ABI takes: of a float32 / int64 ndarray, of a CUDA tensor (None: null)
+def _f32p(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
+def _i64p(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+
+
+def _devp(t):
+    return ctypes.c_void_p() if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _host_results(shape):
+    """(D float32, I int64) of a host search"""
+    return np.empty(shape, np.float32), np.empty(shape, np.int64)
+
+
+def _device_results(shape, device):
+    import torch
+    return torch.empty(shape, dtype=torch.float32, device=device), torch.empty(shape, dtype=torch.int64, device=device)
 
 
 # ---- argument checks of the rows-by-id calls: no handle needed, a mistake raises ValueError before the library is called
@@ -59,12 +83,12 @@ def _as_queries(q, d, what):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
-def _score_args(q, ids, d):
-    """(q float32 [nq, d], ids int64 [nq, m]) of score_ids."""
-    q = _as_queries(q, d, "score_ids")
-    ids = _as_ids(ids, 2, "score_ids")
+def _pair_args(q, ids, d, what):
+    """(q float32 [nq, d], ids int64 [nq, m]) of score_ids / rank_ids."""
+    q = _as_queries(q, d, what)
+    ids = _as_ids(ids, 2, what)
     if ids.shape[0] != q.shape[0]:
-        raise ValueError(f"score_ids: {q.shape[0]} queries but ids of shape {ids.shape} (one list per query)")
+        raise ValueError(f"{what}: {q.shape[0]} queries but ids of shape {ids.shape} (one list per query)")
     return q, ids
 
 
@@ -94,26 +118,8 @@ def _queries_tensor(q, d, what):
     return q.contiguous().float()
 
 
-def _score_args_tensor(q, ids, d):
-    q = _queries_tensor(q, d, "score_ids_tensor")
-    ids = _ids_tensor(ids, 2, "score_ids_tensor")
-    if ids.shape[0] != q.shape[0]:
-        raise ValueError(f"score_ids_tensor: {q.shape[0]} queries but ids of shape {tuple(ids.shape)} (one list per query)")
-    if ids.device != q.device:
-        raise ValueError(f"score_ids_tensor: q on {q.device} but ids on {ids.device}")
-    return q, ids
-
-
-def _rank_args(q, ids, d):
-    """(q float32 [nq, d], ids int64 [nq, m]) of rank_ids."""
-    q = _as_queries(q, d, "rank_ids")
-    ids = _as_ids(ids, 2, "rank_ids")
-    if ids.shape[0] != q.shape[0]:
-        raise ValueError(f"rank_ids: {q.shape[0]} queries but ids of shape {ids.shape} (one list per query)")
-    return q, ids
-
-
-def _rank_args_tensor(q, ids, d, what="rank_ids_tensor"):
+def _pair_args_tensor(q, ids, d, what):
+    """(q float32 CUDA [nq, d], ids int64 CUDA [nq, m]) of score_ids_tensor / rank_ids_tensor / count_ahead_tensor."""
     q = _queries_tensor(q, d, what)
     ids = _ids_tensor(ids, 2, what)
     if ids.shape[0] != q.shape[0]:
@@ -126,7 +132,7 @@ def _rank_args_tensor(q, ids, d, what="rank_ids_tensor"):
 def _count_args_tensor(q, ref_scores, ref_bounds, d, what="count_ahead_tensor"):
     """(q float32 CUDA [nq, d], ref_scores float32 CUDA [nq, m], ref_bounds int64 CUDA [nq, m]) of count_ahead_tensor."""
     import torch
-    q, ref_bounds = _rank_args_tensor(q, ref_bounds, d, what)
+    q, ref_bounds = _pair_args_tensor(q, ref_bounds, d, what)
     if not isinstance(ref_scores, torch.Tensor) or not ref_scores.is_cuda:
         raise ValueError(f"{what}: ref_scores must be a CUDA tensor")
     if ref_scores.dtype != torch.float32:
@@ -207,7 +213,7 @@ class FlatIPIndex:
         x = np.ascontiguousarray(x, dtype=np.float32)
         if x.ndim != 2 or x.shape[1] != self.d:
             raise ValueError(f"add expects [n, {self.d}] float32, got {x.shape}")
-        _lib.check(_lib.lib().hac_index_add(self._h, x.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), x.shape[0]))
+        _lib.check(_lib.lib().hac_index_add(self._h, _f32p(x), x.shape[0]))
 
     def search(self, q, k):
         """D, I = index.search(query_embeddings, topN) -> float32 [nq,k], int64 [nq,k]."""
@@ -215,11 +221,8 @@ class FlatIPIndex:
         if q.ndim != 2 or q.shape[1] != self.d:
             raise ValueError(f"search expects [nq, {self.d}] float32, got {q.shape}")
         k = int(k)
-        D = np.empty((q.shape[0], k), np.float32)
-        I = np.empty((q.shape[0], k), np.int64)
-        _lib.check(_lib.lib().hac_index_search(self._h, q.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), q.shape[0], k,
-                                               D.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                               I.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        D, I = _host_results((q.shape[0], k))
+        _lib.check(_lib.lib().hac_index_search(self._h, _f32p(q), q.shape[0], k, _f32p(D), _i64p(I)))
         return D, I
 
     def search_excluding(self, q, k, exclude):
@@ -227,12 +230,8 @@ class FlatIPIndex:
         allowed; any other id outside [0, ntotal) raises HacError.  The search runs at k + e <= HAC_MAX_K (include/haconvdr.h);
         faiss: SearchParameters(sel=IDSelectorNot(IDSelectorBatch(ids))), one selector per query."""
         q, k, exclude = _exclude_args(q, k, exclude, self.d)
-        D = np.empty((q.shape[0], k), np.float32)
-        I = np.empty((q.shape[0], k), np.int64)
-        _lib.check(_lib.lib().hac_index_search_excluding(self._h, q.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), q.shape[0], k,
-                                                         exclude.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), exclude.shape[1],
-                                                         D.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                                         I.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        D, I = _host_results((q.shape[0], k))
+        _lib.check(_lib.lib().hac_index_search_excluding(self._h, _f32p(q), q.shape[0], k, _i64p(exclude), exclude.shape[1], _f32p(D), _i64p(I)))
         return D, I
 
     def reset(self):
@@ -249,7 +248,7 @@ class FlatIPIndex:
         if n is None:
             n = self.ntotal - i0
         out = np.empty((max(n, 0), self.d), np.float32)
-        _lib.check(_lib.lib().hac_index_reconstruct(self._h, i0, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        _lib.check(_lib.lib().hac_index_reconstruct(self._h, i0, n, _f32p(out)))
         return out
 
     def reconstruct_batch(self, ids):
@@ -257,8 +256,7 @@ class FlatIPIndex:
         of all-ones words, the NaN faiss writes there; any other id outside [0, ntotal) raises HacError."""
         ids = _as_ids(ids, 1, "reconstruct_batch")
         out = np.empty((ids.shape[0], self.d), np.float32)
-        _lib.check(_lib.lib().hac_index_reconstruct_ids(self._h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ids.shape[0],
-                                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        _lib.check(_lib.lib().hac_index_reconstruct_ids(self._h, _i64p(ids), ids.shape[0], _f32p(out)))
         return out
 
     def reconstruct(self, i):
@@ -274,11 +272,9 @@ class FlatIPIndex:
     def score_ids(self, q, ids):
         """Exact scores of named rows: q float32 [nq, d], ids int64 [nq, m] -> float32 [nq, m], the canonical score of every
         (q[i], row ids[i, j]) -- the bits a search returns for that pair.  -1 scores -FLT_MAX; NaN scores stay NaN."""
-        q, ids = _score_args(q, ids, self.d)
+        q, ids = _pair_args(q, ids, self.d, "score_ids")
         D = np.empty(ids.shape, np.float32)
-        _lib.check(_lib.lib().hac_index_score_ids(self._h, q.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), q.shape[0],
-                                                  ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ids.shape[1],
-                                                  D.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        _lib.check(_lib.lib().hac_index_score_ids(self._h, _f32p(q), q.shape[0], _i64p(ids), ids.shape[1], _f32p(D)))
         return D
 
     def rank_ids(self, q, ids):
@@ -286,11 +282,9 @@ class FlatIPIndex:
         ids[i, j] takes in an unbounded search of q[i] (order: score desc, row asc) -- no ceiling at HAC_MAX_K, and
         rank_ids(q, I)[i, j] == j for the I of any search.  -1 for the id -1 and for a row whose score is NaN (no search
         returns it); any other id outside [0, ntotal) raises HacError.  One pass over the rows per (16 queries, 8 ids)."""
-        q, ids = _rank_args(q, ids, self.d)
+        q, ids = _pair_args(q, ids, self.d, "rank_ids")
         R = np.empty(ids.shape, np.int64)
-        _lib.check(_lib.lib().hac_index_rank_ids(self._h, q.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), q.shape[0],
-                                                 ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ids.shape[1],
-                                                 R.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        _lib.check(_lib.lib().hac_index_rank_ids(self._h, _f32p(q), q.shape[0], _i64p(ids), ids.shape[1], _i64p(R)))
         return R
 
     # ---- device-resident variants (torch tensors on the index's GPU) -------
@@ -300,40 +294,28 @@ class FlatIPIndex:
         here before mixing in host-API calls."""
         assert x.is_cuda and x.dtype.is_floating_point and x.dim() == 2 and x.shape[1] == self.d
         x = x.contiguous().float()
-        _lib.check(_lib.lib().hac_index_add_device(self._h, ctypes.c_void_p(x.data_ptr()), x.shape[0], _stream_ptr(stream)))
-        _keep_alive(x, stream)
+        _lib.check(_lib.lib().hac_index_add_device(self._h, _devp(x), x.shape[0], _stream_ptr(stream)))
+        _keep_alive(stream, x)
 
     def search_tensor(self, q, k, id_map=None, stream=None):
         """q: torch float32 CUDA [nq, d] -> (D float32 [nq,k], I int64 [nq,k]) CUDA tensors,
         enqueued on the current stream (no host sync).  id_map: optional int64 CUDA
         tensor [ntotal], fuses ``passage_embedding2id[I]`` (:110)."""
-        import torch
         assert q.is_cuda and q.dim() == 2 and q.shape[1] == self.d
         q = q.contiguous().float()
-        D = torch.empty((q.shape[0], k), dtype=torch.float32, device=q.device)
-        I = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
-        mp = ctypes.c_void_p(id_map.data_ptr()) if id_map is not None else ctypes.c_void_p()
-        _lib.check(_lib.lib().hac_index_search_device(self._h, ctypes.c_void_p(q.data_ptr()), q.shape[0], int(k),
-                                                      ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()), mp,
-                                                      _stream_ptr(stream)))
-        for t in (q, D, I):
-            _keep_alive(t, stream)
+        D, I = _device_results((q.shape[0], k), q.device)
+        _lib.check(_lib.lib().hac_index_search_device(self._h, _devp(q), q.shape[0], int(k), _devp(D), _devp(I), _devp(id_map), _stream_ptr(stream)))
+        _keep_alive(stream, q, D, I)
         return D, I
 
     def search_excluding_tensor(self, q, k, exclude, id_map=None, stream=None):
         """search_tensor over (rows minus the query's excluded rows): exclude int64 CUDA [nq, e] ROW ids (not id_map's), any id
         outside [0, ntotal) is ignored.  No host sync; capturable after one call of the largest (nq, k + e)."""
-        import torch
         q, k, exclude = _exclude_args_tensor(q, k, exclude, self.d)
-        D = torch.empty((q.shape[0], k), dtype=torch.float32, device=q.device)
-        I = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
-        mp = ctypes.c_void_p(id_map.data_ptr()) if id_map is not None else ctypes.c_void_p()
-        _lib.check(_lib.lib().hac_index_search_excluding_device(self._h, ctypes.c_void_p(q.data_ptr()), q.shape[0], k,
-                                                                ctypes.c_void_p(exclude.data_ptr()), exclude.shape[1],
-                                                                ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()), mp,
-                                                                _stream_ptr(stream)))
-        for t in (q, exclude, D, I):
-            _keep_alive(t, stream)
+        D, I = _device_results((q.shape[0], k), q.device)
+        _lib.check(_lib.lib().hac_index_search_excluding_device(self._h, _devp(q), q.shape[0], k, _devp(exclude), exclude.shape[1], _devp(D), _devp(I),
+                                                                _devp(id_map), _stream_ptr(stream)))
+        _keep_alive(stream, q, exclude, D, I)
         return D, I
 
     def search_keys_tensor(self, q, k, pos_base=0, stream=None):
@@ -341,11 +323,8 @@ class FlatIPIndex:
         import torch
         q = q.contiguous().float()
         keys = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
-        _lib.check(_lib.lib().hac_index_search_keys_device(self._h, ctypes.c_void_p(q.data_ptr()), q.shape[0], int(k),
-                                                           ctypes.c_void_p(keys.data_ptr()), int(pos_base),
-                                                           _stream_ptr(stream)))
-        for t in (q, keys):
-            _keep_alive(t, stream)
+        _lib.check(_lib.lib().hac_index_search_keys_device(self._h, _devp(q), q.shape[0], int(k), _devp(keys), int(pos_base), _stream_ptr(stream)))
+        _keep_alive(stream, q, keys)
         return keys
 
     def reconstruct_tensor(self, ids=None, i0=0, n=None, stream=None):
@@ -357,40 +336,33 @@ class FlatIPIndex:
             i0, n = _as_range(i0, n, "reconstruct_tensor")
             if n is None:
                 n = self.ntotal - i0
-            idp = ctypes.c_void_p()
             dev = torch.device("cuda", self.devices[0])
         else:
             ids = _ids_tensor(ids, 1, "reconstruct_tensor")
-            i0, n, idp, dev = 0, ids.shape[0], ctypes.c_void_p(ids.data_ptr()), ids.device
+            i0, n, dev = 0, ids.shape[0], ids.device
         out = torch.empty((max(n, 0), self.d), dtype=torch.float32, device=dev)
-        _lib.check(_lib.lib().hac_index_reconstruct_device(self._h, idp, i0, n, ctypes.c_void_p(out.data_ptr()), _stream_ptr(stream)))
-        for t in (ids, out):
-            if t is not None:
-                _keep_alive(t, stream)
+        _lib.check(_lib.lib().hac_index_reconstruct_device(self._h, _devp(ids), i0, n, _devp(out), _stream_ptr(stream)))
+        _keep_alive(stream, out, *(() if ids is None else (ids,)))
         return out
 
     def score_ids_tensor(self, q, ids, stream=None):
         """q: float32 CUDA [nq, d], ids: int64 CUDA [nq, m] -> float32 CUDA [nq, m]; no host sync.  Any id outside
         [0, ntotal), -1 included, scores -FLT_MAX."""
         import torch
-        q, ids = _score_args_tensor(q, ids, self.d)
+        q, ids = _pair_args_tensor(q, ids, self.d, "score_ids_tensor")
         D = torch.empty(tuple(ids.shape), dtype=torch.float32, device=q.device)
-        _lib.check(_lib.lib().hac_index_score_ids_device(self._h, ctypes.c_void_p(q.data_ptr()), q.shape[0], ctypes.c_void_p(ids.data_ptr()),
-                                                         ids.shape[1], ctypes.c_void_p(D.data_ptr()), _stream_ptr(stream)))
-        for t in (q, ids, D):
-            _keep_alive(t, stream)
+        _lib.check(_lib.lib().hac_index_score_ids_device(self._h, _devp(q), q.shape[0], _devp(ids), ids.shape[1], _devp(D), _stream_ptr(stream)))
+        _keep_alive(stream, q, ids, D)
         return D
 
     def rank_ids_tensor(self, q, ids, stream=None):
         """q: float32 CUDA [nq, d], ids: int64 CUDA [nq, m] -> int64 CUDA [nq, m], rank_ids without a host sync.  Any id outside
         [0, ntotal), -1 included, ranks -1.  Capturable after one call of the largest (nq, m)."""
         import torch
-        q, ids = _rank_args_tensor(q, ids, self.d)
+        q, ids = _pair_args_tensor(q, ids, self.d, "rank_ids_tensor")
         R = torch.empty(tuple(ids.shape), dtype=torch.int64, device=q.device)
-        _lib.check(_lib.lib().hac_index_rank_ids_device(self._h, ctypes.c_void_p(q.data_ptr()), q.shape[0], ctypes.c_void_p(ids.data_ptr()),
-                                                        ids.shape[1], ctypes.c_void_p(R.data_ptr()), _stream_ptr(stream)))
-        for t in (q, ids, R):
-            _keep_alive(t, stream)
+        _lib.check(_lib.lib().hac_index_rank_ids_device(self._h, _devp(q), q.shape[0], _devp(ids), ids.shape[1], _devp(R), _stream_ptr(stream)))
+        _keep_alive(stream, q, ids, R)
         return R
 
     def count_ahead_tensor(self, q, ref_scores, ref_bounds, stream=None):
@@ -401,11 +373,9 @@ class FlatIPIndex:
         import torch
         q, ref_scores, ref_bounds = _count_args_tensor(q, ref_scores, ref_bounds, self.d)
         C = torch.empty(tuple(ref_bounds.shape), dtype=torch.int64, device=q.device)
-        _lib.check(_lib.lib().hac_index_count_ahead_device(self._h, ctypes.c_void_p(q.data_ptr()), q.shape[0], ctypes.c_void_p(ref_scores.data_ptr()),
-                                                           ctypes.c_void_p(ref_bounds.data_ptr()), ref_bounds.shape[1],
-                                                           ctypes.c_void_p(C.data_ptr()), _stream_ptr(stream)))
-        for t in (q, ref_scores, ref_bounds, C):
-            _keep_alive(t, stream)
+        _lib.check(_lib.lib().hac_index_count_ahead_device(self._h, _devp(q), q.shape[0], _devp(ref_scores), _devp(ref_bounds), ref_bounds.shape[1],
+                                                           _devp(C), _stream_ptr(stream)))
+        _keep_alive(stream, q, ref_scores, ref_bounds, C)
         return C
 
     def search_and_reconstruct_tensor(self, q, k, stream=None):
@@ -445,8 +415,7 @@ def merge_keys(lists, stream=None):
     L, nq, k = lists.shape
     lists = lists.contiguous()
     out = torch.empty((nq, k), dtype=torch.int64, device=lists.device)
-    _lib.check(_lib.lib().hac_merge_keys_device(lists.device.index or 0, ctypes.c_void_p(lists.data_ptr()), L, nq, k,
-                                                ctypes.c_void_p(out.data_ptr()), _stream_ptr(stream)))
+    _lib.check(_lib.lib().hac_merge_keys_device(lists.device.index or 0, _devp(lists), L, nq, k, _devp(out), _stream_ptr(stream)))
     return out
 
 
@@ -456,23 +425,17 @@ def filter_keys(keys, exclude_pos, k, stream=None):
     import torch
     keys, exclude_pos, k = _filter_args(keys, exclude_pos, k)
     out = torch.empty((keys.shape[0], k), dtype=torch.int64, device=keys.device)
-    _lib.check(_lib.lib().hac_filter_keys_device(keys.device.index or 0, ctypes.c_void_p(keys.data_ptr()), keys.shape[0], keys.shape[1],
-                                                 ctypes.c_void_p(exclude_pos.data_ptr()), exclude_pos.shape[1], k,
-                                                 ctypes.c_void_p(out.data_ptr()), _stream_ptr(stream)))
-    for t in (keys, exclude_pos, out):
-        _keep_alive(t, stream)
+    _lib.check(_lib.lib().hac_filter_keys_device(keys.device.index or 0, _devp(keys), keys.shape[0], keys.shape[1], _devp(exclude_pos),
+                                                 exclude_pos.shape[1], k, _devp(out), _stream_ptr(stream)))
+    _keep_alive(stream, keys, exclude_pos, out)
     return out
 
 
 def keys_to_results(keys, id_map=None, stream=None):
     """keys [nq,k] -> (D float32, I int64); id_map optional int64 CUDA tensor (position -> id)."""
-    import torch
     keys = keys.contiguous()
-    D = torch.empty(keys.shape, dtype=torch.float32, device=keys.device)
-    I = torch.empty(keys.shape, dtype=torch.int64, device=keys.device)
-    mp = ctypes.c_void_p(id_map.data_ptr()) if id_map is not None else ctypes.c_void_p()
-    _lib.check(_lib.lib().hac_keys_to_results_device(keys.device.index or 0, ctypes.c_void_p(keys.data_ptr()), keys.numel(), mp,
-                                                     ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()),
+    D, I = _device_results(keys.shape, keys.device)
+    _lib.check(_lib.lib().hac_keys_to_results_device(keys.device.index or 0, _devp(keys), keys.numel(), _devp(id_map), _devp(D), _devp(I),
                                                      _stream_ptr(stream)))
     return D, I
 

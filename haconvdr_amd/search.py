@@ -230,16 +230,20 @@ class ResidentCorpus:
         at = np.minimum(np.searchsorted(sorted_ids, pid, side="left"), len(sorted_ids) - 1)
         return np.where(sorted_ids[at] == pid, order[at], -1).astype(np.int64)
 
-    def score(self, query_embeddings, passage_ids):
-        """Exact scores of named passages -- dense re-ranking of another system's run (a BM25 top-1000, the gold passages):
-        query_embeddings float32 [nq,768], passage_ids int64 [nq,m] -> float64 [nq,m], the score search() gives that pair;
-        -FLT_MAX where the passage is in no block."""
+    def _pairs(self, query_embeddings, passage_ids, what):
+        """(host queries, rows int64 [nq, m]) of score / rank"""
         import torch
         q = query_embeddings.cpu().numpy() if isinstance(query_embeddings, torch.Tensor) else query_embeddings
         pid = np.asarray(passage_ids)
         if pid.ndim != 2:
-            raise ValueError(f"score: passage_ids must be [nq, m], got shape {pid.shape}")
-        return self.index.score_ids(q, self.rows_of(pid)).astype(np.float64)
+            raise ValueError(f"{what}: passage_ids must be [nq, m], got shape {pid.shape}")
+        return q, self.rows_of(pid)
+
+    def score(self, query_embeddings, passage_ids):
+        """Exact scores of named passages -- dense re-ranking of another system's run (a BM25 top-1000, the gold passages):
+        query_embeddings float32 [nq,768], passage_ids int64 [nq,m] -> float64 [nq,m], the score search() gives that pair;
+        -FLT_MAX where the passage is in no block."""
+        return self.index.score_ids(*self._pairs(query_embeddings, passage_ids, "score")).astype(np.float64)
 
     def rank(self, query_embeddings, passage_ids):
         """Exact corpus rank of named passages: query_embeddings float32 [nq,768], passage_ids int64 [nq,m] EXTERNAL ids ->
@@ -247,12 +251,7 @@ class ResidentCorpus:
         the id (or the row's score is NaN).  The rank is over ROWS, not over de-duplicated passage ids: an id several rows
         carry resolves to the first of them (rows_of), and the other rows that carry it count as rows in front or behind like
         any other -- the TREC writer's per-query de-duplication (trec.output_test_res) is not applied."""
-        import torch
-        q = query_embeddings.cpu().numpy() if isinstance(query_embeddings, torch.Tensor) else query_embeddings
-        pid = np.asarray(passage_ids)
-        if pid.ndim != 2:
-            raise ValueError(f"rank: passage_ids must be [nq, m], got shape {pid.shape}")
-        return self.index.rank_ids(q, self.rows_of(pid))
+        return self.index.rank_ids(*self._pairs(query_embeddings, passage_ids, "rank"))
 
     def reconstruct(self, passage_ids):
         """passage_ids int64 [n] -> float32 [n,768], the embeddings as the blocks hold them (all-ones words for an absent id)."""

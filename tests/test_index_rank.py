@@ -48,10 +48,10 @@ def test_count_kernels_use_no_scratch():
 # argument checks (no handle)
 def test_rank_args_pass_good_arguments_through():
     from haconvdr_amd import index
-    q, ids = index._rank_args(np.zeros((3, 96), np.float64), np.zeros((3, 5), np.int32), 96)
+    q, ids = index._pair_args(np.zeros((3, 96), np.float64), np.zeros((3, 5), np.int32), 96, "rank_ids")
     assert q.dtype == np.float32 and ids.dtype == np.int64 and ids.shape == (3, 5) and ids.flags.c_contiguous
-    assert index._rank_args(np.zeros((3, 96)), np.zeros((3, 0), np.int64), 96)[1].shape == (3, 0)
-    assert index._rank_args(np.zeros((0, 96)), np.zeros((0, 4), np.int64), 96)[0].shape == (0, 96)
+    assert index._pair_args(np.zeros((3, 96)), np.zeros((3, 0), np.int64), 96, "rank_ids")[1].shape == (3, 0)
+    assert index._pair_args(np.zeros((0, 96)), np.zeros((0, 4), np.int64), 96, "rank_ids")[0].shape == (0, 96)
 
 
 @pytest.mark.parametrize("q, ids", [
@@ -66,7 +66,7 @@ def test_rank_args_pass_good_arguments_through():
 def test_rank_args_raise_value_error(q, ids):
     from haconvdr_amd import index
     with pytest.raises(ValueError):
-        index._rank_args(q, ids, 96)
+        index._pair_args(q, ids, 96, "rank_ids")
 
 
 def test_tensor_checks_refuse_host_tensors():
@@ -74,9 +74,9 @@ def test_tensor_checks_refuse_host_tensors():
     import torch
     from haconvdr_amd import index
     with pytest.raises(ValueError):
-        index._rank_args_tensor(torch.zeros(3, 96), torch.zeros(3, 5, dtype=torch.int64), 96)
+        index._pair_args_tensor(torch.zeros(3, 96), torch.zeros(3, 5, dtype=torch.int64), 96, "rank_ids_tensor")
     with pytest.raises(ValueError):
-        index._rank_args_tensor(np.zeros((3, 96), np.float32), np.zeros((3, 5), np.int64), 96)
+        index._pair_args_tensor(np.zeros((3, 96), np.float32), np.zeros((3, 5), np.int64), 96, "rank_ids_tensor")
     with pytest.raises(ValueError):
         index._count_args_tensor(torch.zeros(3, 96), torch.zeros(3, 5), torch.zeros(3, 5, dtype=torch.int64), 96)
 

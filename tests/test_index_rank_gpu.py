@@ -12,7 +12,7 @@ import pytest
 
 from haconvdr_amd import synth
 from tests import rank_ref
-from tests.test_index_rows_gpu import hostile_corpus
+from tests.test_index_rows_gpu import PAIR_MC, STAGE_BYTES, hostile_corpus, pair_chunk_corpus, pair_chunk_ids
 from tests.test_search_plans_gpu import _adversarial, _index
 
 pytestmark = pytest.mark.gpu
@@ -356,3 +356,28 @@ def test_resident_corpus_rank(oracle):
     np.testing.assert_array_equal(got, want)
     with pytest.raises(ValueError):
         rc.rank(q, ext)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 12. the host form across both of its chunk loops (sizes: tests/test_index_rows_gpu.py, 11.): QC = 64 MiB // (2^20 * 20 +
+# 4d) = 3 queries and 2^20 columns at a time.  A column chunk of 2^20 ids is 131072 chunks of MT = 8: the launch loop steps
+# over its 65535-wide grid limit twice.  Rows 5 and 120 are identical and lie on different shards of the two-shard index.
+@pytest.mark.parametrize("devices", [(0,), (0, 0)])
+def test_ranks_across_both_chunk_loops(devices, oracle):
+    x, q6 = pair_chunk_corpus()
+    n, d = x.shape
+    nq = 4
+    q = q6[:nq]
+    assert STAGE_BYTES // (PAIR_MC * 20 + 4 * d) == 3                   # query chunks 3 + 1, column chunks 2^20 + 1
+    ids = pair_chunk_ids(0xC53, nq, n)
+    assert ids.min() == -1 and ids.max() == n - 1
+    table = rank_ref.rank_ids_from_scores(rank_ref.canon_scores(oracle, x, q), np.tile(np.arange(n, dtype=np.int64), (nq, 1)))
+    assert (table[:, 120] == table[:, 5] + 1).all()                     # the tie pair: neighbours, the lower row first
+    want = np.take_along_axis(table, np.clip(ids, 0, None), 1)
+    want[ids < 0] = -1
+    idx = _index(d, x, devices=devices)
+    got = idx.rank_ids(q, ids)
+    assert got.dtype == np.int64
+    np.testing.assert_array_equal(got, want)
+    assert PAIR_MC // parse_plan(idx.last_plan())["MT"] > 2 * 65535     # (the plan is the last column chunk's: MT alone is read)
+    idx.check_status()

@@ -105,7 +105,7 @@ def test_score_args_check():
     from haconvdr_amd import index
     q = np.zeros((3, 96), np.float64)
     ids = np.zeros((3, 5), np.int32)
-    qq, ii = index._score_args(q, ids, 96)
+    qq, ii = index._pair_args(q, ids, 96, "score_ids")
     assert qq.dtype == np.float32 and ii.dtype == np.int64 and qq.shape == (3, 96) and ii.shape == (3, 5)
     for bad_q, bad_ids in ((np.zeros((3, 95)), ids),                       # wrong dimension
                            (np.zeros(96), ids),                            # one query must still be [1, d]
@@ -115,7 +115,7 @@ def test_score_args_check():
                            (np.zeros((3, 96), np.complex64), ids),
                            (np.zeros((3, 96), object), ids)):
         with pytest.raises(ValueError):
-            index._score_args(bad_q, bad_ids, 96)
+            index._pair_args(bad_q, bad_ids, 96, "score_ids")
 
 
 @pytest.mark.parametrize("k", [0, -1, 2049, 1.5, "10", True])
@@ -137,5 +137,5 @@ def test_tensor_checks_refuse_host_tensors_and_wrong_dtypes():
     with pytest.raises(ValueError):
         index._queries_tensor(torch.zeros(2, 96), 96, "test")
     with pytest.raises(ValueError):
-        index._score_args_tensor(torch.zeros(2, 96), torch.zeros(2, 3, dtype=torch.int64), 96)
+        index._pair_args_tensor(torch.zeros(2, 96), torch.zeros(2, 3, dtype=torch.int64), 96, "score_ids_tensor")
     # (dtype and rank mistakes on real CUDA tensors: tests/test_index_rows_gpu.py)

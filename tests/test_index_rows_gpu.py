@@ -473,3 +473,72 @@ def test_resident_corpus_scores_and_reconstructs_by_passage_id(tmp_path, oracle)
         rc.rows_of(np.array([1.5]))
     with pytest.raises(ValueError):
         rc.score(q, pids[0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 11. the host forms across their staging chunks.  The sizes follow from the host code: rows are staged stage_rows() =
+# 64 MiB / 4d (down to a multiple of 64) at a time; a pair matrix goes MC = 2^20 columns and QC = 64 MiB // (MC *
+# bytes per pair + 4d) queries at a time.  One device, and two shards on one device (the positions scatter of
+# reconstruct_batch, the write-back that leaves the other shard's slots alone).
+STAGE_BYTES, PAIR_MC = 64 << 20, 1 << 20
+_CHUNKED = {}
+
+
+def stage_chunk_corpus():
+    """d = 1024 (the widest row: the fewest rows per chunk), one full staging chunk + one group + one row"""
+    if "rows" not in _CHUNKED:
+        d = 1024
+        chunk = STAGE_BYTES // (4 * d) // 64 * 64
+        assert chunk == 16384
+        _CHUNKED["rows"] = hostile_corpus(0xC40, chunk + 65, d)
+    return _CHUNKED["rows"]
+
+
+def pair_chunk_corpus():
+    """(x [130, 32] finite with rows 5 and 120 identical -- on different shards of a two-shard index --, 6 queries)"""
+    if "pairs" not in _CHUNKED:
+        d, n = 32, 130
+        x = synth.embeddings(0xC50, n, d)
+        x[120] = x[5]
+        _CHUNKED["pairs"] = (x, synth.embeddings(0xC51, 6, d))
+    return _CHUNKED["pairs"]
+
+
+def pair_chunk_ids(seed, nq, n):
+    """int64 [nq, 2^20 + 1] over [-1, n)"""
+    m = PAIR_MC + 1
+    return (synth.uniform_u32(seed, nq * m) % np.uint32(n + 1)).astype(np.int64).reshape(nq, m) - 1
+
+
+@pytest.mark.parametrize("devices", [(0,), (0, 0)])
+def test_rows_across_a_staging_chunk(devices):
+    x = stage_chunk_corpus()
+    n, d = x.shape
+    idx = _index(d, x, devices=devices)
+    assert_bits(idx.reconstruct_n(), x, "whole index: two chunks")
+    assert_bits(idx.reconstruct_n(16383, 3), x[16383:16386], "a range across the chunk edge")
+    perm = np.argsort(synth.uniform_u32(0xC41, n), kind="stable").astype(np.int64)
+    assert sorted(perm.tolist()) == list(range(n))
+    pad = np.array([0, 64, 16383, 16384, n - 1])
+    perm[pad] = -1
+    w = bits(idx.reconstruct_batch(perm))
+    assert (w[pad] == ONES).all()
+    keep = perm >= 0
+    np.testing.assert_array_equal(w[keep], bits(x[perm[keep]]))
+    idx.check_status()
+
+
+@pytest.mark.parametrize("devices", [(0,), (0, 0)])
+def test_scores_across_both_chunk_loops(devices, oracle):
+    x, q = pair_chunk_corpus()
+    n, d = x.shape
+    nq = len(q)
+    assert STAGE_BYTES // (PAIR_MC * 12 + 4 * d) == 5 and nq == 6       # query chunks 5 + 1, column chunks 2^20 + 1
+    ids = pair_chunk_ids(0xC52, nq, n)
+    assert ids.min() == -1 and ids.max() == n - 1 and (ids[:, -1] >= 0).any()
+    table = canon(oracle.ip_scores(x, q))
+    want = np.take_along_axis(table, np.clip(ids, 0, None), 1)
+    want[ids < 0] = -FMAX
+    idx = _index(d, x, devices=devices)
+    assert_bits(idx.score_ids(q, ids), want)
+    idx.check_status()

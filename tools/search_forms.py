@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Development: one search per form of the index's host driver (exact kernels, prefilter with its tile / chunk / pass forms,
-the host- and the device-decided fallback, a captured search, shards, the debug options), each on the smallest corpus that
-reaches the form.  Per case one line: name, last_plan(), sha256 of the D and I bytes.  Two libraries that drive the same
+the host- and the device-decided fallback, a captured search, shards, the by-id calls and their refusals, the debug options),
+each on the smallest corpus that reaches the form.  Per case one line: name, last_plan(), sha256 of the D and I bytes.  Two libraries that drive the same
 kernels the same way print the same lines (HAC_LIBRARY_PATH picks the library); under `rocprofv3 --kernel-trace` the run
 gives the launch sequence to compare.
   [HAC_LIBRARY_PATH=other/libhaconvdr.so] python tools/search_forms.py"""
+import ctypes
 import hashlib
 import os
 import sys
@@ -122,6 +123,86 @@ def main():
     report("shards search", idx, D, I)
     report("shards reconstruct", None, idx.reconstruct_batch(I[0]))
     report("shards score_ids", None, idx.score_ids(qs, I))
+
+    # ---- the by-id calls and search_excluding, host and tensor form, on one shard and on the two above; then every refusal
+    # of theirs with its code and full message
+    def refused(name, call):
+        try:
+            call()
+            raise AssertionError(f"{name}: not refused")
+        except _lib.HacError as e:
+            print(f"refused {name} | code {e.code}: {e}", flush=True)
+        except ValueError as e:
+            print(f"refused {name} | ValueError: {e}", flush=True)
+
+    def cuda(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+    def cpu(t):
+        torch.cuda.synchronize()
+        return t.cpu().numpy()
+
+    one = FlatIPIndex(768)
+    one.add(xs[:1000])
+    one.add(xs[1000:1001])
+    one.add(xs[1001:])
+    n = len(xs)
+    ids = (synth.uniform_u32(31339, 6 * 50) % np.uint32(n + 1)).astype(np.int64).reshape(6, 50) - 1
+    ids[0, :2] = (7, 1507)                           # a pair of identical rows
+    excl = I[:, :7].copy()
+    excl[:, 3] = -1
+    for name, ix in (("one", one), ("shards", idx)):
+        report(f"{name} reconstruct_n", None, ix.reconstruct_n(), ix.reconstruct_n(999, 5))
+        report(f"{name} reconstruct_batch", None, ix.reconstruct_batch(ids[1]))
+        report(f"{name} score_ids", None, ix.score_ids(qs, ids))
+        report(f"{name} rank_ids", ix, ix.rank_ids(qs, ids))
+        report(f"{name} search_excluding", ix, *ix.search_excluding(qs, 100, excl))
+    qt, it = cuda(qs), cuda(ids)
+    report("one reconstruct_tensor", None, cpu(one.reconstruct_tensor(it[1])), cpu(one.reconstruct_tensor(i0=999, n=5)))
+    St = one.score_ids_tensor(qt, it)
+    report("one score_ids_tensor", None, cpu(St))
+    report("one rank_ids_tensor", one, cpu(one.rank_ids_tensor(qt, it)))
+    report("one count_ahead_tensor", one, cpu(one.count_ahead_tensor(qt, St, it)))
+    report("one search_excluding_tensor", one, *[cpu(t) for t in one.search_excluding_tensor(qt, 100, cuda(excl))])
+    bad = ids.copy()
+    bad[2, 5] = n
+    for name, ix in (("one", one), ("shards", idx)):
+        refused(f"{name} reconstruct_batch id", lambda: ix.reconstruct_batch(bad[2]))
+        refused(f"{name} reconstruct_n range", lambda: ix.reconstruct_n(n - 1, 2))
+        refused(f"{name} score_ids id", lambda: ix.score_ids(qs, bad))
+        refused(f"{name} rank_ids id", lambda: ix.rank_ids(qs, bad))
+        refused(f"{name} search_excluding id", lambda: ix.search_excluding(qs, 10, bad[:, :9]))
+        refused(f"{name} search_excluding k + e", lambda: ix.search_excluding(qs, 2040, excl.repeat(2, axis=1)))
+    refused("shards reconstruct_tensor", lambda: idx.reconstruct_tensor(it[1]))
+    refused("shards reconstruct_tensor range", lambda: idx.reconstruct_tensor(i0=0, n=4))
+    refused("shards score_ids_tensor", lambda: idx.score_ids_tensor(qt, it))
+    refused("shards rank_ids_tensor", lambda: idx.rank_ids_tensor(qt, it))
+    refused("shards count_ahead_tensor", lambda: idx.count_ahead_tensor(qt, St, it))
+    refused("shards search_excluding_tensor", lambda: idx.search_excluding_tensor(qt, 10, cuda(excl)))
+    refused("one reconstruct_tensor range", lambda: one.reconstruct_tensor(i0=n - 1, n=2))
+    # (what the Python layer refuses first, and pointers it always aligns: the C entry points themselves)
+    L, vp = _lib.lib(), ctypes.c_void_p
+    out = torch.empty((6, 50, 2), dtype=torch.int64, device="cuda")
+    st = vp(torch.cuda.current_stream().cuda_stream)
+    Dh, Ih = np.empty((6, 2040), np.float32), np.empty((6, 2040), np.int64)
+    f32p, i64p = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)
+    for name, call in (
+            ("C search_excluding k + e", lambda: L.hac_index_search_excluding(one._h, qs.ctypes.data_as(f32p), 6, 2040, excl.ctypes.data_as(i64p), 9,
+                                                                               Dh.ctypes.data_as(f32p), Ih.ctypes.data_as(i64p))),
+            ("C search_excluding_device k + e", lambda: L.hac_index_search_excluding_device(one._h, vp(qt.data_ptr()), 6, 2040, vp(it.data_ptr()), 9,
+                                                                                             vp(out.data_ptr()), vp(out.data_ptr()), vp(), st)),
+            ("C reconstruct_device out + 4", lambda: L.hac_index_reconstruct_device(one._h, vp(it.data_ptr()), 0, 1, vp(out.data_ptr() + 4), st)),
+            ("C reconstruct_device range out + 4", lambda: L.hac_index_reconstruct_device(one._h, vp(), 0, 1, vp(out.data_ptr() + 4), st)),
+            ("C score_ids_device q + 4", lambda: L.hac_index_score_ids_device(one._h, vp(qt.data_ptr() + 4), 1, vp(it.data_ptr()), 50, vp(out.data_ptr()), st)),
+            ("C rank_ids_device q + 4", lambda: L.hac_index_rank_ids_device(one._h, vp(qt.data_ptr() + 4), 1, vp(it.data_ptr()), 50, vp(out.data_ptr()), st)),
+            ("C count_ahead_device q + 4", lambda: L.hac_index_count_ahead_device(one._h, vp(qt.data_ptr() + 4), 1, vp(St.data_ptr()), vp(it.data_ptr()), 50,
+                                                                                   vp(out.data_ptr()), st)),
+            ("C score_ids_device null", lambda: L.hac_index_score_ids_device(one._h, vp(), 1, vp(it.data_ptr()), 50, vp(out.data_ptr()), st)),
+            ("C rank_ids null", lambda: L.hac_index_rank_ids(one._h, None, 1, ids.ctypes.data_as(i64p), 50, Ih.ctypes.data_as(i64p)))):
+        refused(name, lambda: _lib.check(call()))
+    torch.cuda.synchronize()
+    one.check_status()
+    idx.check_status()
 
     # ---- debug options: an allocation that finds the device full takes the row copies back (rescore_rows = 1: the next search
     # builds them again); a pass bound that is reached
