@@ -33,6 +33,29 @@
 //     use than the weight rows (measured: the k-loop with every DMA redirected to an L2-resident tile was 12-17 % faster).
 //     The stream continues across output tiles (persistent workgroups, XCD-aware tile runs), so neither the first load of a
 //     tile nor the epilogue's stores stall the matrix pipe.
+//   * QKV and FFN-up (EPI != EPI8_RESID) run ONE phase per k-tile and group instead of the two described above: DMA pieces + 16 reads +
+//     lgkmcnt(0) | s_barrier | 64 MFMAs with the eight A_1 reads woven in (into the registers A_0 was in: no register more) | s_barrier
+//     -- two barrier intervals per k-tile, not four.  There group 0 stages the WEIGHTS and group 1 the ACTIVATIONS: each operand is staged
+//     by the group that reads it LAST, so that group's own program order, not a barrier, stands between its last read of a slot and the
+//     restage, and a whole k-tile goes out in the one loading part that follows.  Barriers b1, b2, ... of a tile, interval I_n between
+//     b_n and b_n+1; L(T) = loading part, M(T) = matrix part of k-tile T; group 0: L(T) in I_2T, M(T) in I_2T+1; group 1 one later:
+//         k-tile T   group 0 reads in   group 1 reads in   slot free from   restaged by, in            with
+//         W_0, W_1   I_2T               I_2T+1             I_2T+2           group 0, L(T+1) = I_2T+2   W(T+2)
+//         A_0        I_2T               I_2T+1             I_2T+2           group 1, L(T+1) = I_2T+3   A_0(T+3)
+//         A_1        I_2T+1 (woven)     I_2T+2 (woven)     I_2T+3           group 1, L(T+1) = I_2T+3   A_1(T+3)
+//       (every read retired, lgkmcnt(0), before the barrier that closes its interval).  Look-ahead, always the staging group's own vmcnt
+//       in front of the barrier behind which the first reader starts:
+//         W(T+1)   issued at the head of group 0's L(T), I_2T     vmcnt(0) at the END of group 0's M(T), I_2T+1; first read I_2T+2:
+//                  ~1.7 long intervals, ~2200 cycles (two-phase form: ~1500)
+//         A(T+2)   issued at the head of group 1's L(T), I_2T+1   vmcnt(8) -- all but L(T+1)'s own pieces -- at the end of group 1's
+//                  L(T+1), I_2T+3; first read (A_0, by group 0) I_2T+4: ~2.7 long intervals, ~3500 cycles (two-phase form: ~3000)
+//     Seams, prologue, stream end: every tile's k-loop starts from A and W k-tiles 0 and 1 landed (prologue: 16 pieces per wave).  Group 1
+//     issues A(T+2) in every L(T) (T = KT-2, KT-1: the next tile's k-tiles 0, 1); group 0 issues W(T+1) in L(T) for T >= 1 and the next
+//     tile's k-tile 1 at the seam, where both groups drain BEFORE the epilogue's stores.  A tile's first k-tile has no vmcnt wait (it
+//     would wait for the previous epilogue's stores).  A loading part that issued nothing (h_left) waits vmcnt(0).
+//     Measured: a steady QKV k-tile 2460 - 2700 cycles against 3100; 512000 rows: QKV 1.72 -> 1.63 ms, FFN-up 2.38 -> 2.28 ms.  With the
+//     two-phase roles (weights landed inside the loading part that issued them) group 1 waited 370 - 480 cycles per k-tile: +1 %; weight
+//     pieces at the head of the matrix part cost 100 - 120 cycles each there: slower than two phases (LABNOTES, "gemm8: one phase").
 //   * accumulators are held TRANSPOSED (MFMA A operand = W rows, B operand = activation rows): lane (m = lane & 15,
 //     g = lane >> 4) owns, for token row m, output features 4g .. 4g+3 of every 16-feature tile -- four consecutive
 //     fp32 = one 16-byte access to the residual stream, and after one v_permlane16_swap per packed register eight
@@ -203,7 +226,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(Gemm8Args g) {
     const int tile0 = run_lo + slot;
     if (tile0 >= run_hi) return;
     const int my_tiles = (run_hi - tile0 + per_xcd - 1) / per_xcd;
-    // ---- the DMA stream: this wave's 1-KiB pieces of ONE operand (group 0: A, group 1: W) in the order k-tile, half, piece,
+    // ---- the DMA stream: this wave's 1-KiB pieces of ONE operand (`so` below; RESID: group 0 A, group 1 W) in the order k-tile, half, piece,
     // over all the workgroup's output tiles.  A half-tile (128 rows x 128 B) is 16 pieces of 8 rows; wave quarter wq = w & 3 of
     // the staging group moves rows wq*32 .. +32 as pieces p = 0..3 (rows +8p; even p: swizzle f(row) = lane >> 4, odd p:
     // 4 + (lane >> 4)).
@@ -219,16 +242,19 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(Gemm8Args g) {
     int s_tile = tile0, s_kt = 0;
     const bf16 *s_A = g.A + (size_t)((mt_lo + s_tile / nxg) << 8) * K, *s_W = g.W + (size_t)((n_base + s_tile % nxg) << 8) * K;
     const int wq = w & 3;
+    // the operand this wave's group stages: 0 = activations, 1 = weights.  RESID: group 0 the activations.  QKV / GELU, whose groups
+    // run ONE phase per k-tile: group 0 the weights -- each operand is staged by the group that is the LAST to read it (see the k-loop)
+    const int so = EPI == EPI8_RESID ? wr : wr ^ 1;
     // 32-bit lane offsets on top of a workgroup-uniform base: the DMA takes its address as SGPR pair + one VGPR
-    const unsigned lsrcE = (unsigned)(((wr ? wq * 64 : wq * 32) + srow) * K + chE);
-    const unsigned lsrcO = (unsigned)(((wr ? wq * 64 : wq * 32) + 8 + srow) * K + chO);
-    const int ring_base = (wr ? 98304 : 0) + wq * 4096, ring_slots = wr ? 4 : 6;
+    const unsigned lsrcE = (unsigned)(((so ? wq * 64 : wq * 32) + srow) * K + chE);
+    const unsigned lsrcO = (unsigned)(((so ? wq * 64 : wq * 32) + 8 + srow) * K + chO);
+    const int ring_base = (so ? 98304 : 0) + wq * 4096, ring_slots = so ? 4 : 6;
     int h_half = 0, h_slot = 0, h_p = 0;
-    const bf16 *h_base = wr ? s_W : s_A;
+    const bf16 *h_base = so ? s_W : s_A;
     long h_left = (long)my_tiles * KT * 8;
     constexpr int N1 = G8_N1, N2 = 8 - N1;             // pieces per wave issued in phase 1 / phase 2 of a k-tile
     auto issue_piece = [&]() __attribute__((always_inline)) {
-        const bf16 *src = h_base + (size_t)(h_half * (wr ? 32 : 128) + (h_p >> 1) * 16) * K + s_kt * 64;
+        const bf16 *src = h_base + (size_t)(h_half * (so ? 32 : 128) + (h_p >> 1) * 16) * K + s_kt * 64;
         unsigned char *dst = smem + ring_base + (h_slot << 14) + h_p * 1024;
         glds16(src + ((h_p & 1) ? lsrcO : lsrcE), dst);
         if (++h_p == 4) {
@@ -239,7 +265,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(Gemm8Args g) {
                 if (++s_kt == KT) {
                     s_kt = 0;
                     s_tile += per_xcd;
-                    h_base = wr ? g.W + (size_t)((n_base + s_tile % nxg) << 8) * K : g.A + (size_t)((mt_lo + s_tile / nxg) << 8) * K;
+                    h_base = so ? g.W + (size_t)((n_base + s_tile % nxg) << 8) * K : g.A + (size_t)((mt_lo + s_tile / nxg) << 8) * K;
                 }
             }
         }
@@ -253,8 +279,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(Gemm8Args g) {
         for (int i = 0; i < n; ++i) issue_piece();
         return true;
     };
-    constexpr std::integral_constant<int, N1> n1tag{};
     constexpr std::integral_constant<int, 16> n16tag{};
+    constexpr std::integral_constant<int, 8> n8ktag{};
 
     // ---- fragment addresses inside a k-tile buffer: slots A0 | A1 | W0 | W1
     const int m16 = lane & 15, kg = lane >> 4, sw = (m16 >> 1) & 7;
@@ -273,8 +299,11 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(Gemm8Args g) {
 #ifdef G8_STAMP2   // phase-level stamps of one steady-state k-tile (tile 3, k-tile 6): where a barrier interval goes
     unsigned long long ph[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #define G8_P(i) if (seq == 3 && kt == 6) ph[i] = __builtin_amdgcn_s_memtime()
+// the one-phase loop (QKV / GELU) has no second loading part: between its two halves of 32 MFMAs, in every stamp of that part
+#define G8_PM() if (seq == 3 && kt == 6) ph[5] = ph[6] = ph[13] = ph[7] = ph[8] = ph[9] = __builtin_amdgcn_s_memtime()
 #else
 #define G8_P(i)
+#define G8_PM()
 #endif
     constexpr bool RL = EPI == EPI8_RESID;   // the RESID epilogue lands its inputs in LDS (see the epilogue)
     f32x4 acc[2][2][4][2];   // [i][j][mt][nt]
@@ -349,6 +378,106 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(Gemm8Args g) {
         for (int kt = 0; kt < KT; ++kt) {
             G8_P(0);
             const unsigned char *kbA = smem + a_cur * 32768, *kbW = smem + 98304 + w_cur * 32768;   // A_0 | A_1, W_0 | W_1
+            if constexpr (!RL) {
+                // ================ QKV / GELU: ONE phase per k-tile and group (two barrier intervals; tables in the header)
+                // ---------------- loading part: DMA pieces, then W_0, W_1, A_0 (the partner group is in its 64 MFMAs)
+                // Group 0: weight k-tile T+1 (slots of T-1: group 1, the last to read them, retired those reads before the barrier
+                // that closed the previous interval); a tile's first k-tile finds k-tile 1 staged.  Group 1: activation k-tile T+2
+                // (slots of T-1: its A_1 half was read last by this group's own matrix part, which ended at the barrier above).
+                // The pieces go out BEFORE the fragment reads (a DMA instruction behind ds_reads of its own wave: ~100 cycles each).
+                const bool staged = (wr || kt) && issue_pieces(n8ktag);
+                __builtin_amdgcn_sched_barrier(0);
+                G8_P(12);
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt) {
+                    wf0[nt][0] = *reinterpret_cast<const bf16x8 *>(kbW + w_row + nt * 2048 + c0);
+                    wf0[nt][1] = *reinterpret_cast<const bf16x8 *>(kbW + w_row + nt * 2048 + c1);
+                    wf1[nt][0] = *reinterpret_cast<const bf16x8 *>(kbW + 16384 + w_row + nt * 2048 + c0);
+                    wf1[nt][1] = *reinterpret_cast<const bf16x8 *>(kbW + 16384 + w_row + nt * 2048 + c1);
+                }
+#pragma unroll
+                for (int mt = 0; mt < 4; ++mt) {
+                    af0[mt][0] = *reinterpret_cast<const bf16x8 *>(kbA + a_row + mt * 2048 + c0);
+                    af0[mt][1] = *reinterpret_cast<const bf16x8 *>(kbA + a_row + mt * 2048 + c1);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                G8_P(1);
+                // Group 1: landed before this barrier, for BOTH groups' reads behind it, is everything older than this part's pieces,
+                // i.e. activation k-tile T+1, whose A_0 group 0 reads in the next interval (issued two intervals ago).  A tile's
+                // first k-tile waits for nothing: what it needs was drained before the previous epilogue, and a counted wait would
+                // also wait for that epilogue's stores (one in-order queue per wave).  Group 0 waits at the END of its matrix part.
+                G8_P(2);
+                if (wr && kt) {
+                    if (staged) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+                    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                }
+                // the reads are retired BEFORE the barrier: the other group may restage the W and A_0 slots right after it
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                G8_P(3);
+                __builtin_amdgcn_s_barrier();
+                G8_P(4);
+                G8_T(3 + (kt < 3 ? kt : 3), seq == 3 && kt < 4);   // first barrier of k-tiles 0..3 of tile 3
+                __builtin_amdgcn_sched_barrier(0);
+                // ---------------- matrix part: 64 MFMAs between two barriers
+                __builtin_amdgcn_s_setprio(1);
+                // Q(0,0), Q(0,1), then Q(1,0), Q(1,1), each in the order (ks, mt, nt).  The read of A_1[mt][ks] goes into af0[mt][ks]
+                // behind the last of the four MFMAs that use that register -- except the last two, A_1[2][1] and A_1[3][1], which go
+                // out behind the first two MFMA groups of the lower half.  Why: hipcc cannot count LDS reads past an LDS-DMA
+                // instruction whose vmcnt it has not seen reach zero (it books the DMA on lgkmcnt too, and this loop never drains
+                // vmcnt), so the wait it places before the first use of a fragment is lgkmcnt(0), whatever was asked for.  This
+                // order puts eight MFMAs (>= 128 cycles) between the youngest read and each of the two places where it waits:
+                // MFMA 33 (A_1[.][0], and [0..1][1]) and MFMA 57 ([2..3][1]).
+                auto read_a1 = [&](auto mttag, auto kstag) __attribute__((always_inline)) {
+                    constexpr int mt = decltype(mttag)::value, ks = decltype(kstag)::value;
+                    __builtin_amdgcn_sched_barrier(0);
+                    af0[mt][ks] = *reinterpret_cast<const bf16x8 *>(kbA + 16384 + a_row + mt * 2048 + (ks ? c1 : c0));
+                    __builtin_amdgcn_sched_barrier(0);
+                };
+                constexpr std::integral_constant<int, 0> i0{};
+                constexpr std::integral_constant<int, 1> i1{};
+                constexpr std::integral_constant<int, 2> i2{};
+                constexpr std::integral_constant<int, 3> i3{};
+                auto mfma4 = [&](auto itag, auto mttag, auto kstag) __attribute__((always_inline)) {
+                    constexpr int i = decltype(itag)::value, mt = decltype(mttag)::value, ks = decltype(kstag)::value;
+#pragma unroll
+                    for (int nt = 0; nt < 2; ++nt) {
+                        acc[i][0][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf0[nt][ks], af0[mt][ks], acc[i][0][mt][nt], 0, 0, 0);
+                        acc[i][1][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf1[nt][ks], af0[mt][ks], acc[i][1][mt][nt], 0, 0, 0);
+                    }
+                };
+                mfma4(i0, i0, i0), read_a1(i0, i0);
+                mfma4(i0, i1, i0), read_a1(i1, i0);
+                mfma4(i0, i2, i0), read_a1(i2, i0);
+                mfma4(i0, i3, i0), read_a1(i3, i0);
+                mfma4(i0, i0, i1), read_a1(i0, i1);
+                mfma4(i0, i1, i1), read_a1(i1, i1);
+                mfma4(i0, i2, i1);
+                mfma4(i0, i3, i1);
+                __builtin_amdgcn_sched_barrier(0);
+                G8_PM();
+                mfma4(i1, i0, i0), read_a1(i2, i1);
+                mfma4(i1, i1, i0), read_a1(i3, i1);
+                mfma4(i1, i2, i0);
+                mfma4(i1, i3, i0);
+                __builtin_amdgcn_sched_barrier(0);
+                mfma4(i1, i0, i1);
+                mfma4(i1, i1, i1);
+                mfma4(i1, i2, i1);
+                mfma4(i1, i3, i1);
+                __builtin_amdgcn_s_setprio(0);
+                G8_P(10);
+                // Group 0: weight k-tile T+1, issued in this k-tile's loading part a whole matrix part ago, has landed before the
+                // barrier behind which group 0 itself is the first to read it (a tile's first k-tile: drained before the epilogue).
+                if (wr == 0 && kt) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                // the A_1 reads are retired BEFORE the closing barrier: group 1 restages that half-slot right behind its own
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                G8_P(11);
+                a_cur = a_cur == 2 ? 0 : a_cur + 1;
+                w_cur ^= 1;
+                continue;
+            }
+            // ================ RESID: two phases of 32 MFMAs per k-tile and group (four barrier intervals)
             // ---------------- phase 1: W_0, W_1, A_0 -> Q(0,0), Q(0,1)
             // Group 0 stages the first N1 pieces of activation k-tile T+2 (slots of T-1: every read of it retired two barriers
             // ago).  Group 1: the last N1 pieces of weight k-tile T+1 -- a tile's first k-tile finds them staged (issued and
@@ -479,7 +608,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(Gemm8Args g) {
         // wait behind them comes a whole k-tile later.
         // (RL: nothing -- the next tile's k-tile 1 is staged from inside the epilogue, whose first counted wait covers k-tile 0)
         if constexpr (!RL) {
-            if (wr == 1) issue_pieces(n1tag);   // the rest of the next tile's weight k-tile 1 (slots of this tile's last k-tile)
+            if (wr == 0) issue_pieces(n8ktag);   // the next tile's weight k-tile 1 (slots of this tile's last k-tile)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         G8_T(1, seq == 2);

@@ -1,6 +1,7 @@
 // Probe of the large-batch GEMM (haconvdr_amd/csrc/gemm8.inc) on the encoder's four shapes at M = 131072: timing, and with
 // -DG8_STAMP in-kernel s_memtime stamps around the tile boundary (epilogue, first k-tiles), with -DG8_STAMP2 phase-level stamps
-// of one steady-state k-tile; -DG8_NO_EPI times the k-loop alone, -DG8_NGSWEEP each column-group count.
+// of one steady-state k-tile (QKV and FFN-up run one phase per k-tile: "R1" is their loading part, M1 / M2 the two halves of their 64
+// MFMAs, every "R2" figure 0); -DG8_NO_EPI times the k-loop alone, -DG8_NGSWEEP each column-group count.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 [-DG8_STAMP] [-DG8_STAMP2] [-DG8_NO_EPI] [-DG8_NGSWEEP] tools/probes/gemm8_probe.hip -o gemm8_probe
 #include "../../haconvdr_amd/csrc/encoder.hip"
 #include <cstdio>
