@@ -1863,6 +1863,10 @@ int fwd_build(hac_encoder *e, const IT *ids, const IT *mask, int B, int L, hipSt
     f.big = f.family == FAM_CLASSIC256;
     f.mean = e->pooling == 1;
     HAC_TRY(reserve_rows(e, f));
+    // The woven attention's counts and item flags (attention()), sized by every forward whose options allow that form, whether or not
+    // a layer takes it this time: pipe_skip_mask may clear between a shape's eager-first forward and its capture, and nothing may be
+    // allocated inside a capture.
+    if (!split && e->attn_mode == 0 && e->attn_pipe != 0) HAC_TRY(e->ws_redo.reserve(((size_t)B * NH + 16) * 4));
     HAC_TRY(seq_layout(e, B, L, f.s));
     seq_prep_kernel<IT><<<dim3(B), dim3(512), 0, st>>>(ids, mask, L, f.s, c.pad_token_id, c.vocab, e->model == 1 ? POS_BERT : POS_ROBERTA);
     seq_offsets_kernel<<<dim3(1), dim3(256), 0, st>>>(f.s, B);
@@ -1921,10 +1925,8 @@ int attention(hac_encoder *e, const Fwd &f, int li, bool last) {
     const bool att_pipe = e->attn_mode == 0 && e->attn_pipe != 0 && att_qs == 1 && !last && (L32 > 256 || e->attn_pipe > 0) &&
                           !(e->attn_pipe < 0 && ((e->pipe_skip_mask >> li) & 1u));      // ("all" pins the woven form: tests of the fix-up pass)
     if (att_pipe) {
-        if (!e->plan.attn_pipe) {      // the forward's first woven layer: workspace, per-layer counts to zero (the flags are zero whenever no pass is pending)
-            HAC_TRY(e->ws_redo.reserve(((size_t)B * NH + 16) * 4));
-            HAC_HIP(hipMemsetAsync(e->ws_redo.p, 0, 64, st));
-        }
+        // the forward's first woven layer: per-layer counts to zero (the flags are zero whenever no pass is pending; fwd_build sized ws_redo)
+        if (!e->plan.attn_pipe) HAC_HIP(hipMemsetAsync(e->ws_redo.p, 0, 64, st));
         a.redo_count = (int *)e->ws_redo.p + (li & 15);
         a.redo_flags = (int *)e->ws_redo.p + 16;
     }
