@@ -90,6 +90,9 @@ int hac_index_add_device(hac_index *idx, const float *x_dev, int64_t n, void *hi
  *
  * Result contract of every search entry point: score = k-ordered fp32 fma chain, order =
  * (score desc, row asc), NaN scores never returned, short lists padded -FLT_MAX / -1.
+ * A query is held to no more than a row is: one with a NaN component scores NaN against every row and returns a list of padding
+ * only, one with +-Inf components returns its +Inf rows in row order, then its -Inf rows, never a row whose chain met Inf * 0 or
+ * Inf - Inf, on every route, and neither costs the other queries of the call anything (tests/test_search_nonfinite_queries_gpu.py).
  * Where it is faster (k <= 192, d % 64 == 0, d >= 192; at once with >= 48 queries and >= 1e8 (query, row) pairs; for fewer --
  * down to ONE query on >= 750 k rows, >= 17 on >= 500 k, >= 2.5e7 pairs on >= 40 k -- when the fp16 image of the rows exists
  * already, or from the third such search after the last add / reset on, which builds it: +50 % of the corpus in HBM) the
