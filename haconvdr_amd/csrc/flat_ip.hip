@@ -1136,6 +1136,7 @@ u32 next_pow2(u32 v) {
 
 #include "scan_split.inc"
 #include "rank.inc"
+#include "range.inc"
 
 // Every instantiation of the two templated scan kernels, once: init raises each one's dynamic-LDS limit from these tables and
 // the launches look their kernel up in them, so an instantiation that is launched is one whose limit was raised.
@@ -1388,6 +1389,7 @@ struct DeviceIndex {
             HAC_HIP(hipFuncSetAttribute((const void *)sample_scores_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(64 * 1024)));
             for (const ScanhEntry &e : SCANH_TABLE) HAC_HIP(hipFuncSetAttribute((const void *)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             HAC_HIP(hipFuncSetAttribute((const void *)count_ahead_kernel<RANK_MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
+            HAC_HIP(hipFuncSetAttribute((const void *)range_emit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             attr_done[device] = true;
         }
         return HAC_OK;
@@ -1409,7 +1411,7 @@ struct DeviceIndex {
         for (PinBuf *b : {&h_pin, &h_fb, &h_stage[0], &h_stage[1]}) b->release();
         for (GrowBuf *b : {&ws_partial, &ws_pcnt, &ws_seedkeys, &ws_thr, &ws_thrglob, &ws_q, &ws_qt, &ws_keys, &ws_D, &ws_I, &ws_stage[0],
                            &ws_stage[1], &ws_err, &ws_norm, &ws_qsplit, &ws_delta, &ws_cand, &ws_akeys, &ws_fail, &ws_stat, &ws_fbidx[0], &ws_fbidx[1],
-                           &ws_fbq[0], &ws_fbq[1], &ws_fbkeys[0], &ws_fbkeys[1], &ws_ids, &ws_rank})
+                           &ws_fbq[0], &ws_fbq[1], &ws_fbkeys[0], &ws_fbkeys[1], &ws_ids, &ws_rank, &ws_range})
             b->release();
         if (h_err) (void)hipHostFree(h_err);
         if (h_plan) (void)hipHostFree(h_plan);
@@ -1814,6 +1816,7 @@ struct DeviceIndex {
     int nseg_live = 0;
 
     GrowBuf ws_ids, ws_rank;   // the by-id calls (rows_host.inc): a chunk's ids; the rank calls' counters and reference scores
+    GrowBuf ws_range;          // range search (rows_host.inc: RangeWs): control words, counters, cursors, staging and the two key buffers
 
     char last_plan[320] = "none";
     // a device-decided prefilter search leaves its fallback count and err / bound on the device: plan() completes the text
@@ -2771,12 +2774,7 @@ int search_host(hac_index *idx, const float *q, int64_t nq, int k, const int64_t
         if (S > 1) {   // shard-local rows -> insertion-order positions of the whole index
             const std::vector<SpanDesc> &sp = idx->spans[si];
             if (!sp.empty()) {
-                if (idx->spans_dirty[si]) {
-                    HAC_TRY(idx->ws_spans[si].reserve(sp.size() * sizeof(SpanDesc)));
-                    HAC_HIP(hipStreamSynchronize(s->stream));
-                    HAC_HIP(hipMemcpy(idx->ws_spans[si].p, sp.data(), sp.size() * sizeof(SpanDesc), hipMemcpyHostToDevice));
-                    idx->spans_dirty[si] = 0;
-                }
+                HAC_TRY(upload_spans(idx, si));
                 const long nk = (long)nq * kq;
                 remap_positions_kernel<<<dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s->stream>>>(
                     (u64 *)s->ws_keys.p, nk, (const SpanDesc *)idx->ws_spans[si].p, (int)sp.size());

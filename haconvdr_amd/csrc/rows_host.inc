@@ -1,7 +1,8 @@
-// Rows by id and their rank (hac_index_reconstruct*, hac_index_score_ids*, hac_index_rank_ids*, hac_index_count_ahead_device):
-// everything between the C ABI and the kernels of flat_ip.hip ("rows by id") and rank.inc.  Included by flat_ip.hip behind
-// hac_index; free functions over one shard (DeviceIndex &), which lends its segment table, its stream, its pinned slab, its
-// staging buffers and the workspaces ws_q / ws_ids / ws_D / ws_I / ws_rank -- nothing of the search state.
+// Rows by id, their rank and range search (hac_index_reconstruct*, hac_index_score_ids*, hac_index_rank_ids*,
+// hac_index_count_ahead_device, hac_index_range_search*): everything between the C ABI and the kernels of flat_ip.hip ("rows by
+// id"), rank.inc and range.inc.  Included by flat_ip.hip behind hac_index; free functions over one shard (DeviceIndex &), which
+// lends its segment table, its stream, its pinned slab, its staging buffers and the workspaces ws_q / ws_ids / ws_D / ws_I /
+// ws_rank / ws_range -- nothing of the search state.
 namespace {
 
 // ---- device forms: enqueue on `st` and return.  The only wait is the segment table's upload after an add / reset / a changed
@@ -100,6 +101,98 @@ int rank_ids_device(DeviceIndex &x, const float *q_dev, int64_t nq, const int64_
     HAC_TRY(x.ws_rank.reserve((size_t)nq * m * 12));
     HAC_TRY(score_ids_device(x, q_dev, nq, ids_dev, m, rank_scores(x, nq, m), st));
     return count_ahead_device(x, "rank_ids", q_dev, nq, rank_scores(x, nq, m), ids_dev, true, m, rank_dev, st);
+}
+
+// ---- range search (range.inc).  The workspace of one call of (nq, cap): control words, counters, lims, the two key buffers
+// (the staged keys share the second one: the scatter has read them before the sort or a merge pass writes there), then the
+// u32 planes.  20 bytes per result of capacity; it grows by the rule of the search workspaces.
+struct RangeWs {
+    u64 *ctl, *counts;
+    long long *lims;
+    u64 *buf[2];
+    u32 *blk, *qcur, *stage_q;
+    static size_t bytes(int64_t nq, int64_t cap) { return ((size_t)RANGE_CTL_WORDS + 2 * nq + 1 + 2 * cap) * 8 + ((size_t)2 * nq + 1 + cap) * 4; }
+    RangeWs(void *p, int64_t nq, int64_t cap) {
+        ctl = (u64 *)p;
+        counts = ctl + RANGE_CTL_WORDS;
+        lims = (long long *)(counts + nq);
+        buf[0] = (u64 *)(lims + nq + 1);
+        buf[1] = buf[0] + cap;
+        blk = (u32 *)(buf[1] + cap);
+        qcur = blk + nq + 1;
+        stage_q = qcur + nq;
+    }
+};
+// merge passes that sort a segment of up to cap keys out of LDS-sorted blocks: ceil(log2(ceil(cap / RANGE_SORT_N)))
+int range_merge_passes(int64_t cap) {
+    int p = 0;
+    for (int64_t blocks = (cap + RANGE_SORT_N - 1) / RANGE_SORT_N; ((int64_t)1 << p) < blocks; ++p) {}
+    return p;
+}
+// the capacity the workspace is sized for: no more results than (query, row) pairs, so a generous cap costs nothing
+int64_t range_cap(const DeviceIndex &x, int64_t nq, int64_t cap) {
+    return x.ntotal == 0 ? 0 : (nq > INT64_MAX / x.ntotal ? cap : std::min<int64_t>(cap, nq * x.ntotal));
+}
+// Everything of a range search that runs on the device, enqueued on `st` (nq > 0, cap >= 0): lims (lims_dev, or the workspace's
+// own when null) is always complete; if the total fits cap, the sorted keys of all queries are in *keys_out, segment by segment,
+// and -- with D_dev -- the results in D_dev / I_dev.  The launches depend on (nq, cap) and the index's size only.
+int range_device(DeviceIndex &x, const char *what, const float *q_dev, int64_t nq, const float *radius_dev, int64_t cap, int64_t *lims_dev, float *D_dev,
+                 int64_t *I_dev, const int64_t *id_map_dev, hipStream_t st, const u64 **keys_out = nullptr) {
+    const int64_t cap_eff = range_cap(x, nq, cap);
+    if (nq > ((int64_t)1 << 30) || cap_eff > ((int64_t)1 << 38))
+        return fail(HAC_ERR_UNSUPPORTED, "%s: %lld queries with room for %lld results in one call exceed the grid", what, (long long)nq, (long long)cap_eff);
+    HAC_TRY(check_dev_ptr(q_dev, what));
+    HAC_TRY(x.ws_range.reserve(RangeWs::bytes(nq, cap_eff)));
+    const RangeWs ws(x.ws_range.p, nq, cap_eff);
+    if (!lims_dev) lims_dev = (int64_t *)ws.lims;
+    HAC_TRY(x.upload_segs(st));
+    HAC_HIP(hipMemsetAsync(ws.ctl, 0, (size_t)(RANGE_CTL_WORDS + nq) * 8, st));
+    const u32 G = (u32)((x.ntotal + GROUP_ROWS - 1) / GROUP_ROWS);
+    long P = 0;
+    int T = 0, QT = (int)std::min<int64_t>(16, nq);
+    size_t lds = range_lds(x.K4, QT);
+    // queries in chunks of QUERY_CHUNK, the grid as count_ahead_device sizes count_ahead_kernel's for the same rows and queries
+    for (int64_t off = 0; off < nq && G > 0; off += DeviceIndex::QUERY_CHUNK) {
+        const int64_t n = std::min<int64_t>(DeviceIndex::QUERY_CHUNK, nq - off);
+        ScanArgs a = x.scan_args(q_dev + (size_t)off * x.d, n);
+        a.QT = QT = (int)std::min<int64_t>(16, n);
+        a.n_items = G;
+        T = (int)((n + a.QT - 1) / a.QT);
+        lds = range_lds(x.K4, a.QT);
+        const int per_cu = std::max(1, std::min<int>((int)std::min<size_t>(LDS_LIMIT / lds, 32 / SCAN_WAVES), 3));
+        P = std::max<long>(1, (long)x.n_cu * per_cu / T);
+        if (P >= 8 && !x.tune.no_p8) P = P / 8 * 8;
+        P = std::max<long>(1, std::min<long>(P, (G + SCAN_WAVES - 1) / SCAN_WAVES));
+        const RangeArgs ra{radius_dev + off, ws.counts + off, ws.ctl + RANGE_CURSOR, ws.buf[1], ws.stage_q, (u64)cap_eff, (u32)off};
+        range_emit_kernel<<<dim3((unsigned)P, (unsigned)T), dim3(SCAN_WAVES * 64), lds, st>>>(a, ra);
+        HAC_HIP(hipGetLastError());
+    }
+    range_offsets_kernel<<<dim3(1), dim3(RANGE_THREADS), 0, st>>>(ws.counts, (long)nq, (u64)cap, ws.ctl, (long long *)lims_dev, ws.blk, ws.qcur);
+    HAC_HIP(hipGetLastError());
+    const int passes = range_merge_passes(cap_eff);
+    if (cap_eff > 0) {
+        const unsigned per_key = (unsigned)((cap_eff + RANGE_THREADS - 1) / RANGE_THREADS);
+        // a segment's blocks: floor(len / N) full ones and at most one more per query
+        const unsigned blocks = (unsigned)(cap_eff / RANGE_SORT_N + std::min<int64_t>(nq, cap_eff));
+        range_scatter_kernel<<<dim3(per_key), dim3(RANGE_THREADS), 0, st>>>(ws.ctl, ws.buf[1], ws.stage_q, (const long long *)lims_dev, ws.qcur, ws.buf[0]);
+        HAC_HIP(hipGetLastError());
+        range_sort_kernel<<<dim3(blocks), dim3(RANGE_THREADS), 0, st>>>(ws.ctl, (const long long *)lims_dev, ws.blk, (long)nq, passes, ws.buf[0], ws.buf[1]);
+        HAC_HIP(hipGetLastError());
+        for (int p = 0; p < passes; ++p) {
+            range_merge_kernel<<<dim3(blocks), dim3(RANGE_THREADS), 0, st>>>(ws.ctl, (const long long *)lims_dev, ws.blk, (long)nq, passes, p, ws.buf[p & 1],
+                                                                            ws.buf[(p + 1) & 1]);
+            HAC_HIP(hipGetLastError());
+        }
+        if (D_dev) {
+            range_results_kernel<<<dim3(per_key), dim3(RANGE_THREADS), 0, st>>>(ws.ctl, ws.buf[passes & 1], (const long long *)id_map_dev, D_dev, (long long *)I_dev);
+            HAC_HIP(hipGetLastError());
+        }
+    }
+    if (keys_out) *keys_out = ws.buf[passes & 1];
+    snprintf(x.last_plan, sizeof x.last_plan, "range_emit_kernel grid=(%ld,%d) QT=%d cap=%lld sort_lds=%d merge_passes=%d lds=%zu", P, T, QT, (long long)cap,
+             RANGE_SORT_N, passes, lds);
+    x.plan_text_slot = -1;
+    return HAC_OK;
 }
 
 // ---- host forms over one shard's rows: synchronous, on the shard's own stream, one chunk in flight.  They run on
@@ -223,6 +316,71 @@ int rank_host(DeviceIndex &x, const float *q, int64_t nq, const int64_t *ids, co
         if (ref_score) return count_ahead_device(x, "count_ahead", qd, nqc, (const float *)x.ws_D.p, id, false, mc, (int64_t *)x.ws_I.p, x.stream);
         return rank_ids_device(x, qd, nqc, id, mc, (int64_t *)x.ws_I.p, x.stream);
     });
+}
+
+// the host's side of the packed key (flat_ip.hip: ord2f, make_key)
+float key_score_host(u64 key) {
+    const u32 o = (u32)(key >> 32), b = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
+    float f;
+    std::memcpy(&f, &b, 4);
+    return f;
+}
+int64_t key_row_host(u64 key) { return (int64_t)(0xFFFFFFFFu - (u32)key); }
+
+// A shard's span table on its device, for remap_positions_kernel (several devices only); waits for the shard's stream when it
+// has to upload.
+int upload_spans(hac_index *idx, int si) {
+    DeviceIndex *s = idx->shards[si];
+    const std::vector<SpanDesc> &sp = idx->spans[si];
+    if (sp.empty() || !idx->spans_dirty[si]) return HAC_OK;
+    HAC_TRY(idx->ws_spans[si].reserve(sp.size() * sizeof(SpanDesc)));
+    HAC_HIP(hipStreamSynchronize(s->stream));
+    HAC_HIP(hipMemcpy(idx->ws_spans[si].p, sp.data(), sp.size() * sizeof(SpanDesc), hipMemcpyHostToDevice));
+    idx->spans_dirty[si] = 0;
+    return HAC_OK;
+}
+
+// Range search over one shard's rows: lims [nq + 1] always; when the shard's total fits cap, its keys, every query's segment
+// sorted, the rows in the numbering of the whole index (several devices: remap_positions_kernel, which keeps a sorted list sorted).
+int range_host(hac_index *idx, int si, const float *q, int64_t nq, const float *radius, int64_t cap, std::vector<int64_t> &lims, std::vector<u64> &keys) {
+    DeviceIndex &x = *idx->shards[si];
+    DeviceGuard g(x.device);
+    if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", x.device);
+    const size_t qbytes = (size_t)nq * x.d * 4, rbytes = (size_t)nq * 4, lbytes = (size_t)(nq + 1) * 8;
+    HAC_TRY(x.ws_q.reserve(qbytes));
+    HAC_TRY(x.ws_D.reserve(rbytes));
+    char *slab = nullptr;   // queries, radii; then lims
+    HAC_TRY(pin_slab(x, std::max(qbytes + rbytes, lbytes), slab));
+    std::memcpy(slab, q, qbytes);
+    std::memcpy(slab + qbytes, radius, rbytes);
+    HAC_HIP(hipMemcpyAsync(x.ws_q.p, slab, qbytes, hipMemcpyHostToDevice, x.stream));
+    HAC_HIP(hipMemcpyAsync(x.ws_D.p, slab + qbytes, rbytes, hipMemcpyHostToDevice, x.stream));
+    const u64 *keys_dev = nullptr;
+    HAC_TRY(range_device(x, "range_search", (const float *)x.ws_q.p, nq, (const float *)x.ws_D.p, cap, nullptr, nullptr, nullptr, nullptr, x.stream, &keys_dev));
+    // (the slab's reuse is ordered behind the uploads by the stream)
+    HAC_HIP(hipMemcpyAsync(slab, RangeWs(x.ws_range.p, nq, range_cap(x, nq, cap)).lims, lbytes, hipMemcpyDeviceToHost, x.stream));
+    HAC_HIP(hipStreamSynchronize(x.stream));
+    lims.resize((size_t)nq + 1);
+    std::memcpy(lims.data(), slab, lbytes);
+    const int64_t total = lims[(size_t)nq];
+    keys.clear();
+    if (total == 0 || total > cap) return HAC_OK;
+    if (idx->shards.size() > 1 && !idx->spans[si].empty()) {
+        HAC_TRY(upload_spans(idx, si));
+        remap_positions_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, x.stream>>>(const_cast<u64 *>(keys_dev), (long)total,
+                                                                                                 (const SpanDesc *)idx->ws_spans[si].p, (int)idx->spans[si].size());
+        HAC_HIP(hipGetLastError());
+    }
+    keys.resize((size_t)total);
+    const int64_t chunk = (int64_t)8 << 20;   // 64 MiB of keys through the pinned slab at a time
+    HAC_TRY(pin_slab(x, (size_t)std::min(chunk, total) * 8, slab));
+    for (int64_t done = 0; done < total; done += chunk) {
+        const size_t n = (size_t)std::min(chunk, total - done);
+        HAC_HIP(hipMemcpyAsync(slab, keys_dev + done, n * 8, hipMemcpyDeviceToHost, x.stream));
+        HAC_HIP(hipStreamSynchronize(x.stream));
+        std::memcpy(keys.data() + done, slab, n * 8);
+    }
+    return HAC_OK;
 }
 
 // ---- the caller's ids.  The first id outside [-1, ntotal) of a host matrix [rows][cols]: the host entry points refuse it (the
@@ -385,6 +543,59 @@ int hac_index_rank_ids(hac_index *idx, const float *q, int64_t nq, const int64_t
         int64_t sum = 0;
         for (int si = 0; si < S; ++si) sum = (sum < 0 || part[si][i] < 0) ? -1 : sum + part[si][i];   // (-1: padding or a NaN score, on every shard alike)
         rank[i] = sum;
+    }
+    return HAC_OK;
+}
+
+int hac_index_range_search_device(hac_index *idx, const float *q_dev, int64_t nq, const float *radius_dev, int64_t cap, int64_t *lims_dev, float *D_dev,
+                                  int64_t *I_dev, const int64_t *id_map_dev, void *hip_stream) {
+    return on_single_shard(idx, "range_search_device", [&](DeviceIndex &s) -> int {
+        if (nq < 0 || cap < 0 || (nq > 0 && (!q_dev || !radius_dev || !lims_dev)) || (cap > 0 && (!D_dev || !I_dev)))
+            return fail(HAC_ERR_INVALID, "range_search_device: bad arguments");
+        if (nq == 0) {
+            if (lims_dev) HAC_HIP(hipMemsetAsync(lims_dev, 0, 8, (hipStream_t)hip_stream));
+            return HAC_OK;
+        }
+        return range_device(s, "range_search_device", q_dev, nq, radius_dev, cap, lims_dev, cap > 0 ? D_dev : nullptr, I_dev, id_map_dev, (hipStream_t)hip_stream);
+    });
+}
+
+int hac_index_range_search(hac_index *idx, const float *q, int64_t nq, const float *radius, int64_t cap, int64_t *lims, float *D, int64_t *I) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    if (nq < 0 || cap < 0 || (nq > 0 && (!q || !radius || !lims)) || (cap > 0 && (!D || !I))) return fail(HAC_ERR_INVALID, "range_search: bad arguments");
+    if (nq == 0) {
+        if (lims) lims[0] = 0;
+        return HAC_OK;
+    }
+    // Every shard answers for its own rows (one host thread each), in the numbering of the whole index; a row is on one shard,
+    // so the counts add up, and a query's list is the merge of the shards' sorted lists by key.  A shard whose own total
+    // exceeds cap hands back no keys: the whole does not fit either.
+    const int S = (int)idx->shards.size();
+    std::vector<std::vector<int64_t>> part(S);
+    std::vector<std::vector<u64>> keys(S);
+    HAC_TRY(for_each_shard(idx, [&](int si) { return range_host(idx, si, q, nq, radius, cap, part[si], keys[si]); }));
+    lims[0] = 0;
+    for (int64_t i = 0; i < nq; ++i) {
+        int64_t n = 0;
+        for (int si = 0; si < S; ++si) n += part[si][i + 1] - part[si][i];
+        lims[i + 1] = lims[i] + n;
+    }
+    if (lims[nq] > cap) return HAC_OK;   // an answer, not an error: D and I stay as they are
+    std::vector<int64_t> at(S);
+    for (int64_t i = 0; i < nq; ++i) {
+        for (int si = 0; si < S; ++si) at[si] = part[si][i];
+        for (int64_t o = lims[i]; o < lims[i + 1]; ++o) {
+            int best = -1;
+            u64 kbest = 0;
+            for (int si = 0; si < S; ++si)
+                if (at[si] < part[si][i + 1] && keys[si][(size_t)at[si]] > kbest) {
+                    best = si;
+                    kbest = keys[si][(size_t)at[si]];
+                }
+            ++at[best];
+            D[o] = key_score_host(kbest);
+            I[o] = key_row_host(kbest);
+        }
     }
     return HAC_OK;
 }

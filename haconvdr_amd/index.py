@@ -144,6 +144,53 @@ def _count_args_tensor(q, ref_scores, ref_bounds, d, what="count_ahead_tensor"):
     return q, ref_scores.contiguous(), ref_bounds
 
 
+def _as_radius(radius, nq, what):
+    """radius of range_search -> contiguous float32 [nq]: a real scalar (faiss's form, one radius for every query) or one
+    value per query.  float64 values are rounded to float32, the precision the scores are compared in."""
+    a = np.asarray(radius)
+    if a.dtype.kind not in "fiu":
+        raise ValueError(f"{what}: radius must be real numbers, got dtype {a.dtype}")
+    if a.ndim == 0:
+        return np.full(nq, a, dtype=np.float32)
+    if a.shape != (nq,):
+        raise ValueError(f"{what}: {nq} queries but radius of shape {a.shape} (a scalar, or one per query)")
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _as_cap(cap, what):
+    if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or int(cap) < 0:
+        raise ValueError(f"{what}: cap must be an integer >= 0 (results), got {cap!r}")
+    return int(cap)
+
+
+def _range_args(q, radius, d, what="range_search"):
+    """(q float32 [nq, d], radius float32 [nq]) of range_search / range_count."""
+    q = _as_queries(q, d, what)
+    return q, _as_radius(radius, q.shape[0], what)
+
+
+def _range_args_tensor(q, radius, cap, id_map, d, what="range_search_tensor"):
+    """(q float32 CUDA [nq, d], radius float32 CUDA [nq], cap, id_map int64 CUDA [ntotal] or None) of range_search_tensor."""
+    import torch
+    q = _queries_tensor(q, d, what)
+    if not isinstance(radius, torch.Tensor) or not radius.is_cuda:
+        raise ValueError(f"{what}: radius must be a CUDA tensor")
+    if radius.dtype != torch.float32:
+        raise ValueError(f"{what}: radius must be float32 (the precision the scores are compared in), got {radius.dtype}")
+    if tuple(radius.shape) != (q.shape[0],):
+        raise ValueError(f"{what}: {q.shape[0]} queries but radius of shape {tuple(radius.shape)} (one per query)")
+    if radius.device != q.device:
+        raise ValueError(f"{what}: q on {q.device} but radius on {radius.device}")
+    cap = _as_cap(cap, what)
+    if id_map is not None:
+        if not isinstance(id_map, torch.Tensor) or not id_map.is_cuda or id_map.dtype != torch.int64 or id_map.dim() != 1:
+            raise ValueError(f"{what}: id_map must be an int64 CUDA tensor [ntotal]")
+        if id_map.device != q.device:
+            raise ValueError(f"{what}: q on {q.device} but id_map on {id_map.device}")
+        id_map = id_map.contiguous()
+    return q, radius.contiguous(), cap, id_map
+
+
 def _check_exclude_shape(nq, k, shape, what):
     if shape[0] != nq:
         raise ValueError(f"{what}: {nq} queries but exclude of shape {tuple(shape)} (one list per query)")
@@ -286,6 +333,50 @@ class FlatIPIndex:
         R = np.empty(ids.shape, np.int64)
         _lib.check(_lib.lib().hac_index_rank_ids(self._h, _f32p(q), q.shape[0], _i64p(ids), ids.shape[1], _i64p(R)))
         return R
+
+    # ---- range search (include/haconvdr.h, "range search") ------------------
+    RANGE_FIRST_CAP = 1024   # results per query the first call of range_search makes room for
+
+    def _range_call(self, q, radius, cap):
+        lims = np.empty(q.shape[0] + 1, np.int64)
+        D, I = _host_results((cap,))
+        null_f, null_i = ctypes.POINTER(ctypes.c_float)(), ctypes.POINTER(ctypes.c_int64)()
+        _lib.check(_lib.lib().hac_index_range_search(self._h, _f32p(q), q.shape[0], _f32p(radius), cap, _i64p(lims),
+                                                     _f32p(D) if cap else null_f, _i64p(I) if cap else null_i))
+        return lims, D, I
+
+    def range_search(self, q, radius):
+        """lims, D, I = index.range_search(q, radius): every row whose score is STRICTLY above the query's radius (a scalar, or
+        float32 [nq]).  lims int64 [nq + 1]; query i owns D[lims[i]:lims[i+1]] (float32) and I[lims[i]:lims[i+1]] (int64 rows),
+        ordered by (score desc, row asc) -- the head of an unbounded search of q[i] (faiss leaves the order open).  NaN scores
+        are in no list; a NaN or +Inf radius gives an empty list.  At most two library calls: the first makes room for
+        RANGE_FIRST_CAP results per query, the second, only if that overflowed, for exactly lims[nq]."""
+        q, radius = _range_args(q, radius, self.d)
+        lims, D, I = self._range_call(q, radius, self.RANGE_FIRST_CAP * q.shape[0])
+        total = int(lims[-1])
+        if total > D.shape[0]:
+            lims, D, I = self._range_call(q, radius, total)
+        return lims, D[:total], I[:total]
+
+    def range_count(self, q, radius):
+        """len of every list range_search(q, radius) returns, int64 [nq], without the lists (the cap = 0 form: one pass over the
+        rows per 16 queries, no sort).  Equals count_ahead(q, radius, 0)."""
+        q, radius = _range_args(q, radius, self.d, "range_count")
+        return np.diff(self._range_call(q, radius, 0)[0])
+
+    def range_search_tensor(self, q, radius, cap, id_map=None, stream=None):
+        """q float32 CUDA [nq, d], radius float32 CUDA [nq], cap = room for results -> (lims int64 [nq + 1], D float32 [cap],
+        I int64 [cap]) CUDA tensors; no host sync.  lims is always exact.  If lims[nq] <= cap, D and I are filled in
+        [0, lims[nq]) and untouched behind; otherwise their contents are unspecified: compare lims[nq] with cap and call again.
+        id_map: optional int64 CUDA [ntotal], I = id_map[row].  Capturable after one call of the largest (nq, cap)."""
+        import torch
+        q, radius, cap, id_map = _range_args_tensor(q, radius, cap, id_map, self.d)
+        lims = torch.empty((q.shape[0] + 1,), dtype=torch.int64, device=q.device)
+        D, I = _device_results((cap,), q.device)
+        _lib.check(_lib.lib().hac_index_range_search_device(self._h, _devp(q), q.shape[0], _devp(radius), cap, _devp(lims), _devp(D) if cap else _devp(None),
+                                                            _devp(I) if cap else _devp(None), _devp(id_map), _stream_ptr(stream)))
+        _keep_alive(stream, q, radius, lims, D, I, *(() if id_map is None else (id_map,)))
+        return lims, D, I
 
     # ---- device-resident variants (torch tensors on the index's GPU) -------
     def add_tensor(self, x, stream=None):

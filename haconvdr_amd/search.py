@@ -253,6 +253,34 @@ class ResidentCorpus:
         any other -- the TREC writer's per-query de-duplication (trec.output_test_res) is not applied."""
         return self.index.rank_ids(*self._pairs(query_embeddings, passage_ids, "rank"))
 
+    # ---- lists whose length follows the scores ---------------------------------------------------------------------
+    def _host_queries(self, query_embeddings):
+        import torch
+        return query_embeddings.cpu().numpy() if isinstance(query_embeddings, torch.Tensor) else query_embeddings
+
+    def range_search(self, query_embeddings, radius):
+        """Every passage scoring STRICTLY above a radius (a scalar, or one float32 per query): query_embeddings float32
+        [nq,768] -> (lims int64 [nq+1], D float64 [total], I int64 [total] EXTERNAL passage ids); query i owns
+        D[lims[i]:lims[i+1]] and I[lims[i]:lims[i+1]], ordered like search() (score desc, row asc) -- the head of a search of
+        unbounded depth.  Over ROWS: an id several rows carry appears once per row."""
+        lims, D, I = self.index.range_search(self._host_queries(query_embeddings), radius)
+        return lims, D.astype(np.float64), self._ids[I]
+
+    def ahead_of(self, query_embeddings, passage_ids):
+        """The rows an unbounded search puts ahead of each query's named passage by SCORE: passage_ids int64 [nq] EXTERNAL ids
+        -> (lims, D, I) as range_search, with the radius score() of that passage.  The comparison is strict: rows that TIE the
+        passage's score are not included, whichever side of it search() lists them on (so len can be below rank() when
+        scores tie), and the passage itself never is.  A passage no block holds, or one whose score is NaN, gives an
+        empty list."""
+        q = self._host_queries(query_embeddings)
+        pid = np.asarray(passage_ids)
+        if pid.ndim != 1:
+            raise ValueError(f"ahead_of: passage_ids must be [nq], got shape {pid.shape}")
+        rows = self.rows_of(pid)[:, None]
+        radius = self.index.score_ids(q, rows)[:, 0]
+        radius = np.where(rows[:, 0] < 0, np.float32(np.inf), radius).astype(np.float32)
+        return self.range_search(q, radius)
+
     def reconstruct(self, passage_ids):
         """passage_ids int64 [n] -> float32 [n,768], the embeddings as the blocks hold them (all-ones words for an absent id)."""
         return self.index.reconstruct_batch(self.rows_of(passage_ids))

@@ -197,7 +197,7 @@ int64_t hac_index_ntotal(const hac_index *idx);
  * a HIP graph once that table is up (run one call outside the capture first).
  *
  * Out of scope: reconstruct through haconvdr_amd.sharded.ShardedSearcher (one process per GPU: reading a row another rank
- * holds would need a collective; its rank() below needs only two all-reduces of [nq, m] words); faiss's range_search and
+ * holds would need a collective; its rank() below needs only two all-reduces of [nq, m] words); faiss's
  * remove_ids; and nothing here changes how search routes or what it returns. */
 /* index.reconstruct_n(i0, n): host float32 [n, d]. */
 int hac_index_reconstruct(hac_index *idx, int64_t i0, int64_t n, float *out);
@@ -249,6 +249,58 @@ int hac_index_count_ahead_device(hac_index *idx, const float *q_dev, int64_t nq,
 int hac_index_rank_ids(hac_index *idx, const float *q, int64_t nq, const int64_t *ids, int64_t m, int64_t *rank);
 int hac_index_rank_ids_device(hac_index *idx, const float *q_dev, int64_t nq, const int64_t *ids_dev, int64_t m, int64_t *rank_dev,
                               void *hip_stream);
+
+/* ---- range search: every row scoring above a per-query radius (faiss: index.range_search) -------------------------------
+ * For a query q and a radius r (float32, one per query):
+ *   range(q, r) = { rows x in [0, ntotal) : s(q, x) is not NaN and s(q, x) > r }
+ * with s the canonical score above and a strict float comparison, as in faiss's inner-product range search: -0.0 == +0.0,
+ * +-Inf are ordinary scores, a NaN or +Inf radius gives an empty list, r = -Inf gives every row whose score is neither NaN
+ * nor -Inf.  Rows behind ntotal (zeros, or stale rows after reset() and a smaller add()) are never returned.  faiss leaves
+ * the order inside a query's list unspecified; here it is the key order, (score desc, row asc), so that
+ *   len(range(q, r)) == count_ahead(q, r, 0);
+ *   range(q, r) is the first len entries of an unbounded search of q: for any k <= HAC_MAX_K the entries of search(q, k) with
+ *     D > r equal the first min(k, len) entries of the range result bit for bit, D and I, on every search route;
+ *   rank_ids(q, I_range)[j] == j for every position j.
+ * Result, in faiss's layout: lims int64 [nq + 1], lims[0] = 0; query i owns D[lims[i] : lims[i + 1]] (float32) and
+ * I[lims[i] : lims[i + 1]] (int64 rows; the device form: id_map_dev[row] when id_map_dev is given).
+ *
+ * The size of the result is not known before the call: both entry points take a capacity `cap`, in results, and are all or
+ * nothing.  lims is always complete and exact, whatever cap is.  If lims[nq] <= cap, D and I are filled in [0, lims[nq]) and
+ * nothing behind that is touched.  If lims[nq] > cap, the host form leaves D and I untouched and the device form may leave
+ * anything in [0, cap) and writes nothing outside it.  Either way the call returns HAC_OK -- an overflow is an answer, not an
+ * error: compare lims[nq] with cap and call again.  cap == 0 with D == I == NULL is a pure count.  The result is a pure
+ * function of the inputs (two identical calls return identical bytes); there is no candidate buffer, no threshold and no
+ * pass bound, so nothing goes to the status ring.
+ *
+ * How (csrc/range.inc): range_emit_kernel streams the rows once per tile of 16 queries in the shape of count_ahead_kernel --
+ * same tiles, same bit-exact MFMA chain -- and, for the groups that have a hit at all, adds to the per-query counters and
+ * appends (query, key) pairs to a staging buffer through one cursor (one atomic per wave and group; pairs at or behind cap are
+ * dropped, counting never stops).  range_offsets_kernel turns the counters into lims and decides fits / overflows on the
+ * device; the kernels behind it read that word and exit on an overflow.  range_scatter_kernel moves the pairs into their
+ * query's segment, range_sort_kernel sorts blocks of 4096 keys in LDS, range_merge_kernel merges longer segments in
+ * ceil(log2(cap / 4096)) passes between two buffers, range_results_kernel writes D and I.
+ * Cost: ceil(nq / 16) passes over the rows at the exact scan's stream rate, whether or not the result fits, plus the sort;
+ * by arithmetic that is 63 passes of 77 GB for 1000 queries over 25M rows (not measured).  A segment of millions of keys
+ * (a radius far below the scores) is sorted correctly but may be slow: every merge pass moves all of it.  The workspace is 20
+ * bytes per result of min(cap, nq * ntotal).
+ *
+ * Host form: q float32 [nq, d], radius float32 [nq]; synchronous, on the index's own stream; works on a multi-device index
+ * (every shard answers for its rows on a host thread of its own, positions are remapped to the index's numbering as search
+ * does, the host adds the shards' counts into lims and, when the total fits, merges each query's per-shard lists by key).  A
+ * device workspace that cannot be allocated is HAC_ERR_OOM.
+ * Device form: single-device index (HAC_ERR_UNSUPPORTED otherwise), 16-byte aligned q_dev (HAC_ERR_INVALID otherwise);
+ * enqueues on hip_stream and never reads back.  The workspace grows by the rule of the search workspaces: run one call of
+ * the largest (nq, cap) before capturing into a HIP graph.  The launches depend on (nq, cap) and the index's size, never on
+ * the data.
+ * Both: nq == 0 is HAC_OK, writes lims[0] = 0 and touches nothing else; HAC_ERR_INVALID for a null q / radius / lims with
+ * nq > 0, for cap < 0 and for cap > 0 with a null D or I.  hac_index_last_plan afterwards reads
+ * "range_emit_kernel grid=(P,T) QT=.. cap=.. sort_lds=4096 merge_passes=.. lds=..".
+ * Out of scope: haconvdr_amd.sharded.ShardedSearcher (one process per GPU: the lists would need a variable-length gather),
+ * remove_ids, and a GEMM-shaped many-query form. */
+int hac_index_range_search(hac_index *idx, const float *q, int64_t nq, const float *radius, int64_t cap, int64_t *lims, float *D,
+                           int64_t *I);
+int hac_index_range_search_device(hac_index *idx, const float *q_dev, int64_t nq, const float *radius_dev, int64_t cap,
+                                  int64_t *lims_dev, float *D_dev, int64_t *I_dev, const int64_t *id_map_dev, void *hip_stream);
 
 /* Device-detected failures of searches enqueued so far (the host entry points report them themselves; the *_device entry
  * points cannot, they never read back).  Waits for the index's own streams only: synchronize YOUR stream first, then call
