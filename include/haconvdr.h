@@ -238,7 +238,8 @@ int hac_index_score_ids_device(hac_index *idx, const float *q_dev, int64_t nq, c
  * hip_stream, never read back and take no slot of the status ring.  Their workspace (counters and reference scores, nq * m * 12
  * bytes) grows by the rule of the search workspaces: run one call of the largest (nq, m) before capturing into a HIP graph.
  * nq == 0 or m == 0 is HAC_OK and touches nothing.  hac_index_last_plan afterwards reads
- * "count_ahead_kernel<MT=8> grid=(P,T) QT=.. chunks=.. lds=..".
+ * "count_ahead_kernel<MT=8> grid=(P,T) QT=.. chunks=.. lds=..".  Queries go out in launches of 1024; the text is the last
+ * launch's (1025 queries: QT=1, T=1).
  * count_ahead is the primitive shards add up: ref_score_dev float32 [nq, m], ref_bound_dev int64 [nq, m], count_dev int64
  * [nq, m] over THIS index's rows (haconvdr_amd.sharded: the owner's score, bounds clamp(id - shard_base, 0, n_local), a sum).
  * Host rank_ids: synchronous, on the index's own stream, staged in chunks like score_ids; on a multi-device index the scores
@@ -294,7 +295,8 @@ int hac_index_rank_ids_device(hac_index *idx, const float *q_dev, int64_t nq, co
  * the data.
  * Both: nq == 0 is HAC_OK, writes lims[0] = 0 and touches nothing else; HAC_ERR_INVALID for a null q / radius / lims with
  * nq > 0, for cap < 0 and for cap > 0 with a null D or I.  hac_index_last_plan afterwards reads
- * "range_emit_kernel grid=(P,T) QT=.. cap=.. sort_lds=4096 merge_passes=.. lds=..".
+ * "range_emit_kernel grid=(P,T) QT=.. cap=.. sort_lds=4096 merge_passes=.. lds=..".  Queries go out in launches of 1024;
+ * grid, QT and lds are the last launch's (1025 queries: QT=1, T=1), cap is the caller's, merge_passes is the call's.
  * Out of scope: haconvdr_amd.sharded.ShardedSearcher (one process per GPU: the lists would need a variable-length gather),
  * remove_ids, and a GEMM-shaped many-query form. */
 int hac_index_range_search(hac_index *idx, const float *q, int64_t nq, const float *radius, int64_t cap, int64_t *lims, float *D,
