@@ -1137,6 +1137,7 @@ u32 next_pow2(u32 v) {
 #include "scan_split.inc"
 #include "rank.inc"
 #include "range.inc"
+#include "remove.inc"
 
 // Every instantiation of the two templated scan kernels, once: init raises each one's dynamic-LDS limit from these tables and
 // the launches look their kernel up in them, so an instantiation that is launched is one whose limit was raised.
@@ -1571,13 +1572,19 @@ struct DeviceIndex {
                 s.h_rows = 0;
                 segs_dirty = true;
             }
-            const long g_lo = (long)(s.h_rows / GROUP_ROWS), g_hi = (long)((s.rows + GROUP_ROWS - 1) / GROUP_ROWS);
-            if (g_hi > g_lo) {
-                half_image_kernel<<<dim3((unsigned)(g_hi - g_lo)), dim3(256), 0, st>>>(s.buf, s.hbuf, g_lo, K4);
-                HAC_HIP(hipGetLastError());
-            }
-            s.h_rows = s.rows;
+            HAC_TRY(fill_half_image(s, st));
         }
+        return HAC_OK;
+    }
+    // the fp16 image of a segment that has one, from its tiles: the groups from the first row that is not current to the last row
+    // (ensure_half_image; remove_rows_shard of rows_host.inc after it has moved the rows)
+    int fill_half_image(Segment &s, hipStream_t st) {
+        const long g_lo = (long)(s.h_rows / GROUP_ROWS), g_hi = (long)((s.rows + GROUP_ROWS - 1) / GROUP_ROWS);
+        if (g_hi > g_lo) {
+            half_image_kernel<<<dim3((unsigned)(g_hi - g_lo)), dim3(256), 0, st>>>(s.buf, s.hbuf, g_lo, K4);
+            HAC_HIP(hipGetLastError());
+        }
+        s.h_rows = s.rows;
         return HAC_OK;
     }
 
@@ -1659,14 +1666,19 @@ struct DeviceIndex {
                 }
                 s.r_rows = 0;
             }
-            const long g_lo = (long)(s.r_rows / GROUP_ROWS), g_hi = (long)((s.rows + GROUP_ROWS - 1) / GROUP_ROWS);
-            if (g_hi > g_lo) {
-                untile_rows_kernel<<<dim3((unsigned)(g_hi - g_lo)), dim3(256), 0, st>>>(s.buf, s.rbuf, g_lo, K4);
-                HAC_HIP(hipGetLastError());
-            }
-            s.r_rows = s.rows;
-            segs_dirty = true;
+            HAC_TRY(fill_row_image(s, st));
         }
+        return HAC_OK;
+    }
+    // the same for a segment's row-major copy (ensure_row_image, remove_rows_shard)
+    int fill_row_image(Segment &s, hipStream_t st) {
+        const long g_lo = (long)(s.r_rows / GROUP_ROWS), g_hi = (long)((s.rows + GROUP_ROWS - 1) / GROUP_ROWS);
+        if (g_hi > g_lo) {
+            untile_rows_kernel<<<dim3((unsigned)(g_hi - g_lo)), dim3(256), 0, st>>>(s.buf, s.rbuf, g_lo, K4);
+            HAC_HIP(hipGetLastError());
+        }
+        s.r_rows = s.rows;
+        segs_dirty = true;
         return HAC_OK;
     }
 

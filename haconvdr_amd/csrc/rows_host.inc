@@ -1,8 +1,8 @@
-// Rows by id, their rank and range search (hac_index_reconstruct*, hac_index_score_ids*, hac_index_rank_ids*,
-// hac_index_count_ahead_device, hac_index_range_search*): everything between the C ABI and the kernels of flat_ip.hip ("rows by
-// id"), rank.inc and range.inc.  Included by flat_ip.hip behind hac_index; free functions over one shard (DeviceIndex &), which
-// lends its segment table, its stream, its pinned slab, its staging buffers and the workspaces ws_q / ws_ids / ws_D / ws_I /
-// ws_rank / ws_range -- nothing of the search state.
+// Rows by id, their rank, range search and removal (hac_index_reconstruct*, hac_index_score_ids*, hac_index_rank_ids*,
+// hac_index_count_ahead_device, hac_index_range_search*, hac_index_remove_ids): everything between the C ABI and the kernels of
+// flat_ip.hip ("rows by id"), rank.inc, range.inc and remove.inc.  Included by flat_ip.hip behind hac_index; free functions over
+// one shard (DeviceIndex &), which lends its segment table, its stream, its pinned slab, its staging buffers and the workspaces
+// ws_q / ws_ids / ws_D / ws_I / ws_rank / ws_range -- nothing of the search state (remove_rows_shard alone changes the segments).
 namespace {
 
 // ---- device forms: enqueue on `st` and return.  The only wait is the segment table's upload after an add / reset / a changed
@@ -438,9 +438,150 @@ int score_ids_shards(hac_index *idx, const RowLocator &loc, const std::vector<in
     for (size_t i = 0; i < at.size(); ++i) local[loc.shard(at[i])][i] = loc.local(at[i], ids[i]);
     return for_each_shard(idx, [&](int si) { return score_ids_host(*idx->shards[si], q, nq, local[si].data(), m, D, true, NOT_MINE); });
 }
+
+// ---- removing rows (hac_index_remove_ids).  rem: this shard's removed rows, local numbering, sorted ascending, no duplicates.
+// What can fail cheaply on a shard, before any shard moves a row: the staging buffers, the id list's device buffer, the slab.
+constexpr int64_t REMOVE_ID_CHUNK = (int64_t)4 << 20;   // ids per upload through the pinned slab (16 MiB)
+int remove_reserve(DeviceIndex &x, size_t R) {
+    if (R == 0) return HAC_OK;
+    DeviceGuard g(x.device);
+    if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", x.device);
+    HAC_TRY(x.stage_reserve());
+    HAC_TRY(x.ws_ids.reserve(R * 4));
+    return x.pin_reserve((size_t)std::min<int64_t>((int64_t)R, REMOVE_ID_CHUNK) * 4);
+}
+// The shard's rows without rem, in place, on the shard's own stream; synchronous.
+//
+// Groups in front of the first removed row are not touched.  Behind it the destination rows go in ascending chunks of at most
+// stage_rows() rows: compact_rows_kernel gathers a chunk into ws_stage[0] (T64 form), device-to-device copies then put the staged
+// groups in their place, one copy per segment piece.  Source and destination are found through the same segment table: segments
+// keep their capacities and fill order, and every segment but the last is full, so the table of the old numbering is the table of
+// the new one for every row below the new total.
+// Why in place is safe: src(j) >= j.  A chunk [a, b) reads old rows >= a and overwrites old rows in [a, b) only, i.e. rows below
+// its own end; every earlier chunk wrote below a and every later chunk reads at or beyond b, so no chunk reads a row another has
+// overwritten.  Within a chunk the stream puts every read (the gather) in front of the first write (the copies).
+// Memory: ws_stage and the id list, nothing that grows with the corpus.
+int remove_rows_shard(DeviceIndex &x, const std::vector<u32> &rem) {
+    const int64_t R = (int64_t)rem.size();
+    if (R == 0) return HAC_OK;
+    DeviceGuard g(x.device);
+    if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", x.device);
+    HAC_TRY(remove_reserve(x, (size_t)R));
+    char *slab = nullptr;
+    for (int64_t done = 0; done < R; done += REMOVE_ID_CHUNK) {
+        const size_t m = (size_t)std::min(REMOVE_ID_CHUNK, R - done);
+        HAC_TRY(pin_slab(x, m * 4, slab));
+        std::memcpy(slab, rem.data() + done, m * 4);
+        HAC_HIP(hipMemcpyAsync((u32 *)x.ws_ids.p + done, slab, m * 4, hipMemcpyHostToDevice, x.stream));
+    }
+    HAC_TRY(x.upload_segs(x.stream));   // (the table of the rows as they are)
+    const int64_t new_rows = x.ntotal - R, first = (int64_t)rem[0];
+    const int64_t g_first = first / GROUP_ROWS, g_end = (new_rows + GROUP_ROWS - 1) / GROUP_ROWS, chunk_groups = x.stage_rows() / GROUP_ROWS;
+    const size_t gbytes = (size_t)GROUP_ROWS * x.d * 4;
+    for (int64_t ga = g_first; ga < g_end; ga += chunk_groups) {
+        const int64_t gb = std::min(ga + chunk_groups, g_end);
+        compact_rows_kernel<<<dim3((unsigned)(gb - ga)), dim3(256), 0, x.stream>>>(x.d_segs, x.nseg_live, (const u32 *)x.ws_ids.p, (u32)R, (long)(ga * GROUP_ROWS),
+                                                                                  (long)new_rows, x.K4, reinterpret_cast<f4 *>(x.ws_stage[0].p));
+        HAC_HIP(hipGetLastError());
+        int64_t gs = 0;   // the segment's first group, as upload_segs numbers it
+        for (Segment &s : x.segs) {
+            if (s.rows == 0) continue;
+            const int64_t ng = (s.rows + GROUP_ROWS - 1) / GROUP_ROWS, lo = std::max(ga, gs), hi = std::min(gb, gs + ng);
+            if (lo < hi)
+                HAC_HIP(hipMemcpyAsync((char *)s.buf + (size_t)(lo - gs) * gbytes, (const char *)x.ws_stage[0].p + (size_t)(lo - ga) * gbytes, (size_t)(hi - lo) * gbytes,
+                                       hipMemcpyDeviceToDevice, x.stream));
+            gs += ng;
+        }
+    }
+    // The segments' rows from the new total, in fill order.  An image that was complete is complete again when the call returns:
+    // current up to the first changed group, then rebuilt from the tiles over the changed groups on the same stream; an
+    // incomplete one stays incomplete (lowered), a segment without one gets none.
+    int64_t r0 = 0, left = new_rows;
+    for (Segment &s : x.segs) {
+        const int64_t old = s.rows, changed = std::min(old, std::max<int64_t>(0, first - r0) / GROUP_ROWS * GROUP_ROWS);
+        const bool h_full = s.hbuf && s.h_rows == old, r_full = s.rbuf && s.r_rows == old;
+        s.rows = std::min(old, left);
+        s.h_rows = std::min({s.h_rows, changed, s.rows});
+        s.r_rows = std::min({s.r_rows, changed, s.rows});
+        if (h_full) HAC_TRY(x.fill_half_image(s, x.stream));
+        if (r_full) HAC_TRY(x.fill_row_image(s, x.stream));
+        left -= s.rows;
+        r0 += old;
+    }
+    HAC_HIP(hipStreamSynchronize(x.stream));
+    // Segments left empty behind the last live one go, with their images (the first stays, as after reset()): add() then
+    // continues in a partial last segment, and every segment but the last holds a multiple of 64 rows.
+    while (x.segs.size() > 1 && x.segs.back().rows == 0) {
+        Segment &s = x.segs.back();
+        HAC_HIP(hipFree(s.buf));
+        if (s.hbuf) HAC_HIP(hipFree(s.hbuf));
+        if (s.rbuf) HAC_HIP(hipFree(s.rbuf));
+        x.segs.pop_back();
+    }
+    x.ntotal = new_rows;
+    x.segs_dirty = true;
+    // as add() leaves them.  ws_norm (the largest |x|^2, the scale of the prefilter's certificate) stays as it is: a bound that
+    // held for a superset of the rows holds for the rows that are left.
+    x.half_image_unavailable = false;
+    x.row_image_unavailable = false;
+    x.split_searches_since_add = 0;
+    x.light_searches_since_add = 0;
+    return HAC_OK;
+}
+
+// The span tables of a multi-device index after the rows rem (global numbering, sorted, no duplicates) have gone.  The survivors
+// of a span are still consecutive in the new global numbering and in the shard's: rows -= the removed rows inside the span,
+// global0 -= the removed rows below the old global0, local0 = the running sum of the shard's spans; empty spans are dropped.
+void rewrite_spans_after_remove(std::vector<std::vector<SpanDesc>> &spans, const std::vector<int64_t> &rem) {
+    for (std::vector<SpanDesc> &shard : spans) {
+        std::vector<SpanDesc> kept;
+        u32 local0 = 0;
+        for (const SpanDesc &sp : shard) {
+            const int64_t below = std::lower_bound(rem.begin(), rem.end(), (int64_t)sp.global0) - rem.begin();
+            const int64_t inside = (std::lower_bound(rem.begin(), rem.end(), (int64_t)sp.global0 + sp.count) - rem.begin()) - below;
+            const u32 count = sp.count - (u32)inside;
+            if (count == 0) continue;
+            kept.push_back(SpanDesc{local0, count, sp.global0 - (u32)below, 0u});
+            local0 += count;
+        }
+        shard.swap(kept);
+    }
+}
 }  // namespace
 
 extern "C" {
+
+int hac_index_remove_ids(hac_index *idx, const int64_t *ids, int64_t n, int64_t *n_removed) {
+    if (n_removed) *n_removed = 0;
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    if (n < 0 || (n > 0 && !ids)) return fail(HAC_ERR_INVALID, "remove_ids: bad arguments");
+    HAC_TRY(check_host_ids("remove_ids", ids, 1, n, idx->ntotal, IdPlace::FLAT));
+    std::vector<int64_t> rem;
+    for (int64_t i = 0; i < n; ++i)
+        if (ids[i] >= 0) rem.push_back(ids[i]);
+    std::sort(rem.begin(), rem.end());
+    rem.erase(std::unique(rem.begin(), rem.end()), rem.end());
+    if (rem.empty()) return HAC_OK;   // nothing named: nothing is touched, the segment table stays as it is
+    const int S = (int)idx->shards.size();
+    std::vector<std::vector<u32>> local(S);
+    if (S == 1) {
+        local[0].assign(rem.begin(), rem.end());
+    } else {   // a shard's local order is the global order: its list comes out sorted
+        const RowLocator loc(idx);
+        const std::vector<int32_t> at = loc.locate(rem.data(), rem.size());
+        for (size_t i = 0; i < rem.size(); ++i) local[loc.shard(at[i])].push_back((u32)loc.local(at[i], rem[i]));
+    }
+    // everything that can fail cheaply on every shard first, then the kernels
+    HAC_TRY(for_each_shard(idx, [&](int si) { return remove_reserve(*idx->shards[si], local[si].size()); }));
+    HAC_TRY(for_each_shard(idx, [&](int si) { return remove_rows_shard(*idx->shards[si], local[si]); }));
+    if (S > 1) {
+        rewrite_spans_after_remove(idx->spans, rem);
+        for (int si = 0; si < S; ++si) idx->spans_dirty[si] = 1;
+    }
+    idx->ntotal -= (int64_t)rem.size();
+    if (n_removed) *n_removed = (int64_t)rem.size();
+    return HAC_OK;
+}
 
 int hac_index_reconstruct_ids(hac_index *idx, const int64_t *ids, int64_t n, float *out) {
     if (!idx) return fail(HAC_ERR_INVALID, "null index");

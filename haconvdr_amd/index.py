@@ -68,6 +68,17 @@ def _as_ids(ids, ndim, what):
     return np.ascontiguousarray(a, dtype=np.int64)
 
 
+def _remove_args(ids, ntotal, what="remove_ids"):
+    """ids of remove_ids -> contiguous int64 [n]: an integer array of one dimension (-1 = padding, duplicates allowed), or a
+    boolean mask of shape [ntotal] (True = the row goes), which becomes its indices."""
+    a = np.asarray(ids)
+    if a.dtype == np.bool_:
+        if a.shape != (ntotal,):
+            raise ValueError(f"{what}: a mask must have shape ({ntotal},), one entry per row, got {a.shape}")
+        return np.flatnonzero(a).astype(np.int64)
+    return _as_ids(a, 1, what)
+
+
 def _as_range(i0, n, what):
     """(i0, n) of reconstruct_n as python ints; n may be None (= up to ntotal, resolved by the caller)."""
     for name, v in (("i0", i0), ("n", n)):
@@ -283,6 +294,16 @@ class FlatIPIndex:
 
     def reset(self):
         _lib.check(_lib.lib().hac_index_reset(self._h))
+
+    def remove_ids(self, ids):
+        """index.remove_ids(ids) -> the number of rows removed.  ids: int64 [n] row ids (-1 = padding, duplicates allowed; any
+        other id outside [0, ntotal) raises HacError and changes nothing) or a boolean mask [ntotal].  The surviving rows keep
+        their bits and order and are renumbered densely from 0 (row j of np.delete(x, ids, axis=0)); in place on the device,
+        synchronous (include/haconvdr.h, "removing rows")."""
+        ids = _remove_args(ids, self.ntotal)
+        removed = ctypes.c_int64(0)
+        _lib.check(_lib.lib().hac_index_remove_ids(self._h, _i64p(ids), ids.shape[0], ctypes.byref(removed)))
+        return int(removed.value)
 
     @property
     def ntotal(self):

@@ -170,7 +170,8 @@ def rows_carrying(sorted_ids, order, exclude):
 
 class ResidentCorpus:
     """All passage blocks of a directory resident in HBM, searched many times (the reference reloads
-    every block for every evaluation run, :77-123).  Same result contract as search_one_by_one."""
+    every block for every evaluation run, :77-123).  Same result contract as search_one_by_one.
+    ``sizes`` describes the blocks as they were loaded: remove() does not change it."""
 
     def __init__(self, passage_embeddings_dir, passage_block_num, index=None, device=0):
         import torch
@@ -214,6 +215,23 @@ class ResidentCorpus:
             rows = rows_carrying(*self._id_lookup(), exclude)
             D, I = self.index.search_excluding_tensor(q.to(self.dev), topN, torch.from_numpy(rows).to(self.dev), id_map=self.id_map)
         return D.cpu().numpy().astype(np.float64), I.cpu().numpy()
+
+    def remove(self, passage_ids):
+        """Drop passages from the resident corpus in place (a withdrawn passage, a duplicate): passage_ids, integers of any
+        shape, EXTERNAL ids (-1 = padding).  Every row that carries one of them goes (an id two blocks hold names two rows), an
+        id no block holds is ignored; returns the number of rows removed.  The rows left keep their order (index.remove_ids),
+        so later results are those of a corpus loaded without the removed rows."""
+        import torch
+        pid = np.asarray(passage_ids)
+        if pid.dtype.kind not in "iu":
+            raise ValueError(f"remove: passage ids must be integers, got dtype {pid.dtype}")
+        rows = rows_carrying(*self._id_lookup(), pid.reshape(1, -1))[0]
+        rows = np.unique(rows[rows >= 0])
+        removed = self.index.remove_ids(rows)
+        self._ids = np.delete(self._ids, rows)
+        self.id_map = torch.from_numpy(self._ids).to(self.dev)
+        self._lookup = None
+        return removed
 
     # ---- the seam of a re-ranker: rows and exact scores by EXTERNAL passage id --------------------------------------
     def rows_of(self, passage_ids):

@@ -197,8 +197,8 @@ int64_t hac_index_ntotal(const hac_index *idx);
  * a HIP graph once that table is up (run one call outside the capture first).
  *
  * Out of scope: reconstruct through haconvdr_amd.sharded.ShardedSearcher (one process per GPU: reading a row another rank
- * holds would need a collective; its rank() below needs only two all-reduces of [nq, m] words); faiss's
- * remove_ids; and nothing here changes how search routes or what it returns. */
+ * holds would need a collective; its rank() below needs only two all-reduces of [nq, m] words); and nothing here changes
+ * how search routes or what it returns. */
 /* index.reconstruct_n(i0, n): host float32 [n, d]. */
 int hac_index_reconstruct(hac_index *idx, int64_t i0, int64_t n, float *out);
 /* index.reconstruct(i) / index.reconstruct_batch(ids): ids host int64 [n]; out host float32 [n, d]. */
@@ -297,12 +297,45 @@ int hac_index_rank_ids_device(hac_index *idx, const float *q_dev, int64_t nq, co
  * nq > 0, for cap < 0 and for cap > 0 with a null D or I.  hac_index_last_plan afterwards reads
  * "range_emit_kernel grid=(P,T) QT=.. cap=.. sort_lds=4096 merge_passes=.. lds=..".  Queries go out in launches of 1024;
  * grid, QT and lds are the last launch's (1025 queries: QT=1, T=1), cap is the caller's, merge_passes is the call's.
- * Out of scope: haconvdr_amd.sharded.ShardedSearcher (one process per GPU: the lists would need a variable-length gather),
- * remove_ids, and a GEMM-shaped many-query form. */
+ * Out of scope: haconvdr_amd.sharded.ShardedSearcher (one process per GPU: the lists would need a variable-length gather)
+ * and a GEMM-shaped many-query form. */
 int hac_index_range_search(hac_index *idx, const float *q, int64_t nq, const float *radius, int64_t cap, int64_t *lims, float *D,
                            int64_t *I);
 int hac_index_range_search_device(hac_index *idx, const float *q_dev, int64_t nq, const float *radius_dev, int64_t cap,
                                   int64_t *lims_dev, float *D_dev, int64_t *I_dev, const int64_t *id_map_dev, void *hip_stream);
+
+/* ---- removing rows: faiss's IndexFlat::remove_ids(IDSelectorBatch(ids)), in place ------------------------------------------
+ * The rows named by ids disappear; every surviving row keeps its bits and its relative order; the survivors are renumbered
+ * densely from 0 -- survivor number j is row j of np.delete(x, unique(ids), axis=0) --; ntotal drops by the number of DISTINCT
+ * rows removed, which is what *n_removed receives (n_removed may be NULL); rows added afterwards continue at the new ntotal.
+ * After the call every entry point (search on every route, search_excluding, reconstruct, score_ids, rank_ids, count_ahead,
+ * range_search) behaves exactly as an index that had been built by adding the surviving rows: the result bits are the same.
+ *
+ * ids: host int64 [n], the rule of the host entry points above: duplicates are allowed, -1 is a padding slot and is ignored,
+ * any other id outside [0, ntotal) is HAC_ERR_INVALID, the message names the first offending id and its position, and NOTHING
+ * is changed.  n == 0, or only padding, is HAC_OK, removes 0 rows and leaves the segment table alone (a captured search stays
+ * valid).
+ *
+ * How (csrc/remove.inc, csrc/rows_host.inc): the ids are sorted and made unique on the host.  Groups of 64 rows in front of the
+ * first removed row are not touched.  Behind it compact_rows_kernel -- one workgroup per destination group, one binary search
+ * per lane over the removed rows, whole 1-KiB chunks out -- gathers ascending chunks of ~64 MiB of destination rows into the
+ * add path's staging buffer, and device-to-device copies put them in place; a destination row never lies behind its source,
+ * so a chunk only overwrites rows that no later chunk reads.  No allocation grows with the corpus.  Segments left empty are
+ * freed with their images; add() continues in the partial last segment.  An fp16 image or a row-major rescoring copy that was
+ * complete before the call is complete when it returns (rebuilt from the tiles over the changed groups); a segment without
+ * one gets none.  Only bits move: NaN payloads, +-Inf, -0.0 and denormals survive.
+ * Cost, with the first removed row at local row f of a shard of n rows: 4 * (n - f) * d * 4 bytes of HBM traffic (every moved
+ * row is read and written twice), plus the image rebuilds over the same groups; removing rows near the end is nearly free,
+ * removing row 0 moves the shard.
+ *
+ * A host call: synchronous, on the index's own stream like add / reset (synchronize your own streams first, as for those); the
+ * segment table changes, so a search captured into a HIP graph before the call must be captured again.  It works on a
+ * multi-device index: the ids are split by shard, every shard compacts its rows on a host thread of its own, and the spans
+ * that translate shard rows to index rows are rewritten.  Everything that can fail cheaply (the id check, the workspaces of
+ * every shard) happens before the first kernel; if a shard still fails after another has finished, the error is reported and
+ * the index must be reset() before it is used again.  There is no *_device form: ntotal has to reach the host.
+ * Out of scope: haconvdr_amd.sharded.ShardedSearcher (removing on one rank moves every later rank's shard_base). */
+int hac_index_remove_ids(hac_index *idx, const int64_t *ids, int64_t n, int64_t *n_removed);
 
 /* Device-detected failures of searches enqueued so far (the host entry points report them themselves; the *_device entry
  * points cannot, they never read back).  Waits for the index's own streams only: synchronize YOUR stream first, then call
