@@ -1138,6 +1138,7 @@ u32 next_pow2(u32 v) {
 #include "rank.inc"
 #include "range.inc"
 #include "remove.inc"
+#include "among.inc"
 
 // Every instantiation of the two templated scan kernels, once: init raises each one's dynamic-LDS limit from these tables and
 // the launches look their kernel up in them, so an instantiation that is launched is one whose limit was raised.
@@ -1412,7 +1413,7 @@ struct DeviceIndex {
         for (PinBuf *b : {&h_pin, &h_fb, &h_stage[0], &h_stage[1]}) b->release();
         for (GrowBuf *b : {&ws_partial, &ws_pcnt, &ws_seedkeys, &ws_thr, &ws_thrglob, &ws_q, &ws_qt, &ws_keys, &ws_D, &ws_I, &ws_stage[0],
                            &ws_stage[1], &ws_err, &ws_norm, &ws_qsplit, &ws_delta, &ws_cand, &ws_akeys, &ws_fail, &ws_stat, &ws_fbidx[0], &ws_fbidx[1],
-                           &ws_fbq[0], &ws_fbq[1], &ws_fbkeys[0], &ws_fbkeys[1], &ws_ids, &ws_rank, &ws_range})
+                           &ws_fbq[0], &ws_fbq[1], &ws_fbkeys[0], &ws_fbkeys[1], &ws_ids, &ws_rank, &ws_range, &ws_among})
             b->release();
         if (h_err) (void)hipHostFree(h_err);
         if (h_plan) (void)hipHostFree(h_plan);
@@ -1829,6 +1830,7 @@ struct DeviceIndex {
 
     GrowBuf ws_ids, ws_rank;   // the by-id calls (rows_host.inc): a chunk's ids; the rank calls' counters and reference scores
     GrowBuf ws_range;          // range search (rows_host.inc: RangeWs): control words, counters, cursors, staging and the two key buffers
+    GrowBuf ws_among;          // search among named rows (rows_host.inc: among_keys_device): a chunk's [queries][P] candidate keys
 
     char last_plan[320] = "none";
     // a device-decided prefilter search leaves its fallback count and err / bound on the device: plan() completes the text

@@ -1,8 +1,9 @@
-// Rows by id, their rank, range search and removal (hac_index_reconstruct*, hac_index_score_ids*, hac_index_rank_ids*,
-// hac_index_count_ahead_device, hac_index_range_search*, hac_index_remove_ids): everything between the C ABI and the kernels of
-// flat_ip.hip ("rows by id"), rank.inc, range.inc and remove.inc.  Included by flat_ip.hip behind hac_index; free functions over
-// one shard (DeviceIndex &), which lends its segment table, its stream, its pinned slab, its staging buffers and the workspaces
-// ws_q / ws_ids / ws_D / ws_I / ws_rank / ws_range -- nothing of the search state (remove_rows_shard alone changes the segments).
+// Rows by id, their rank, range search, removal and search among named rows (hac_index_reconstruct*, hac_index_score_ids*,
+// hac_index_rank_ids*, hac_index_count_ahead_device, hac_index_range_search*, hac_index_remove_ids, hac_index_search_among*):
+// everything between the C ABI and the kernels of flat_ip.hip ("rows by id"), rank.inc, range.inc, remove.inc and among.inc.
+// Included by flat_ip.hip behind hac_index; free functions over one shard (DeviceIndex &), which lends its segment table, its
+// stream, its pinned slab, its staging buffers and the workspaces ws_q / ws_ids / ws_D / ws_I / ws_keys / ws_rank / ws_range /
+// ws_among -- nothing of the search state (remove_rows_shard alone changes the segments).
 namespace {
 
 // ---- device forms: enqueue on `st` and return.  The only wait is the segment table's upload after an add / reset / a changed
@@ -101,6 +102,43 @@ int rank_ids_device(DeviceIndex &x, const float *q_dev, int64_t nq, const int64_
     HAC_TRY(x.ws_rank.reserve((size_t)nq * m * 12));
     HAC_TRY(score_ids_device(x, q_dev, nq, ids_dev, m, rank_scores(x, nq, m), st));
     return count_ahead_device(x, "rank_ids", q_dev, nq, rank_scores(x, nq, m), ids_dev, true, m, rank_dev, st);
+}
+
+// ---- search among named rows (among.inc)
+int check_among_size(const char *what, int k, int64_t m) {
+    if (k < 1 || k > HAC_MAX_K || m < 0 || m > HAC_MAX_AMONG)
+        return fail(HAC_ERR_INVALID, "%s: k=%d, m=%lld: needs 1 <= k <= %d and 0 <= m <= %d (one LDS sort block of candidates per query)", what, k,
+                    (long long)m, HAC_MAX_K, HAC_MAX_AMONG);
+    return HAC_OK;
+}
+// keys_out[i] = the k keys of among(q[i], cand[i], k), positions pos_base + row, enqueued on `st` (nq > 0, k and m checked).  The
+// [queries][P] candidate keys of at most 64 MiB of queries at a time live in ws_among, which grows by the rule of the search
+// workspaces; the launches depend on (nq, m, k) only.
+int among_keys_device(DeviceIndex &x, const char *what, const float *q_dev, int64_t nq, int k, const int64_t *cand_dev, int64_t m, u64 *keys_out,
+                      u32 pos_base, hipStream_t st) {
+    if (m == 0) {   // lists of padding only
+        HAC_HIP(hipMemsetAsync(keys_out, 0, (size_t)nq * k * 8, st));
+        return HAC_OK;
+    }
+    HAC_TRY(check_dev_ptr(q_dev, what));
+    if ((uint64_t)pos_base + (uint64_t)x.ntotal > 0xFFFFFFFFull) return fail(HAC_ERR_UNSUPPORTED, "row positions exceed 32 bits");
+    const u32 P = next_pow2((u32)m), bpq = (u32)((m + 255) / 256);
+    const int64_t QC = std::min<int64_t>(nq, std::max<int64_t>(1, ((int64_t)64 << 20) / ((int64_t)P * 8)));   // (<= 2^23 queries: the grids fit)
+    HAC_TRY(x.ws_among.reserve((size_t)QC * P * 8));
+    HAC_TRY(x.upload_segs(st));
+    const size_t lds = among_lds(P);
+    for (int64_t off = 0; off < nq; off += QC) {
+        const int64_t n = std::min(QC, nq - off);
+        among_keys_kernel<<<dim3((unsigned)(n * bpq)), dim3(256), 0, st>>>(x.d_segs, x.d_rimg, x.nseg_live, q_dev + (size_t)off * x.d,
+                                                                          (const long long *)cand_dev + (size_t)off * m, (long)m, bpq, P, (long)x.ntotal, x.K4,
+                                                                          pos_base, (u64 *)x.ws_among.p);
+        HAC_HIP(hipGetLastError());
+        among_select_kernel<<<dim3((unsigned)n), dim3(AMONG_THREADS), lds, st>>>((const u64 *)x.ws_among.p, P, k, keys_out + (size_t)off * k);
+        HAC_HIP(hipGetLastError());
+    }
+    snprintf(x.last_plan, sizeof x.last_plan, "among_keys_kernel grid=%lld among_select_kernel P=%u k=%d lds=%zu", (long long)(std::min(QC, nq) * bpq), P, k, lds);
+    x.plan_text_slot = -1;
+    return HAC_OK;
 }
 
 // ---- range search (range.inc).  The workspace of one call of (nq, cap): control words, counters, lims, the two key buffers
@@ -439,6 +477,42 @@ int score_ids_shards(hac_index *idx, const RowLocator &loc, const std::vector<in
     return for_each_shard(idx, [&](int si) { return score_ids_host(*idx->shards[si], q, nq, local[si].data(), m, D, true, NOT_MINE); });
 }
 
+// ---- search among named rows, the host form.  One shard's keys of the whole call, [nq][k] in its ws_keys, on its own stream:
+// cand holds the shard's local rows (-1: padding, or a row of another shard), m > 0.  Queries and lists are staged through the pinned
+// slab in chunks of ~64 MiB, one chunk in flight; with several devices the positions are then those of the whole index
+// (remap_positions_kernel, as search does).  Returns with the shard's stream idle.
+int among_shard(hac_index *idx, int si, const float *q, int64_t nq, int k, const int64_t *cand, int64_t m) {
+    DeviceIndex &x = *idx->shards[si];
+    DeviceGuard g(x.device);
+    if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", x.device);
+    const size_t q_bytes = (size_t)x.d * 4, c_bytes = (size_t)m * 8;
+    const int64_t QC = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(((size_t)64 << 20) / (q_bytes + c_bytes))));
+    HAC_TRY(x.ws_q.reserve(QC * q_bytes));
+    HAC_TRY(x.ws_ids.reserve(QC * c_bytes));
+    HAC_TRY(x.ws_keys.reserve((size_t)nq * k * 8));
+    char *slab = nullptr;   // queries, lists
+    HAC_TRY(pin_slab(x, QC * (q_bytes + c_bytes), slab));
+    for (int64_t q0 = 0; q0 < nq; q0 += QC) {
+        const int64_t nqc = std::min(QC, nq - q0);
+        std::memcpy(slab, q + (size_t)q0 * x.d, nqc * q_bytes);
+        HAC_HIP(hipMemcpyAsync(x.ws_q.p, slab, nqc * q_bytes, hipMemcpyHostToDevice, x.stream));
+        std::memcpy(slab + QC * q_bytes, cand + (size_t)q0 * m, nqc * c_bytes);
+        HAC_HIP(hipMemcpyAsync(x.ws_ids.p, slab + QC * q_bytes, nqc * c_bytes, hipMemcpyHostToDevice, x.stream));
+        HAC_TRY(among_keys_device(x, "search_among", (const float *)x.ws_q.p, nqc, k, (const int64_t *)x.ws_ids.p, m, (u64 *)x.ws_keys.p + (size_t)q0 * k, 0u,
+                                  x.stream));
+        HAC_HIP(hipStreamSynchronize(x.stream));   // (the slab is the next chunk's)
+    }
+    if (idx->shards.size() > 1 && !idx->spans[si].empty()) {
+        HAC_TRY(upload_spans(idx, si));
+        const long nk = (long)nq * k;
+        remap_positions_kernel<<<dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, x.stream>>>((u64 *)x.ws_keys.p, nk, (const SpanDesc *)idx->ws_spans[si].p,
+                                                                                             (int)idx->spans[si].size());
+        HAC_HIP(hipGetLastError());
+        HAC_HIP(hipStreamSynchronize(x.stream));
+    }
+    return HAC_OK;
+}
+
 // ---- removing rows (hac_index_remove_ids).  rem: this shard's removed rows, local numbering, sorted ascending, no duplicates.
 // What can fail cheaply on a shard, before any shard moves a row: the staging buffers, the id list's device buffer, the slab.
 constexpr int64_t REMOVE_ID_CHUNK = (int64_t)4 << 20;   // ids per upload through the pinned slab (16 MiB)
@@ -684,6 +758,84 @@ int hac_index_rank_ids(hac_index *idx, const float *q, int64_t nq, const int64_t
         int64_t sum = 0;
         for (int si = 0; si < S; ++si) sum = (sum < 0 || part[si][i] < 0) ? -1 : sum + part[si][i];   // (-1: padding or a NaN score, on every shard alike)
         rank[i] = sum;
+    }
+    return HAC_OK;
+}
+
+int hac_index_search_among_keys_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const int64_t *cand_dev, int64_t m, uint64_t *keys_dev,
+                                       uint32_t pos_base, void *hip_stream) {
+    return on_single_shard(idx, "search_among_keys_device", [&](DeviceIndex &s) -> int {
+        HAC_TRY(check_among_size("search_among_keys_device", k, m));
+        if (nq < 0 || (nq > 0 && (!q_dev || !keys_dev || (m > 0 && !cand_dev)))) return fail(HAC_ERR_INVALID, "search_among_keys_device: bad arguments");
+        if (nq == 0) return HAC_OK;
+        return among_keys_device(s, "search_among_keys_device", q_dev, nq, k, cand_dev, m, (u64 *)keys_dev, pos_base, (hipStream_t)hip_stream);
+    });
+}
+
+int hac_index_search_among_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const int64_t *cand_dev, int64_t m, float *D_dev, int64_t *I_dev,
+                                  const int64_t *id_map_dev, void *hip_stream) {
+    return on_single_shard(idx, "search_among_device", [&](DeviceIndex &s) -> int {
+        HAC_TRY(check_among_size("search_among_device", k, m));
+        if (nq < 0 || (nq > 0 && (!q_dev || !D_dev || !I_dev || (m > 0 && !cand_dev)))) return fail(HAC_ERR_INVALID, "search_among_device: bad arguments");
+        if (nq == 0) return HAC_OK;
+        HAC_TRY(s.ws_keys.reserve((size_t)nq * k * 8));
+        HAC_TRY(among_keys_device(s, "search_among_device", q_dev, nq, k, cand_dev, m, (u64 *)s.ws_keys.p, 0u, (hipStream_t)hip_stream));
+        return hac_keys_to_results_device(s.device, (const uint64_t *)s.ws_keys.p, nq * k, id_map_dev, D_dev, I_dev, hip_stream);
+    });
+}
+
+int hac_index_search_among(hac_index *idx, const float *q, int64_t nq, int k, const int64_t *cand, int64_t m, float *D, int64_t *I) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    HAC_TRY(check_among_size("search_among", k, m));
+    if (nq < 0 || (nq > 0 && (!q || !D || !I || (m > 0 && !cand)))) return fail(HAC_ERR_INVALID, "search_among: bad arguments");
+    if (nq == 0) return HAC_OK;
+    const size_t total = (size_t)nq * k;
+    if (m == 0) {   // lists of padding only
+        std::fill(D, D + total, -FLT_MAX);
+        std::fill(I, I + total, (int64_t)-1);
+        return HAC_OK;
+    }
+    HAC_TRY(check_host_ids("search_among", cand, nq, m, idx->ntotal, IdPlace::QUERY_COLUMN, "padding"));
+    // Every shard selects among the candidates it holds (one host thread each; a row lives in one shard, so no repeat crosses
+    // shards), in the numbering of the whole index; the slabs are merged at k on the first device, as search merges them.
+    const int S = (int)idx->shards.size();
+    DeviceIndex *s0 = idx->shards[0];
+    if (S == 1) {
+        HAC_TRY(among_shard(idx, 0, q, nq, k, cand, m));
+    } else {
+        const RowLocator loc(idx);
+        const std::vector<int32_t> at = loc.locate(cand, (size_t)(nq * m));
+        std::vector<std::vector<int64_t>> local(S, std::vector<int64_t>(at.size(), -1));
+        for (size_t i = 0; i < at.size(); ++i)
+            if (at[i] >= 0) local[loc.shard(at[i])][i] = loc.local(at[i], cand[i]);
+        {
+            DeviceGuard g0(s0->device);
+            HAC_TRY(idx->ws_lists.reserve((size_t)S * total * 8));
+            HAC_TRY(idx->ws_out.reserve(total * 8));
+        }
+        HAC_TRY(for_each_shard(idx, [&](int si) { return among_shard(idx, si, q, nq, k, local[si].data(), m); }));
+    }
+    DeviceGuard g0(s0->device);
+    const uint64_t *final_keys = (const uint64_t *)s0->ws_keys.p;
+    if (S > 1) {   // (on shard 0's stream, never the null stream: see search_host)
+        for (int si = 0; si < S; ++si)
+            HAC_HIP(hipMemcpyAsync((char *)idx->ws_lists.p + (size_t)si * total * 8, idx->shards[si]->ws_keys.p, total * 8, hipMemcpyDeviceToDevice, s0->stream));
+        HAC_TRY(hac_merge_keys_device(s0->device, (const uint64_t *)idx->ws_lists.p, S, nq, k, (uint64_t *)idx->ws_out.p, s0->stream));
+        final_keys = (const uint64_t *)idx->ws_out.p;
+    }
+    // the keys come back through the pinned slab a chunk at a time; the host unpacks them (key_score_host, key_row_host)
+    const size_t chunk = (size_t)8 << 20;
+    char *slab = nullptr;
+    HAC_TRY(pin_slab(*s0, std::min(chunk, total) * 8, slab));
+    for (size_t done = 0; done < total; done += chunk) {
+        const size_t n = std::min(chunk, total - done);
+        HAC_HIP(hipMemcpyAsync(slab, final_keys + done, n * 8, hipMemcpyDeviceToHost, s0->stream));
+        HAC_HIP(hipStreamSynchronize(s0->stream));
+        const u64 *kk = reinterpret_cast<const u64 *>(slab);
+        for (size_t i = 0; i < n; ++i) {
+            D[done + i] = kk[i] ? key_score_host(kk[i]) : -FLT_MAX;
+            I[done + i] = kk[i] ? key_row_host(kk[i]) : -1;
+        }
     }
     return HAC_OK;
 }

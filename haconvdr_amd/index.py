@@ -228,6 +228,40 @@ def _exclude_args_tensor(q, k, exclude, d, what="search_excluding_tensor"):
     return q, k, exclude
 
 
+def _check_among_shape(nq, shape, what):
+    if shape[0] != nq:
+        raise ValueError(f"{what}: {nq} queries but cand of shape {tuple(shape)} (one list per query)")
+    if shape[1] > _lib.HAC_MAX_AMONG:
+        raise ValueError(f"{what}: m = {shape[1]} candidates per query exceed {_lib.HAC_MAX_AMONG} (one LDS sort block)")
+
+
+def _among_args(q, k, cand, d, what="search_among"):
+    """(q float32 [nq, d], k, cand int64 [nq, m]) of search_among."""
+    q = _as_queries(q, d, what)
+    k = _as_k(k, what)
+    cand = _as_ids(cand, 2, what)
+    _check_among_shape(q.shape[0], cand.shape, what)
+    return q, k, cand
+
+
+def _among_args_tensor(q, k, cand, id_map, d, what="search_among_tensor"):
+    """(q float32 CUDA [nq, d], k, cand int64 CUDA [nq, m], id_map int64 CUDA [ntotal] or None) of search_among*_tensor."""
+    import torch
+    q = _queries_tensor(q, d, what)
+    k = _as_k(k, what)
+    cand = _ids_tensor(cand, 2, what)
+    _check_among_shape(q.shape[0], cand.shape, what)
+    if cand.device != q.device:
+        raise ValueError(f"{what}: q on {q.device} but cand on {cand.device}")
+    if id_map is not None:
+        if not isinstance(id_map, torch.Tensor) or not id_map.is_cuda or id_map.dtype != torch.int64 or id_map.dim() != 1:
+            raise ValueError(f"{what}: id_map must be an int64 CUDA tensor [ntotal]")
+        if id_map.device != q.device:
+            raise ValueError(f"{what}: q on {q.device} but id_map on {id_map.device}")
+        id_map = id_map.contiguous()
+    return q, k, cand, id_map
+
+
 def _filter_args(keys, exclude_pos, k, what="filter_keys"):
     """(keys int64 CUDA [nq, kin], exclude_pos int64 CUDA [nq, e], k in [1, kin]) of filter_keys."""
     keys = _ids_tensor(keys, 2, what)
@@ -290,6 +324,16 @@ class FlatIPIndex:
         q, k, exclude = _exclude_args(q, k, exclude, self.d)
         D, I = _host_results((q.shape[0], k))
         _lib.check(_lib.lib().hac_index_search_excluding(self._h, _f32p(q), q.shape[0], k, _i64p(exclude), exclude.shape[1], _f32p(D), _i64p(I)))
+        return D, I
+
+    def search_among(self, q, k, cand):
+        """search(q, k) over the query's candidate rows only: cand int64 [nq, m] row ids, a set (a row named twice appears once),
+        -1 = padding anywhere in the list; any other id outside [0, ntotal) raises HacError.  m <= HAC_MAX_AMONG; k may exceed m
+        (the tail is padding).  Rows whose score is NaN are in no list (include/haconvdr.h, "search among named rows");
+        faiss: SearchParameters(sel=IDSelectorBatch(ids)), one selector per query."""
+        q, k, cand = _among_args(q, k, cand, self.d)
+        D, I = _host_results((q.shape[0], k))
+        _lib.check(_lib.lib().hac_index_search_among(self._h, _f32p(q), q.shape[0], k, _i64p(cand), cand.shape[1], _f32p(D), _i64p(I)))
         return D, I
 
     def reset(self):
@@ -429,6 +473,28 @@ class FlatIPIndex:
                                                                 _devp(id_map), _stream_ptr(stream)))
         _keep_alive(stream, q, exclude, D, I)
         return D, I
+
+    def search_among_tensor(self, q, k, cand, id_map=None, stream=None):
+        """search_tensor over the query's candidate rows only: cand int64 CUDA [nq, m] ROW ids (not id_map's), a set; any id
+        outside [0, ntotal), -1 included, is ignored.  id_map: optional int64 CUDA [ntotal], I = id_map[row].  No host sync;
+        capturable after one call of the largest (nq, m, k)."""
+        q, k, cand, id_map = _among_args_tensor(q, k, cand, id_map, self.d)
+        D, I = _device_results((q.shape[0], k), q.device)
+        _lib.check(_lib.lib().hac_index_search_among_device(self._h, _devp(q), q.shape[0], k, _devp(cand), cand.shape[1], _devp(D), _devp(I),
+                                                            _devp(id_map), _stream_ptr(stream)))
+        _keep_alive(stream, q, cand, D, I, *(() if id_map is None else (id_map,)))
+        return D, I
+
+    def search_among_keys_tensor(self, q, k, cand, pos_base=0, stream=None):
+        """search_among_tensor's sorted packed keys (int64 view of uint64) [nq, k], positions pos_base + row: the unit exchanged
+        between shards (merge_keys, keys_to_results)."""
+        import torch
+        q, k, cand, _ = _among_args_tensor(q, k, cand, None, self.d, "search_among_keys_tensor")
+        keys = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
+        _lib.check(_lib.lib().hac_index_search_among_keys_device(self._h, _devp(q), q.shape[0], k, _devp(cand), cand.shape[1], _devp(keys),
+                                                                 int(pos_base), _stream_ptr(stream)))
+        _keep_alive(stream, q, cand, keys)
+        return keys
 
     def search_keys_tensor(self, q, k, pos_base=0, stream=None):
         """Packed top-k keys (int64 view of uint64) [nq, k]; the unit exchanged between shards."""

@@ -271,6 +271,24 @@ class ResidentCorpus:
         any other -- the TREC writer's per-query de-duplication (trec.output_test_res) is not applied."""
         return self.index.rank_ids(*self._pairs(query_embeddings, passage_ids, "rank"))
 
+    def rerank(self, query_embeddings, passage_ids, topN):
+        """Dense re-ranking of another system's run, as a ranking: query_embeddings float32 [nq,768] (numpy or CUDA tensor),
+        passage_ids int64 [nq, m] EXTERNAL ids (-1 = padding) -> (D float64 [nq,topN], I int64 [nq,topN] external ids) like
+        search(), over the query's named passages only.  The candidates are every row that carries one of the ids
+        (rows_carrying: an id two blocks hold names two rows, and both are ranked); an id no block holds adds nothing; lists
+        shorter than topN are padded with -FLT_MAX / -1.  Raises ValueError if the widest row list exceeds HAC_MAX_AMONG."""
+        import torch
+        from . import _lib
+        q = query_embeddings if isinstance(query_embeddings, torch.Tensor) else torch.from_numpy(
+            np.ascontiguousarray(query_embeddings, dtype=np.float32))
+        rows = rows_carrying(*self._id_lookup(), passage_ids)
+        if rows.shape[0] != q.shape[0]:
+            raise ValueError(f"rerank: {q.shape[0]} queries but passage_ids of shape {np.asarray(passage_ids).shape} (one list per query)")
+        if rows.shape[1] > _lib.HAC_MAX_AMONG:
+            raise ValueError(f"rerank: the widest list names {rows.shape[1]} rows, more than {_lib.HAC_MAX_AMONG}")
+        D, I = self.index.search_among_tensor(q.to(self.dev), topN, torch.from_numpy(rows).to(self.dev), id_map=self.id_map)
+        return D.cpu().numpy().astype(np.float64), I.cpu().numpy()
+
     # ---- lists whose length follows the scores ---------------------------------------------------------------------
     def _host_queries(self, query_embeddings):
         import torch

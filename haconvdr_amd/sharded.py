@@ -29,9 +29,10 @@ class ShardedSearcher:
     filter(keys [nq, k + e], exclude [nq, e], k) -> [nq, k]            (default: HIP filter kernel)
     local_scores(q, local_ids [nq, m]) -> float32 [nq, m]              (default: index.score_ids_tensor)
     count_ahead(q, ref_scores, ref_bounds [nq, m]) -> int64 [nq, m]    (default: index.count_ahead_tensor)
-    The six hooks exist so that the distributed plumbing can be exercised on CPU with
+    local_among_keys(q, k, local_cand [nq, m], pos_base) -> [nq, k]    (default: index.search_among_keys_tensor)
+    The seven hooks exist so that the distributed plumbing can be exercised on CPU with
     gloo and a test double; the product path always uses the HIP defaults.
-    n_local: rows this rank holds (default: index.ntotal when rank() is called).
+    n_local: rows this rank holds (default: index.ntotal when rank() / search_among() is called).
 
     exclude (optional, int64 [nq, e], on the keys' device): per query, GLOBAL positions (shard_base + local row) that must
     not be returned, identical on every rank; < 0 is padding.  Every rank then searches k + e, the all-gather and the merge
@@ -40,7 +41,7 @@ class ShardedSearcher:
     """
 
     def __init__(self, index, shard_base, group=None, id_map=None, local_keys=None, merge=None, to_results=None, filter=None,
-                 local_scores=None, count_ahead=None, n_local=None):
+                 local_scores=None, count_ahead=None, n_local=None, local_among_keys=None):
         from . import index as _index
         self.index = index
         self.shard_base = int(shard_base)
@@ -53,13 +54,9 @@ class ShardedSearcher:
         self._local_scores = local_scores or (lambda q, ids: index.score_ids_tensor(q, ids))
         self._count_ahead = count_ahead or (lambda q, s, b: index.count_ahead_tensor(q, s, b))
         self._n_local = n_local
+        self._local_among_keys = local_among_keys or (lambda q, k, cand, base: index.search_among_keys_tensor(q, k, cand, pos_base=base))
 
-    def search_keys(self, q, k, exclude=None):
-        if exclude is not None:
-            if exclude.dim() != 2 or exclude.shape[0] != q.shape[0]:
-                raise ValueError(f"exclude must be [nq, e] with nq = {q.shape[0]}, got shape {tuple(exclude.shape)}")
-            return self._filter(self.search_keys(q, k + exclude.shape[1]), exclude, k)
-        keys = self._local_keys(q, k, self.shard_base)
+    def _gather_and_merge(self, keys):
         if not dist.is_initialized():
             return keys                                   # a single process holding the whole corpus
         world = dist.get_world_size(self.group)
@@ -68,8 +65,34 @@ class ShardedSearcher:
         dist.all_gather_into_tensor(gathered, keys.contiguous(), group=self.group)
         return self._merge(gathered.view(world, nq, k))
 
+    def search_keys(self, q, k, exclude=None):
+        if exclude is not None:
+            if exclude.dim() != 2 or exclude.shape[0] != q.shape[0]:
+                raise ValueError(f"exclude must be [nq, e] with nq = {q.shape[0]}, got shape {tuple(exclude.shape)}")
+            return self._filter(self.search_keys(q, k + exclude.shape[1]), exclude, k)
+        return self._gather_and_merge(self._local_keys(q, k, self.shard_base))
+
     def search(self, q, k, exclude=None):
         return self._to_results(self.search_keys(q, k, exclude), self.id_map)
+
+    def search_among_keys(self, q, k, cand):
+        """The merged keys [nq, k] of search_among."""
+        if cand.dim() != 2 or cand.shape[0] != q.shape[0]:
+            raise ValueError(f"cand must be [nq, m] with nq = {q.shape[0]}, got shape {tuple(cand.shape)}")
+        if cand.dtype != torch.int64:
+            raise ValueError(f"cand must be int64, got {cand.dtype}")
+        n_local = int(self.index.ntotal if self._n_local is None else self._n_local)
+        local = cand - self.shard_base
+        mine = (cand >= 0) & (local >= 0) & (local < n_local)
+        local = torch.where(mine, local, torch.full_like(local, -1)).contiguous()
+        return self._gather_and_merge(self._local_among_keys(q, k, local, self.shard_base))
+
+    def search_among(self, q, k, cand):
+        """Exact top-k over each query's candidate rows, over the whole sharded corpus: cand int64 [nq, m] GLOBAL positions
+        (shard_base + local row), identical on every rank, a set, < 0 is padding -> (D, I) like search().  Every rank selects among
+        the candidates it holds (positions it does not hold become -1, the rest cand - shard_base; a row lives on one rank, so no
+        repeat crosses ranks), then the same one all-gather and merge as search_keys, at k."""
+        return self._to_results(self.search_among_keys(q, k, cand), self.id_map)
 
     def rank(self, q, ids):
         """Exact rank of named rows over the whole sharded corpus: ids int64 [nq, m] GLOBAL positions (shard_base + local row),

@@ -51,6 +51,7 @@ typedef enum {
 
 #define HAC_MAX_K 2048      /* faiss-gpu 1.7.2 has the same top-k ceiling */
 #define HAC_MAX_D 1024
+#define HAC_MAX_AMONG 4096  /* candidates per query of hac_index_search_among*: one LDS sort block (range search's sort_lds) */
 
 /* ------------------------------------------------------------------ errors */
 /* Message of the last failing call on this thread ("" if none).  Never NULL. */
@@ -303,6 +304,53 @@ int hac_index_range_search(hac_index *idx, const float *q, int64_t nq, const flo
                            int64_t *I);
 int hac_index_range_search_device(hac_index *idx, const float *q_dev, int64_t nq, const float *radius_dev, int64_t cap,
                                   int64_t *lims_dev, float *D_dev, int64_t *I_dev, const int64_t *id_map_dev, void *hip_stream);
+
+/* ---- search among named rows: exact top-k over each query's candidate rows ---------------------------------------------
+ * faiss: SearchParameters(sel=IDSelectorBatch(ids)), one selector per query -- the positive form of search_excluding, and the
+ * ranking behind score_ids (dense re-ranking of another system's run, a BM25 top-1000).  For a query q and a candidate list c
+ * (int64 row ids in the index's own numbering, as in "rows by id"; m per query):
+ *   among(q, c, k) = the first k entries of { rows r in set(c), 0 <= r < ntotal, s(q, r) not NaN }
+ *                    ordered by (s desc, r asc), padded with D = -FLT_MAX, I = -1
+ * s is the canonical score: the k-ordered fmaf chain plus the "+ 0.0f" of a packed key, the same bits score_ids and every
+ * search route return.  The list is a SET: a row named twice appears once.  -1 is padding and may stand anywhere in the list.
+ * A NaN query gives padding only; +-Inf scores are ordinary scores, as in search.  Three consequences:
+ *   - for D, I = search(q, k') on any route and k <= k': among(q, any permutation of I[i] with repeats and -1 mixed in, k)
+ *     == search(q, k), D bit for bit;
+ *   - D_among[i][j] has the bits of score_ids(q, I_among)[i][j] wherever I_among >= 0;
+ *   - with E the complement of set(c) and k + |E| <= HAC_MAX_K: among(q, c, k) == search_excluding(q, k, E).
+ * Limits: 1 <= k <= HAC_MAX_K (k may exceed m: the tail is padding) and 0 <= m <= HAC_MAX_AMONG = 4096, one LDS sort block;
+ * anything else is HAC_ERR_INVALID, and the message names k, m and the ceiling.  Longer lists would need a block merge that
+ * removes repeats across blocks: out of scope.  nq == 0 is HAC_OK and touches nothing; m == 0 with nq > 0 is HAC_OK and
+ * writes lists of padding only (cand may then be NULL).
+ * Ids outside [0, ntotal) follow the rows-by-id rule: the *_device forms ignore them; the host form ignores -1 and returns
+ * HAC_ERR_INVALID for any other, names the first offending id with its (query, column), and writes nothing.
+ *
+ * How (csrc/among.inc): among_keys_kernel has score_ids_kernel's grid and gather -- one workgroup per (query, 256 candidates),
+ * the query row in LDS, the row read from the row-major rescoring copy where it is current and from the tiles otherwise -- and
+ * writes the packed key of (score, pos_base + row) into a [nq][P] workspace, P the power of two >= m; 0 for an id outside the
+ * rows, a NaN score and the slots m..P.  among_select_kernel, one workgroup per query, sorts the P keys in LDS (bitonic,
+ * descending; 32 KiB at the ceiling), drops repeats (equal non-zero keys are the same row and, sorted, neighbours) and compacts
+ * the first k distinct non-zero keys by a block prefix count into [nq][k], the rest 0.  No atomics: the result is a pure
+ * function of the inputs (two identical calls return identical bytes); nothing goes to the status ring.
+ * Cost, by arithmetic (not measured): per query m gathered rows of 4d bytes -- contiguous out of the row-major copy, one useful
+ * 16-byte piece per 64-byte sector out of the tiles -- plus one LDS sort of P keys; 1000 queries x 1000 candidates at d = 768
+ * gather 3.1 GB (12.3 GB of sectors out of the tiles).  The corpus size does not enter.
+ *
+ * Host form: synchronous, on the index's own stream; one id check before the first kernel, queries and lists staged in chunks
+ * of ~64 MiB.  It works on a multi-device index: the ids are translated to (shard, local row), every shard produces its
+ * [nq, k] keys on a host thread of its own, positions are remapped as search does, and the slabs are merged at k on the first
+ * device (a row lives in one shard, so no repeat crosses shards).
+ * Device forms: single-device index (HAC_ERR_UNSUPPORTED otherwise), 16-byte aligned q_dev (HAC_ERR_INVALID otherwise); they
+ * enqueue on hip_stream, never read back and take no slot of the status ring.  id_map_dev as in hac_index_search_device.  The
+ * keys form writes the sorted packed keys [nq, k] with positions pos_base + row, the unit hac_merge_keys_device merges.  The
+ * key workspace grows by the rule of the search workspaces: run one call of the largest (nq, m, k) before capturing into a
+ * HIP graph; capturable once the segment table is up.  hac_index_last_plan afterwards reads
+ * "among_keys_kernel grid=G among_select_kernel P=.. k=.. lds=..". */
+int hac_index_search_among(hac_index *idx, const float *q, int64_t nq, int k, const int64_t *cand, int64_t m, float *D, int64_t *I);
+int hac_index_search_among_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const int64_t *cand_dev, int64_t m,
+                                  float *D_dev, int64_t *I_dev, const int64_t *id_map_dev, void *hip_stream);
+int hac_index_search_among_keys_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const int64_t *cand_dev, int64_t m,
+                                       uint64_t *keys_dev, uint32_t pos_base, void *hip_stream);
 
 /* ---- removing rows: faiss's IndexFlat::remove_ids(IDSelectorBatch(ids)), in place ------------------------------------------
  * The rows named by ids disappear; every surviving row keeps its bits and its relative order; the survivors are renumbered
