@@ -33,6 +33,7 @@
 #include <cstring>
 #include <numeric>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 namespace hac {
@@ -1139,6 +1140,7 @@ u32 next_pow2(u32 v) {
 #include "range.inc"
 #include "remove.inc"
 #include "among.inc"
+#include "masked.inc"
 
 // Every instantiation of the two templated scan kernels, once: init raises each one's dynamic-LDS limit from these tables and
 // the launches look their kernel up in them, so an instantiation that is launched is one whose limit was raised.
@@ -1192,6 +1194,8 @@ struct DeviceIndex {
         int debug_oom = 0;               // tests: the next N allocations the index needs behave as if their first attempt had found the device full (malloc_reclaiming)
         int scan_passes = 0;             // prefilter scan: 0 by size, 1..5 pins the number of passes (threshold refreshes between them)
         int pass_cut[2] = {0, 0};        // where the passes end, in thousandths of the row groups (option "scan_pass_cuts" = "a,b"); 0 = by size
+        int masked_p = 0;                // search_masked: row streams per query tile; 0 = as make_plan sizes scan16's (tests pin 1: one workgroup walks every group)
+        int debug_masked_tiles = 0;      // tests: search_masked's query tiles per launch (0 = by the list workspace), so that a small call spans several launches
     } tune;
     // Passes of the prefilter's main scan (search_keys_split) and where they end (row groups, whole rounds).  A refresh costs a
     // kernel tail + a selection (~0.1 ms): only scans of a few milliseconds are cut, and only with seeded thresholds (the refresh
@@ -1297,6 +1301,13 @@ struct DeviceIndex {
         } else if (n == "debug_max_pass") {
             if (!parse_int(v, 0, 1000000, t)) return fail(HAC_ERR_INVALID, "index option debug_max_pass = '%s': an integer >= 0", v.c_str());
             tune.debug_max_pass = (int)t;
+        } else if (n == "masked_p") {
+            if (v == "auto") t = 0;
+            else if (!parse_int(v, 1, 4096, t)) return fail(HAC_ERR_INVALID, "index option masked_p = '%s': auto | an integer 1..4096", v.c_str());
+            tune.masked_p = (int)t;
+        } else if (n == "debug_masked_tiles") {
+            if (!parse_int(v, 0, 65535, t)) return fail(HAC_ERR_INVALID, "index option debug_masked_tiles = '%s': an integer 0..65535", v.c_str());
+            tune.debug_masked_tiles = (int)t;
         } else if (n == "seed_groups_max") {
             if (!parse_int(v, 0, LONG_MAX, t)) return fail(HAC_ERR_INVALID, "index option seed_groups_max = '%s': an integer >= 0 (0 = 14 sqrt(groups))", v.c_str());
             tune.seed_groups_max = t <= 0 ? 0 : (int)std::max<long>(768, std::min<long>(t, 1 << 30));
@@ -1392,6 +1403,8 @@ struct DeviceIndex {
             for (const ScanhEntry &e : SCANH_TABLE) HAC_HIP(hipFuncSetAttribute((const void *)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             HAC_HIP(hipFuncSetAttribute((const void *)count_ahead_kernel<RANK_MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             HAC_HIP(hipFuncSetAttribute((const void *)range_emit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
+            // (DYNAMIC LDS: without it a large k, whose candidate buffers pass the default 64 KiB, fails to launch)
+            HAC_HIP(hipFuncSetAttribute((const void *)scan16_masked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             attr_done[device] = true;
         }
         return HAC_OK;
@@ -1413,7 +1426,7 @@ struct DeviceIndex {
         for (PinBuf *b : {&h_pin, &h_fb, &h_stage[0], &h_stage[1]}) b->release();
         for (GrowBuf *b : {&ws_partial, &ws_pcnt, &ws_seedkeys, &ws_thr, &ws_thrglob, &ws_q, &ws_qt, &ws_keys, &ws_D, &ws_I, &ws_stage[0],
                            &ws_stage[1], &ws_err, &ws_norm, &ws_qsplit, &ws_delta, &ws_cand, &ws_akeys, &ws_fail, &ws_stat, &ws_fbidx[0], &ws_fbidx[1],
-                           &ws_fbq[0], &ws_fbq[1], &ws_fbkeys[0], &ws_fbkeys[1], &ws_ids, &ws_rank, &ws_range, &ws_among})
+                           &ws_fbq[0], &ws_fbq[1], &ws_fbkeys[0], &ws_fbkeys[1], &ws_ids, &ws_rank, &ws_range, &ws_among, &ws_mgroups, &ws_mcnt, &ws_masks})
             b->release();
         if (h_err) (void)hipHostFree(h_err);
         if (h_plan) (void)hipHostFree(h_plan);
@@ -1831,6 +1844,8 @@ struct DeviceIndex {
     GrowBuf ws_ids, ws_rank;   // the by-id calls (rows_host.inc): a chunk's ids; the rank calls' counters and reference scores
     GrowBuf ws_range;          // range search (rows_host.inc: RangeWs): control words, counters, cursors, staging and the two key buffers
     GrowBuf ws_among;          // search among named rows (rows_host.inc: among_keys_device): a chunk's [queries][P] candidate keys
+    GrowBuf ws_mgroups, ws_mcnt;   // search inside a bitmap (search_keys_masked): one launch's group lists u32 [tiles][G], the call's counters u32 [tiles]
+    GrowBuf ws_masks;          // its host form (rows_host.inc: masked_shard): a chunk's masks and mask_of
 
     char last_plan[320] = "none";
     // a device-decided prefilter search leaves its fallback count and err / bound on the device: plan() completes the text
@@ -1911,12 +1926,12 @@ struct DeviceIndex {
 
     static size_t scanq_lds(int NQ, int C) { return (size_t)NQ * (2 * 16 * 16 + (size_t)C * 8 + 8) + 16; }
 
-    int make_plan(int64_t nq, int k, u32 n_items, Plan &pl) const {
+    int make_plan(int64_t nq, int k, u32 n_items, Plan &pl, bool scan16_only = false) const {
         pl.kind = 0;
         pl.NT = 0;
         pl.W = SCAN_WAVES;
         // many queries: GEMM-shaped kernel, NQ = 32*NT queries per workgroup
-        if (nq > 16 && K4 % 16 == 0 && !tune.force_scan16) {
+        if (nq > 16 && K4 % 16 == 0 && !tune.force_scan16 && !scan16_only) {
             const int C2 = (int)std::max<u32>(32u, next_pow2((u32)k + 1u));
             int best_nt = 0;
             int64_t best_pad = 0;
@@ -2068,6 +2083,83 @@ struct DeviceIndex {
                                                                                    keys_out, nullptr, nq_dev, (int)nq, (u32)(pl.P * pl.n_qtiles),
                                                                                    (u32)pl.QT, thrglob(), (u32 *)ws_err.p);
         HAC_HIP(hipGetLastError());
+        return HAC_OK;
+    }
+
+    // ---- search inside a bitmap (masked.inc).  keys_out: device u64 [nq][k]; masks u64 [n_masks][words], mask_of int64 [nq] or
+    // null (n_masks == 1: mask 0, n_masks == nq: mask i for query i), all on the device; arguments checked by the entry points
+    // (words == ceil(ntotal / 64) above all: the kernels index a mask row by the group).
+    // A kind-0 plan at any nq (QT and C by make_plan's scan16 arithmetic), NO threshold seeding (thr_init stays null: a sample
+    // of unmasked rows gives bounds the masked set may not meet), then the existing select_keys_kernel.  The queries are cut
+    // into launches of whole tiles so that the list workspace u32 [tiles][G] stays within 64 MiB and, like search_keys, within
+    // QUERY_CHUNK queries; every launch holds at least one tile and works at offsets of its own into the queries, mask_of (or
+    // the masks, when query i uses mask i), the counters and keys_out.  The lists, the survivors and the thresholds are one
+    // launch's and are reused by the next, in stream order.  Every workspace is a GrowBuf sized by (nq, k) and the rows alone:
+    // after one call of the largest shape a call allocates nothing and can be captured.
+    int search_keys_masked(const float *q_dev, int64_t nq, int k, const u64 *masks_dev, int64_t n_masks, int64_t words, const int64_t *mask_of_dev,
+                           u64 *keys_out, u32 pos_base, hipStream_t st) {
+        if (nq == 0) return HAC_OK;
+        HAC_TRY(check_search_args(q_dev, pos_base));
+        if (ntotal == 0) {
+            HAC_HIP(hipMemsetAsync(keys_out, 0, (size_t)nq * k * 8, st));
+            return HAC_OK;
+        }
+        HAC_TRY(upload_segs(st));
+        const u32 G = (u32)((ntotal + GROUP_ROWS - 1) / GROUP_ROWS);
+        Plan pl0, pl;
+        HAC_TRY(make_plan(nq, k, G, pl0, true));
+        const int QT = pl0.QT;
+        int64_t TL = std::max<int64_t>(1, ((int64_t)64 << 20) / ((int64_t)G * 4));   // tiles per launch
+        TL = std::min<int64_t>(TL, std::max<int64_t>(1, QUERY_CHUNK / QT));
+        if (tune.debug_masked_tiles > 0) TL = std::min<int64_t>(TL, tune.debug_masked_tiles);
+        TL = std::min<int64_t>(TL, pl0.n_qtiles);
+        const int64_t QL = TL * QT;   // queries per launch
+        HAC_TRY(make_plan(std::min(nq, QL), k, G, pl, true));   // P for the tiles of one launch; QT and C as above
+        if (tune.masked_p > 0) pl.P = (int)std::max<long>(1, std::min<long>(tune.masked_p, (G + SCAN_WAVES - 1) / SCAN_WAVES));
+        const int64_t launches = (pl0.n_qtiles + TL - 1) / TL;
+        HAC_TRY(ws_mgroups.reserve((size_t)TL * G * 4));
+        HAC_TRY(ws_mcnt.reserve((size_t)pl0.n_qtiles * 4));
+        HAC_TRY(ws_partial.reserve((size_t)std::min(nq, QL) * pl.P * k * 8));
+        HAC_TRY(ws_pcnt.reserve((size_t)std::min(nq, QL) * 4));
+        HAC_TRY(ws_thrglob.reserve(((size_t)TL * QT + THR_CTL_WORDS) * 4));
+        HAC_HIP(hipMemsetAsync(ws_mcnt.p, 0, (size_t)pl0.n_qtiles * 4, st));
+        const unsigned gx = (G + 255u) / 256u;
+        snprintf(last_plan, sizeof last_plan, "mask_groups_kernel grid=(%u,%lld) scan16_masked_kernel<W=%d> grid=(%d,%lld) QT=%d C=%d lds=%zu launches=%lld", gx,
+                 (long long)TL, SCAN_WAVES, pl.P, (long long)TL, QT, pl.C, pl.lds_scan, (long long)launches);
+        plan_text_slot = -1;
+        const int np2 = (int)next_pow2((u32)k);
+        for (int64_t l = 0; l < launches; ++l) {
+            const int64_t off = l * QL, n = std::min(QL, nq - off), tiles = (n + QT - 1) / QT;
+            MaskArgs m{};
+            m.per_query = (!mask_of_dev && n_masks != 1) ? 1 : 0;
+            m.masks = m.per_query ? masks_dev + (size_t)off * words : masks_dev;
+            m.mask_of = mask_of_dev ? (const long long *)mask_of_dev + off : nullptr;
+            m.n_masks = (long)n_masks;
+            m.words = (long)words;
+            m.groups = (u32 *)ws_mgroups.p;
+            m.n_groups = (u32 *)ws_mcnt.p + l * TL;
+            m.G = G;
+            ScanArgs a = scan_args(q_dev + (size_t)off * d, n);
+            a.k = k;
+            a.C = pl.C;
+            a.QT = QT;
+            a.thr_glob = thrglob();
+            a.partial = (u64 *)ws_partial.p;
+            a.partial_cnt = (u32 *)ws_pcnt.p;
+            a.pos_base = pos_base;
+            mask_groups_kernel<<<dim3(gx, (unsigned)tiles), dim3(256), 0, st>>>(m, (int)n, QT, (long)ntotal);
+            HAC_HIP(hipGetLastError());
+            HAC_HIP(hipMemsetAsync(ws_pcnt.p, 0, (size_t)n * 4, st));
+            HAC_TRY(clear_thrglob((size_t)tiles * QT, st));
+            HAC_TRY(prof_begin(st));
+            scan16_masked_kernel<<<dim3((unsigned)pl.P, (unsigned)tiles), dim3(SCAN_WAVES * 64), pl.lds_scan, st>>>(a, m);
+            HAC_HIP(hipGetLastError());
+            HAC_TRY(prof_end(st));
+            select_keys_kernel<<<dim3((unsigned)n), dim3(256), (size_t)np2 * 8, st>>>((const u64 *)ws_partial.p, (size_t)pl.P * k, (const u32 *)ws_pcnt.p,
+                                                                                      (u32)((size_t)pl.P * k), k, np2, keys_out + (size_t)off * k, nullptr, nullptr, (int)n,
+                                                                                      (u32)(pl.P * tiles), (u32)QT, thrglob(), (u32 *)ws_err.p);
+            HAC_HIP(hipGetLastError());
+        }
         return HAC_OK;
     }
 

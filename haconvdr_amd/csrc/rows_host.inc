@@ -513,6 +513,37 @@ int among_shard(hac_index *idx, int si, const float *q, int64_t nq, int k, const
     return HAC_OK;
 }
 
+// The end of a host search whose shards have left their [nq][k] keys (positions of the whole index) in their ws_keys, streams
+// idle: several devices are merged at k on the first one (ws_lists / ws_out: reserved by the caller), as search merges them;
+// the keys come back through the pinned slab a chunk at a time and the host unpacks them (key_score_host, key_row_host).
+int shard_keys_to_host(hac_index *idx, int64_t nq, int k, float *D, int64_t *I) {
+    const int S = (int)idx->shards.size();
+    const size_t total = (size_t)nq * k;
+    DeviceIndex *s0 = idx->shards[0];
+    DeviceGuard g0(s0->device);
+    const uint64_t *final_keys = (const uint64_t *)s0->ws_keys.p;
+    if (S > 1) {   // (on shard 0's stream, never the null stream: see search_host)
+        for (int si = 0; si < S; ++si)
+            HAC_HIP(hipMemcpyAsync((char *)idx->ws_lists.p + (size_t)si * total * 8, idx->shards[si]->ws_keys.p, total * 8, hipMemcpyDeviceToDevice, s0->stream));
+        HAC_TRY(hac_merge_keys_device(s0->device, (const uint64_t *)idx->ws_lists.p, S, nq, k, (uint64_t *)idx->ws_out.p, s0->stream));
+        final_keys = (const uint64_t *)idx->ws_out.p;
+    }
+    const size_t chunk = (size_t)8 << 20;
+    char *slab = nullptr;
+    HAC_TRY(pin_slab(*s0, std::min(chunk, total) * 8, slab));
+    for (size_t done = 0; done < total; done += chunk) {
+        const size_t n = std::min(chunk, total - done);
+        HAC_HIP(hipMemcpyAsync(slab, final_keys + done, n * 8, hipMemcpyDeviceToHost, s0->stream));
+        HAC_HIP(hipStreamSynchronize(s0->stream));
+        const u64 *kk = reinterpret_cast<const u64 *>(slab);
+        for (size_t i = 0; i < n; ++i) {
+            D[done + i] = kk[i] ? key_score_host(kk[i]) : -FLT_MAX;
+            I[done + i] = kk[i] ? key_row_host(kk[i]) : -1;
+        }
+    }
+    return HAC_OK;
+}
+
 // ---- removing rows (hac_index_remove_ids).  rem: this shard's removed rows, local numbering, sorted ascending, no duplicates.
 // What can fail cheaply on a shard, before any shard moves a row: the staging buffers, the id list's device buffer, the slab.
 constexpr int64_t REMOVE_ID_CHUNK = (int64_t)4 << 20;   // ids per upload through the pinned slab (16 MiB)
@@ -621,9 +652,166 @@ void rewrite_spans_after_remove(std::vector<std::vector<SpanDesc>> &spans, const
         shard.swap(kept);
     }
 }
+
+// ---- search inside a bitmap (masked.inc; DeviceIndex::search_keys_masked)
+int check_masked_args(const char *what, const hac_index *idx, int64_t nq, int k, int64_t n_masks, int64_t words, bool has_mask_of, bool pointers_ok) {
+    if (k < 1 || k > HAC_MAX_K) return fail(HAC_ERR_INVALID, "%s: k=%d out of range [1, %d]", what, k, HAC_MAX_K);
+    if (nq < 0 || !pointers_ok) return fail(HAC_ERR_INVALID, "%s: bad arguments", what);
+    if (nq == 0) return HAC_OK;
+    const int64_t W = (idx->ntotal + 63) / 64;
+    if (words != W)
+        return fail(HAC_ERR_INVALID, "%s: words=%lld, but %lld rows need %lld words per mask (a mask packed before an add or a remove?)", what, (long long)words,
+                    (long long)idx->ntotal, (long long)W);
+    if (n_masks < 1) return fail(HAC_ERR_INVALID, "%s: n_masks=%lld: needs at least one mask", what, (long long)n_masks);
+    if (!has_mask_of && n_masks != 1 && n_masks != nq)
+        return fail(HAC_ERR_INVALID, "%s: mask_of is null with %lld masks for %lld queries: needs n_masks == 1 (one mask for all) or n_masks == nq (mask i for query i)",
+                    what, (long long)n_masks, (long long)nq);
+    return HAC_OK;
+}
+
+// bits [s0, s0 + n) of src -> bits [d0, d0 + n) of dst, up to 64 at a time (dst's other bits stay)
+void copy_bits(const u64 *src, int64_t s0, u64 *dst, int64_t d0, int64_t n) {
+    while (n > 0) {
+        const int so = (int)(s0 & 63), dof = (int)(d0 & 63);
+        const int take = (int)std::min<int64_t>(n, 64 - std::max(so, dof));   // within one word on both sides
+        const u64 field = take == 64 ? ~0ull : ((1ull << take) - 1ull);
+        const u64 v = (src[s0 >> 6] >> so) & field;
+        u64 &dw = dst[d0 >> 6];
+        dw = (dw & ~(field << dof)) | (v << dof);
+        s0 += take;
+        d0 += take;
+        n -= take;
+    }
+}
+
+// One shard's keys of the whole call, [nq][k] in its ws_keys, on its own stream: every query under ITS shard's slice of its
+// mask.  mask_of: checked, one entry per query.  Queries are staged in chunks whose queries, distinct masks and mask_of fit
+// ~64 MiB (at least one query); a chunk uploads only the masks its queries name, renumbered from 0.  With several devices the
+// slice is cut out of the caller's mask span by span (SpanDesc: local0, count, global0) and the positions are then those of
+// the whole index (remap_positions_kernel, as search does).  Returns with the shard's stream idle.
+int masked_shard(hac_index *idx, int si, const float *q, int64_t nq, int k, const u64 *masks, int64_t words, const int64_t *mask_of) {
+    DeviceIndex &x = *idx->shards[si];
+    DeviceGuard g(x.device);
+    if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", x.device);
+    const bool sliced = idx->shards.size() > 1;
+    const int64_t Wl = (x.ntotal + 63) / 64;   // words of a local mask
+    HAC_TRY(x.ws_keys.reserve((size_t)nq * k * 8));
+    if (x.ntotal == 0) {   // a shard without rows: padding only
+        HAC_HIP(hipMemsetAsync(x.ws_keys.p, 0, (size_t)nq * k * 8, x.stream));
+        HAC_HIP(hipStreamSynchronize(x.stream));
+        return HAC_OK;
+    }
+    const size_t q_bytes = (size_t)x.d * 4, m_bytes = (size_t)Wl * 8, budget = (size_t)64 << 20;
+    std::vector<int64_t> slot_of;                 // of the chunk: local mask number -> the caller's mask
+    std::vector<int64_t> local_of;                // of the chunk: per query, its local mask number
+    std::unordered_map<int64_t, int64_t> seen;    // the caller's mask -> local number
+    for (int64_t q0 = 0; q0 < nq;) {
+        slot_of.clear();
+        local_of.clear();
+        seen.clear();
+        int64_t nqc = 0;
+        while (q0 + nqc < nq) {
+            const int64_t mo = mask_of[q0 + nqc];
+            const bool is_new = seen.find(mo) == seen.end();
+            const size_t need = (size_t)(nqc + 1) * (q_bytes + 8) + (slot_of.size() + (is_new ? 1 : 0)) * m_bytes;
+            if (nqc > 0 && need > budget) break;
+            if (is_new) {
+                seen.emplace(mo, (int64_t)slot_of.size());
+                slot_of.push_back(mo);
+            }
+            local_of.push_back(seen[mo]);
+            ++nqc;
+        }
+        const size_t nm = slot_of.size();
+        HAC_TRY(x.ws_q.reserve(nqc * q_bytes));
+        HAC_TRY(x.ws_masks.reserve(nm * m_bytes + (size_t)nqc * 8));
+        char *slab = nullptr;   // queries, masks, mask_of
+        HAC_TRY(pin_slab(x, nqc * q_bytes + nm * m_bytes + (size_t)nqc * 8, slab));
+        std::memcpy(slab, q + (size_t)q0 * x.d, nqc * q_bytes);
+        u64 *hm = reinterpret_cast<u64 *>(slab + nqc * q_bytes);
+        for (size_t s = 0; s < nm; ++s) {
+            const u64 *src = masks + (size_t)slot_of[s] * words;
+            u64 *dst = hm + s * Wl;
+            if (!sliced) {
+                std::memcpy(dst, src, m_bytes);
+            } else {
+                std::memset(dst, 0, m_bytes);
+                for (const SpanDesc &sp : idx->spans[si]) copy_bits(src, (int64_t)sp.global0, dst, (int64_t)sp.local0, (int64_t)sp.count);
+            }
+        }
+        std::memcpy(hm + nm * Wl, local_of.data(), (size_t)nqc * 8);
+        HAC_HIP(hipMemcpyAsync(x.ws_q.p, slab, nqc * q_bytes, hipMemcpyHostToDevice, x.stream));
+        HAC_HIP(hipMemcpyAsync(x.ws_masks.p, hm, nm * m_bytes + (size_t)nqc * 8, hipMemcpyHostToDevice, x.stream));
+        const u64 *md = (const u64 *)x.ws_masks.p;
+        HAC_TRY(x.search_keys_masked((const float *)x.ws_q.p, nqc, k, md, (int64_t)nm, Wl, (const int64_t *)(md + nm * Wl), (u64 *)x.ws_keys.p + (size_t)q0 * k, 0u,
+                                     x.stream));
+        HAC_HIP(hipStreamSynchronize(x.stream));   // (the slab is the next chunk's)
+        q0 += nqc;
+    }
+    if (sliced && !idx->spans[si].empty()) {
+        HAC_TRY(upload_spans(idx, si));
+        const long nk = (long)nq * k;
+        remap_positions_kernel<<<dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, x.stream>>>((u64 *)x.ws_keys.p, nk, (const SpanDesc *)idx->ws_spans[si].p,
+                                                                                             (int)idx->spans[si].size());
+        HAC_HIP(hipGetLastError());
+        HAC_HIP(hipStreamSynchronize(x.stream));
+    }
+    return HAC_OK;
+}
 }  // namespace
 
 extern "C" {
+
+int hac_index_search_masked_keys_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const uint64_t *masks_dev, int64_t n_masks, int64_t words,
+                                        const int64_t *mask_of_dev, uint64_t *keys_dev, uint32_t pos_base, void *hip_stream) {
+    return on_single_shard(idx, "search_masked_keys_device", [&](DeviceIndex &s) -> int {
+        HAC_TRY(check_masked_args("search_masked_keys_device", idx, nq, k, n_masks, words, mask_of_dev != nullptr, nq <= 0 || (q_dev && keys_dev && (masks_dev || words == 0))));
+        if (nq == 0) return HAC_OK;
+        return s.search_keys_masked(q_dev, nq, k, (const u64 *)masks_dev, n_masks, words, mask_of_dev, (u64 *)keys_dev, pos_base, (hipStream_t)hip_stream);
+    });
+}
+
+int hac_index_search_masked_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const uint64_t *masks_dev, int64_t n_masks, int64_t words,
+                                   const int64_t *mask_of_dev, float *D_dev, int64_t *I_dev, const int64_t *id_map_dev, void *hip_stream) {
+    return on_single_shard(idx, "search_masked_device", [&](DeviceIndex &s) -> int {
+        HAC_TRY(check_masked_args("search_masked_device", idx, nq, k, n_masks, words, mask_of_dev != nullptr, nq <= 0 || (q_dev && D_dev && I_dev && (masks_dev || words == 0))));
+        if (nq == 0) return HAC_OK;
+        HAC_TRY(s.ws_keys.reserve((size_t)nq * k * 8));
+        HAC_TRY(s.search_keys_masked(q_dev, nq, k, (const u64 *)masks_dev, n_masks, words, mask_of_dev, (u64 *)s.ws_keys.p, 0u, (hipStream_t)hip_stream));
+        return hac_keys_to_results_device(s.device, (const uint64_t *)s.ws_keys.p, nq * k, id_map_dev, D_dev, I_dev, hip_stream);
+    });
+}
+
+int hac_index_search_masked(hac_index *idx, const float *q, int64_t nq, int k, const uint64_t *masks, int64_t n_masks, int64_t words, const int64_t *mask_of,
+                            float *D, int64_t *I) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    HAC_TRY(check_masked_args("search_masked", idx, nq, k, n_masks, words, mask_of != nullptr, nq <= 0 || (q && D && I && (masks || words == 0))));
+    if (nq == 0) return HAC_OK;
+    const size_t total = (size_t)nq * k;
+    if (idx->ntotal == 0) {   // padding only
+        std::fill(D, D + total, -FLT_MAX);
+        std::fill(I, I + total, (int64_t)-1);
+        return HAC_OK;
+    }
+    std::vector<int64_t> mo((size_t)nq);
+    for (int64_t i = 0; i < nq; ++i) {
+        mo[(size_t)i] = mask_of ? mask_of[i] : (n_masks == 1 ? 0 : i);
+        if (mo[(size_t)i] < 0 || mo[(size_t)i] >= n_masks)
+            return fail(HAC_ERR_INVALID, "search_masked: mask_of[%lld] = %lld of query %lld is outside [0, %lld)", (long long)i, (long long)mo[(size_t)i], (long long)i,
+                        (long long)n_masks);
+    }
+    // Every shard searches its own rows under its own slice of every mask (one host thread each), in the numbering of the whole
+    // index; the slabs are merged at k on the first device, as search merges them.
+    const int S = (int)idx->shards.size();
+    DeviceIndex *s0 = idx->shards[0];
+    if (S > 1) {
+        DeviceGuard g0(s0->device);
+        HAC_TRY(idx->ws_lists.reserve((size_t)S * total * 8));
+        HAC_TRY(idx->ws_out.reserve(total * 8));
+    }
+    HAC_TRY(for_each_shard(idx, [&](int si) { return masked_shard(idx, si, q, nq, k, (const u64 *)masks, words, mo.data()); }));
+    return shard_keys_to_host(idx, nq, k, D, I);
+}
 
 int hac_index_remove_ids(hac_index *idx, const int64_t *ids, int64_t n, int64_t *n_removed) {
     if (n_removed) *n_removed = 0;
@@ -815,29 +1003,7 @@ int hac_index_search_among(hac_index *idx, const float *q, int64_t nq, int k, co
         }
         HAC_TRY(for_each_shard(idx, [&](int si) { return among_shard(idx, si, q, nq, k, local[si].data(), m); }));
     }
-    DeviceGuard g0(s0->device);
-    const uint64_t *final_keys = (const uint64_t *)s0->ws_keys.p;
-    if (S > 1) {   // (on shard 0's stream, never the null stream: see search_host)
-        for (int si = 0; si < S; ++si)
-            HAC_HIP(hipMemcpyAsync((char *)idx->ws_lists.p + (size_t)si * total * 8, idx->shards[si]->ws_keys.p, total * 8, hipMemcpyDeviceToDevice, s0->stream));
-        HAC_TRY(hac_merge_keys_device(s0->device, (const uint64_t *)idx->ws_lists.p, S, nq, k, (uint64_t *)idx->ws_out.p, s0->stream));
-        final_keys = (const uint64_t *)idx->ws_out.p;
-    }
-    // the keys come back through the pinned slab a chunk at a time; the host unpacks them (key_score_host, key_row_host)
-    const size_t chunk = (size_t)8 << 20;
-    char *slab = nullptr;
-    HAC_TRY(pin_slab(*s0, std::min(chunk, total) * 8, slab));
-    for (size_t done = 0; done < total; done += chunk) {
-        const size_t n = std::min(chunk, total - done);
-        HAC_HIP(hipMemcpyAsync(slab, final_keys + done, n * 8, hipMemcpyDeviceToHost, s0->stream));
-        HAC_HIP(hipStreamSynchronize(s0->stream));
-        const u64 *kk = reinterpret_cast<const u64 *>(slab);
-        for (size_t i = 0; i < n; ++i) {
-            D[done + i] = kk[i] ? key_score_host(kk[i]) : -FLT_MAX;
-            I[done + i] = kk[i] ? key_row_host(kk[i]) : -1;
-        }
-    }
-    return HAC_OK;
+    return shard_keys_to_host(idx, nq, k, D, I);
 }
 
 int hac_index_range_search_device(hac_index *idx, const float *q_dev, int64_t nq, const float *radius_dev, int64_t cap, int64_t *lims_dev, float *D_dev,

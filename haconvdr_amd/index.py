@@ -262,6 +262,133 @@ def _among_args_tensor(q, k, cand, id_map, d, what="search_among_tensor"):
     return q, k, cand, id_map
 
 
+# ---- bitmaps of search_masked (include/haconvdr.h, "search inside a bitmap"): row r is bit r & 63 of word r >> 6
+def mask_words(ntotal):
+    """words per mask of an index of ntotal rows"""
+    return (int(ntotal) + 63) // 64
+
+
+def pack_mask(mask):
+    """bool [ntotal] or [n_masks, ntotal] (ndarray or CUDA tensor) -> the packed words as int64 [W] or [n_masks, W], W =
+    ceil(ntotal / 64), of the same kind; int64 is the view torch can hold: a word with bit 63 set is negative.  The bytes are
+    np.packbits(mask, bitorder="little"), faiss's IDSelectorBitmap bitmap, zero padded to whole words."""
+    if isinstance(mask, np.ndarray) or not hasattr(mask, "is_cuda"):
+        a = np.asarray(mask)
+        if a.dtype != np.bool_ or a.ndim not in (1, 2):
+            raise ValueError(f"pack_mask: needs bool [ntotal] or [n_masks, ntotal], got {a.dtype} {a.shape}")
+        W = mask_words(a.shape[-1])
+        padded = np.zeros(a.shape[:-1] + (W * 64,), np.bool_)
+        padded[..., :a.shape[-1]] = a
+        return np.packbits(padded, axis=-1, bitorder="little").view("<u8").view(np.int64).reshape(a.shape[:-1] + (W,))
+    import torch
+    if mask.dtype != torch.bool or mask.dim() not in (1, 2):
+        raise ValueError(f"pack_mask: needs bool [ntotal] or [n_masks, ntotal], got {mask.dtype} {tuple(mask.shape)}")
+    n = mask.shape[-1]
+    W = mask_words(n)
+    padded = torch.zeros(tuple(mask.shape[:-1]) + (W * 64,), dtype=torch.int64, device=mask.device)
+    padded[..., :n] = mask
+    # bit b of a word: the sum of distinct powers of two cannot carry; 1 << 63 wraps to the sign bit, as the word wants
+    weights = torch.ones(64, dtype=torch.int64, device=mask.device) << torch.arange(64, dtype=torch.int64, device=mask.device)
+    return (padded.reshape(tuple(mask.shape[:-1]) + (W, 64)) * weights).sum(dim=-1)
+
+
+def unpack_mask(words, ntotal):
+    """pack_mask's inverse: int64 / uint64 words [W] or [n_masks, W] (ndarray or tensor) -> bool [ntotal] or [n_masks, ntotal]
+    ndarray; bits at or above ntotal are dropped."""
+    a = words.cpu().numpy() if hasattr(words, "is_cuda") else np.asarray(words)
+    if a.dtype not in (np.int64, np.uint64) or a.ndim not in (1, 2) or a.shape[-1] != mask_words(ntotal):
+        raise ValueError(f"unpack_mask: needs int64 / uint64 [.., {mask_words(ntotal)}] for {ntotal} rows, got {a.dtype} {a.shape}")
+    b = np.ascontiguousarray(a).view(np.uint64).astype("<u8").view(np.uint8)
+    return np.unpackbits(b, axis=-1, bitorder="little")[..., :int(ntotal)].astype(np.bool_)
+
+
+def range_mask(ntotal, lo, hi):
+    """The packed mask int64 [W] of the rows [lo, hi) (clipped to [0, ntotal)): faiss's IDSelectorRange."""
+    for name, v in (("ntotal", ntotal), ("lo", lo), ("hi", hi)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"range_mask: {name} must be an integer, got {v!r}")
+    if ntotal < 0:
+        raise ValueError(f"range_mask: ntotal = {ntotal} is negative")
+    m = np.zeros(int(ntotal), np.bool_)
+    m[max(0, int(lo)):max(0, int(hi))] = True
+    return pack_mask(m)
+
+
+def _check_mask_of(mask_of_shape, n_masks, nq, what):
+    if mask_of_shape is None:
+        if n_masks != 1 and n_masks != nq:
+            raise ValueError(f"{what}: {n_masks} masks for {nq} queries and no mask_of: needs one mask, one per query, or mask_of")
+    elif tuple(mask_of_shape) != (nq,):
+        raise ValueError(f"{what}: {nq} queries but mask_of of shape {tuple(mask_of_shape)} (one entry per query)")
+
+
+def _as_masks(masks, mask_of, nq, ntotal, what):
+    """(words int64 [n_masks, W], mask_of int64 [nq] or None) of nq queries over ntotal rows.  masks: bool [ntotal] or
+    [n_masks, ntotal], or packed uint64 / int64 [W] or [n_masks, W]."""
+    a = np.asarray(masks)
+    if a.ndim not in (1, 2):
+        raise ValueError(f"{what}: masks must have 1 or 2 dimensions, got shape {a.shape}")
+    if a.dtype == np.bool_:
+        if a.shape[-1] != ntotal:
+            raise ValueError(f"{what}: a bool mask needs one entry per row, {ntotal}, got shape {a.shape}")
+        a = pack_mask(a)
+    elif a.dtype in (np.int64, np.uint64):
+        if a.shape[-1] != mask_words(ntotal):
+            raise ValueError(f"{what}: packed masks need {mask_words(ntotal)} words for {ntotal} rows, got shape {a.shape} "
+                             "(packed before an add or a remove?)")
+    else:
+        raise ValueError(f"{what}: masks must be bool, or packed uint64 / int64 words, got dtype {a.dtype}")
+    a = np.ascontiguousarray(a.reshape((a.shape[0] if a.ndim == 2 else 1, a.shape[-1]))).view(np.int64)
+    if a.shape[0] < 1:
+        raise ValueError(f"{what}: needs at least one mask")
+    if mask_of is not None:
+        mask_of = _as_ids(mask_of, 1, what)
+        _check_mask_of(mask_of.shape, a.shape[0], nq, what)   # (its values: the library refuses one outside [0, n_masks), as it refuses ids)
+    else:
+        _check_mask_of(None, a.shape[0], nq, what)
+    return a, mask_of
+
+
+def _masked_args(q, k, masks, mask_of, d, ntotal, what="search_masked"):
+    """(q float32 [nq, d], k, words int64 [n_masks, W], mask_of int64 [nq] or None) of search_masked."""
+    q = _as_queries(q, d, what)
+    k = _as_k(k, what)
+    words, mask_of = _as_masks(masks, mask_of, q.shape[0], ntotal, what)
+    return q, k, words, mask_of
+
+
+def _masked_args_tensor(q, k, masks, mask_of, id_map, d, ntotal, what="search_masked_tensor"):
+    """(q float32 CUDA [nq, d], k, masks int64 CUDA [n_masks, W], mask_of int64 CUDA [nq] or None, id_map) of search_masked*_tensor."""
+    import torch
+    q = _queries_tensor(q, d, what)
+    k = _as_k(k, what)
+    if not isinstance(masks, torch.Tensor) or not masks.is_cuda:
+        raise ValueError(f"{what}: masks must be a CUDA tensor (pack_mask of a bool tensor)")
+    if masks.dtype != torch.int64:
+        raise ValueError(f"{what}: masks must be packed int64 words, got {masks.dtype}")
+    if masks.dim() != 2 or masks.shape[0] < 1 or masks.shape[1] != mask_words(ntotal):
+        raise ValueError(f"{what}: masks must be [n_masks >= 1, {mask_words(ntotal)}] for {ntotal} rows, got shape {tuple(masks.shape)} "
+                         "(packed before an add or a remove?)")
+    if masks.device != q.device:
+        raise ValueError(f"{what}: q on {q.device} but masks on {masks.device}")
+    if mask_of is not None:
+        if not isinstance(mask_of, torch.Tensor) or not mask_of.is_cuda or mask_of.dtype != torch.int64:
+            raise ValueError(f"{what}: mask_of must be an int64 CUDA tensor [nq]")
+        _check_mask_of(mask_of.shape, masks.shape[0], q.shape[0], what)
+        if mask_of.device != q.device:
+            raise ValueError(f"{what}: q on {q.device} but mask_of on {mask_of.device}")
+        mask_of = mask_of.contiguous()
+    else:
+        _check_mask_of(None, masks.shape[0], q.shape[0], what)
+    if id_map is not None:
+        if not isinstance(id_map, torch.Tensor) or not id_map.is_cuda or id_map.dtype != torch.int64 or id_map.dim() != 1:
+            raise ValueError(f"{what}: id_map must be an int64 CUDA tensor [ntotal]")
+        if id_map.device != q.device:
+            raise ValueError(f"{what}: q on {q.device} but id_map on {id_map.device}")
+        id_map = id_map.contiguous()
+    return q, k, masks.contiguous(), mask_of, id_map
+
+
 def _filter_args(keys, exclude_pos, k, what="filter_keys"):
     """(keys int64 CUDA [nq, kin], exclude_pos int64 CUDA [nq, e], k in [1, kin]) of filter_keys."""
     keys = _ids_tensor(keys, 2, what)
@@ -334,6 +461,20 @@ class FlatIPIndex:
         q, k, cand = _among_args(q, k, cand, self.d)
         D, I = _host_results((q.shape[0], k))
         _lib.check(_lib.lib().hac_index_search_among(self._h, _f32p(q), q.shape[0], k, _i64p(cand), cand.shape[1], _f32p(D), _i64p(I)))
+        return D, I
+
+    def search_masked(self, q, k, masks, mask_of=None):
+        """search(q, k) over the rows a bitmap selects: masks bool [ntotal] or [n_masks, ntotal], or packed uint64 / int64
+        [W] or [n_masks, W] (pack_mask; W = ceil(ntotal / 64)); mask_of int64 [nq] names each query's mask and may be None with
+        one mask (every query uses it) or nq masks (query i uses mask i); an entry outside [0, n_masks) raises HacError.  Rows
+        whose score is NaN are in no list; k may exceed the selected rows (the tail is padding).  Any number of rows may be
+        selected (include/haconvdr.h, "search inside a bitmap"); faiss: SearchParameters(sel=IDSelectorBitmap(n, bitmap)),
+        IDSelectorRange (range_mask), IDSelectorNot (~mask)."""
+        q, k, words, mask_of = _masked_args(q, k, masks, mask_of, self.d, self.ntotal)
+        D, I = _host_results((q.shape[0], k))
+        null_i = ctypes.POINTER(ctypes.c_int64)()
+        _lib.check(_lib.lib().hac_index_search_masked(self._h, _f32p(q), q.shape[0], k, words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                                      words.shape[0], words.shape[1], null_i if mask_of is None else _i64p(mask_of), _f32p(D), _i64p(I)))
         return D, I
 
     def reset(self):
@@ -494,6 +635,29 @@ class FlatIPIndex:
         _lib.check(_lib.lib().hac_index_search_among_keys_device(self._h, _devp(q), q.shape[0], k, _devp(cand), cand.shape[1], _devp(keys),
                                                                  int(pos_base), _stream_ptr(stream)))
         _keep_alive(stream, q, cand, keys)
+        return keys
+
+    def search_masked_tensor(self, q, k, masks, mask_of=None, id_map=None, stream=None):
+        """search_tensor over the rows a bitmap selects: masks packed int64 CUDA [n_masks, W] (pack_mask of a bool CUDA tensor),
+        mask_of int64 CUDA [nq] or None (one mask, or one per query); a query whose mask_of entry is outside [0, n_masks) gets
+        an empty list and no error.  id_map: optional int64 CUDA [ntotal], I = id_map[row].  No host sync; capturable after one
+        call of the largest (nq, k, n_masks)."""
+        q, k, masks, mask_of, id_map = _masked_args_tensor(q, k, masks, mask_of, id_map, self.d, self.ntotal)
+        D, I = _device_results((q.shape[0], k), q.device)
+        _lib.check(_lib.lib().hac_index_search_masked_device(self._h, _devp(q), q.shape[0], k, _devp(masks), masks.shape[0], masks.shape[1], _devp(mask_of),
+                                                             _devp(D), _devp(I), _devp(id_map), _stream_ptr(stream)))
+        _keep_alive(stream, q, masks, D, I, *(t for t in (mask_of, id_map) if t is not None))
+        return D, I
+
+    def search_masked_keys_tensor(self, q, k, masks, mask_of=None, pos_base=0, stream=None):
+        """search_masked_tensor's sorted packed keys (int64 view of uint64) [nq, k], positions pos_base + row: the unit exchanged
+        between shards (merge_keys, keys_to_results)."""
+        import torch
+        q, k, masks, mask_of, _ = _masked_args_tensor(q, k, masks, mask_of, None, self.d, self.ntotal, "search_masked_keys_tensor")
+        keys = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
+        _lib.check(_lib.lib().hac_index_search_masked_keys_device(self._h, _devp(q), q.shape[0], k, _devp(masks), masks.shape[0], masks.shape[1],
+                                                                  _devp(mask_of), _devp(keys), int(pos_base), _stream_ptr(stream)))
+        _keep_alive(stream, q, masks, keys, *(() if mask_of is None else (mask_of,)))
         return keys
 
     def search_keys_tensor(self, q, k, pos_base=0, stream=None):

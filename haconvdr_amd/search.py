@@ -201,15 +201,54 @@ class ResidentCorpus:
             self._lookup = (self._ids[order], order.astype(np.int64))
         return self._lookup
 
-    def search(self, query_embeddings, topN, exclude=None):
+    def rows_mask(self, passage_ids):
+        """bool [ntotal], true at every row that carries one of the EXTERNAL passage ids (integers of any shape, -1 = padding;
+        an id two blocks hold sets two rows, an id no block holds sets none): a mask for search(within=).  Nothing is cached: a
+        mask describes the rows as they are now, and remove() renumbers them."""
+        pid = np.asarray(passage_ids)
+        if pid.dtype.kind not in "iu":
+            raise ValueError(f"rows_mask: passage ids must be integers, got dtype {pid.dtype}")
+        rows = rows_carrying(*self._id_lookup(), pid.reshape(1, -1))[0]
+        mask = np.zeros(len(self._ids), np.bool_)
+        mask[rows[rows >= 0]] = True
+        return mask
+
+    def first_rows_mask(self):
+        """bool [ntotal], true at the first row of each external id: searching within it gives lists without repeated passage
+        ids, filled to topN (the TREC writer de-duplicates per query afterwards and leaves filler at the tail)."""
+        sorted_ids, order = self._id_lookup()   # (stable sort: equal ids keep row order)
+        mask = np.zeros(len(self._ids), np.bool_)
+        if len(sorted_ids):
+            first = np.ones(len(sorted_ids), np.bool_)
+            first[1:] = sorted_ids[1:] != sorted_ids[:-1]
+            mask[order[first]] = True
+        return mask
+
+    def search(self, query_embeddings, topN, exclude=None, within=None, within_of=None):
         """query_embeddings: float32 [nq,768] (numpy or CUDA tensor) -> (D float64 [nq,topN], I int64 [nq,topN]).
         exclude: optional int64 [nq, e] EXTERNAL passage ids (-1 = padding) the query must not get back -- its gold passages
         when mining hard negatives, what a conversation has already shown; every row that carries such an id is left out, an
-        id no block holds is ignored, and the list is still filled to topN (the search runs at topN + the widest row list)."""
+        id no block holds is ignored, and the list is still filled to topN (the search runs at topN + the widest row list).
+        within: optional masks over the ROWS, bool [ntotal] or [n_masks, ntotal] (rows_mask, first_rows_mask, a topic's or a
+        block's rows) or packed words (index.pack_mask): only selected rows are returned, however many or few they are
+        (index.search_masked; faiss's IDSelectorBitmap); within_of int64 [nq] names each query's mask (None: one mask for all,
+        or one per query).  exclude and within together raise ValueError: fold the exclusions into per-query masks
+        (within & ~rows_mask(ids))."""
         import torch
         q = query_embeddings if isinstance(query_embeddings, torch.Tensor) else torch.from_numpy(
             np.ascontiguousarray(query_embeddings, dtype=np.float32))
-        if exclude is None:
+        if exclude is not None and within is not None:
+            raise ValueError("search: exclude and within together are not supported: fold the exclusions into per-query masks")
+        if within_of is not None and within is None:
+            raise ValueError("search: within_of without within")
+        if within is not None:
+            from .index import _as_masks
+            words, mask_of = _as_masks(within, within_of, q.shape[0], self.ntotal, "search(within=)")
+            if mask_of is not None and mask_of.size and (mask_of.min() < 0 or mask_of.max() >= words.shape[0]):
+                raise ValueError(f"search(within=): within_of names a mask outside [0, {words.shape[0]})")   # (the tensor form would answer with an empty list)
+            D, I = self.index.search_masked_tensor(q.to(self.dev), topN, torch.from_numpy(words).to(self.dev),
+                                                   None if mask_of is None else torch.from_numpy(mask_of).to(self.dev), id_map=self.id_map)
+        elif exclude is None:
             D, I = self.index.search_tensor(q.to(self.dev), topN, id_map=self.id_map)
         else:
             rows = rows_carrying(*self._id_lookup(), exclude)

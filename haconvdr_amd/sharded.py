@@ -30,7 +30,8 @@ class ShardedSearcher:
     local_scores(q, local_ids [nq, m]) -> float32 [nq, m]              (default: index.score_ids_tensor)
     count_ahead(q, ref_scores, ref_bounds [nq, m]) -> int64 [nq, m]    (default: index.count_ahead_tensor)
     local_among_keys(q, k, local_cand [nq, m], pos_base) -> [nq, k]    (default: index.search_among_keys_tensor)
-    The seven hooks exist so that the distributed plumbing can be exercised on CPU with
+    local_masked_keys(q, k, local_masks [n_masks, W], mask_of, pos_base) -> [nq, k]   (default: index.search_masked_keys_tensor)
+    The eight hooks exist so that the distributed plumbing can be exercised on CPU with
     gloo and a test double; the product path always uses the HIP defaults.
     n_local: rows this rank holds (default: index.ntotal when rank() / search_among() is called).
 
@@ -41,7 +42,7 @@ class ShardedSearcher:
     """
 
     def __init__(self, index, shard_base, group=None, id_map=None, local_keys=None, merge=None, to_results=None, filter=None,
-                 local_scores=None, count_ahead=None, n_local=None, local_among_keys=None):
+                 local_scores=None, count_ahead=None, n_local=None, local_among_keys=None, local_masked_keys=None):
         from . import index as _index
         self.index = index
         self.shard_base = int(shard_base)
@@ -55,6 +56,7 @@ class ShardedSearcher:
         self._count_ahead = count_ahead or (lambda q, s, b: index.count_ahead_tensor(q, s, b))
         self._n_local = n_local
         self._local_among_keys = local_among_keys or (lambda q, k, cand, base: index.search_among_keys_tensor(q, k, cand, pos_base=base))
+        self._local_masked_keys = local_masked_keys or (lambda q, k, masks, mask_of, base: index.search_masked_keys_tensor(q, k, masks, mask_of, pos_base=base))
 
     def _gather_and_merge(self, keys):
         if not dist.is_initialized():
@@ -93,6 +95,23 @@ class ShardedSearcher:
         the candidates it holds (positions it does not hold become -1, the rest cand - shard_base; a row lives on one rank, so no
         repeat crosses ranks), then the same one all-gather and merge as search_keys, at k."""
         return self._to_results(self.search_among_keys(q, k, cand), self.id_map)
+
+    def search_masked_keys(self, q, k, local_masks, mask_of=None):
+        """The merged keys [nq, k] of search_masked."""
+        if local_masks.dim() != 2 or local_masks.dtype != torch.int64:
+            raise ValueError(f"local_masks must be packed int64 [n_masks, W], got {local_masks.dtype} {tuple(local_masks.shape)}")
+        if mask_of is not None and (mask_of.dim() != 1 or mask_of.shape[0] != q.shape[0] or mask_of.dtype != torch.int64):
+            raise ValueError(f"mask_of must be int64 [nq] with nq = {q.shape[0]}, got {mask_of.dtype} {tuple(mask_of.shape)}")
+        if mask_of is None and local_masks.shape[0] not in (1, q.shape[0]):
+            raise ValueError(f"{local_masks.shape[0]} masks for {q.shape[0]} queries and no mask_of: needs one mask, one per query, or mask_of")
+        return self._gather_and_merge(self._local_masked_keys(q, k, local_masks, mask_of, self.shard_base))
+
+    def search_masked(self, q, k, local_masks, mask_of=None):
+        """Exact top-k over the rows a bitmap selects, over the whole sharded corpus -> (D, I) like search().  local_masks: packed
+        int64 [n_masks, W_local] (index.pack_mask) over THIS RANK'S OWN rows -- bit r is local row r, global position shard_base
+        + r --, the same number of masks on every rank; mask_of int64 [nq] (or None: one mask, or one per query) is identical on
+        every rank.  Every rank searches its rows under its masks, then the same one all-gather and merge as search_keys, at k."""
+        return self._to_results(self.search_masked_keys(q, k, local_masks, mask_of), self.id_map)
 
     def rank(self, q, ids):
         """Exact rank of named rows over the whole sharded corpus: ids int64 [nq, m] GLOBAL positions (shard_base + local row),

@@ -352,6 +352,60 @@ int hac_index_search_among_device(hac_index *idx, const float *q_dev, int64_t nq
 int hac_index_search_among_keys_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const int64_t *cand_dev, int64_t m,
                                        uint64_t *keys_dev, uint32_t pos_base, void *hip_stream);
 
+/* ---- search inside a bitmap: exact top-k over the rows a bitmap selects ---------------------------------------------------
+ * faiss: SearchParameters(sel=IDSelectorBitmap(n, bitmap)), and IDSelectorRange / IDSelectorNot over large sets -- what lies
+ * between search_among (at most HAC_MAX_AMONG named rows) and search_excluding (at most HAC_MAX_K - k rows left out): a tenth
+ * of the corpus, one block, everything but 50 000 rows.  For a query q and a mask M:
+ *   masked(q, M, k) = the first k entries of { rows r : 0 <= r < ntotal, bit r of M set, s(q, r) not NaN }
+ *                     ordered by (s desc, r asc), padded with D = -FLT_MAX, I = -1
+ * s is the canonical score: the k-ordered fmaf chain plus the "+ 0.0f" of a packed key, the same bits search returns.
+ * Mask layout: masks is uint64 [n_masks][words], words = ceil(ntotal / 64); row r is bit r & 63 of word r >> 6, so a word is
+ * exactly one 64-row group of the tiles.  Viewed as bytes on a little-endian host the words are faiss's IDSelectorBitmap bitmap,
+ * np.packbits(bool, bitorder="little").  Bits at or above ntotal are ignored.
+ * Which mask a query uses: mask_of is int64 [nq], the mask of each query.  A NULL mask_of means mask 0 for every query when
+ * n_masks == 1 and mask i for query i when n_masks == nq; any other NULL case is HAC_ERR_INVALID.
+ * Identities (proved on the CPU over the oracle by tests/test_index_masked.py):
+ *   - an all-ones mask: masked(q, M, k) == search(q, k);
+ *   - M the mask of a set S, |S| <= HAC_MAX_AMONG: masked(q, M, k) == search_among(q, k, S);
+ *   - M the complement of a set E, k + |E| <= HAC_MAX_K: masked(q, M, k) == search_excluding(q, k, E);
+ *   - masked(q, M, k) == the rows of range_search(q, -inf) that M selects, cut at k (then, if there is room, the selected rows
+ *     scoring -Inf, which the strict comparison of a radius leaves out and every search lists last).
+ * Arguments: words must equal ceil(ntotal / 64), otherwise HAC_ERR_INVALID -- which refuses a mask packed before an add or a
+ * remove changed the size; 1 <= k <= HAC_MAX_K; n_masks >= 1 when nq > 0.  nq == 0 is HAC_OK and touches nothing; ntotal == 0
+ * gives lists of padding only (words is then 0 and masks may be NULL).
+ * mask_of out of range: the host form returns HAC_ERR_INVALID for an entry outside [0, n_masks), names the query and writes
+ * nothing; in the *_device forms that query gets an empty list, all padding, and no error -- the split the by-id calls make.
+ *
+ * How (csrc/masked.inc): mask_groups_kernel builds, per query tile, the list of the 64-row groups in which the OR of the tile's
+ * queries' mask words is non-zero (clipped to ntotal in the last group; ballot + prefix, one atomic per wave; the order of a
+ * list is unspecified and does not matter).  scan16_masked_kernel is a copy of scan16_kernel whose work items are that list:
+ * the same row stream, the same bit-exact MFMA chain, the same candidate buffers and compaction; its epilogue appends a row
+ * only if the lane's own query's mask word has the row's bit.  A row is tested before it becomes a candidate, so every
+ * threshold comes from selected rows and is a proven lower bound of the masked k-th score: the result does not depend on the
+ * number of row streams, the list order or the launch cuts (two identical calls return identical bytes).  No threshold
+ * seeding: a sample of unmasked rows would give bounds the masked set cannot meet.  select_keys_kernel finishes, as in search.
+ * Cost: one pass over nq x words mask words, then ceil(nq / QT) passes (QT = 16 queries, fewer at large k), each streaming its
+ * tile's selected groups from the fp32 tiles -- a selective mask costs its own rows, not the corpus.  Built for selective masks
+ * or few queries: a dense mask under many queries costs one corpus pass per 16 queries, the price of rank_ids; for a small
+ * complement use search_excluding.  The queries are cut into launches of whole tiles so that the list workspace
+ * (uint32 [tiles][groups]) stays within 64 MiB.
+ *
+ * Host form: synchronous, on the index's own stream; queries and the masks they name are staged in chunks of ~64 MiB.  It
+ * works on a multi-device index: each shard searches its own rows under its own slice of every mask (the host copies the bit
+ * ranges span by span), the lists are remapped and merged at k on the first device like search's.
+ * Device forms: single-device index (HAC_ERR_UNSUPPORTED otherwise), 16-byte aligned q_dev; they enqueue on hip_stream and
+ * never read back.  id_map_dev as in hac_index_search_device.  The keys form writes the sorted packed keys [nq, k] with
+ * positions pos_base + row.  The workspaces grow by the rule of the search workspaces: run one call of the largest
+ * (nq, k, n_masks) before capturing into a HIP graph.  Test switches (hac_index_set_option): "masked_p" = "auto" | 1..4096 row
+ * streams per query tile, "debug_masked_tiles" = 0 | the most query tiles per launch.  hac_index_last_plan afterwards reads
+ * "mask_groups_kernel grid=(..) scan16_masked_kernel<W=4> grid=(P,tiles) QT=.. C=.. lds=.. launches=..". */
+int hac_index_search_masked(hac_index *idx, const float *q, int64_t nq, int k, const uint64_t *masks, int64_t n_masks, int64_t words,
+                            const int64_t *mask_of, float *D, int64_t *I);
+int hac_index_search_masked_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const uint64_t *masks_dev, int64_t n_masks, int64_t words,
+                                   const int64_t *mask_of_dev, float *D_dev, int64_t *I_dev, const int64_t *id_map_dev, void *hip_stream);
+int hac_index_search_masked_keys_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const uint64_t *masks_dev, int64_t n_masks, int64_t words,
+                                        const int64_t *mask_of_dev, uint64_t *keys_dev, uint32_t pos_base, void *hip_stream);
+
 /* ---- removing rows: faiss's IndexFlat::remove_ids(IDSelectorBatch(ids)), in place ------------------------------------------
  * The rows named by ids disappear; every surviving row keeps its bits and its relative order; the survivors are renumbered
  * densely from 0 -- survivor number j is row j of np.delete(x, unique(ids), axis=0) --; ntotal drops by the number of DISTINCT
@@ -413,6 +467,8 @@ int hac_index_last_status(hac_index *idx);
  * reset of an index that has none -- an index searched once per block, the reference's add / search / reset loop, never pays for
  * it --, kept current across later adds, best effort: when the allocation fails the tiles are read as before); "1" builds it with the
  * first such search at any size, "0" never (and frees one that exists, as does growing past the size).  Same bits either way.
+ * "masked_p" = "auto" | "1" .. "4096" and "debug_masked_tiles" = integer >= 0: tests of hac_index_search_masked* ("search inside a
+ * bitmap": row streams per query tile; the most query tiles per launch, 0 = by the list workspace).  Same bits either way.
  * Any other name or value is HAC_ERR_INVALID (never a silent default).
  * The HAC_<NAME> environment variables give the defaults and are read once, in hac_index_create. */
 int hac_index_set_option(hac_index *idx, const char *name, const char *value);
