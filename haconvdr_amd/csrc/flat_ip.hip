@@ -1141,6 +1141,7 @@ u32 next_pow2(u32 v) {
 #include "remove.inc"
 #include "among.inc"
 #include "masked.inc"
+#include "grouped.inc"
 
 // Every instantiation of the two templated scan kernels, once: init raises each one's dynamic-LDS limit from these tables and
 // the launches look their kernel up in them, so an instantiation that is launched is one whose limit was raised.
@@ -1195,6 +1196,8 @@ struct DeviceIndex {
         int scan_passes = 0;             // prefilter scan: 0 by size, 1..5 pins the number of passes (threshold refreshes between them)
         int pass_cut[2] = {0, 0};        // where the passes end, in thousandths of the row groups (option "scan_pass_cuts" = "a,b"); 0 = by size
         int masked_p = 0;                // search_masked: row streams per query tile; 0 = as make_plan sizes scan16's (tests pin 1: one workgroup walks every group)
+        int grouped_p = 0;               // search_grouped: row streams per query tile; 0 = by the resident workgroups (tests pin 1: one workgroup walks every compaction)
+        int debug_grouped_tiles = 0;     // tests: search_grouped's query tiles per launch (0 = by QUERY_CHUNK), so that a small call spans several launches
         int debug_masked_tiles = 0;      // tests: search_masked's query tiles per launch (0 = by the list workspace), so that a small call spans several launches
     } tune;
     // Passes of the prefilter's main scan (search_keys_split) and where they end (row groups, whole rounds).  A refresh costs a
@@ -1305,6 +1308,13 @@ struct DeviceIndex {
             if (v == "auto") t = 0;
             else if (!parse_int(v, 1, 4096, t)) return fail(HAC_ERR_INVALID, "index option masked_p = '%s': auto | an integer 1..4096", v.c_str());
             tune.masked_p = (int)t;
+        } else if (n == "grouped_p") {
+            if (v == "auto") t = 0;
+            else if (!parse_int(v, 1, 4096, t)) return fail(HAC_ERR_INVALID, "index option grouped_p = '%s': auto | an integer 1..4096", v.c_str());
+            tune.grouped_p = (int)t;
+        } else if (n == "debug_grouped_tiles") {
+            if (!parse_int(v, 0, 65535, t)) return fail(HAC_ERR_INVALID, "index option debug_grouped_tiles = '%s': an integer 0..65535", v.c_str());
+            tune.debug_grouped_tiles = (int)t;
         } else if (n == "debug_masked_tiles") {
             if (!parse_int(v, 0, 65535, t)) return fail(HAC_ERR_INVALID, "index option debug_masked_tiles = '%s': an integer 0..65535", v.c_str());
             tune.debug_masked_tiles = (int)t;
@@ -1405,6 +1415,8 @@ struct DeviceIndex {
             HAC_HIP(hipFuncSetAttribute((const void *)range_emit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             // (DYNAMIC LDS: without it a large k, whose candidate buffers pass the default 64 KiB, fails to launch)
             HAC_HIP(hipFuncSetAttribute((const void *)scan16_masked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
+            HAC_HIP(hipFuncSetAttribute((const void *)scan16_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
+            HAC_HIP(hipFuncSetAttribute((const void *)grouped_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, grouped_select_cm(HAC_MAX_K) * 16));   // (beside its static words)
             attr_done[device] = true;
         }
         return HAC_OK;
@@ -1426,7 +1438,7 @@ struct DeviceIndex {
         for (PinBuf *b : {&h_pin, &h_fb, &h_stage[0], &h_stage[1]}) b->release();
         for (GrowBuf *b : {&ws_partial, &ws_pcnt, &ws_seedkeys, &ws_thr, &ws_thrglob, &ws_q, &ws_qt, &ws_keys, &ws_D, &ws_I, &ws_stage[0],
                            &ws_stage[1], &ws_err, &ws_norm, &ws_qsplit, &ws_delta, &ws_cand, &ws_akeys, &ws_fail, &ws_stat, &ws_fbidx[0], &ws_fbidx[1],
-                           &ws_fbq[0], &ws_fbq[1], &ws_fbkeys[0], &ws_fbkeys[1], &ws_ids, &ws_rank, &ws_range, &ws_among, &ws_mgroups, &ws_mcnt, &ws_masks})
+                           &ws_fbq[0], &ws_fbq[1], &ws_fbkeys[0], &ws_fbkeys[1], &ws_ids, &ws_rank, &ws_range, &ws_among, &ws_mgroups, &ws_mcnt, &ws_masks, &ws_labels})
             b->release();
         if (h_err) (void)hipHostFree(h_err);
         if (h_plan) (void)hipHostFree(h_plan);
@@ -1846,6 +1858,7 @@ struct DeviceIndex {
     GrowBuf ws_among;          // search among named rows (rows_host.inc: among_keys_device): a chunk's [queries][P] candidate keys
     GrowBuf ws_mgroups, ws_mcnt;   // search inside a bitmap (search_keys_masked): one launch's group lists u32 [tiles][G], the call's counters u32 [tiles]
     GrowBuf ws_masks;          // its host form (rows_host.inc: masked_shard): a chunk's masks and mask_of
+    GrowBuf ws_labels;         // search by group, host form (rows_host.inc: grouped_shard): the shard's slice of the labels
 
     char last_plan[320] = "none";
     // a device-decided prefilter search leaves its fallback count and err / bound on the device: plan() completes the text
@@ -2158,6 +2171,90 @@ struct DeviceIndex {
             select_keys_kernel<<<dim3((unsigned)n), dim3(256), (size_t)np2 * 8, st>>>((const u64 *)ws_partial.p, (size_t)pl.P * k, (const u32 *)ws_pcnt.p,
                                                                                       (u32)((size_t)pl.P * k), k, np2, keys_out + (size_t)off * k, nullptr, nullptr, (int)n,
                                                                                       (u32)(pl.P * tiles), (u32)QT, thrglob(), (u32 *)ws_err.p);
+            HAC_HIP(hipGetLastError());
+        }
+        return HAC_OK;
+    }
+
+    // ---- search by group (grouped.inc).  keys_out: device u64 [nq][k]; group_of_dev int64 [ntotal] on the device; arguments
+    // checked by the entry points (n_labels == ntotal above all: the kernels index the labels by the row).
+    // scan16's plan plus one scratch array of C keys per compacting wave: C = next_pow2(k + 64 * SCAN_WAVES), QT = the most
+    // queries, at most 16, with QT * (d * 4 + C * 8) + min(SCAN_WAVES, QT) * C * 8 + 128 <= LDS_LIMIT (QT falls below 16 at
+    // large k).  No threshold seeding.  The queries go in launches of whole tiles, at most QUERY_CHUNK queries each; the
+    // survivors and the thresholds are one launch's and are reused by the next, in stream order.  Every workspace is a GrowBuf
+    // sized by (nq, k) and the rows alone: after one call of the largest shape a call allocates nothing and can be captured.
+    static int grouped_select_cm(int k) { return (int)std::max<u32>(1024u, next_pow2((u32)k + 256u)); }
+    int grouped_plan(int64_t nq, int k, Plan &pl) const {
+        pl.kind = 0;
+        pl.NT = 0;
+        pl.W = SCAN_WAVES;
+        pl.C = (int)next_pow2((u32)k + 64u * SCAN_WAVES);
+        const size_t per_q = (size_t)K4 * 16 + (size_t)pl.C * 8, fixed = 16 * 4 + 16 * 4;
+        int qt = 0;
+        for (int t = 1; t <= 16; ++t)
+            if ((size_t)t * per_q + (size_t)std::min(SCAN_WAVES, t) * pl.C * 8 + fixed <= LDS_LIMIT) qt = t;
+        if (qt < 1) return fail(HAC_ERR_UNSUPPORTED, "k=%d with d=%d does not fit the LDS candidate buffers", k, d);
+        qt = (int)std::min<int64_t>(qt, nq);
+        pl.QT = qt;
+        pl.lds_scan = (size_t)qt * per_q + (size_t)std::min(SCAN_WAVES, qt) * pl.C * 8 + fixed;
+        pl.n_qtiles = (int)((nq + qt - 1) / qt);
+        return HAC_OK;
+    }
+    int search_keys_grouped(const float *q_dev, int64_t nq, int k, const int64_t *group_of_dev, u64 *keys_out, hipStream_t st) {
+        if (nq == 0) return HAC_OK;
+        HAC_TRY(check_search_args(q_dev, 0u));
+        if (ntotal == 0) {
+            HAC_HIP(hipMemsetAsync(keys_out, 0, (size_t)nq * k * 8, st));
+            return HAC_OK;
+        }
+        HAC_TRY(upload_segs(st));
+        const u32 G = (u32)((ntotal + GROUP_ROWS - 1) / GROUP_ROWS);
+        Plan pl;
+        HAC_TRY(grouped_plan(nq, k, pl));
+        const int QT = pl.QT;
+        int64_t TL = std::max<int64_t>(1, QUERY_CHUNK / QT);   // tiles per launch
+        if (tune.debug_grouped_tiles > 0) TL = std::min<int64_t>(TL, tune.debug_grouped_tiles);
+        TL = std::min<int64_t>(TL, pl.n_qtiles);
+        const int64_t QL = TL * QT;   // queries per launch
+        // row streams per tile: the resident workgroups (LDS- and wave-limited, as make_plan counts them) over a launch's tiles
+        const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(LDS_LIMIT / pl.lds_scan, 32 / SCAN_WAVES), 4));
+        long P = std::max<long>(1, (long)n_cu * per_cu / TL);
+        if (P >= 8 && !tune.no_p8) P = P / 8 * 8;
+        if (tune.grouped_p > 0) P = tune.grouped_p;
+        P = std::max<long>(1, std::min<long>(P, (G + SCAN_WAVES - 1) / SCAN_WAVES));
+        pl.P = (int)P;
+        const int64_t launches = (pl.n_qtiles + TL - 1) / TL;
+        const int Cm = grouped_select_cm(k);
+        HAC_TRY(ws_partial.reserve((size_t)std::min(nq, QL) * pl.P * k * 8));
+        HAC_TRY(ws_pcnt.reserve((size_t)std::min(nq, QL) * 4));
+        HAC_TRY(ws_thrglob.reserve(((size_t)TL * QT + THR_CTL_WORDS) * 4));
+        snprintf(last_plan, sizeof last_plan, "scan16_grouped_kernel<W=%d> grid=(%d,%lld) QT=%d C=%d lds=%zu grouped_select_kernel n_in=%lld launches=%lld", SCAN_WAVES,
+                 pl.P, (long long)TL, QT, pl.C, pl.lds_scan, (long long)pl.P * k, (long long)launches);
+        plan_text_slot = -1;
+        GroupArgs gr{};
+        gr.group_of = (const long long *)group_of_dev;
+        gr.n_labels = (long)ntotal;
+        gr.pos_base = 0u;
+        for (int64_t l = 0; l < launches; ++l) {
+            const int64_t off = l * QL, n = std::min(QL, nq - off), tiles = (n + QT - 1) / QT;
+            ScanArgs a = scan_args(q_dev + (size_t)off * d, n);
+            a.k = k;
+            a.C = pl.C;
+            a.QT = QT;
+            a.g_step = 1;
+            a.n_items = G;
+            a.thr_glob = thrglob();
+            a.partial = (u64 *)ws_partial.p;
+            a.partial_cnt = (u32 *)ws_pcnt.p;
+            a.pos_base = 0u;
+            HAC_HIP(hipMemsetAsync(ws_pcnt.p, 0, (size_t)n * 4, st));
+            HAC_TRY(clear_thrglob((size_t)tiles * QT, st));
+            HAC_TRY(prof_begin(st));
+            scan16_grouped_kernel<<<dim3((unsigned)pl.P, (unsigned)tiles), dim3(SCAN_WAVES * 64), pl.lds_scan, st>>>(a, gr);
+            HAC_HIP(hipGetLastError());
+            HAC_TRY(prof_end(st));
+            grouped_select_kernel<<<dim3((unsigned)n), dim3(256), (size_t)Cm * 16, st>>>((const u64 *)ws_partial.p, 0, 0, (size_t)pl.P * k, (const u32 *)ws_pcnt.p,
+                                                                                         (u32)((size_t)pl.P * k), k, Cm, gr, keys_out + (size_t)off * k);
             HAC_HIP(hipGetLastError());
         }
         return HAC_OK;
@@ -2593,6 +2690,7 @@ struct hac_index {
     // multi-device merge workspace lives on shard 0
     GrowBuf ws_lists, ws_out;
     GrowBuf ws_excl;   // hac_index_search_excluding: the host's exclusion lists, on shard 0
+    GrowBuf ws_glabels;   // hac_index_search_grouped on several devices: the whole label array, on shard 0 (the merge reads it)
     // n_dev > 1: per shard, its share of every add() (see remap_positions_kernel)
     std::vector<std::vector<SpanDesc>> spans;
     std::vector<GrowBuf> ws_spans;
@@ -2693,6 +2791,7 @@ void hac_index_destroy(hac_index *idx) {
         DeviceGuard g(idx->shards[0]->device);
         idx->ws_lists.release();
         idx->ws_out.release();
+        idx->ws_glabels.release();
         idx->ws_excl.release();
     }
     for (size_t i = 0; i < idx->shards.size(); ++i) {

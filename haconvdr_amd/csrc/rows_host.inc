@@ -516,6 +516,7 @@ int among_shard(hac_index *idx, int si, const float *q, int64_t nq, int k, const
 // The end of a host search whose shards have left their [nq][k] keys (positions of the whole index) in their ws_keys, streams
 // idle: several devices are merged at k on the first one (ws_lists / ws_out: reserved by the caller), as search merges them;
 // the keys come back through the pinned slab a chunk at a time and the host unpacks them (key_score_host, key_row_host).
+int keys_to_host(DeviceIndex *s0, const uint64_t *final_keys, size_t total, float *D, int64_t *I);
 int shard_keys_to_host(hac_index *idx, int64_t nq, int k, float *D, int64_t *I) {
     const int S = (int)idx->shards.size();
     const size_t total = (size_t)nq * k;
@@ -528,6 +529,10 @@ int shard_keys_to_host(hac_index *idx, int64_t nq, int k, float *D, int64_t *I) 
         HAC_TRY(hac_merge_keys_device(s0->device, (const uint64_t *)idx->ws_lists.p, S, nq, k, (uint64_t *)idx->ws_out.p, s0->stream));
         final_keys = (const uint64_t *)idx->ws_out.p;
     }
+    return keys_to_host(s0, final_keys, total, D, I);
+}
+// `total` keys on s0's device -> (D, I) on the host, through s0's pinned slab a chunk at a time (s0's device is current)
+int keys_to_host(DeviceIndex *s0, const uint64_t *final_keys, size_t total, float *D, int64_t *I) {
     const size_t chunk = (size_t)8 << 20;
     char *slab = nullptr;
     HAC_TRY(pin_slab(*s0, std::min(chunk, total) * 8, slab));
@@ -758,6 +763,73 @@ int masked_shard(hac_index *idx, int si, const float *q, int64_t nq, int k, cons
     }
     return HAC_OK;
 }
+
+// ---- search by group (grouped.inc; DeviceIndex::search_keys_grouped)
+int check_grouped_args(const char *what, const hac_index *idx, int64_t nq, int k, int64_t n_labels, bool pointers_ok) {
+    if (k < 1 || k > HAC_MAX_K) return fail(HAC_ERR_INVALID, "%s: k=%d out of range [1, %d]", what, k, HAC_MAX_K);
+    if (nq < 0 || !pointers_ok) return fail(HAC_ERR_INVALID, "%s: bad arguments", what);
+    if (nq == 0) return HAC_OK;
+    if (n_labels != idx->ntotal)
+        return fail(HAC_ERR_INVALID, "%s: n_labels=%lld, but the index holds %lld rows: one label per row (labels made before an add or a remove?)", what,
+                    (long long)n_labels, (long long)idx->ntotal);
+    return HAC_OK;
+}
+
+// One shard's keys of the whole call, [nq][k] in its ws_keys, on its own stream: its rows under ITS slice of the labels (checked:
+// all in [0, 2^32)), cut out of the caller's array span by span with several devices; the positions are then those of the whole
+// index (remap_positions_kernel, as search does).  The labels are uploaded once per call, the queries in chunks of ~64 MiB
+// through the pinned slab.  Returns with the shard's stream idle.
+int grouped_shard(hac_index *idx, int si, const float *q, int64_t nq, int k, const int64_t *group_of) {
+    DeviceIndex &x = *idx->shards[si];
+    DeviceGuard g(x.device);
+    if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", x.device);
+    const bool sliced = idx->shards.size() > 1;
+    HAC_TRY(x.ws_keys.reserve((size_t)nq * k * 8));
+    if (x.ntotal == 0) {   // a shard without rows: padding only
+        HAC_HIP(hipMemsetAsync(x.ws_keys.p, 0, (size_t)nq * k * 8, x.stream));
+        HAC_HIP(hipStreamSynchronize(x.stream));
+        return HAC_OK;
+    }
+    HAC_TRY(x.ws_labels.reserve((size_t)x.ntotal * 8));
+    std::vector<int64_t> local;   // (lives until the stream is idle)
+    const int64_t *src = group_of;
+    if (sliced) {
+        local.assign((size_t)x.ntotal, 0);
+        int64_t covered = 0;
+        for (const SpanDesc &sp : idx->spans[si]) {   // the spans tile the shard's rows and lie inside the index's: anything else is a broken table, never a guessed label
+            if ((int64_t)sp.local0 != covered || (int64_t)sp.local0 + sp.count > x.ntotal || (int64_t)sp.global0 + sp.count > idx->ntotal)
+                return fail(HAC_ERR_INTERNAL, "search_grouped: span (local %u, count %u, global %u) of shard %d does not fit its %lld rows", sp.local0, sp.count, sp.global0, si,
+                            (long long)x.ntotal);
+            std::memcpy(local.data() + sp.local0, group_of + sp.global0, (size_t)sp.count * 8);
+            covered += sp.count;
+        }
+        if (covered != x.ntotal) return fail(HAC_ERR_INTERNAL, "search_grouped: the spans of shard %d cover %lld of its %lld rows", si, (long long)covered, (long long)x.ntotal);
+        src = local.data();
+    }
+    HAC_HIP(hipMemcpyAsync(x.ws_labels.p, src, (size_t)x.ntotal * 8, hipMemcpyHostToDevice, x.stream));
+    HAC_HIP(hipStreamSynchronize(x.stream));
+    const size_t q_bytes = (size_t)x.d * 4;
+    const int64_t chunk = std::max<int64_t>(1, (int64_t)(((size_t)64 << 20) / q_bytes));
+    HAC_TRY(x.ws_q.reserve((size_t)std::min(chunk, nq) * q_bytes));
+    for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
+        const int64_t nqc = std::min(chunk, nq - q0);
+        char *slab = nullptr;
+        HAC_TRY(pin_slab(x, (size_t)nqc * q_bytes, slab));
+        std::memcpy(slab, q + (size_t)q0 * x.d, (size_t)nqc * q_bytes);
+        HAC_HIP(hipMemcpyAsync(x.ws_q.p, slab, (size_t)nqc * q_bytes, hipMemcpyHostToDevice, x.stream));
+        HAC_TRY(x.search_keys_grouped((const float *)x.ws_q.p, nqc, k, (const int64_t *)x.ws_labels.p, (u64 *)x.ws_keys.p + (size_t)q0 * k, x.stream));
+        HAC_HIP(hipStreamSynchronize(x.stream));   // (the slab is the next chunk's)
+    }
+    if (sliced && !idx->spans[si].empty()) {
+        HAC_TRY(upload_spans(idx, si));
+        const long nk = (long)nq * k;
+        remap_positions_kernel<<<dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, x.stream>>>((u64 *)x.ws_keys.p, nk, (const SpanDesc *)idx->ws_spans[si].p,
+                                                                                             (int)idx->spans[si].size());
+        HAC_HIP(hipGetLastError());
+        HAC_HIP(hipStreamSynchronize(x.stream));
+    }
+    return HAC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -811,6 +883,72 @@ int hac_index_search_masked(hac_index *idx, const float *q, int64_t nq, int k, c
     }
     HAC_TRY(for_each_shard(idx, [&](int si) { return masked_shard(idx, si, q, nq, k, (const u64 *)masks, words, mo.data()); }));
     return shard_keys_to_host(idx, nq, k, D, I);
+}
+
+int hac_index_search_grouped_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const int64_t *group_of_dev, int64_t n_labels, float *D_dev,
+                                    int64_t *I_dev, int64_t *G_dev, const int64_t *id_map_dev, void *hip_stream) {
+    return on_single_shard(idx, "search_grouped_device", [&](DeviceIndex &s) -> int {
+        HAC_TRY(check_grouped_args("search_grouped_device", idx, nq, k, n_labels, nq <= 0 || (q_dev && D_dev && I_dev && (group_of_dev || n_labels == 0))));
+        if (nq == 0) return HAC_OK;
+        hipStream_t st = (hipStream_t)hip_stream;
+        HAC_TRY(s.ws_keys.reserve((size_t)nq * k * 8));
+        HAC_TRY(s.search_keys_grouped(q_dev, nq, k, group_of_dev, (u64 *)s.ws_keys.p, st));
+        GroupArgs gr{};
+        gr.group_of = (const long long *)group_of_dev;
+        gr.n_labels = (long)n_labels;
+        const long n = (long)nq * k;
+        grouped_results_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>((const u64 *)s.ws_keys.p, n, (const long long *)id_map_dev, gr, D_dev,
+                                                                                      (long long *)I_dev, (long long *)G_dev);
+        HAC_HIP(hipGetLastError());
+        return HAC_OK;
+    });
+}
+
+int hac_index_search_grouped(hac_index *idx, const float *q, int64_t nq, int k, const int64_t *group_of, int64_t n_labels, float *D, int64_t *I, int64_t *G) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    HAC_TRY(check_grouped_args("search_grouped", idx, nq, k, n_labels, nq <= 0 || (q && D && I && (group_of || n_labels == 0))));
+    if (nq == 0) return HAC_OK;
+    for (int64_t r = 0; r < n_labels; ++r)
+        if (group_of[r] < 0 || group_of[r] > 0xFFFFFFFFll)
+            return fail(HAC_ERR_INVALID, "search_grouped: group_of[%lld] = %lld is outside [0, 2^32)", (long long)r, (long long)group_of[r]);
+    const size_t total = (size_t)nq * k;
+    if (idx->ntotal == 0) {   // padding only
+        std::fill(D, D + total, -FLT_MAX);
+        std::fill(I, I + total, (int64_t)-1);
+        if (G) std::fill(G, G + total, (int64_t)-1);
+        return HAC_OK;
+    }
+    // Every shard searches its own rows under its own slice of the labels (one host thread each) and leaves at most k distinct
+    // groups per query, in the numbering of the whole index; the first device then reduces the shards' lists to the best key of
+    // every label under the whole label array (grouped_select_kernel: a group may have rows on several shards).
+    const int S = (int)idx->shards.size();
+    DeviceIndex *s0 = idx->shards[0];
+    if (S > 1) {
+        DeviceGuard g0(s0->device);
+        HAC_TRY(idx->ws_lists.reserve((size_t)S * total * 8));
+        HAC_TRY(idx->ws_out.reserve(total * 8));
+        HAC_TRY(idx->ws_glabels.reserve((size_t)n_labels * 8));
+    }
+    HAC_TRY(for_each_shard(idx, [&](int si) { return grouped_shard(idx, si, q, nq, k, group_of); }));
+    DeviceGuard g0(s0->device);
+    const uint64_t *final_keys = (const uint64_t *)s0->ws_keys.p;
+    if (S > 1) {   // (on shard 0's stream, never the null stream: see search_host)
+        for (int si = 0; si < S; ++si)
+            HAC_HIP(hipMemcpyAsync((char *)idx->ws_lists.p + (size_t)si * total * 8, idx->shards[si]->ws_keys.p, total * 8, hipMemcpyDeviceToDevice, s0->stream));
+        HAC_HIP(hipMemcpyAsync(idx->ws_glabels.p, group_of, (size_t)n_labels * 8, hipMemcpyHostToDevice, s0->stream));
+        GroupArgs gr{};
+        gr.group_of = (const long long *)idx->ws_glabels.p;
+        gr.n_labels = (long)n_labels;
+        const int Cm = DeviceIndex::grouped_select_cm(k);
+        grouped_select_kernel<<<dim3((unsigned)nq), dim3(256), (size_t)Cm * 16, s0->stream>>>((const u64 *)idx->ws_lists.p, S, total, (size_t)k, nullptr, 0u, k, Cm, gr,
+                                                                                            (u64 *)idx->ws_out.p);
+        HAC_HIP(hipGetLastError());
+        final_keys = (const uint64_t *)idx->ws_out.p;
+    }
+    HAC_TRY(keys_to_host(s0, final_keys, total, D, I));
+    if (G)
+        for (size_t i = 0; i < total; ++i) G[i] = I[i] >= 0 ? group_of[I[i]] : (int64_t)-1;
+    return HAC_OK;
 }
 
 int hac_index_remove_ids(hac_index *idx, const int64_t *ids, int64_t n, int64_t *n_removed) {

@@ -389,6 +389,48 @@ def _masked_args_tensor(q, k, masks, mask_of, id_map, d, ntotal, what="search_ma
     return q, k, masks.contiguous(), mask_of, id_map
 
 
+# ---- labels of search_grouped (include/haconvdr.h, "search by group"): one int64 label in [0, 2^32) per row
+def _grouped_args(q, k, group_of, d, ntotal, what="search_grouped"):
+    """(q float32 [nq, d], k, group_of int64 [ntotal]) of search_grouped.  The values are the library's to check: it names the
+    first row whose label lies outside [0, 2^32)."""
+    q = _as_queries(q, d, what)
+    k = _as_k(k, what)
+    a = np.asarray(group_of)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"{what}: group_of must be integers, got dtype {a.dtype}")
+    if a.ndim != 1:
+        raise ValueError(f"{what}: group_of must have 1 dimension, one label per row, got shape {a.shape}")
+    if a.shape[0] != ntotal:
+        raise ValueError(f"{what}: {a.shape[0]} labels but the index holds {ntotal} rows (labels made before an add or a remove?)")
+    if a.dtype == np.uint64 and a.size and int(a.max()) > np.iinfo(np.int64).max:
+        raise ValueError(f"{what}: label {int(a.max())} does not fit int64")
+    return q, k, np.ascontiguousarray(a, dtype=np.int64)
+
+
+def _grouped_args_tensor(q, k, group_of, id_map, d, ntotal, what="search_grouped_tensor"):
+    """(q float32 CUDA [nq, d], k, group_of int64 CUDA [ntotal], id_map int64 CUDA [ntotal] or None) of search_grouped_tensor."""
+    import torch
+    q = _queries_tensor(q, d, what)
+    k = _as_k(k, what)
+    if not isinstance(group_of, torch.Tensor) or not group_of.is_cuda:
+        raise ValueError(f"{what}: group_of must be a CUDA tensor")
+    if group_of.dtype != torch.int64:
+        raise ValueError(f"{what}: group_of must be int64, got {group_of.dtype}")
+    if group_of.dim() != 1:
+        raise ValueError(f"{what}: group_of must have 1 dimension, one label per row, got shape {tuple(group_of.shape)}")
+    if group_of.shape[0] != ntotal:
+        raise ValueError(f"{what}: {group_of.shape[0]} labels but the index holds {ntotal} rows (labels made before an add or a remove?)")
+    if group_of.device != q.device:
+        raise ValueError(f"{what}: q on {q.device} but group_of on {group_of.device}")
+    if id_map is not None:
+        if not isinstance(id_map, torch.Tensor) or not id_map.is_cuda or id_map.dtype != torch.int64 or id_map.dim() != 1:
+            raise ValueError(f"{what}: id_map must be an int64 CUDA tensor [ntotal]")
+        if id_map.device != q.device:
+            raise ValueError(f"{what}: q on {q.device} but id_map on {id_map.device}")
+        id_map = id_map.contiguous()
+    return q, k, group_of.contiguous(), id_map
+
+
 def _filter_args(keys, exclude_pos, k, what="filter_keys"):
     """(keys int64 CUDA [nq, kin], exclude_pos int64 CUDA [nq, e], k in [1, kin]) of filter_keys."""
     keys = _ids_tensor(keys, 2, what)
@@ -476,6 +518,19 @@ class FlatIPIndex:
         _lib.check(_lib.lib().hac_index_search_masked(self._h, _f32p(q), q.shape[0], k, words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
                                                       words.shape[0], words.shape[1], null_i if mask_of is None else _i64p(mask_of), _f32p(D), _i64p(I)))
         return D, I
+
+    def search_grouped(self, q, k, group_of, return_groups=False):
+        """The k best GROUPS of rows per query, each by its best row: group_of int64 [ntotal] labels in [0, 2^32), one per row
+        (a label outside that range raises HacError naming the row).  -> (D, I), the score and row of each group's
+        representative ordered by (score desc, row asc), padded with -FLT_MAX / -1 when fewer than k labels occur; with
+        return_groups also G = group_of[I] (-1 in padding).  Exact however many rows a group has (include/haconvdr.h,
+        "search by group"); the labels are uploaded on every call.  faiss: grouped search (IDGrouper)."""
+        q, k, group_of = _grouped_args(q, k, group_of, self.d, self.ntotal)
+        D, I = _host_results((q.shape[0], k))
+        G = np.empty((q.shape[0], k), np.int64) if return_groups else None
+        _lib.check(_lib.lib().hac_index_search_grouped(self._h, _f32p(q), q.shape[0], k, _i64p(group_of), group_of.shape[0], _f32p(D), _i64p(I),
+                                                       ctypes.POINTER(ctypes.c_int64)() if G is None else _i64p(G)))
+        return (D, I, G) if return_groups else (D, I)
 
     def reset(self):
         _lib.check(_lib.lib().hac_index_reset(self._h))
@@ -659,6 +714,19 @@ class FlatIPIndex:
                                                                   _devp(mask_of), _devp(keys), int(pos_base), _stream_ptr(stream)))
         _keep_alive(stream, q, masks, keys, *(() if mask_of is None else (mask_of,)))
         return keys
+
+    def search_grouped_tensor(self, q, k, group_of, id_map=None, return_groups=False, stream=None):
+        """search_grouped on the device: group_of int64 CUDA [ntotal]; a row whose label lies outside [0, 2^32) is in no list and
+        raises nothing.  id_map: optional int64 CUDA [ntotal], I = id_map[row]; G (with return_groups) stays the row's own label.
+        No host sync; capturable after one call of the largest (nq, k)."""
+        import torch
+        q, k, group_of, id_map = _grouped_args_tensor(q, k, group_of, id_map, self.d, self.ntotal)
+        D, I = _device_results((q.shape[0], k), q.device)
+        G = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device) if return_groups else None
+        _lib.check(_lib.lib().hac_index_search_grouped_device(self._h, _devp(q), q.shape[0], k, _devp(group_of), group_of.shape[0], _devp(D), _devp(I),
+                                                              _devp(G), _devp(id_map), _stream_ptr(stream)))
+        _keep_alive(stream, q, group_of, D, I, *(t for t in (G, id_map) if t is not None))
+        return (D, I, G) if return_groups else (D, I)
 
     def search_keys_tensor(self, q, k, pos_base=0, stream=None):
         """Packed top-k keys (int64 view of uint64) [nq, k]; the unit exchanged between shards."""

@@ -255,6 +255,42 @@ class ResidentCorpus:
             D, I = self.index.search_excluding_tensor(q.to(self.dev), topN, torch.from_numpy(rows).to(self.dev), id_map=self.id_map)
         return D.cpu().numpy().astype(np.float64), I.cpu().numpy()
 
+    def _passage_labels(self):
+        """int64 CUDA [ntotal]: the rows' external passage ids relabelled densely (0 .. distinct ids - 1), the default groups of
+        search_distinct.  Kept on the device for the rows as they are now: remove() replaces the id array and with it this."""
+        import torch
+        cached = getattr(self, "_labels", None)
+        if cached is None or cached[0] is not self._ids:
+            dense = np.unique(self._ids, return_inverse=True)[1].astype(np.int64).reshape(-1)
+            self._labels = cached = (self._ids, torch.from_numpy(dense).to(self.dev))
+        return cached[1]
+
+    def search_distinct(self, query_embeddings, topN, group_of=None):
+        """search, with every group of rows represented once, by its best row: (D float64 [nq,topN], passage ids int64
+        [nq,topN]) of the topN best groups, exact however many rows a group has (index.search_grouped_tensor; faiss's grouped
+        search).  group_of=None: a group is the rows that carry one external passage id -- a full list of distinct passage
+        ids, what output_test_res's seen_pid de-dup leaves of a list that was long enough.  group_of: an integer array over the
+        EXTERNAL ids, group_of[passage id] = the group (the page of a passage), values in [0, 2^32); every id a row carries must
+        index it.  Fewer than topN groups: the tail is -FLT_MAX / -1."""
+        import torch
+        q = query_embeddings if isinstance(query_embeddings, torch.Tensor) else torch.from_numpy(
+            np.ascontiguousarray(query_embeddings, dtype=np.float32))
+        if group_of is None:
+            labels = self._passage_labels()
+        else:
+            g = np.asarray(group_of)
+            if g.dtype.kind not in "iu" or g.ndim != 1:
+                raise ValueError(f"search_distinct: group_of must be a 1-D integer array over the passage ids, got {g.dtype} {g.shape}")
+            if len(self._ids) and (self._ids.min() < 0 or self._ids.max() >= g.shape[0]):
+                raise ValueError(f"search_distinct: group_of has {g.shape[0]} entries but the rows carry passage ids in "
+                                 f"[{int(self._ids.min())}, {int(self._ids.max())}]")
+            rows = g[self._ids].astype(np.int64)
+            if rows.size and (rows.min() < 0 or rows.max() >= 2 ** 32):
+                raise ValueError("search_distinct: group_of values must lie in [0, 2^32)")
+            labels = torch.from_numpy(np.ascontiguousarray(rows)).to(self.dev)
+        D, I = self.index.search_grouped_tensor(q.to(self.dev), topN, labels, id_map=self.id_map)
+        return D.cpu().numpy().astype(np.float64), I.cpu().numpy()
+
     def remove(self, passage_ids):
         """Drop passages from the resident corpus in place (a withdrawn passage, a duplicate): passage_ids, integers of any
         shape, EXTERNAL ids (-1 = padding).  Every row that carries one of them goes (an id two blocks hold names two rows), an

@@ -406,6 +406,67 @@ int hac_index_search_masked_device(hac_index *idx, const float *q_dev, int64_t n
 int hac_index_search_masked_keys_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const uint64_t *masks_dev, int64_t n_masks, int64_t words,
                                         const int64_t *mask_of_dev, uint64_t *keys_dev, uint32_t pos_base, void *hip_stream);
 
+/* ---- search by group: exact top-k groups of rows, each by its best row -----------------------------------------------------
+ * faiss: grouped search (IDGrouper, since 1.8) -- a run of distinct passages where several rows share a passage id, page-level
+ * retrieval over chunk rows, MaxP scoring, hard negatives from distinct documents.  For a query q, labels g[r] (one per row)
+ * and k:
+ *   rep(q, G)        = the row of group G with the greatest key (score desc, row asc) among its rows whose score is not NaN;
+ *                      a group with no such row has none
+ *   grouped(q, g, k) = the first k of { rep(q, G) : G a label that occurs } by (score desc, row asc),
+ *                      padded with D = -FLT_MAX, I = -1
+ * s is the canonical score: the k-ordered fmaf chain plus the "+ 0.0f" of a packed key, the same bits search returns.  Rows
+ * behind ntotal, and stale rows after reset() plus a smaller add(), belong to no group.  +-Inf scores are ordinary scores and a
+ * NaN query gives padding only, as everywhere else.  In other words: an unbounded search of q, reduced to the first row of every
+ * label and cut at k.  search(q, k') followed by a de-dup is NOT this: it stops being exact as soon as one group owns more than
+ * k' - k of the leading rows, and k' ends at HAC_MAX_K.
+ * Identities (proved on the CPU over the oracle by tests/test_index_grouped.py, asserted on the GPU):
+ *   - labels all distinct (arange(ntotal)): grouped(q, g, k) == search(q, k), bit for bit on every k;
+ *   - one label for every row: search(q, 1) followed by padding;
+ *   - grouped(q, g, k) == search_masked(q, k, M_q), M_q the per-query mask of { rep(q, G) };
+ *   - rank_ids(q, I_grouped)[j] is strictly increasing in j and >= j, and score_ids of I_grouped has the bits of D_grouped;
+ *   - grouped is the rows of range_search(q, -inf) kept at their label's first occurrence and cut at k, then the -Inf-scoring
+ *     representatives if there is room.
+ * Labels: group_of is int64 [n_labels], values in [0, 2^32) -- what offset2pid / passage_embedding2id hold, and 32 bits let a
+ * (label, list position) pair fit one 64-bit LDS word.  n_labels must equal ntotal, otherwise HAC_ERR_INVALID -- which refuses
+ * labels made before an add or a remove.  The array is a per-call argument like id_map_dev: the index holds no new state, and
+ * add, remove_ids and reset need no new rule.  A label outside the range: the host form returns HAC_ERR_INVALID, names the first
+ * offending row and writes nothing; the *_device form cannot look, so there such a row is in no list -- it is dropped before it
+ * can contribute to any threshold, and a group that loses its best row this way is represented by its next.
+ * Results: D, I as search; G (may be NULL) receives G[i][j] = group_of[row of slot j], the row's own label and never id_map's
+ * value, -1 in padding slots.  1 <= k <= HAC_MAX_K; a k whose buffers do not fit LDS fails as search does, naming k.  nq == 0 is
+ * HAC_OK and touches nothing; ntotal == 0 gives padding only.
+ *
+ * How (csrc/grouped.inc): scan16_grouped_kernel is a copy of scan16_kernel -- the same row stream, the same bit-exact MFMA
+ * chain, the same candidate buffers -- whose compaction sorts the buffer, gathers each entry's label, keeps only the best entry
+ * of every label (a second sort, of (label << 32 | list position) words in a scratch LDS array) and cuts to k.  Only when k
+ * distinct labels remain does the k-th key become the query's threshold: it is then the k-th best of k distinct groups' entries,
+ * a proven lower bound of the k-th group score, so the result does not depend on the number of row streams, the launch cuts or
+ * the order of work.  A buffer full of one group's rows shrinks to one entry and the scan goes on.  No threshold seeding and no
+ * fp16 prefilter: a sample of rows says nothing about groups.  grouped_select_kernel (one workgroup per query, no atomics)
+ * reduces the workgroups' survivors the same way; it is also the merge of the multi-device host form.
+ * Cost (by arithmetic, NOT measured here; DESIGN.md records one timing): ceil(nq / QT) passes over the rows at the exact scan's
+ * stream rate, QT = 16 queries and fewer at large k (the scratch array takes LDS: QT = 2 at k = 2048, d = 768), plus two LDS
+ * sorts and one ordered pass per compaction where scan16 has one sort.  Until k distinct groups have been seen every row is a
+ * candidate: a corpus led by one giant group compacts every (C - k) / 256 rounds throughout.
+ *
+ * Host form: synchronous, on the index's own stream.  Labels (8 bytes per row) and queries are staged to the device on EVERY
+ * call: a caller that searches the same labels repeatedly should hold them on the device and use the device form.  It works on
+ * a multi-device index: every shard searches its rows under its slice of the labels, the per-shard lists (at most k distinct
+ * groups each) are remapped as search does and merged on the first device by grouped_select_kernel, reading the whole label
+ * array there.
+ * Device form: single-device index (HAC_ERR_UNSUPPORTED otherwise), 16-byte aligned q_dev; enqueues on hip_stream and never
+ * reads back; id_map_dev as in hac_index_search_device.  The workspaces grow by the rule of the search workspaces: run one call
+ * of the largest (nq, k) before capturing into a HIP graph.  Test switches (hac_index_set_option): "grouped_p" = "auto" |
+ * 1..4096 row streams per query tile, "debug_grouped_tiles" = 0 | the most query tiles per launch.  hac_index_last_plan
+ * afterwards reads "scan16_grouped_kernel<W=4> grid=(P,T) QT=.. C=.. lds=.. grouped_select_kernel n_in=.. launches=..".
+ * Out of scope: haconvdr_amd.sharded.ShardedSearcher (a group may span ranks: the merge would need the labels of other ranks'
+ * rows); a keys form; a GEMM-shaped many-query form; a certified fast path (search at k' > k through the prefilter, accepted
+ * when k distinct labels appear, the grouped scan only for the rest). */
+int hac_index_search_grouped(hac_index *idx, const float *q, int64_t nq, int k, const int64_t *group_of, int64_t n_labels, float *D, int64_t *I,
+                             int64_t *G /* may be NULL */);
+int hac_index_search_grouped_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const int64_t *group_of_dev, int64_t n_labels, float *D_dev,
+                                    int64_t *I_dev, int64_t *G_dev /* may be NULL */, const int64_t *id_map_dev, void *hip_stream);
+
 /* ---- removing rows: faiss's IndexFlat::remove_ids(IDSelectorBatch(ids)), in place ------------------------------------------
  * The rows named by ids disappear; every surviving row keeps its bits and its relative order; the survivors are renumbered
  * densely from 0 -- survivor number j is row j of np.delete(x, unique(ids), axis=0) --; ntotal drops by the number of DISTINCT
@@ -469,6 +530,8 @@ int hac_index_last_status(hac_index *idx);
  * first such search at any size, "0" never (and frees one that exists, as does growing past the size).  Same bits either way.
  * "masked_p" = "auto" | "1" .. "4096" and "debug_masked_tiles" = integer >= 0: tests of hac_index_search_masked* ("search inside a
  * bitmap": row streams per query tile; the most query tiles per launch, 0 = by the list workspace).  Same bits either way.
+ * "grouped_p" = "auto" | "1" .. "4096" and "debug_grouped_tiles" = integer >= 0: the same two switches of hac_index_search_grouped*
+ * ("search by group").  Same bits either way.
  * Any other name or value is HAC_ERR_INVALID (never a silent default).
  * The HAC_<NAME> environment variables give the defaults and are read once, in hac_index_create. */
 int hac_index_set_option(hac_index *idx, const char *name, const char *value);
