@@ -1855,10 +1855,10 @@ struct DeviceIndex {
 
     GrowBuf ws_ids, ws_rank;   // the by-id calls (rows_host.inc): a chunk's ids; the rank calls' counters and reference scores
     GrowBuf ws_range;          // range search (rows_host.inc: RangeWs): control words, counters, cursors, staging and the two key buffers
-    GrowBuf ws_among;          // search among named rows (rows_host.inc: among_keys_device): a chunk's [queries][P] candidate keys
+    GrowBuf ws_among;          // search among named rows (search_host.inc: among_keys_device): a chunk's [queries][P] candidate keys
     GrowBuf ws_mgroups, ws_mcnt;   // search inside a bitmap (search_keys_masked): one launch's group lists u32 [tiles][G], the call's counters u32 [tiles]
-    GrowBuf ws_masks;          // its host form (rows_host.inc: masked_shard): a chunk's masks and mask_of
-    GrowBuf ws_labels;         // search by group, host form (rows_host.inc: grouped_shard): the shard's slice of the labels
+    GrowBuf ws_masks;          // its host form (search_host.inc: masked_shard): a chunk's masks and mask_of
+    GrowBuf ws_labels;         // search by group, host form (search_host.inc: grouped_shard): the shard's slice of the labels
 
     char last_plan[320] = "none";
     // a device-decided prefilter search leaves its fallback count and err / bound on the device: plan() completes the text
@@ -1937,9 +1937,44 @@ struct DeviceIndex {
         size_t lds_scan;
     };
 
+    // The query tiles of a call (search_keys_masked, search_keys_grouped) in launches of whole tiles: at most `most` tiles each
+    // (a debug option > 0 lowers it: tests cut a small call into several launches), at least one.
+    struct TileLaunches {
+        int QT;
+        int64_t TL, QL, launches;   // tiles and queries per launch
+        TileLaunches(const Plan &pl, int64_t most, int debug_tiles) : QT(pl.QT) {
+            TL = std::max<int64_t>(1, most);
+            if (debug_tiles > 0) TL = std::min<int64_t>(TL, debug_tiles);
+            TL = std::min<int64_t>(TL, pl.n_qtiles);
+            QL = TL * QT;
+            launches = (pl.n_qtiles + TL - 1) / TL;
+        }
+        // body(launch, its first query, its queries, its tiles): every launch works at offsets of its own
+        template <class Body>
+        int each(int64_t nq, Body body) const {
+            for (int64_t l = 0; l < launches; ++l) {
+                const int64_t off = l * QL, n = std::min(QL, nq - off);
+                HAC_TRY(body(l, off, n, (n + QT - 1) / QT));
+            }
+            return HAC_OK;
+        }
+    };
+
     static size_t scanq_lds(int NQ, int C) { return (size_t)NQ * (2 * 16 * 16 + (size_t)C * 8 + 8) + 16; }
 
-    int make_plan(int64_t nq, int k, u32 n_items, Plan &pl, bool scan16_only = false) const {
+    // Row streams per query tile, the grid.x of every kernel that walks the rows: the workgroups resident on the device (per CU
+    // as many as LDS and waves allow, at most `cap`: the caller's bound by the kernel's registers) over a launch's `tiles` query
+    // tiles, or `pinned` when > 0 (tests); never more than give each of a workgroup's `waves` waves one of the `items`.
+    long row_streams(size_t lds, int waves, int cap, int64_t tiles, u32 items, int pinned) const {
+        const int per_cu = std::max(1, std::min<int>((int)std::min<size_t>(LDS_LIMIT / lds, 32 / waves), cap));
+        long P = std::max<long>(1, (long)n_cu * per_cu / tiles);
+        if (P >= 8 && !tune.no_p8) P = P / 8 * 8;  // same-row workgroups of different query tiles share an XCD (L2)
+        if (pinned > 0) P = pinned;
+        return std::max<long>(1, std::min<long>(P, (items + waves - 1) / waves));
+    }
+
+    // pinned_p: row_streams' (0: by the resident workgroups)
+    int make_plan(int64_t nq, int k, u32 n_items, Plan &pl, bool scan16_only = false, int pinned_p = 0) const {
         pl.kind = 0;
         pl.NT = 0;
         pl.W = SCAN_WAVES;
@@ -1978,15 +2013,8 @@ struct DeviceIndex {
             pl.lds_scan = per_q * qt + fixed;
         }
         pl.n_qtiles = (int)((nq + pl.QT - 1) / pl.QT);
-        // resident workgroups: LDS- and wave-limited
-        int per_cu = (int)std::min<size_t>(LDS_LIMIT / pl.lds_scan, 32 / pl.W);
-        per_cu = std::max(1, std::min(per_cu, pl.kind == 1 ? 2 : 4));
-        const long resident = (long)n_cu * per_cu;
-        long P = std::max<long>(1, resident / pl.n_qtiles);
-        if (P >= 8 && !tune.no_p8) P = P / 8 * 8;  // same-row workgroups of different query tiles share an XCD (L2)
-        const long maxP = (n_items + pl.W - 1) / pl.W;
-        P = std::max<long>(1, std::min(P, maxP));
-        pl.P = (int)P;
+        // resident workgroups per CU: LDS- and wave-limited, at most 4 of scan16's shape and 2 of scanq's
+        pl.P = (int)row_streams(pl.lds_scan, pl.W, pl.kind == 1 ? 2 : 4, pl.n_qtiles, n_items, pinned_p);
         return HAC_OK;
     }
 
@@ -2001,24 +2029,32 @@ struct DeviceIndex {
         a.n_rows = (long)ntotal;
         return a;
     }
-    int run_scan(const Plan &pl, const float *q_dev, int64_t nq, int k, u32 G, const float *thr_init, u32 pos_base, hipStream_t st, const int *nq_dev, bool cleared) {
+    // ... and those of a launch that collects every query's survivors for a top-k select (run_scan, search_keys_masked,
+    // search_keys_grouped): the plan's tile, the survivors' buffers and counters, the thresholds
+    ScanArgs topk_scan_args(const float *q_dev, int64_t nq, int k, const Plan &pl, u32 pos_base) const {
         ScanArgs a = scan_args(q_dev, nq);
-        a.nq_dev = nq_dev;
-        a.qt = reinterpret_cast<const float4 *>(ws_qt.p);
         a.k = k;
         a.C = pl.C;
         a.QT = pl.QT;
-        a.g_step = 1;
-        a.n_items = G;
-        a.thr_init = thr_init;
         a.thr_glob = thrglob();
         a.partial = (u64 *)ws_partial.p;
         a.partial_cnt = (u32 *)ws_pcnt.p;
         a.pos_base = pos_base;
-        if (!cleared) {     // (the device-decided fallback's first chunk: gather_rows_kernel has cleared both)
-            HAC_HIP(hipMemsetAsync(ws_pcnt.p, 0, (size_t)nq * 4, st));
-            HAC_TRY(clear_thrglob((size_t)pl.n_qtiles * pl.QT, st));
-        }
+        return a;
+    }
+    // in front of such a launch: no survivors yet for its nq queries, no thresholds for its nq_pad query slots
+    int reset_topk_scan(size_t nq, size_t nq_pad, hipStream_t st) {
+        HAC_HIP(hipMemsetAsync(ws_pcnt.p, 0, nq * 4, st));
+        return clear_thrglob(nq_pad, st);
+    }
+    int run_scan(const Plan &pl, const float *q_dev, int64_t nq, int k, u32 G, const float *thr_init, u32 pos_base, hipStream_t st, const int *nq_dev, bool cleared) {
+        ScanArgs a = topk_scan_args(q_dev, nq, k, pl, pos_base);
+        a.nq_dev = nq_dev;
+        a.qt = reinterpret_cast<const float4 *>(ws_qt.p);
+        a.g_step = 1;
+        a.n_items = G;
+        a.thr_init = thr_init;
+        if (!cleared) HAC_TRY(reset_topk_scan((size_t)nq, (size_t)pl.n_qtiles * pl.QT, st));   // (cleared: the device-decided fallback's first chunk, gather_rows_kernel has done both)
         HAC_TRY(prof_begin(st));
         if (pl.kind == 0) {
             scan16_kernel<<<dim3((unsigned)pl.P, (unsigned)pl.n_qtiles), dim3(SCAN_WAVES * 64), pl.lds_scan, st>>>(a);
@@ -2122,14 +2158,10 @@ struct DeviceIndex {
         Plan pl0, pl;
         HAC_TRY(make_plan(nq, k, G, pl0, true));
         const int QT = pl0.QT;
-        int64_t TL = std::max<int64_t>(1, ((int64_t)64 << 20) / ((int64_t)G * 4));   // tiles per launch
-        TL = std::min<int64_t>(TL, std::max<int64_t>(1, QUERY_CHUNK / QT));
-        if (tune.debug_masked_tiles > 0) TL = std::min<int64_t>(TL, tune.debug_masked_tiles);
-        TL = std::min<int64_t>(TL, pl0.n_qtiles);
-        const int64_t QL = TL * QT;   // queries per launch
-        HAC_TRY(make_plan(std::min(nq, QL), k, G, pl, true));   // P for the tiles of one launch; QT and C as above
-        if (tune.masked_p > 0) pl.P = (int)std::max<long>(1, std::min<long>(tune.masked_p, (G + SCAN_WAVES - 1) / SCAN_WAVES));
-        const int64_t launches = (pl0.n_qtiles + TL - 1) / TL;
+        const TileLaunches tl(pl0, std::min<int64_t>(((int64_t)64 << 20) / ((int64_t)G * 4), QUERY_CHUNK / QT), tune.debug_masked_tiles);
+        const int64_t TL = tl.TL, QL = tl.QL, launches = tl.launches;
+        // P for the tiles of one launch (at most 4 resident workgroups per CU, as scan16: the same shape); QT and C as above
+        HAC_TRY(make_plan(std::min(nq, QL), k, G, pl, true, tune.masked_p));
         HAC_TRY(ws_mgroups.reserve((size_t)TL * G * 4));
         HAC_TRY(ws_mcnt.reserve((size_t)pl0.n_qtiles * 4));
         HAC_TRY(ws_partial.reserve((size_t)std::min(nq, QL) * pl.P * k * 8));
@@ -2141,8 +2173,7 @@ struct DeviceIndex {
                  (long long)TL, SCAN_WAVES, pl.P, (long long)TL, QT, pl.C, pl.lds_scan, (long long)launches);
         plan_text_slot = -1;
         const int np2 = (int)next_pow2((u32)k);
-        for (int64_t l = 0; l < launches; ++l) {
-            const int64_t off = l * QL, n = std::min(QL, nq - off), tiles = (n + QT - 1) / QT;
+        return tl.each(nq, [&](int64_t l, int64_t off, int64_t n, int64_t tiles) -> int {
             MaskArgs m{};
             m.per_query = (!mask_of_dev && n_masks != 1) ? 1 : 0;
             m.masks = m.per_query ? masks_dev + (size_t)off * words : masks_dev;
@@ -2152,18 +2183,10 @@ struct DeviceIndex {
             m.groups = (u32 *)ws_mgroups.p;
             m.n_groups = (u32 *)ws_mcnt.p + l * TL;
             m.G = G;
-            ScanArgs a = scan_args(q_dev + (size_t)off * d, n);
-            a.k = k;
-            a.C = pl.C;
-            a.QT = QT;
-            a.thr_glob = thrglob();
-            a.partial = (u64 *)ws_partial.p;
-            a.partial_cnt = (u32 *)ws_pcnt.p;
-            a.pos_base = pos_base;
+            const ScanArgs a = topk_scan_args(q_dev + (size_t)off * d, n, k, pl, pos_base);
             mask_groups_kernel<<<dim3(gx, (unsigned)tiles), dim3(256), 0, st>>>(m, (int)n, QT, (long)ntotal);
             HAC_HIP(hipGetLastError());
-            HAC_HIP(hipMemsetAsync(ws_pcnt.p, 0, (size_t)n * 4, st));
-            HAC_TRY(clear_thrglob((size_t)tiles * QT, st));
+            HAC_TRY(reset_topk_scan((size_t)n, (size_t)tiles * QT, st));
             HAC_TRY(prof_begin(st));
             scan16_masked_kernel<<<dim3((unsigned)pl.P, (unsigned)tiles), dim3(SCAN_WAVES * 64), pl.lds_scan, st>>>(a, m);
             HAC_HIP(hipGetLastError());
@@ -2172,8 +2195,8 @@ struct DeviceIndex {
                                                                                       (u32)((size_t)pl.P * k), k, np2, keys_out + (size_t)off * k, nullptr, nullptr, (int)n,
                                                                                       (u32)(pl.P * tiles), (u32)QT, thrglob(), (u32 *)ws_err.p);
             HAC_HIP(hipGetLastError());
-        }
-        return HAC_OK;
+            return HAC_OK;
+        });
     }
 
     // ---- search by group (grouped.inc).  keys_out: device u64 [nq][k]; group_of_dev int64 [ntotal] on the device; arguments
@@ -2212,18 +2235,10 @@ struct DeviceIndex {
         Plan pl;
         HAC_TRY(grouped_plan(nq, k, pl));
         const int QT = pl.QT;
-        int64_t TL = std::max<int64_t>(1, QUERY_CHUNK / QT);   // tiles per launch
-        if (tune.debug_grouped_tiles > 0) TL = std::min<int64_t>(TL, tune.debug_grouped_tiles);
-        TL = std::min<int64_t>(TL, pl.n_qtiles);
-        const int64_t QL = TL * QT;   // queries per launch
-        // row streams per tile: the resident workgroups (LDS- and wave-limited, as make_plan counts them) over a launch's tiles
-        const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(LDS_LIMIT / pl.lds_scan, 32 / SCAN_WAVES), 4));
-        long P = std::max<long>(1, (long)n_cu * per_cu / TL);
-        if (P >= 8 && !tune.no_p8) P = P / 8 * 8;
-        if (tune.grouped_p > 0) P = tune.grouped_p;
-        P = std::max<long>(1, std::min<long>(P, (G + SCAN_WAVES - 1) / SCAN_WAVES));
-        pl.P = (int)P;
-        const int64_t launches = (pl.n_qtiles + TL - 1) / TL;
+        const TileLaunches tl(pl, QUERY_CHUNK / QT, tune.debug_grouped_tiles);
+        const int64_t TL = tl.TL, QL = tl.QL, launches = tl.launches;
+        // row streams per tile: over a launch's tiles, at most 4 resident workgroups per CU, as make_plan counts scan16's (the same shape)
+        pl.P = (int)row_streams(pl.lds_scan, SCAN_WAVES, 4, TL, G, tune.grouped_p);
         const int Cm = grouped_select_cm(k);
         HAC_TRY(ws_partial.reserve((size_t)std::min(nq, QL) * pl.P * k * 8));
         HAC_TRY(ws_pcnt.reserve((size_t)std::min(nq, QL) * 4));
@@ -2235,20 +2250,11 @@ struct DeviceIndex {
         gr.group_of = (const long long *)group_of_dev;
         gr.n_labels = (long)ntotal;
         gr.pos_base = 0u;
-        for (int64_t l = 0; l < launches; ++l) {
-            const int64_t off = l * QL, n = std::min(QL, nq - off), tiles = (n + QT - 1) / QT;
-            ScanArgs a = scan_args(q_dev + (size_t)off * d, n);
-            a.k = k;
-            a.C = pl.C;
-            a.QT = QT;
+        return tl.each(nq, [&](int64_t, int64_t off, int64_t n, int64_t tiles) -> int {
+            ScanArgs a = topk_scan_args(q_dev + (size_t)off * d, n, k, pl, 0u);
             a.g_step = 1;
             a.n_items = G;
-            a.thr_glob = thrglob();
-            a.partial = (u64 *)ws_partial.p;
-            a.partial_cnt = (u32 *)ws_pcnt.p;
-            a.pos_base = 0u;
-            HAC_HIP(hipMemsetAsync(ws_pcnt.p, 0, (size_t)n * 4, st));
-            HAC_TRY(clear_thrglob((size_t)tiles * QT, st));
+            HAC_TRY(reset_topk_scan((size_t)n, (size_t)tiles * QT, st));
             HAC_TRY(prof_begin(st));
             scan16_grouped_kernel<<<dim3((unsigned)pl.P, (unsigned)tiles), dim3(SCAN_WAVES * 64), pl.lds_scan, st>>>(a, gr);
             HAC_HIP(hipGetLastError());
@@ -2256,8 +2262,8 @@ struct DeviceIndex {
             grouped_select_kernel<<<dim3((unsigned)n), dim3(256), (size_t)Cm * 16, st>>>((const u64 *)ws_partial.p, 0, 0, (size_t)pl.P * k, (const u32 *)ws_pcnt.p,
                                                                                          (u32)((size_t)pl.P * k), k, Cm, gr, keys_out + (size_t)off * k);
             HAC_HIP(hipGetLastError());
-        }
-        return HAC_OK;
+            return HAC_OK;
+        });
     }
 
     // ---- split-bf16 prefilter + exact rescoring (scan_split.inc): same results, ~3x the query rate when the
@@ -2749,6 +2755,7 @@ int first_shard_error(hac_index *idx, F fn) {
 }  // namespace
 
 #include "rows_host.inc"
+#include "search_host.inc"
 
 extern "C" {
 
@@ -2910,141 +2917,6 @@ int hac_filter_keys_device(int device, const uint64_t *keys_dev, int64_t nq, int
     HAC_HIP(hipGetLastError());
     return HAC_OK;
 }
-
-int hac_index_search_device(hac_index *idx, const float *q_dev, int64_t nq, int k, float *D_dev, int64_t *I_dev,
-                            const int64_t *id_map_dev, void *hip_stream) {
-    return on_single_shard(idx, "search_device", [&](DeviceIndex &s) -> int {
-        HAC_TRY(check_k(k));
-        if (nq < 0 || (nq > 0 && (!q_dev || !D_dev || !I_dev))) return fail(HAC_ERR_INVALID, "search: bad arguments");
-        if (nq == 0) return HAC_OK;
-        HAC_TRY(s.ws_keys.reserve((size_t)nq * k * 8));
-        HAC_TRY(s.search_keys(q_dev, nq, k, (u64 *)s.ws_keys.p, 0u, (hipStream_t)hip_stream, true));
-        return hac_keys_to_results_device(s.device, (const uint64_t *)s.ws_keys.p, nq * k, id_map_dev, D_dev, I_dev, hip_stream);
-    });
-}
-
-// The top-k of (rows minus E), |E| <= e, lies inside the top-(k + e) of the rows, in the same order: search k + e keys, filter.
-int hac_index_search_excluding_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const int64_t *excl_dev, int e, float *D_dev,
-                                      int64_t *I_dev, const int64_t *id_map_dev, void *hip_stream) {
-    return on_single_shard(idx, "search_excluding_device", [&](DeviceIndex &s) -> int {
-        HAC_TRY(check_k_e(k, e));
-        if (e == 0) return hac_index_search_device(idx, q_dev, nq, k, D_dev, I_dev, id_map_dev, hip_stream);
-        if (nq < 0 || (nq > 0 && (!q_dev || !excl_dev || !D_dev || !I_dev))) return fail(HAC_ERR_INVALID, "search_excluding: bad arguments");
-        if (nq == 0) return HAC_OK;
-        const int kq = k + e;
-        HAC_TRY(s.ws_keys.reserve((size_t)nq * kq * 8));
-        HAC_TRY(idx->ws_out.reserve((size_t)nq * k * 8));
-        HAC_TRY(s.search_keys(q_dev, nq, kq, (u64 *)s.ws_keys.p, 0u, (hipStream_t)hip_stream, true));
-        // (row ids are the positions the keys carry, pos_base = 0; an id outside [0, ntotal) is padding or names no key)
-        HAC_TRY(hac_filter_keys_device(s.device, (const uint64_t *)s.ws_keys.p, nq, kq, excl_dev, e, k, (uint64_t *)idx->ws_out.p, hip_stream));
-        return hac_keys_to_results_device(s.device, (const uint64_t *)idx->ws_out.p, nq * k, id_map_dev, D_dev, I_dev, hip_stream);
-    });
-}
-
-}  // extern "C"
-
-namespace {
-// The host driver of hac_index_search (e == 0: kq == k, no filter) and hac_index_search_excluding (the shards search, are
-// remapped and merged at kq = k + e; the merged lists are filtered down to k on shard 0).  Arguments checked by the callers.
-int search_host(hac_index *idx, const float *q, int64_t nq, int k, const int64_t *excl, int e, float *D, int64_t *I) {
-    const int kq = k + e;
-    const int S = (int)idx->shards.size();
-    const size_t qbytes = (size_t)nq * idx->d * 4, ebytes = (size_t)nq * e * 8;
-    // each shard searches its rows; positions are global (shard base + local row)
-    DeviceIndex *s0 = idx->shards[0];
-    {
-        DeviceGuard g0(s0->device);
-        HAC_TRY(idx->ws_lists.reserve((size_t)S * nq * kq * 8));
-        HAC_TRY(idx->ws_out.reserve((size_t)nq * kq * 8));
-        if (e) HAC_TRY(idx->ws_excl.reserve(ebytes));
-    }
-    // every shard searches its own rows on its own stream (for_each_shard)
-    auto search_shard = [&](int si) -> int {
-        DeviceIndex *s = idx->shards[si];
-        DeviceGuard g(s->device);
-        if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", s->device);
-        HAC_TRY(s->ws_q.reserve(qbytes));
-        HAC_TRY(s->ws_keys.reserve((size_t)nq * kq * 8));
-        const size_t xbytes = si == 0 ? ebytes : 0;   // the exclusion lists travel behind shard 0's queries
-        HAC_TRY(s->pin_reserve(std::max(qbytes + xbytes, (size_t)nq * k * 12)));
-        HAC_HIP(hipStreamSynchronize(s->stream));
-        std::memcpy(s->h_pin.p, q, qbytes);
-        HAC_HIP(hipMemcpyAsync(s->ws_q.p, s->h_pin.p, qbytes, hipMemcpyHostToDevice, s->stream));
-        if (xbytes) {
-            std::memcpy((char *)s->h_pin.p + qbytes, excl, xbytes);
-            HAC_HIP(hipMemcpyAsync(idx->ws_excl.p, (char *)s->h_pin.p + qbytes, xbytes, hipMemcpyHostToDevice, s->stream));
-        }
-        HAC_TRY(s->search_keys((const float *)s->ws_q.p, nq, kq, (u64 *)s->ws_keys.p, 0u, s->stream));
-        HAC_HIP(hipMemcpyAsync(s->h_err, s->ws_err.p, 8, hipMemcpyDeviceToHost, s->stream));   // checked after the final wait
-        if (S > 1) {   // shard-local rows -> insertion-order positions of the whole index
-            const std::vector<SpanDesc> &sp = idx->spans[si];
-            if (!sp.empty()) {
-                HAC_TRY(upload_spans(idx, si));
-                const long nk = (long)nq * kq;
-                remap_positions_kernel<<<dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s->stream>>>(
-                    (u64 *)s->ws_keys.p, nk, (const SpanDesc *)idx->ws_spans[si].p, (int)sp.size());
-                HAC_HIP(hipGetLastError());
-            }
-            HAC_HIP(hipStreamSynchronize(s->stream));
-        }
-        return HAC_OK;
-    };
-    HAC_TRY(for_each_shard(idx, search_shard));
-    DeviceGuard g0(s0->device);
-    const uint64_t *final_keys = (const uint64_t *)s0->ws_keys.p;
-    if (S > 1) {
-        // gather the per-shard key slabs on shard 0's stream (never the null stream: the index
-        // streams are non-blocking, a legacy-stream D2D copy would not be ordered with them)
-        for (int si = 0; si < S; ++si) {
-            DeviceIndex *s = idx->shards[si];
-            HAC_HIP(hipMemcpyAsync((char *)idx->ws_lists.p + (size_t)si * nq * kq * 8, s->ws_keys.p, (size_t)nq * kq * 8,
-                                   hipMemcpyDeviceToDevice, s0->stream));
-        }
-        HAC_TRY(hac_merge_keys_device(s0->device, (const uint64_t *)idx->ws_lists.p, S, nq, kq, (uint64_t *)idx->ws_out.p, s0->stream));
-        final_keys = (const uint64_t *)idx->ws_out.p;
-    }
-    if (e) {   // the kq best of all rows -> the k best of (rows minus the query's excluded rows); the merge's input slabs are free by now
-        uint64_t *filtered = (uint64_t *)(S > 1 ? idx->ws_lists.p : idx->ws_out.p);
-        HAC_TRY(hac_filter_keys_device(s0->device, final_keys, nq, kq, (const int64_t *)idx->ws_excl.p, e, k, filtered, s0->stream));
-        final_keys = filtered;
-    }
-    HAC_TRY(s0->ws_D.reserve((size_t)nq * k * 4));
-    HAC_TRY(s0->ws_I.reserve((size_t)nq * k * 8));
-    HAC_TRY(hac_keys_to_results_device(s0->device, final_keys, nq * k, nullptr, (float *)s0->ws_D.p, (int64_t *)s0->ws_I.p, s0->stream));
-    char *hp = (char *)s0->h_pin.p;
-    HAC_HIP(hipMemcpyAsync(hp, s0->ws_I.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s0->stream));
-    HAC_HIP(hipMemcpyAsync(hp + (size_t)nq * k * 8, s0->ws_D.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s0->stream));
-    HAC_HIP(hipStreamSynchronize(s0->stream));
-    std::memcpy(I, hp, (size_t)nq * k * 8);
-    std::memcpy(D, hp + (size_t)nq * k * 8, (size_t)nq * k * 4);
-    // a scan workgroup that ran into its pass bound: the results are delivered (the affected lists EMPTY), the call says so
-    // (every shard's words are read and cleared before returning: a word left set would be blamed on a later search)
-    return first_shard_error(idx, [](DeviceIndex *s) { return s->check_err(s->stream); });
-}
-}  // namespace
-
-extern "C" {
-
-int hac_index_search(hac_index *idx, const float *q, int64_t nq, int k, float *D, int64_t *I) {
-    if (!idx) return fail(HAC_ERR_INVALID, "null index");
-    HAC_TRY(check_k(k));
-    if (nq < 0 || (nq > 0 && (!q || !D || !I))) return fail(HAC_ERR_INVALID, "search: bad arguments");
-    if (nq == 0) return HAC_OK;
-    return search_host(idx, q, nq, k, nullptr, 0, D, I);
-}
-
-int hac_index_search_excluding(hac_index *idx, const float *q, int64_t nq, int k, const int64_t *excl, int e, float *D, int64_t *I) {
-    if (!idx) return fail(HAC_ERR_INVALID, "null index");
-    HAC_TRY(check_k_e(k, e));
-    if (nq < 0 || (nq > 0 && (!q || !D || !I || (e > 0 && !excl)))) return fail(HAC_ERR_INVALID, "search_excluding: bad arguments");
-    if (nq == 0) return HAC_OK;
-    HAC_TRY(check_host_ids("search_excluding", excl, nq, e, idx->ntotal, IdPlace::QUERY_COLUMN, "padding"));   // (-1 is padding; any other id outside the index is the caller's mistake)
-    return search_host(idx, q, nq, k, excl, e, D, I);
-}
-
-}  // extern "C"
-
-extern "C" {
 
 int hac_index_last_status(hac_index *idx) {
     if (!idx) return fail(HAC_ERR_INVALID, "null index");

@@ -1,9 +1,9 @@
-// Rows by id, their rank, range search, removal and search among named rows (hac_index_reconstruct*, hac_index_score_ids*,
-// hac_index_rank_ids*, hac_index_count_ahead_device, hac_index_range_search*, hac_index_remove_ids, hac_index_search_among*):
-// everything between the C ABI and the kernels of flat_ip.hip ("rows by id"), rank.inc, range.inc, remove.inc and among.inc.
-// Included by flat_ip.hip behind hac_index; free functions over one shard (DeviceIndex &), which lends its segment table, its
-// stream, its pinned slab, its staging buffers and the workspaces ws_q / ws_ids / ws_D / ws_I / ws_keys / ws_rank / ws_range /
-// ws_among -- nothing of the search state (remove_rows_shard alone changes the segments).
+// Rows by id, their rank, range search and removal (hac_index_reconstruct*, hac_index_score_ids*, hac_index_rank_ids*,
+// hac_index_count_ahead_device, hac_index_range_search*, hac_index_remove_ids): everything between the C ABI and the kernels of
+// flat_ip.hip ("rows by id"), rank.inc, range.inc and remove.inc.  Included by flat_ip.hip behind hac_index; free functions
+// over one shard (DeviceIndex &), which lends its segment table, its stream, its pinned slab, its staging buffers and the
+// workspaces ws_q / ws_ids / ws_D / ws_I / ws_rank / ws_range -- nothing of the search state (remove_rows_shard alone changes
+// the segments).  The searches that return top-k keys are search_host.inc's, which follows and uses the helpers here.
 namespace {
 
 // ---- device forms: enqueue on `st` and return.  The only wait is the segment table's upload after an add / reset / a changed
@@ -75,10 +75,7 @@ int count_ahead_device(DeviceIndex &x, const char *what, const float *q_dev, int
         const int T = (int)((n + a.QT - 1) / a.QT);
         const size_t lds = rank_lds(x.K4, a.QT, RANK_MT);
         // resident workgroups per CU: LDS-limited like scan16's, and 3 by the kernel's registers (144 of 512 per SIMD, one wave of a workgroup each)
-        const int per_cu = std::max(1, std::min<int>((int)std::min<size_t>(LDS_LIMIT / lds, 32 / SCAN_WAVES), 3));
-        long P = std::max<long>(1, (long)x.n_cu * per_cu / T);
-        if (P >= 8 && !x.tune.no_p8) P = P / 8 * 8;
-        P = std::max<long>(1, std::min<long>(P, (G + SCAN_WAVES - 1) / SCAN_WAVES));
+        const long P = x.row_streams(lds, SCAN_WAVES, 3, T, G, 0);
         RankArgs ra{ref_score_dev + (size_t)off * m, (const long long *)ref_bound_dev + (size_t)off * m, rank_counters(x) + (size_t)off * m, (long)m, 0u};
         for (int64_t c0 = 0; c0 < chunks; c0 += 65535) {
             ra.chunk0 = (u32)c0;
@@ -102,43 +99,6 @@ int rank_ids_device(DeviceIndex &x, const float *q_dev, int64_t nq, const int64_
     HAC_TRY(x.ws_rank.reserve((size_t)nq * m * 12));
     HAC_TRY(score_ids_device(x, q_dev, nq, ids_dev, m, rank_scores(x, nq, m), st));
     return count_ahead_device(x, "rank_ids", q_dev, nq, rank_scores(x, nq, m), ids_dev, true, m, rank_dev, st);
-}
-
-// ---- search among named rows (among.inc)
-int check_among_size(const char *what, int k, int64_t m) {
-    if (k < 1 || k > HAC_MAX_K || m < 0 || m > HAC_MAX_AMONG)
-        return fail(HAC_ERR_INVALID, "%s: k=%d, m=%lld: needs 1 <= k <= %d and 0 <= m <= %d (one LDS sort block of candidates per query)", what, k,
-                    (long long)m, HAC_MAX_K, HAC_MAX_AMONG);
-    return HAC_OK;
-}
-// keys_out[i] = the k keys of among(q[i], cand[i], k), positions pos_base + row, enqueued on `st` (nq > 0, k and m checked).  The
-// [queries][P] candidate keys of at most 64 MiB of queries at a time live in ws_among, which grows by the rule of the search
-// workspaces; the launches depend on (nq, m, k) only.
-int among_keys_device(DeviceIndex &x, const char *what, const float *q_dev, int64_t nq, int k, const int64_t *cand_dev, int64_t m, u64 *keys_out,
-                      u32 pos_base, hipStream_t st) {
-    if (m == 0) {   // lists of padding only
-        HAC_HIP(hipMemsetAsync(keys_out, 0, (size_t)nq * k * 8, st));
-        return HAC_OK;
-    }
-    HAC_TRY(check_dev_ptr(q_dev, what));
-    if ((uint64_t)pos_base + (uint64_t)x.ntotal > 0xFFFFFFFFull) return fail(HAC_ERR_UNSUPPORTED, "row positions exceed 32 bits");
-    const u32 P = next_pow2((u32)m), bpq = (u32)((m + 255) / 256);
-    const int64_t QC = std::min<int64_t>(nq, std::max<int64_t>(1, ((int64_t)64 << 20) / ((int64_t)P * 8)));   // (<= 2^23 queries: the grids fit)
-    HAC_TRY(x.ws_among.reserve((size_t)QC * P * 8));
-    HAC_TRY(x.upload_segs(st));
-    const size_t lds = among_lds(P);
-    for (int64_t off = 0; off < nq; off += QC) {
-        const int64_t n = std::min(QC, nq - off);
-        among_keys_kernel<<<dim3((unsigned)(n * bpq)), dim3(256), 0, st>>>(x.d_segs, x.d_rimg, x.nseg_live, q_dev + (size_t)off * x.d,
-                                                                          (const long long *)cand_dev + (size_t)off * m, (long)m, bpq, P, (long)x.ntotal, x.K4,
-                                                                          pos_base, (u64 *)x.ws_among.p);
-        HAC_HIP(hipGetLastError());
-        among_select_kernel<<<dim3((unsigned)n), dim3(AMONG_THREADS), lds, st>>>((const u64 *)x.ws_among.p, P, k, keys_out + (size_t)off * k);
-        HAC_HIP(hipGetLastError());
-    }
-    snprintf(x.last_plan, sizeof x.last_plan, "among_keys_kernel grid=%lld among_select_kernel P=%u k=%d lds=%zu", (long long)(std::min(QC, nq) * bpq), P, k, lds);
-    x.plan_text_slot = -1;
-    return HAC_OK;
 }
 
 // ---- range search (range.inc).  The workspace of one call of (nq, cap): control words, counters, lims, the two key buffers
@@ -197,10 +157,7 @@ int range_device(DeviceIndex &x, const char *what, const float *q_dev, int64_t n
         a.n_items = G;
         T = (int)((n + a.QT - 1) / a.QT);
         lds = range_lds(x.K4, a.QT);
-        const int per_cu = std::max(1, std::min<int>((int)std::min<size_t>(LDS_LIMIT / lds, 32 / SCAN_WAVES), 3));
-        P = std::max<long>(1, (long)x.n_cu * per_cu / T);
-        if (P >= 8 && !x.tune.no_p8) P = P / 8 * 8;
-        P = std::max<long>(1, std::min<long>(P, (G + SCAN_WAVES - 1) / SCAN_WAVES));
+        P = x.row_streams(lds, SCAN_WAVES, 3, T, G, 0);   // (3 workgroups per CU at most, as count_ahead_kernel: the same registers)
         const RangeArgs ra{radius_dev + off, ws.counts + off, ws.ctl + RANGE_CURSOR, ws.buf[1], ws.stage_q, (u64)cap_eff, (u32)off};
         range_emit_kernel<<<dim3((unsigned)P, (unsigned)T), dim3(SCAN_WAVES * 64), lds, st>>>(a, ra);
         HAC_HIP(hipGetLastError());
@@ -365,21 +322,9 @@ float key_score_host(u64 key) {
 }
 int64_t key_row_host(u64 key) { return (int64_t)(0xFFFFFFFFu - (u32)key); }
 
-// A shard's span table on its device, for remap_positions_kernel (several devices only); waits for the shard's stream when it
-// has to upload.
-int upload_spans(hac_index *idx, int si) {
-    DeviceIndex *s = idx->shards[si];
-    const std::vector<SpanDesc> &sp = idx->spans[si];
-    if (sp.empty() || !idx->spans_dirty[si]) return HAC_OK;
-    HAC_TRY(idx->ws_spans[si].reserve(sp.size() * sizeof(SpanDesc)));
-    HAC_HIP(hipStreamSynchronize(s->stream));
-    HAC_HIP(hipMemcpy(idx->ws_spans[si].p, sp.data(), sp.size() * sizeof(SpanDesc), hipMemcpyHostToDevice));
-    idx->spans_dirty[si] = 0;
-    return HAC_OK;
-}
-
 // Range search over one shard's rows: lims [nq + 1] always; when the shard's total fits cap, its keys, every query's segment
-// sorted, the rows in the numbering of the whole index (several devices: remap_positions_kernel, which keeps a sorted list sorted).
+// sorted, the rows in the numbering of the whole index (several devices: remap_keys, which keeps a sorted list sorted).
+int remap_keys(hac_index *idx, int si, u64 *keys, int64_t n);   // (search_host.inc)
 int range_host(hac_index *idx, int si, const float *q, int64_t nq, const float *radius, int64_t cap, std::vector<int64_t> &lims, std::vector<u64> &keys) {
     DeviceIndex &x = *idx->shards[si];
     DeviceGuard g(x.device);
@@ -403,12 +348,7 @@ int range_host(hac_index *idx, int si, const float *q, int64_t nq, const float *
     const int64_t total = lims[(size_t)nq];
     keys.clear();
     if (total == 0 || total > cap) return HAC_OK;
-    if (idx->shards.size() > 1 && !idx->spans[si].empty()) {
-        HAC_TRY(upload_spans(idx, si));
-        remap_positions_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, x.stream>>>(const_cast<u64 *>(keys_dev), (long)total,
-                                                                                                 (const SpanDesc *)idx->ws_spans[si].p, (int)idx->spans[si].size());
-        HAC_HIP(hipGetLastError());
-    }
+    HAC_TRY(remap_keys(idx, si, const_cast<u64 *>(keys_dev), total));
     keys.resize((size_t)total);
     const int64_t chunk = (int64_t)8 << 20;   // 64 MiB of keys through the pinned slab at a time
     HAC_TRY(pin_slab(x, (size_t)std::min(chunk, total) * 8, slab));
@@ -475,78 +415,6 @@ int score_ids_shards(hac_index *idx, const RowLocator &loc, const std::vector<in
     std::vector<std::vector<int64_t>> local(loc.S, std::vector<int64_t>(at.size(), NOT_MINE));
     for (size_t i = 0; i < at.size(); ++i) local[loc.shard(at[i])][i] = loc.local(at[i], ids[i]);
     return for_each_shard(idx, [&](int si) { return score_ids_host(*idx->shards[si], q, nq, local[si].data(), m, D, true, NOT_MINE); });
-}
-
-// ---- search among named rows, the host form.  One shard's keys of the whole call, [nq][k] in its ws_keys, on its own stream:
-// cand holds the shard's local rows (-1: padding, or a row of another shard), m > 0.  Queries and lists are staged through the pinned
-// slab in chunks of ~64 MiB, one chunk in flight; with several devices the positions are then those of the whole index
-// (remap_positions_kernel, as search does).  Returns with the shard's stream idle.
-int among_shard(hac_index *idx, int si, const float *q, int64_t nq, int k, const int64_t *cand, int64_t m) {
-    DeviceIndex &x = *idx->shards[si];
-    DeviceGuard g(x.device);
-    if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", x.device);
-    const size_t q_bytes = (size_t)x.d * 4, c_bytes = (size_t)m * 8;
-    const int64_t QC = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(((size_t)64 << 20) / (q_bytes + c_bytes))));
-    HAC_TRY(x.ws_q.reserve(QC * q_bytes));
-    HAC_TRY(x.ws_ids.reserve(QC * c_bytes));
-    HAC_TRY(x.ws_keys.reserve((size_t)nq * k * 8));
-    char *slab = nullptr;   // queries, lists
-    HAC_TRY(pin_slab(x, QC * (q_bytes + c_bytes), slab));
-    for (int64_t q0 = 0; q0 < nq; q0 += QC) {
-        const int64_t nqc = std::min(QC, nq - q0);
-        std::memcpy(slab, q + (size_t)q0 * x.d, nqc * q_bytes);
-        HAC_HIP(hipMemcpyAsync(x.ws_q.p, slab, nqc * q_bytes, hipMemcpyHostToDevice, x.stream));
-        std::memcpy(slab + QC * q_bytes, cand + (size_t)q0 * m, nqc * c_bytes);
-        HAC_HIP(hipMemcpyAsync(x.ws_ids.p, slab + QC * q_bytes, nqc * c_bytes, hipMemcpyHostToDevice, x.stream));
-        HAC_TRY(among_keys_device(x, "search_among", (const float *)x.ws_q.p, nqc, k, (const int64_t *)x.ws_ids.p, m, (u64 *)x.ws_keys.p + (size_t)q0 * k, 0u,
-                                  x.stream));
-        HAC_HIP(hipStreamSynchronize(x.stream));   // (the slab is the next chunk's)
-    }
-    if (idx->shards.size() > 1 && !idx->spans[si].empty()) {
-        HAC_TRY(upload_spans(idx, si));
-        const long nk = (long)nq * k;
-        remap_positions_kernel<<<dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, x.stream>>>((u64 *)x.ws_keys.p, nk, (const SpanDesc *)idx->ws_spans[si].p,
-                                                                                             (int)idx->spans[si].size());
-        HAC_HIP(hipGetLastError());
-        HAC_HIP(hipStreamSynchronize(x.stream));
-    }
-    return HAC_OK;
-}
-
-// The end of a host search whose shards have left their [nq][k] keys (positions of the whole index) in their ws_keys, streams
-// idle: several devices are merged at k on the first one (ws_lists / ws_out: reserved by the caller), as search merges them;
-// the keys come back through the pinned slab a chunk at a time and the host unpacks them (key_score_host, key_row_host).
-int keys_to_host(DeviceIndex *s0, const uint64_t *final_keys, size_t total, float *D, int64_t *I);
-int shard_keys_to_host(hac_index *idx, int64_t nq, int k, float *D, int64_t *I) {
-    const int S = (int)idx->shards.size();
-    const size_t total = (size_t)nq * k;
-    DeviceIndex *s0 = idx->shards[0];
-    DeviceGuard g0(s0->device);
-    const uint64_t *final_keys = (const uint64_t *)s0->ws_keys.p;
-    if (S > 1) {   // (on shard 0's stream, never the null stream: see search_host)
-        for (int si = 0; si < S; ++si)
-            HAC_HIP(hipMemcpyAsync((char *)idx->ws_lists.p + (size_t)si * total * 8, idx->shards[si]->ws_keys.p, total * 8, hipMemcpyDeviceToDevice, s0->stream));
-        HAC_TRY(hac_merge_keys_device(s0->device, (const uint64_t *)idx->ws_lists.p, S, nq, k, (uint64_t *)idx->ws_out.p, s0->stream));
-        final_keys = (const uint64_t *)idx->ws_out.p;
-    }
-    return keys_to_host(s0, final_keys, total, D, I);
-}
-// `total` keys on s0's device -> (D, I) on the host, through s0's pinned slab a chunk at a time (s0's device is current)
-int keys_to_host(DeviceIndex *s0, const uint64_t *final_keys, size_t total, float *D, int64_t *I) {
-    const size_t chunk = (size_t)8 << 20;
-    char *slab = nullptr;
-    HAC_TRY(pin_slab(*s0, std::min(chunk, total) * 8, slab));
-    for (size_t done = 0; done < total; done += chunk) {
-        const size_t n = std::min(chunk, total - done);
-        HAC_HIP(hipMemcpyAsync(slab, final_keys + done, n * 8, hipMemcpyDeviceToHost, s0->stream));
-        HAC_HIP(hipStreamSynchronize(s0->stream));
-        const u64 *kk = reinterpret_cast<const u64 *>(slab);
-        for (size_t i = 0; i < n; ++i) {
-            D[done + i] = kk[i] ? key_score_host(kk[i]) : -FLT_MAX;
-            I[done + i] = kk[i] ? key_row_host(kk[i]) : -1;
-        }
-    }
-    return HAC_OK;
 }
 
 // ---- removing rows (hac_index_remove_ids).  rem: this shard's removed rows, local numbering, sorted ascending, no duplicates.
@@ -657,299 +525,9 @@ void rewrite_spans_after_remove(std::vector<std::vector<SpanDesc>> &spans, const
         shard.swap(kept);
     }
 }
-
-// ---- search inside a bitmap (masked.inc; DeviceIndex::search_keys_masked)
-int check_masked_args(const char *what, const hac_index *idx, int64_t nq, int k, int64_t n_masks, int64_t words, bool has_mask_of, bool pointers_ok) {
-    if (k < 1 || k > HAC_MAX_K) return fail(HAC_ERR_INVALID, "%s: k=%d out of range [1, %d]", what, k, HAC_MAX_K);
-    if (nq < 0 || !pointers_ok) return fail(HAC_ERR_INVALID, "%s: bad arguments", what);
-    if (nq == 0) return HAC_OK;
-    const int64_t W = (idx->ntotal + 63) / 64;
-    if (words != W)
-        return fail(HAC_ERR_INVALID, "%s: words=%lld, but %lld rows need %lld words per mask (a mask packed before an add or a remove?)", what, (long long)words,
-                    (long long)idx->ntotal, (long long)W);
-    if (n_masks < 1) return fail(HAC_ERR_INVALID, "%s: n_masks=%lld: needs at least one mask", what, (long long)n_masks);
-    if (!has_mask_of && n_masks != 1 && n_masks != nq)
-        return fail(HAC_ERR_INVALID, "%s: mask_of is null with %lld masks for %lld queries: needs n_masks == 1 (one mask for all) or n_masks == nq (mask i for query i)",
-                    what, (long long)n_masks, (long long)nq);
-    return HAC_OK;
-}
-
-// bits [s0, s0 + n) of src -> bits [d0, d0 + n) of dst, up to 64 at a time (dst's other bits stay)
-void copy_bits(const u64 *src, int64_t s0, u64 *dst, int64_t d0, int64_t n) {
-    while (n > 0) {
-        const int so = (int)(s0 & 63), dof = (int)(d0 & 63);
-        const int take = (int)std::min<int64_t>(n, 64 - std::max(so, dof));   // within one word on both sides
-        const u64 field = take == 64 ? ~0ull : ((1ull << take) - 1ull);
-        const u64 v = (src[s0 >> 6] >> so) & field;
-        u64 &dw = dst[d0 >> 6];
-        dw = (dw & ~(field << dof)) | (v << dof);
-        s0 += take;
-        d0 += take;
-        n -= take;
-    }
-}
-
-// One shard's keys of the whole call, [nq][k] in its ws_keys, on its own stream: every query under ITS shard's slice of its
-// mask.  mask_of: checked, one entry per query.  Queries are staged in chunks whose queries, distinct masks and mask_of fit
-// ~64 MiB (at least one query); a chunk uploads only the masks its queries name, renumbered from 0.  With several devices the
-// slice is cut out of the caller's mask span by span (SpanDesc: local0, count, global0) and the positions are then those of
-// the whole index (remap_positions_kernel, as search does).  Returns with the shard's stream idle.
-int masked_shard(hac_index *idx, int si, const float *q, int64_t nq, int k, const u64 *masks, int64_t words, const int64_t *mask_of) {
-    DeviceIndex &x = *idx->shards[si];
-    DeviceGuard g(x.device);
-    if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", x.device);
-    const bool sliced = idx->shards.size() > 1;
-    const int64_t Wl = (x.ntotal + 63) / 64;   // words of a local mask
-    HAC_TRY(x.ws_keys.reserve((size_t)nq * k * 8));
-    if (x.ntotal == 0) {   // a shard without rows: padding only
-        HAC_HIP(hipMemsetAsync(x.ws_keys.p, 0, (size_t)nq * k * 8, x.stream));
-        HAC_HIP(hipStreamSynchronize(x.stream));
-        return HAC_OK;
-    }
-    const size_t q_bytes = (size_t)x.d * 4, m_bytes = (size_t)Wl * 8, budget = (size_t)64 << 20;
-    std::vector<int64_t> slot_of;                 // of the chunk: local mask number -> the caller's mask
-    std::vector<int64_t> local_of;                // of the chunk: per query, its local mask number
-    std::unordered_map<int64_t, int64_t> seen;    // the caller's mask -> local number
-    for (int64_t q0 = 0; q0 < nq;) {
-        slot_of.clear();
-        local_of.clear();
-        seen.clear();
-        int64_t nqc = 0;
-        while (q0 + nqc < nq) {
-            const int64_t mo = mask_of[q0 + nqc];
-            const bool is_new = seen.find(mo) == seen.end();
-            const size_t need = (size_t)(nqc + 1) * (q_bytes + 8) + (slot_of.size() + (is_new ? 1 : 0)) * m_bytes;
-            if (nqc > 0 && need > budget) break;
-            if (is_new) {
-                seen.emplace(mo, (int64_t)slot_of.size());
-                slot_of.push_back(mo);
-            }
-            local_of.push_back(seen[mo]);
-            ++nqc;
-        }
-        const size_t nm = slot_of.size();
-        HAC_TRY(x.ws_q.reserve(nqc * q_bytes));
-        HAC_TRY(x.ws_masks.reserve(nm * m_bytes + (size_t)nqc * 8));
-        char *slab = nullptr;   // queries, masks, mask_of
-        HAC_TRY(pin_slab(x, nqc * q_bytes + nm * m_bytes + (size_t)nqc * 8, slab));
-        std::memcpy(slab, q + (size_t)q0 * x.d, nqc * q_bytes);
-        u64 *hm = reinterpret_cast<u64 *>(slab + nqc * q_bytes);
-        for (size_t s = 0; s < nm; ++s) {
-            const u64 *src = masks + (size_t)slot_of[s] * words;
-            u64 *dst = hm + s * Wl;
-            if (!sliced) {
-                std::memcpy(dst, src, m_bytes);
-            } else {
-                std::memset(dst, 0, m_bytes);
-                for (const SpanDesc &sp : idx->spans[si]) copy_bits(src, (int64_t)sp.global0, dst, (int64_t)sp.local0, (int64_t)sp.count);
-            }
-        }
-        std::memcpy(hm + nm * Wl, local_of.data(), (size_t)nqc * 8);
-        HAC_HIP(hipMemcpyAsync(x.ws_q.p, slab, nqc * q_bytes, hipMemcpyHostToDevice, x.stream));
-        HAC_HIP(hipMemcpyAsync(x.ws_masks.p, hm, nm * m_bytes + (size_t)nqc * 8, hipMemcpyHostToDevice, x.stream));
-        const u64 *md = (const u64 *)x.ws_masks.p;
-        HAC_TRY(x.search_keys_masked((const float *)x.ws_q.p, nqc, k, md, (int64_t)nm, Wl, (const int64_t *)(md + nm * Wl), (u64 *)x.ws_keys.p + (size_t)q0 * k, 0u,
-                                     x.stream));
-        HAC_HIP(hipStreamSynchronize(x.stream));   // (the slab is the next chunk's)
-        q0 += nqc;
-    }
-    if (sliced && !idx->spans[si].empty()) {
-        HAC_TRY(upload_spans(idx, si));
-        const long nk = (long)nq * k;
-        remap_positions_kernel<<<dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, x.stream>>>((u64 *)x.ws_keys.p, nk, (const SpanDesc *)idx->ws_spans[si].p,
-                                                                                             (int)idx->spans[si].size());
-        HAC_HIP(hipGetLastError());
-        HAC_HIP(hipStreamSynchronize(x.stream));
-    }
-    return HAC_OK;
-}
-
-// ---- search by group (grouped.inc; DeviceIndex::search_keys_grouped)
-int check_grouped_args(const char *what, const hac_index *idx, int64_t nq, int k, int64_t n_labels, bool pointers_ok) {
-    if (k < 1 || k > HAC_MAX_K) return fail(HAC_ERR_INVALID, "%s: k=%d out of range [1, %d]", what, k, HAC_MAX_K);
-    if (nq < 0 || !pointers_ok) return fail(HAC_ERR_INVALID, "%s: bad arguments", what);
-    if (nq == 0) return HAC_OK;
-    if (n_labels != idx->ntotal)
-        return fail(HAC_ERR_INVALID, "%s: n_labels=%lld, but the index holds %lld rows: one label per row (labels made before an add or a remove?)", what,
-                    (long long)n_labels, (long long)idx->ntotal);
-    return HAC_OK;
-}
-
-// One shard's keys of the whole call, [nq][k] in its ws_keys, on its own stream: its rows under ITS slice of the labels (checked:
-// all in [0, 2^32)), cut out of the caller's array span by span with several devices; the positions are then those of the whole
-// index (remap_positions_kernel, as search does).  The labels are uploaded once per call, the queries in chunks of ~64 MiB
-// through the pinned slab.  Returns with the shard's stream idle.
-int grouped_shard(hac_index *idx, int si, const float *q, int64_t nq, int k, const int64_t *group_of) {
-    DeviceIndex &x = *idx->shards[si];
-    DeviceGuard g(x.device);
-    if (!g.ok) return fail(HAC_ERR_HIP, "cannot select HIP device %d", x.device);
-    const bool sliced = idx->shards.size() > 1;
-    HAC_TRY(x.ws_keys.reserve((size_t)nq * k * 8));
-    if (x.ntotal == 0) {   // a shard without rows: padding only
-        HAC_HIP(hipMemsetAsync(x.ws_keys.p, 0, (size_t)nq * k * 8, x.stream));
-        HAC_HIP(hipStreamSynchronize(x.stream));
-        return HAC_OK;
-    }
-    HAC_TRY(x.ws_labels.reserve((size_t)x.ntotal * 8));
-    std::vector<int64_t> local;   // (lives until the stream is idle)
-    const int64_t *src = group_of;
-    if (sliced) {
-        local.assign((size_t)x.ntotal, 0);
-        int64_t covered = 0;
-        for (const SpanDesc &sp : idx->spans[si]) {   // the spans tile the shard's rows and lie inside the index's: anything else is a broken table, never a guessed label
-            if ((int64_t)sp.local0 != covered || (int64_t)sp.local0 + sp.count > x.ntotal || (int64_t)sp.global0 + sp.count > idx->ntotal)
-                return fail(HAC_ERR_INTERNAL, "search_grouped: span (local %u, count %u, global %u) of shard %d does not fit its %lld rows", sp.local0, sp.count, sp.global0, si,
-                            (long long)x.ntotal);
-            std::memcpy(local.data() + sp.local0, group_of + sp.global0, (size_t)sp.count * 8);
-            covered += sp.count;
-        }
-        if (covered != x.ntotal) return fail(HAC_ERR_INTERNAL, "search_grouped: the spans of shard %d cover %lld of its %lld rows", si, (long long)covered, (long long)x.ntotal);
-        src = local.data();
-    }
-    HAC_HIP(hipMemcpyAsync(x.ws_labels.p, src, (size_t)x.ntotal * 8, hipMemcpyHostToDevice, x.stream));
-    HAC_HIP(hipStreamSynchronize(x.stream));
-    const size_t q_bytes = (size_t)x.d * 4;
-    const int64_t chunk = std::max<int64_t>(1, (int64_t)(((size_t)64 << 20) / q_bytes));
-    HAC_TRY(x.ws_q.reserve((size_t)std::min(chunk, nq) * q_bytes));
-    for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
-        const int64_t nqc = std::min(chunk, nq - q0);
-        char *slab = nullptr;
-        HAC_TRY(pin_slab(x, (size_t)nqc * q_bytes, slab));
-        std::memcpy(slab, q + (size_t)q0 * x.d, (size_t)nqc * q_bytes);
-        HAC_HIP(hipMemcpyAsync(x.ws_q.p, slab, (size_t)nqc * q_bytes, hipMemcpyHostToDevice, x.stream));
-        HAC_TRY(x.search_keys_grouped((const float *)x.ws_q.p, nqc, k, (const int64_t *)x.ws_labels.p, (u64 *)x.ws_keys.p + (size_t)q0 * k, x.stream));
-        HAC_HIP(hipStreamSynchronize(x.stream));   // (the slab is the next chunk's)
-    }
-    if (sliced && !idx->spans[si].empty()) {
-        HAC_TRY(upload_spans(idx, si));
-        const long nk = (long)nq * k;
-        remap_positions_kernel<<<dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, x.stream>>>((u64 *)x.ws_keys.p, nk, (const SpanDesc *)idx->ws_spans[si].p,
-                                                                                             (int)idx->spans[si].size());
-        HAC_HIP(hipGetLastError());
-        HAC_HIP(hipStreamSynchronize(x.stream));
-    }
-    return HAC_OK;
-}
 }  // namespace
 
 extern "C" {
-
-int hac_index_search_masked_keys_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const uint64_t *masks_dev, int64_t n_masks, int64_t words,
-                                        const int64_t *mask_of_dev, uint64_t *keys_dev, uint32_t pos_base, void *hip_stream) {
-    return on_single_shard(idx, "search_masked_keys_device", [&](DeviceIndex &s) -> int {
-        HAC_TRY(check_masked_args("search_masked_keys_device", idx, nq, k, n_masks, words, mask_of_dev != nullptr, nq <= 0 || (q_dev && keys_dev && (masks_dev || words == 0))));
-        if (nq == 0) return HAC_OK;
-        return s.search_keys_masked(q_dev, nq, k, (const u64 *)masks_dev, n_masks, words, mask_of_dev, (u64 *)keys_dev, pos_base, (hipStream_t)hip_stream);
-    });
-}
-
-int hac_index_search_masked_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const uint64_t *masks_dev, int64_t n_masks, int64_t words,
-                                   const int64_t *mask_of_dev, float *D_dev, int64_t *I_dev, const int64_t *id_map_dev, void *hip_stream) {
-    return on_single_shard(idx, "search_masked_device", [&](DeviceIndex &s) -> int {
-        HAC_TRY(check_masked_args("search_masked_device", idx, nq, k, n_masks, words, mask_of_dev != nullptr, nq <= 0 || (q_dev && D_dev && I_dev && (masks_dev || words == 0))));
-        if (nq == 0) return HAC_OK;
-        HAC_TRY(s.ws_keys.reserve((size_t)nq * k * 8));
-        HAC_TRY(s.search_keys_masked(q_dev, nq, k, (const u64 *)masks_dev, n_masks, words, mask_of_dev, (u64 *)s.ws_keys.p, 0u, (hipStream_t)hip_stream));
-        return hac_keys_to_results_device(s.device, (const uint64_t *)s.ws_keys.p, nq * k, id_map_dev, D_dev, I_dev, hip_stream);
-    });
-}
-
-int hac_index_search_masked(hac_index *idx, const float *q, int64_t nq, int k, const uint64_t *masks, int64_t n_masks, int64_t words, const int64_t *mask_of,
-                            float *D, int64_t *I) {
-    if (!idx) return fail(HAC_ERR_INVALID, "null index");
-    HAC_TRY(check_masked_args("search_masked", idx, nq, k, n_masks, words, mask_of != nullptr, nq <= 0 || (q && D && I && (masks || words == 0))));
-    if (nq == 0) return HAC_OK;
-    const size_t total = (size_t)nq * k;
-    if (idx->ntotal == 0) {   // padding only
-        std::fill(D, D + total, -FLT_MAX);
-        std::fill(I, I + total, (int64_t)-1);
-        return HAC_OK;
-    }
-    std::vector<int64_t> mo((size_t)nq);
-    for (int64_t i = 0; i < nq; ++i) {
-        mo[(size_t)i] = mask_of ? mask_of[i] : (n_masks == 1 ? 0 : i);
-        if (mo[(size_t)i] < 0 || mo[(size_t)i] >= n_masks)
-            return fail(HAC_ERR_INVALID, "search_masked: mask_of[%lld] = %lld of query %lld is outside [0, %lld)", (long long)i, (long long)mo[(size_t)i], (long long)i,
-                        (long long)n_masks);
-    }
-    // Every shard searches its own rows under its own slice of every mask (one host thread each), in the numbering of the whole
-    // index; the slabs are merged at k on the first device, as search merges them.
-    const int S = (int)idx->shards.size();
-    DeviceIndex *s0 = idx->shards[0];
-    if (S > 1) {
-        DeviceGuard g0(s0->device);
-        HAC_TRY(idx->ws_lists.reserve((size_t)S * total * 8));
-        HAC_TRY(idx->ws_out.reserve(total * 8));
-    }
-    HAC_TRY(for_each_shard(idx, [&](int si) { return masked_shard(idx, si, q, nq, k, (const u64 *)masks, words, mo.data()); }));
-    return shard_keys_to_host(idx, nq, k, D, I);
-}
-
-int hac_index_search_grouped_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const int64_t *group_of_dev, int64_t n_labels, float *D_dev,
-                                    int64_t *I_dev, int64_t *G_dev, const int64_t *id_map_dev, void *hip_stream) {
-    return on_single_shard(idx, "search_grouped_device", [&](DeviceIndex &s) -> int {
-        HAC_TRY(check_grouped_args("search_grouped_device", idx, nq, k, n_labels, nq <= 0 || (q_dev && D_dev && I_dev && (group_of_dev || n_labels == 0))));
-        if (nq == 0) return HAC_OK;
-        hipStream_t st = (hipStream_t)hip_stream;
-        HAC_TRY(s.ws_keys.reserve((size_t)nq * k * 8));
-        HAC_TRY(s.search_keys_grouped(q_dev, nq, k, group_of_dev, (u64 *)s.ws_keys.p, st));
-        GroupArgs gr{};
-        gr.group_of = (const long long *)group_of_dev;
-        gr.n_labels = (long)n_labels;
-        const long n = (long)nq * k;
-        grouped_results_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>((const u64 *)s.ws_keys.p, n, (const long long *)id_map_dev, gr, D_dev,
-                                                                                      (long long *)I_dev, (long long *)G_dev);
-        HAC_HIP(hipGetLastError());
-        return HAC_OK;
-    });
-}
-
-int hac_index_search_grouped(hac_index *idx, const float *q, int64_t nq, int k, const int64_t *group_of, int64_t n_labels, float *D, int64_t *I, int64_t *G) {
-    if (!idx) return fail(HAC_ERR_INVALID, "null index");
-    HAC_TRY(check_grouped_args("search_grouped", idx, nq, k, n_labels, nq <= 0 || (q && D && I && (group_of || n_labels == 0))));
-    if (nq == 0) return HAC_OK;
-    for (int64_t r = 0; r < n_labels; ++r)
-        if (group_of[r] < 0 || group_of[r] > 0xFFFFFFFFll)
-            return fail(HAC_ERR_INVALID, "search_grouped: group_of[%lld] = %lld is outside [0, 2^32)", (long long)r, (long long)group_of[r]);
-    const size_t total = (size_t)nq * k;
-    if (idx->ntotal == 0) {   // padding only
-        std::fill(D, D + total, -FLT_MAX);
-        std::fill(I, I + total, (int64_t)-1);
-        if (G) std::fill(G, G + total, (int64_t)-1);
-        return HAC_OK;
-    }
-    // Every shard searches its own rows under its own slice of the labels (one host thread each) and leaves at most k distinct
-    // groups per query, in the numbering of the whole index; the first device then reduces the shards' lists to the best key of
-    // every label under the whole label array (grouped_select_kernel: a group may have rows on several shards).
-    const int S = (int)idx->shards.size();
-    DeviceIndex *s0 = idx->shards[0];
-    if (S > 1) {
-        DeviceGuard g0(s0->device);
-        HAC_TRY(idx->ws_lists.reserve((size_t)S * total * 8));
-        HAC_TRY(idx->ws_out.reserve(total * 8));
-        HAC_TRY(idx->ws_glabels.reserve((size_t)n_labels * 8));
-    }
-    HAC_TRY(for_each_shard(idx, [&](int si) { return grouped_shard(idx, si, q, nq, k, group_of); }));
-    DeviceGuard g0(s0->device);
-    const uint64_t *final_keys = (const uint64_t *)s0->ws_keys.p;
-    if (S > 1) {   // (on shard 0's stream, never the null stream: see search_host)
-        for (int si = 0; si < S; ++si)
-            HAC_HIP(hipMemcpyAsync((char *)idx->ws_lists.p + (size_t)si * total * 8, idx->shards[si]->ws_keys.p, total * 8, hipMemcpyDeviceToDevice, s0->stream));
-        HAC_HIP(hipMemcpyAsync(idx->ws_glabels.p, group_of, (size_t)n_labels * 8, hipMemcpyHostToDevice, s0->stream));
-        GroupArgs gr{};
-        gr.group_of = (const long long *)idx->ws_glabels.p;
-        gr.n_labels = (long)n_labels;
-        const int Cm = DeviceIndex::grouped_select_cm(k);
-        grouped_select_kernel<<<dim3((unsigned)nq), dim3(256), (size_t)Cm * 16, s0->stream>>>((const u64 *)idx->ws_lists.p, S, total, (size_t)k, nullptr, 0u, k, Cm, gr,
-                                                                                            (u64 *)idx->ws_out.p);
-        HAC_HIP(hipGetLastError());
-        final_keys = (const uint64_t *)idx->ws_out.p;
-    }
-    HAC_TRY(keys_to_host(s0, final_keys, total, D, I));
-    if (G)
-        for (size_t i = 0; i < total; ++i) G[i] = I[i] >= 0 ? group_of[I[i]] : (int64_t)-1;
-    return HAC_OK;
-}
 
 int hac_index_remove_ids(hac_index *idx, const int64_t *ids, int64_t n, int64_t *n_removed) {
     if (n_removed) *n_removed = 0;
@@ -1086,62 +664,6 @@ int hac_index_rank_ids(hac_index *idx, const float *q, int64_t nq, const int64_t
         rank[i] = sum;
     }
     return HAC_OK;
-}
-
-int hac_index_search_among_keys_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const int64_t *cand_dev, int64_t m, uint64_t *keys_dev,
-                                       uint32_t pos_base, void *hip_stream) {
-    return on_single_shard(idx, "search_among_keys_device", [&](DeviceIndex &s) -> int {
-        HAC_TRY(check_among_size("search_among_keys_device", k, m));
-        if (nq < 0 || (nq > 0 && (!q_dev || !keys_dev || (m > 0 && !cand_dev)))) return fail(HAC_ERR_INVALID, "search_among_keys_device: bad arguments");
-        if (nq == 0) return HAC_OK;
-        return among_keys_device(s, "search_among_keys_device", q_dev, nq, k, cand_dev, m, (u64 *)keys_dev, pos_base, (hipStream_t)hip_stream);
-    });
-}
-
-int hac_index_search_among_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const int64_t *cand_dev, int64_t m, float *D_dev, int64_t *I_dev,
-                                  const int64_t *id_map_dev, void *hip_stream) {
-    return on_single_shard(idx, "search_among_device", [&](DeviceIndex &s) -> int {
-        HAC_TRY(check_among_size("search_among_device", k, m));
-        if (nq < 0 || (nq > 0 && (!q_dev || !D_dev || !I_dev || (m > 0 && !cand_dev)))) return fail(HAC_ERR_INVALID, "search_among_device: bad arguments");
-        if (nq == 0) return HAC_OK;
-        HAC_TRY(s.ws_keys.reserve((size_t)nq * k * 8));
-        HAC_TRY(among_keys_device(s, "search_among_device", q_dev, nq, k, cand_dev, m, (u64 *)s.ws_keys.p, 0u, (hipStream_t)hip_stream));
-        return hac_keys_to_results_device(s.device, (const uint64_t *)s.ws_keys.p, nq * k, id_map_dev, D_dev, I_dev, hip_stream);
-    });
-}
-
-int hac_index_search_among(hac_index *idx, const float *q, int64_t nq, int k, const int64_t *cand, int64_t m, float *D, int64_t *I) {
-    if (!idx) return fail(HAC_ERR_INVALID, "null index");
-    HAC_TRY(check_among_size("search_among", k, m));
-    if (nq < 0 || (nq > 0 && (!q || !D || !I || (m > 0 && !cand)))) return fail(HAC_ERR_INVALID, "search_among: bad arguments");
-    if (nq == 0) return HAC_OK;
-    const size_t total = (size_t)nq * k;
-    if (m == 0) {   // lists of padding only
-        std::fill(D, D + total, -FLT_MAX);
-        std::fill(I, I + total, (int64_t)-1);
-        return HAC_OK;
-    }
-    HAC_TRY(check_host_ids("search_among", cand, nq, m, idx->ntotal, IdPlace::QUERY_COLUMN, "padding"));
-    // Every shard selects among the candidates it holds (one host thread each; a row lives in one shard, so no repeat crosses
-    // shards), in the numbering of the whole index; the slabs are merged at k on the first device, as search merges them.
-    const int S = (int)idx->shards.size();
-    DeviceIndex *s0 = idx->shards[0];
-    if (S == 1) {
-        HAC_TRY(among_shard(idx, 0, q, nq, k, cand, m));
-    } else {
-        const RowLocator loc(idx);
-        const std::vector<int32_t> at = loc.locate(cand, (size_t)(nq * m));
-        std::vector<std::vector<int64_t>> local(S, std::vector<int64_t>(at.size(), -1));
-        for (size_t i = 0; i < at.size(); ++i)
-            if (at[i] >= 0) local[loc.shard(at[i])][i] = loc.local(at[i], cand[i]);
-        {
-            DeviceGuard g0(s0->device);
-            HAC_TRY(idx->ws_lists.reserve((size_t)S * total * 8));
-            HAC_TRY(idx->ws_out.reserve(total * 8));
-        }
-        HAC_TRY(for_each_shard(idx, [&](int si) { return among_shard(idx, si, q, nq, k, local[si].data(), m); }));
-    }
-    return shard_keys_to_host(idx, nq, k, D, I);
 }
 
 int hac_index_range_search_device(hac_index *idx, const float *q_dev, int64_t nq, const float *radius_dev, int64_t cap, int64_t *lims_dev, float *D_dev,

@@ -517,3 +517,24 @@ def test_resident_corpus_distinct_passages(oracle):
     D, I = rc.search_distinct(q, k)
     grouped_ref.assert_same((D.astype(np.float32), I), (wD, pids[left][wI], None), "after remove")
     rc.index.check_status()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 12. the host form across its staging chunks: the queries go 64 MiB // 4d at a time through the pinned slab.  d = 1024 (the
+# widest row: the fewest queries per chunk), 200 hostile rows on two shards of one device, so the slice of the labels and the
+# remap take part; the case and its scores are those of tests/test_index_masked_gpu.py's section 13.
+@pytest.mark.parametrize("past", [0, 1])
+def test_host_form_across_a_query_chunk(past, oracle):
+    from tests.test_index_masked_gpu import SEAM_BYTES, SEAM_D, SEAM_K, SEAM_N, SEAM_NQ, seam_case
+    x, q, S = seam_case(oracle)
+    chunk = SEAM_BYTES // (4 * SEAM_D)
+    assert chunk == 16384 and chunk + 1 == SEAM_NQ
+    nq = chunk + past
+    labels = (np.arange(SEAM_N, dtype=np.int64) * 7) % 23                  # every group has rows on both shards
+    want = grouped_ref.grouped_from_scores(S[:nq], labels, SEAM_K)
+    assert (want[1][4:] >= 0).all()
+    idx = _index(SEAM_D, x, devices=(0, 0))
+    grouped_ref.assert_same(idx.search_grouped(q[:nq], SEAM_K, labels, return_groups=True), want, f"{nq} queries, chunks of {chunk}")
+    plan = parse_plan(idx.last_plan())
+    assert (plan["QT"] == 1) == (past == 1), plan                          # the last chunk held one query, or a full tile's
+    idx.check_status()

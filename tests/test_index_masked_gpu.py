@@ -537,3 +537,74 @@ def test_two_identical_calls_return_identical_bytes():
     from haconvdr_amd.index import pack_mask
     assert torch.equal(pack_mask(torch.from_numpy(masks).cuda()).cpu(), torch.from_numpy(pack_mask(masks)))
     idx.check_status()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 13. the host form across its staging chunks.  The sizes follow from the host code: a chunk's queries (4d bytes and 8 of
+# mask_of each) and the distinct masks they name (8 * ceil(shard rows / 64) bytes each) fit 64 MiB, and a chunk uploads only
+# the masks it names, renumbered from 0.  d = 1024 (the widest row: the fewest queries per chunk), 200 hostile rows on two
+# shards of one device, so the slice of every mask and the remap take part.
+SEAM_BYTES, SEAM_D, SEAM_N, SEAM_NQ, SEAM_K = 64 << 20, 1024, 200, 16385, 5
+_SEAM = {}
+
+
+def seam_case(oracle):
+    """(x [200, 1024] hostile, q [16385, 1024], their canonical scores): computed once, shared by the chunk-seam cases of
+    search_masked and search_grouped, never changed"""
+    if not _SEAM:
+        x = hostile_corpus(0xAE0, SEAM_N, SEAM_D)
+        q = hostile_queries(0xAE1, SEAM_NQ, SEAM_D)
+        with np.errstate(all="ignore"):
+            S = rank_ref.canon_scores(oracle, x, q)
+        for a in (x, q, S):
+            a.setflags(write=False)
+        _SEAM["case"] = (x, q, S)
+    return _SEAM["case"]
+
+
+def shard_rows(n, shards):
+    """the rows of every shard of _index(d, x, devices=(0,) * shards): each of the three adds is dealt in contiguous pieces"""
+    from tests.test_search_plans_gpu import _cuts
+    c1, c2 = _cuts(n)
+    return [sum(m // shards + (s < m % shards) for m in (c1, c2 - c1, n - c2)) for s in range(shards)]
+
+
+def _seam_mask_bytes():
+    words = {-(-rows // 64) for rows in shard_rows(SEAM_N, 2)}
+    assert len(words) == 1                                                 # both shards cut their chunks at the same query
+    return 8 * words.pop()
+
+
+@pytest.mark.parametrize("past", [0, 1])
+def test_host_form_across_a_chunk_of_shared_masks(past, oracle):
+    x, q, S = seam_case(oracle)
+    m_bytes = _seam_mask_bytes()
+    cut = (SEAM_BYTES - 3 * m_bytes) // (4 * SEAM_D + 8)                   # the largest n with n * (4d + 8) + 3 * m_bytes <= 64 MiB
+    assert cut * (4 * SEAM_D + 8) + 3 * m_bytes <= SEAM_BYTES < (cut + 1) * (4 * SEAM_D + 8) + 3 * m_bytes and cut + 1 <= SEAM_NQ
+    nq = cut + past
+    r = np.arange(SEAM_N)
+    masks = np.stack([r % 3 == 0, r % 3 == 1, r % 3 == 2])               # pairwise disjoint: an answer from the wrong mask shares no row
+    mask_of = (np.arange(nq) % 2).astype(np.int64)
+    mask_of[cut:] = 2                                                      # the second chunk names mask 2 alone: its local mask 0
+    want = masked_ref.masked_from_scores(S[:nq], masks, mask_of, SEAM_K)
+    assert (want[1][4:, 0] >= 0).all() and all((want[1][i][want[1][i] >= 0] % 3 == mask_of[i]).all() for i in (1, 2, cut - 1, nq - 1))
+    idx = _index(SEAM_D, x, devices=(0, 0))
+    masked_ref.assert_same(idx.search_masked(q[:nq], SEAM_K, masks, mask_of), want, f"{nq} queries, the cut at {cut}")
+    plan = parse_plan(idx.last_plan())
+    assert (plan["QT"] == 1) == (past == 1), plan                          # the last chunk held one query, or a full tile's
+    idx.check_status()
+
+
+def test_host_form_across_a_chunk_of_a_mask_per_query(oracle):
+    x, q, S = seam_case(oracle)
+    m_bytes = _seam_mask_bytes()
+    cut = SEAM_BYTES // (4 * SEAM_D + 8 + m_bytes)                         # every query brings a new mask
+    nq = cut + 1
+    assert nq <= SEAM_NQ
+    masks = masked_cases.random_masks(0xAE2, nq, SEAM_N, 2)
+    want = masked_ref.masked_from_scores(S[:nq], masks, None, SEAM_K)
+    assert (want[1][4:, 0] >= 0).all()
+    idx = _index(SEAM_D, x, devices=(0, 0))
+    masked_ref.assert_same(idx.search_masked(q[:nq], SEAM_K, masks), want, f"{nq} queries and masks, the cut at {cut}")
+    assert parse_plan(idx.last_plan())["QT"] == 1
+    idx.check_status()
