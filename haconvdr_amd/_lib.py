@@ -13,6 +13,7 @@ _LIB = None
 
 HAC_MAX_K = 2048
 HAC_MAX_AMONG = 4096   # include/haconvdr.h: candidates per query of search_among
+HAC_AFTER_START = -2   # include/haconvdr.h: the cursor row of search_after that starts a query from the start
 HAC_ERR_INVALID = 1    # include/haconvdr.h: a bad argument
 HAC_ERR_UNSUPPORTED = 4
 HAC_ERR_INTERNAL = 5   # include/haconvdr.h: the device detected a broken invariant of the library (never a hang, never wrong bits)
@@ -61,6 +62,9 @@ def _declare(L):
     L.hac_index_search_masked_keys_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, i64, i64, vp, vp, ctypes.c_uint32, vp]
     L.hac_index_search_grouped.argtypes = [vp, c_f32p, i64, ctypes.c_int, ctypes.POINTER(i64), i64, c_f32p, ctypes.POINTER(i64), ctypes.POINTER(i64)]
     L.hac_index_search_grouped_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, i64, vp, vp, vp, vp, vp]
+    L.hac_index_search_after.argtypes = [vp, c_f32p, i64, ctypes.c_int, c_f32p, ctypes.POINTER(i64), c_f32p, ctypes.POINTER(i64)]
+    L.hac_index_search_after_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, vp, vp, vp, vp, vp]
+    L.hac_index_search_after_keys_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, vp, ctypes.c_uint32, vp]
     L.hac_index_ntotal.argtypes = [vp]
     L.hac_index_ntotal.restype = i64
     L.hac_index_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p]
@@ -105,7 +109,8 @@ def _declare(L):
                  "hac_index_range_search", "hac_index_range_search_device", "hac_index_remove_ids",
                  "hac_index_search_among", "hac_index_search_among_device", "hac_index_search_among_keys_device",
                  "hac_index_search_masked", "hac_index_search_masked_device", "hac_index_search_masked_keys_device",
-                 "hac_index_search_grouped", "hac_index_search_grouped_device"):
+                 "hac_index_search_grouped", "hac_index_search_grouped_device",
+                 "hac_index_search_after", "hac_index_search_after_device", "hac_index_search_after_keys_device"):
         getattr(L, name).restype = ctypes.c_int
 
 
@@ -122,6 +127,7 @@ EXPORTED_SYMBOLS = (
     "hac_index_search_among", "hac_index_search_among_device", "hac_index_search_among_keys_device",
     "hac_index_search_masked", "hac_index_search_masked_device", "hac_index_search_masked_keys_device",
     "hac_index_search_grouped", "hac_index_search_grouped_device",
+    "hac_index_search_after", "hac_index_search_after_device", "hac_index_search_after_keys_device",
     "hac_encoder_create", "hac_encoder_destroy", "hac_encoder_set_weight", "hac_encoder_finalize", "hac_encoder_forward",
     "hac_encoder_forward_device", "hac_encoder_set_option", "hac_encoder_last_plan", "hac_encoder_set_profiling", "hac_encoder_profile_drain",
     "hac_encoder_profile_drain_class", "hac_encoder_last_clock", "hac_encoder_attention_redo", "hac_encoder_layer_state",

@@ -1142,6 +1142,7 @@ u32 next_pow2(u32 v) {
 #include "among.inc"
 #include "masked.inc"
 #include "grouped.inc"
+#include "after.inc"
 
 // Every instantiation of the two templated scan kernels, once: init raises each one's dynamic-LDS limit from these tables and
 // the launches look their kernel up in them, so an instantiation that is launched is one whose limit was raised.
@@ -1199,6 +1200,8 @@ struct DeviceIndex {
         int grouped_p = 0;               // search_grouped: row streams per query tile; 0 = by the resident workgroups (tests pin 1: one workgroup walks every compaction)
         int debug_grouped_tiles = 0;     // tests: search_grouped's query tiles per launch (0 = by QUERY_CHUNK), so that a small call spans several launches
         int debug_masked_tiles = 0;      // tests: search_masked's query tiles per launch (0 = by the list workspace), so that a small call spans several launches
+        int after_p = 0;                 // search_after: row streams per query tile; 0 = as make_plan sizes scan16's (tests pin 1: one workgroup walks every group)
+        int debug_after_tiles = 0;       // tests: search_after's query tiles per launch (0 = by QUERY_CHUNK), so that a small call spans several launches
     } tune;
     // Passes of the prefilter's main scan (search_keys_split) and where they end (row groups, whole rounds).  A refresh costs a
     // kernel tail + a selection (~0.1 ms): only scans of a few milliseconds are cut, and only with seeded thresholds (the refresh
@@ -1318,6 +1321,13 @@ struct DeviceIndex {
         } else if (n == "debug_masked_tiles") {
             if (!parse_int(v, 0, 65535, t)) return fail(HAC_ERR_INVALID, "index option debug_masked_tiles = '%s': an integer 0..65535", v.c_str());
             tune.debug_masked_tiles = (int)t;
+        } else if (n == "after_p") {
+            if (v == "auto") t = 0;
+            else if (!parse_int(v, 1, 4096, t)) return fail(HAC_ERR_INVALID, "index option after_p = '%s': auto | an integer 1..4096", v.c_str());
+            tune.after_p = (int)t;
+        } else if (n == "debug_after_tiles") {
+            if (!parse_int(v, 0, 65535, t)) return fail(HAC_ERR_INVALID, "index option debug_after_tiles = '%s': an integer 0..65535", v.c_str());
+            tune.debug_after_tiles = (int)t;
         } else if (n == "seed_groups_max") {
             if (!parse_int(v, 0, LONG_MAX, t)) return fail(HAC_ERR_INVALID, "index option seed_groups_max = '%s': an integer >= 0 (0 = 14 sqrt(groups))", v.c_str());
             tune.seed_groups_max = t <= 0 ? 0 : (int)std::max<long>(768, std::min<long>(t, 1 << 30));
@@ -1416,6 +1426,7 @@ struct DeviceIndex {
             // (DYNAMIC LDS: without it a large k, whose candidate buffers pass the default 64 KiB, fails to launch)
             HAC_HIP(hipFuncSetAttribute((const void *)scan16_masked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             HAC_HIP(hipFuncSetAttribute((const void *)scan16_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
+            HAC_HIP(hipFuncSetAttribute((const void *)scan16_after_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             HAC_HIP(hipFuncSetAttribute((const void *)grouped_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, grouped_select_cm(HAC_MAX_K) * 16));   // (beside its static words)
             attr_done[device] = true;
         }
@@ -1438,7 +1449,7 @@ struct DeviceIndex {
         for (PinBuf *b : {&h_pin, &h_fb, &h_stage[0], &h_stage[1]}) b->release();
         for (GrowBuf *b : {&ws_partial, &ws_pcnt, &ws_seedkeys, &ws_thr, &ws_thrglob, &ws_q, &ws_qt, &ws_keys, &ws_D, &ws_I, &ws_stage[0],
                            &ws_stage[1], &ws_err, &ws_norm, &ws_qsplit, &ws_delta, &ws_cand, &ws_akeys, &ws_fail, &ws_stat, &ws_fbidx[0], &ws_fbidx[1],
-                           &ws_fbq[0], &ws_fbq[1], &ws_fbkeys[0], &ws_fbkeys[1], &ws_ids, &ws_rank, &ws_range, &ws_among, &ws_mgroups, &ws_mcnt, &ws_masks, &ws_labels})
+                           &ws_fbq[0], &ws_fbq[1], &ws_fbkeys[0], &ws_fbkeys[1], &ws_ids, &ws_rank, &ws_range, &ws_among, &ws_mgroups, &ws_mcnt, &ws_masks, &ws_labels, &ws_after})
             b->release();
         if (h_err) (void)hipHostFree(h_err);
         if (h_plan) (void)hipHostFree(h_plan);
@@ -1859,6 +1870,7 @@ struct DeviceIndex {
     GrowBuf ws_mgroups, ws_mcnt;   // search inside a bitmap (search_keys_masked): one launch's group lists u32 [tiles][G], the call's counters u32 [tiles]
     GrowBuf ws_masks;          // its host form (search_host.inc: masked_shard): a chunk's masks and mask_of
     GrowBuf ws_labels;         // search by group, host form (search_host.inc: grouped_shard): the shard's slice of the labels
+    GrowBuf ws_after;          // search behind a cursor (search_host.inc): the bounds u64 [queries] of a (score, row) call, or of a host chunk
 
     char last_plan[320] = "none";
     // a device-decided prefilter search leaves its fallback count and err / bound on the device: plan() completes the text
@@ -2189,6 +2201,54 @@ struct DeviceIndex {
             HAC_TRY(reset_topk_scan((size_t)n, (size_t)tiles * QT, st));
             HAC_TRY(prof_begin(st));
             scan16_masked_kernel<<<dim3((unsigned)pl.P, (unsigned)tiles), dim3(SCAN_WAVES * 64), pl.lds_scan, st>>>(a, m);
+            HAC_HIP(hipGetLastError());
+            HAC_TRY(prof_end(st));
+            select_keys_kernel<<<dim3((unsigned)n), dim3(256), (size_t)np2 * 8, st>>>((const u64 *)ws_partial.p, (size_t)pl.P * k, (const u32 *)ws_pcnt.p,
+                                                                                      (u32)((size_t)pl.P * k), k, np2, keys_out + (size_t)off * k, nullptr, nullptr, (int)n,
+                                                                                      (u32)(pl.P * tiles), (u32)QT, thrglob(), (u32 *)ws_err.p);
+            HAC_HIP(hipGetLastError());
+            return HAC_OK;
+        });
+    }
+
+    // ---- search behind a cursor (after.inc).  keys_out: device u64 [nq][k]; bounds_dev u64 [nq] on the device, each query's
+    // exclusive upper key bound in the position space of pos_base (null: every query starts from the start); arguments checked
+    // by the entry points.
+    // A kind-0 plan at any nq (QT and C by make_plan's scan16 arithmetic) over every group, NO threshold seeding (thr_init stays
+    // null: a sample of rows gives bounds the rows behind the cursor may not meet), then the existing select_keys_kernel.  The
+    // queries go in launches of whole tiles, at most QUERY_CHUNK queries each; the survivors and the thresholds are one launch's
+    // and are reused by the next, in stream order.  Every workspace is a GrowBuf sized by (nq, k) and the rows alone: after one
+    // call of the largest shape a call allocates nothing and can be captured.
+    int search_keys_after(const float *q_dev, int64_t nq, int k, const u64 *bounds_dev, u64 *keys_out, u32 pos_base, hipStream_t st) {
+        if (nq == 0) return HAC_OK;
+        HAC_TRY(check_search_args(q_dev, pos_base));
+        if (ntotal == 0) {
+            HAC_HIP(hipMemsetAsync(keys_out, 0, (size_t)nq * k * 8, st));
+            return HAC_OK;
+        }
+        HAC_TRY(upload_segs(st));
+        const u32 G = (u32)((ntotal + GROUP_ROWS - 1) / GROUP_ROWS);
+        Plan pl0, pl;
+        HAC_TRY(make_plan(nq, k, G, pl0, true));
+        const int QT = pl0.QT;
+        const TileLaunches tl(pl0, QUERY_CHUNK / QT, tune.debug_after_tiles);
+        const int64_t TL = tl.TL, QL = tl.QL, launches = tl.launches;
+        // P for the tiles of one launch (at most 4 resident workgroups per CU, as scan16: the same shape); QT and C as above
+        HAC_TRY(make_plan(std::min(nq, QL), k, G, pl, true, tune.after_p));
+        HAC_TRY(ws_partial.reserve((size_t)std::min(nq, QL) * pl.P * k * 8));
+        HAC_TRY(ws_pcnt.reserve((size_t)std::min(nq, QL) * 4));
+        HAC_TRY(ws_thrglob.reserve(((size_t)TL * QT + THR_CTL_WORDS) * 4));
+        snprintf(last_plan, sizeof last_plan, "scan16_after_kernel<W=%d> grid=(%d,%lld) QT=%d C=%d lds=%zu launches=%lld", SCAN_WAVES, pl.P, (long long)TL, QT, pl.C,
+                 pl.lds_scan, (long long)launches);
+        plan_text_slot = -1;
+        const int np2 = (int)next_pow2((u32)k);
+        return tl.each(nq, [&](int64_t, int64_t off, int64_t n, int64_t tiles) -> int {
+            ScanArgs a = topk_scan_args(q_dev + (size_t)off * d, n, k, pl, pos_base);
+            a.g_step = 1;
+            a.n_items = G;
+            HAC_TRY(reset_topk_scan((size_t)n, (size_t)tiles * QT, st));
+            HAC_TRY(prof_begin(st));
+            scan16_after_kernel<<<dim3((unsigned)pl.P, (unsigned)tiles), dim3(SCAN_WAVES * 64), pl.lds_scan, st>>>(a, bounds_dev ? bounds_dev + off : nullptr);
             HAC_HIP(hipGetLastError());
             HAC_TRY(prof_end(st));
             select_keys_kernel<<<dim3((unsigned)n), dim3(256), (size_t)np2 * 8, st>>>((const u64 *)ws_partial.p, (size_t)pl.P * k, (const u32 *)ws_pcnt.p,

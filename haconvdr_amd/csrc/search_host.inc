@@ -1,6 +1,6 @@
 // The searches that return top-k keys (hac_index_search*, hac_index_search_excluding*, hac_index_search_among*,
-// hac_index_search_masked*, hac_index_search_grouped*): everything between the C ABI and DeviceIndex::search_keys /
-// search_keys_masked / search_keys_grouped and the kernels of among.inc.  Included by flat_ip.hip behind rows_host.inc (whose
+// hac_index_search_masked*, hac_index_search_grouped*, hac_index_search_after*): everything between the C ABI and
+// DeviceIndex::search_keys / search_keys_masked / search_keys_grouped / search_keys_after and the kernels of among.inc.  Included by flat_ip.hip behind rows_host.inc (whose
 // pin_slab, check_host_ids, RowLocator and key_*_host it uses).  Every host form is built from the same plain pieces, each of
 // which exists once: a shard's frame around its staging (shard_keys), the chunked query upload (for_query_chunks), the remap to
 // positions of the whole index (remap_keys), the gather and merge on shard 0 (reserve_merge_ws, gather_shard_keys,
@@ -392,6 +392,38 @@ int grouped_shard(hac_index *idx, int si, const float *q, int64_t nq, int k, con
         });
     });
 }
+
+// ---- search behind a cursor (after.inc; DeviceIndex::search_keys_after)
+int check_after_args(const char *what, int64_t nq, int k, bool pointers_ok) {
+    if (k < 1 || k > HAC_MAX_K) return fail(HAC_ERR_INVALID, "%s: k=%d out of range [1, %d]", what, k, HAC_MAX_K);
+    if (nq < 0 || !pointers_ok) return fail(HAC_ERR_INVALID, "%s: bad arguments", what);
+    return HAC_OK;
+}
+
+// The bound of a cursor (s, r) whose score is not NaN, r >= -1 a row in the numbering of the rows searched: the key of
+// (s, r), computed in 64 bits -- r == -1 (a shard with no row at or before the cursor's) gives (ord + 1) << 32, below which
+// every row tying s lies; r at or above 2^32 - 1 packs as 2^32 - 1.  after_bounds_kernel's rule, on the host.
+u64 cursor_bound_host(float s, int64_t r) {
+    s = s + 0.0f;
+    u32 b;
+    std::memcpy(&b, &s, 4);
+    const u32 ord = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return ((u64)ord << 32) + (u64)(0xFFFFFFFFll - std::min<int64_t>(r, 0xFFFFFFFFll));
+}
+
+// The host form on one shard (shard_keys): every query under ITS shard's bound.  The queries go in chunks of ~64 MiB, each
+// chunk's bounds behind its queries in the slab.
+int after_shard(hac_index *idx, int si, const float *q, int64_t nq, int k, const u64 *bounds) {
+    return shard_keys(idx, si, nq, k, [&](DeviceIndex &x) -> int {
+        const int64_t QC = std::max<int64_t>(1, (int64_t)(((size_t)64 << 20) / ((size_t)x.d * 4 + 8)));
+        HAC_TRY(x.ws_after.reserve((size_t)std::min(QC, nq) * 8));
+        return for_query_chunks(x, q, nq, QC, 8, [&](int64_t q0, int64_t nqc, char *slab) -> int {
+            std::memcpy(slab, bounds + q0, (size_t)nqc * 8);
+            HAC_HIP(hipMemcpyAsync(x.ws_after.p, slab, (size_t)nqc * 8, hipMemcpyHostToDevice, x.stream));
+            return x.search_keys_after((const float *)x.ws_q.p, nqc, k, (const u64 *)x.ws_after.p, (u64 *)x.ws_keys.p + (size_t)q0 * k, 0u, x.stream);
+        });
+    });
+}
 }  // namespace
 
 extern "C" {
@@ -594,6 +626,86 @@ int hac_index_search_grouped(hac_index *idx, const float *q, int64_t nq, int k, 
     if (G)
         for (size_t i = 0; i < total; ++i) G[i] = I[i] >= 0 ? group_of[I[i]] : (int64_t)-1;
     return HAC_OK;
+}
+
+int hac_index_search_after_keys_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const uint64_t *after_keys_dev, uint64_t *keys_dev, uint32_t pos_base,
+                                       void *hip_stream) {
+    return on_single_shard(idx, "search_after_keys_device", [&](DeviceIndex &s) -> int {
+        HAC_TRY(check_after_args("search_after_keys_device", nq, k, nq <= 0 || (q_dev && keys_dev)));
+        if (nq == 0) return HAC_OK;
+        return s.search_keys_after(q_dev, nq, k, (const u64 *)after_keys_dev, (u64 *)keys_dev, pos_base, (hipStream_t)hip_stream);
+    });
+}
+
+int hac_index_search_after_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const float *after_score_dev, const int64_t *after_row_dev, float *D_dev,
+                                  int64_t *I_dev, const int64_t *id_map_dev, void *hip_stream) {
+    return on_single_shard(idx, "search_after_device", [&](DeviceIndex &s) -> int {
+        HAC_TRY(check_after_args("search_after_device", nq, k, nq <= 0 || (q_dev && D_dev && I_dev)));
+        if ((after_score_dev == nullptr) != (after_row_dev == nullptr))
+            return fail(HAC_ERR_INVALID, "search_after_device: after_score and after_row go together: both given, or both null (every query from the start)");
+        if (nq == 0) return HAC_OK;
+        hipStream_t st = (hipStream_t)hip_stream;
+        const u64 *bounds = nullptr;
+        if (after_row_dev) {
+            HAC_TRY(s.ws_after.reserve((size_t)nq * 8));
+            after_bounds_kernel<<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st>>>(after_score_dev, (const long long *)after_row_dev, (long)nq, (u64 *)s.ws_after.p);
+            HAC_HIP(hipGetLastError());
+            bounds = (const u64 *)s.ws_after.p;
+        }
+        return keys_then_results(s, nq, k, id_map_dev, D_dev, I_dev, hip_stream,
+                                 [&](u64 *keys) { return s.search_keys_after(q_dev, nq, k, bounds, keys, 0u, st); });
+    });
+}
+
+int hac_index_search_after(hac_index *idx, const float *q, int64_t nq, int k, const float *after_score, const int64_t *after_row, float *D, int64_t *I) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    HAC_TRY(check_after_args("search_after", nq, k, nq <= 0 || (q && D && I)));
+    if ((after_score == nullptr) != (after_row == nullptr))
+        return fail(HAC_ERR_INVALID, "search_after: after_score and after_row go together: both given, or both null (every query from the start)");
+    if (nq == 0) return HAC_OK;
+    if (after_row)
+        for (int64_t i = 0; i < nq; ++i)
+            if (after_row[i] < HAC_AFTER_START)
+                return fail(HAC_ERR_INVALID, "search_after: after_row[%lld] = %lld of query %lld is below %d (a row, -1 = an exhausted list, %d = the start)", (long long)i,
+                            (long long)after_row[i], (long long)i, HAC_AFTER_START, HAC_AFTER_START);
+    if (idx->ntotal == 0) {
+        fill_padding((size_t)nq * k, D, I);
+        return HAC_OK;
+    }
+    // Every shard searches its own rows behind its own bound (one host thread each).  The cursor is in the numbering of the
+    // whole index: a shard's bound names its last row at or before the cursor's row, b_local = (its rows at global positions
+    // <= b) - 1 -- a shard's local order is the global order, so its rows tying s_ref behind b are exactly its rows behind
+    // b_local; -1 makes every tying row of the shard eligible (cursor_bound_host).  The slabs are remapped and merged at k on the
+    // first device, as search merges them.
+    const int S = (int)idx->shards.size();
+    std::vector<std::vector<u64>> bounds(S, std::vector<u64>((size_t)nq, ~0ull));
+    if (after_row) {
+        const RowLocator loc(idx);   // (one device: no spans, never asked)
+        std::vector<int32_t> at;
+        if (S > 1) {   // the span of every cursor row the index holds
+            std::vector<int64_t> inside((size_t)nq);
+            for (int64_t i = 0; i < nq; ++i) inside[(size_t)i] = after_row[i] < idx->ntotal ? std::max<int64_t>(after_row[i], -1) : -1;
+            at = loc.locate(inside.data(), (size_t)nq);
+        }
+        for (int64_t i = 0; i < nq; ++i) {
+            const int64_t b = after_row[i];
+            const float s = after_score[i];
+            if (b == HAC_AFTER_START) continue;
+            for (int si = 0; si < S; ++si) {
+                int64_t r = b;
+                if (S > 1 && b >= idx->ntotal) r = idx->shards[si]->ntotal - 1;   // every row of the shard lies before b
+                else if (S > 1 && b >= 0) {
+                    const int32_t a = at[(size_t)i];
+                    if (a < 0) return fail(HAC_ERR_INTERNAL, "search_after: no span holds row %lld of %lld", (long long)b, (long long)idx->ntotal);
+                    r = loc.rows_below(a, b, si) - (loc.shard(a) == si ? 0 : 1);
+                }
+                bounds[si][(size_t)i] = (b < 0 || s != s) ? 0ull : cursor_bound_host(s, r);
+            }
+        }
+    }
+    if (S > 1) HAC_TRY(reserve_merge_ws(idx, (size_t)nq * k));
+    HAC_TRY(for_each_shard(idx, [&](int si) { return after_shard(idx, si, q, nq, k, bounds[si].data()); }));
+    return shard_keys_to_host(idx, nq, k, D, I);
 }
 
 }  // extern "C"

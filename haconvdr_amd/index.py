@@ -431,6 +431,132 @@ def _grouped_args_tensor(q, k, group_of, id_map, d, ntotal, what="search_grouped
     return q, k, group_of.contiguous(), id_map
 
 
+# ---- cursors of search_after (include/haconvdr.h, "search behind a cursor"): a (score, row) pair per query, or a packed key
+AFTER_START = _lib.HAC_AFTER_START   # the cursor row that starts a query from the start
+
+
+def cursor_keys(scores, rows, pos_base=0):
+    """(scores float32 [..], rows int64 [..]) cursors -> their packed keys as int64 (the view of uint64 torch can hold) of the
+    same shape and kind (ndarray or CUDA tensor), in the position space of pos_base: search_after_keys_tensor's after_keys.  The
+    rule of after_bounds_kernel: a NaN score, row -1 (a padding slot) and a row below -2 give 0, the exhausted list; row
+    AFTER_START gives all-ones, the start; otherwise ord(score + 0.0) << 32 | 2^32 - 1 - min(pos_base + row, 2^32 - 1)."""
+    if isinstance(pos_base, bool) or not isinstance(pos_base, (int, np.integer)) or not 0 <= int(pos_base) <= 0xFFFFFFFF:
+        raise ValueError(f"cursor_keys: pos_base must be an integer in [0, 2^32), got {pos_base!r}")
+    pos_base = int(pos_base)
+    if hasattr(scores, "is_cuda") or hasattr(rows, "is_cuda"):
+        import torch
+        if not (isinstance(scores, torch.Tensor) and isinstance(rows, torch.Tensor)) or scores.device != rows.device:
+            raise ValueError("cursor_keys: scores and rows must be tensors on one device (or both ndarrays)")
+        if scores.dtype != torch.float32 or rows.dtype != torch.int64 or tuple(scores.shape) != tuple(rows.shape):
+            raise ValueError(f"cursor_keys: needs float32 scores and int64 rows of one shape, got {scores.dtype} {tuple(scores.shape)} "
+                             f"and {rows.dtype} {tuple(rows.shape)}")
+        s = scores.contiguous() + 0.0                                          # -0.0 -> +0.0
+        b = s.view(torch.int32).to(torch.int64)                               # the bits, sign-extended
+        hi = torch.where(b < 0, ~b, b - 0x80000000)                           # ord(score) as a SIGNED 32-bit value: hi << 32 stays inside int64
+        pos = torch.clamp(torch.clamp(rows, min=0) + pos_base, max=0xFFFFFFFF)    # (rows up to 2^63 - 1: clamp first)
+        pos = torch.where(rows >= 0xFFFFFFFF, torch.full_like(rows, 0xFFFFFFFF), pos)
+        keys = hi * (1 << 32) + (0xFFFFFFFF - pos)
+        keys = torch.where((rows < 0) | torch.isnan(s), torch.zeros_like(keys), keys)
+        return torch.where(rows == AFTER_START, torch.full_like(keys, -1), keys)
+    s = np.asarray(scores)
+    r = np.asarray(rows)
+    if s.dtype != np.float32 or r.dtype.kind not in "iu" or s.shape != r.shape:
+        raise ValueError(f"cursor_keys: needs float32 scores and integer rows of one shape, got {s.dtype} {s.shape} and {r.dtype} {r.shape}")
+    r = r.astype(np.int64)
+    s = (s + np.float32(0.0)).astype(np.float32)                              # -0.0 -> +0.0
+    b = np.ascontiguousarray(s).view(np.uint32)
+    ord_ = np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000)).astype(np.uint64)
+    pos = np.where(r >= 0xFFFFFFFF, 0xFFFFFFFF, np.minimum(np.maximum(r, 0) + pos_base, 0xFFFFFFFF)).astype(np.uint64)
+    keys = (ord_ << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - pos)
+    keys = np.where((r < 0) | np.isnan(s), np.uint64(0), keys)
+    keys = np.where(r == AFTER_START, np.uint64(0xFFFFFFFFFFFFFFFF), keys)
+    return keys.astype(np.uint64).view(np.int64)
+
+
+def _after_args(q, k, after, d, what="search_after"):
+    """(q float32 [nq, d], k, scores float32 [nq] or None, rows int64 [nq] or None) of search_after; after: None (every query
+    from the start) or a pair (scores [nq] float32 -- the bits a search returned --, rows [nq] integers >= -2)."""
+    q = _as_queries(q, d, what)
+    k = _as_k(k, what)
+    if after is None:
+        return q, k, None, None
+    if not isinstance(after, (tuple, list)) or len(after) != 2:
+        raise ValueError(f"{what}: after must be None or a pair (scores [nq], rows [nq])")
+    scores = np.asarray(after[0])
+    if scores.dtype != np.float32:
+        raise ValueError(f"{what}: cursor scores must be float32 (the bits a search returns), got dtype {scores.dtype}")
+    if scores.shape != (q.shape[0],):
+        raise ValueError(f"{what}: {q.shape[0]} queries but cursor scores of shape {scores.shape} (one per query)")
+    rows = np.asarray(after[1])
+    if rows.dtype.kind not in "iu":
+        raise ValueError(f"{what}: cursor rows must be integers, got dtype {rows.dtype}")
+    if rows.shape != (q.shape[0],):
+        raise ValueError(f"{what}: {q.shape[0]} queries but cursor rows of shape {rows.shape} (one per query)")
+    rows = _as_ids(rows, 1, what)
+    if rows.size and int(rows.min()) < AFTER_START:
+        at = int(np.flatnonzero(rows < AFTER_START)[0])
+        raise ValueError(f"{what}: cursor row {int(rows[at])} of query {at} is below {AFTER_START} (a row, -1 = an exhausted list, "
+                         f"{AFTER_START} = the start)")
+    return q, k, np.ascontiguousarray(scores), rows
+
+
+def _check_id_map_tensor(id_map, q, what):
+    import torch
+    if id_map is None:
+        return None
+    if not isinstance(id_map, torch.Tensor) or not id_map.is_cuda or id_map.dtype != torch.int64 or id_map.dim() != 1:
+        raise ValueError(f"{what}: id_map must be an int64 CUDA tensor [ntotal]")
+    if id_map.device != q.device:
+        raise ValueError(f"{what}: q on {q.device} but id_map on {id_map.device}")
+    return id_map.contiguous()
+
+
+def _after_args_tensor(q, k, after, id_map, d, what="search_after_tensor"):
+    """(q float32 CUDA [nq, d], k, scores float32 CUDA [nq] or None, rows int64 CUDA [nq] or None, id_map) of
+    search_after_tensor.  The rows' values are the device's to read: one below -2 gives that query an empty list."""
+    import torch
+    q = _queries_tensor(q, d, what)
+    k = _as_k(k, what)
+    id_map = _check_id_map_tensor(id_map, q, what)
+    if after is None:
+        return q, k, None, None, id_map
+    if not isinstance(after, (tuple, list)) or len(after) != 2:
+        raise ValueError(f"{what}: after must be None or a pair (scores [nq], rows [nq])")
+    scores, rows = after
+    if not isinstance(scores, torch.Tensor) or not scores.is_cuda or not isinstance(rows, torch.Tensor) or not rows.is_cuda:
+        raise ValueError(f"{what}: cursor scores and rows must be CUDA tensors")
+    if scores.dtype != torch.float32:
+        raise ValueError(f"{what}: cursor scores must be float32 (the bits a search returns), got {scores.dtype}")
+    if rows.dtype != torch.int64:
+        raise ValueError(f"{what}: cursor rows must be int64, got {rows.dtype}")
+    for name, t in (("scores", scores), ("rows", rows)):
+        if tuple(t.shape) != (q.shape[0],):
+            raise ValueError(f"{what}: {q.shape[0]} queries but cursor {name} of shape {tuple(t.shape)} (one per query)")
+        if t.device != q.device:
+            raise ValueError(f"{what}: q on {q.device} but cursor {name} on {t.device}")
+    return q, k, scores.contiguous(), rows.contiguous(), id_map
+
+
+def _after_keys_args_tensor(q, k, after_keys, pos_base, d, what="search_after_keys_tensor"):
+    """(q float32 CUDA [nq, d], k, after_keys int64 CUDA [nq] or None, pos_base) of search_after_keys_tensor."""
+    import torch
+    q = _queries_tensor(q, d, what)
+    k = _as_k(k, what)
+    if isinstance(pos_base, bool) or not isinstance(pos_base, (int, np.integer)) or not 0 <= int(pos_base) <= 0xFFFFFFFF:
+        raise ValueError(f"{what}: pos_base must be an integer in [0, 2^32), got {pos_base!r}")
+    if after_keys is not None:
+        if not isinstance(after_keys, torch.Tensor) or not after_keys.is_cuda:
+            raise ValueError(f"{what}: after_keys must be a CUDA tensor (cursor_keys, or the last column of a key list)")
+        if after_keys.dtype != torch.int64:
+            raise ValueError(f"{what}: after_keys must be int64 (the view of the packed uint64 keys), got {after_keys.dtype}")
+        if tuple(after_keys.shape) != (q.shape[0],):
+            raise ValueError(f"{what}: {q.shape[0]} queries but after_keys of shape {tuple(after_keys.shape)} (one per query)")
+        if after_keys.device != q.device:
+            raise ValueError(f"{what}: q on {q.device} but after_keys on {after_keys.device}")
+        after_keys = after_keys.contiguous()
+    return q, k, after_keys, int(pos_base)
+
+
 def _filter_args(keys, exclude_pos, k, what="filter_keys"):
     """(keys int64 CUDA [nq, kin], exclude_pos int64 CUDA [nq, e], k in [1, kin]) of filter_keys."""
     keys = _ids_tensor(keys, 2, what)
@@ -531,6 +657,20 @@ class FlatIPIndex:
         _lib.check(_lib.lib().hac_index_search_grouped(self._h, _f32p(q), q.shape[0], k, _i64p(group_of), group_of.shape[0], _f32p(D), _i64p(I),
                                                        ctypes.POINTER(ctypes.c_int64)() if G is None else _i64p(G)))
         return (D, I, G) if return_groups else (D, I)
+
+    def search_after(self, q, k, after=None):
+        """The next page: search(q, k) over the rows BEHIND each query's cursor in the order (score desc, row asc).  after: None
+        (every query from the start: search(q, k)) or a pair (scores float32 [nq], rows int64 [nq]), e.g. (D[:, -1], I[:, -1])
+        of the page before.  Row r is listed iff its score is not NaN and lies below the cursor's, or equals it with r > the
+        cursor row; the cursor row need not exist.  Row -1 (a padding slot: the list had ended) and a NaN score give an empty
+        list, row AFTER_START the start; a row below -2 raises ValueError.  No ceiling at HAC_MAX_K on the depth, and a page
+        costs the same at any depth (include/haconvdr.h, "search behind a cursor")."""
+        q, k, scores, rows = _after_args(q, k, after, self.d)
+        D, I = _host_results((q.shape[0], k))
+        null_f, null_i = ctypes.POINTER(ctypes.c_float)(), ctypes.POINTER(ctypes.c_int64)()
+        _lib.check(_lib.lib().hac_index_search_after(self._h, _f32p(q), q.shape[0], k, null_f if scores is None else _f32p(scores),
+                                                     null_i if rows is None else _i64p(rows), _f32p(D), _i64p(I)))
+        return D, I
 
     def reset(self):
         _lib.check(_lib.lib().hac_index_reset(self._h))
@@ -727,6 +867,31 @@ class FlatIPIndex:
                                                               _devp(G), _devp(id_map), _stream_ptr(stream)))
         _keep_alive(stream, q, group_of, D, I, *(t for t in (G, id_map) if t is not None))
         return (D, I, G) if return_groups else (D, I)
+
+    def search_after_tensor(self, q, k, after=None, id_map=None, stream=None):
+        """search_after on the device: after None or (scores float32 CUDA [nq], rows int64 CUDA [nq]); a query whose cursor row
+        is below -2 gets an empty list and no error.  id_map: optional int64 CUDA [ntotal], I = id_map[row] -- it remaps the
+        result only: cursor rows are the index's own rows, so a caller that maps ids pages with search_after_keys_tensor.  No
+        host sync; capturable after one call of the largest (nq, k)."""
+        q, k, scores, rows, id_map = _after_args_tensor(q, k, after, id_map, self.d)
+        D, I = _device_results((q.shape[0], k), q.device)
+        _lib.check(_lib.lib().hac_index_search_after_device(self._h, _devp(q), q.shape[0], k, _devp(scores), _devp(rows), _devp(D), _devp(I),
+                                                            _devp(id_map), _stream_ptr(stream)))
+        _keep_alive(stream, q, D, I, *(t for t in (scores, rows, id_map) if t is not None))
+        return D, I
+
+    def search_after_keys_tensor(self, q, k, after_keys=None, pos_base=0, stream=None):
+        """search_after_tensor's sorted packed keys (int64 view of uint64) [nq, k], positions pos_base + row: the unit exchanged
+        between shards (merge_keys, keys_to_results).  after_keys: int64 CUDA [nq] packed cursors in the same position space
+        (cursor_keys, or the last column of any sorted key list: search_keys_tensor's, a merged list's, this call's own); 0 = an
+        exhausted list, -1 (all-ones) = the start; None starts every query from the start."""
+        import torch
+        q, k, after_keys, pos_base = _after_keys_args_tensor(q, k, after_keys, pos_base, self.d)
+        keys = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
+        _lib.check(_lib.lib().hac_index_search_after_keys_device(self._h, _devp(q), q.shape[0], k, _devp(after_keys), _devp(keys), pos_base,
+                                                                 _stream_ptr(stream)))
+        _keep_alive(stream, q, keys, *(() if after_keys is None else (after_keys,)))
+        return keys
 
     def search_keys_tensor(self, q, k, pos_base=0, stream=None):
         """Packed top-k keys (int64 view of uint64) [nq, k]; the unit exchanged between shards."""

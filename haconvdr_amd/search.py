@@ -392,6 +392,50 @@ class ResidentCorpus:
         radius = np.where(rows[:, 0] < 0, np.float32(np.inf), radius).astype(np.float32)
         return self.range_search(q, radius)
 
+    # ---- lists deeper than HAC_MAX_K, and the rows behind a passage (index.search_after*) ---------------------------
+    def search_deep(self, query_embeddings, depth, page=1024):
+        """search() to ANY depth: query_embeddings float32 [nq,768] (numpy or CUDA tensor) -> (D float64 [nq,depth], I int64
+        [nq,depth] EXTERNAL passage ids), the head of an unbounded search, padded with -FLT_MAX / -1 behind the last row whose
+        score is not NaN.  The list is fetched in pages of `page` <= HAC_MAX_K rows: page one through search's own routes
+        (index.search_keys_tensor), every later page behind the last key of the page before it
+        (index.search_after_keys_tensor), each at the cost of an exact scan whatever its depth; the keys are unpacked once, at
+        the end.  Over ROWS, like search()."""
+        import torch
+        from . import _lib
+        from .index import keys_to_results
+        for name, v in (("depth", depth), ("page", page)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+                raise ValueError(f"search_deep: {name} must be an integer >= 1, got {v!r}")
+        depth, page = int(depth), int(page)
+        if page > _lib.HAC_MAX_K:
+            raise ValueError(f"search_deep: page = {page} exceeds {_lib.HAC_MAX_K}")
+        q = query_embeddings if isinstance(query_embeddings, torch.Tensor) else torch.from_numpy(
+            np.ascontiguousarray(query_embeddings, dtype=np.float32))
+        q = q.to(self.dev)
+        pages = [self.index.search_keys_tensor(q, min(page, depth))]
+        got = pages[0].shape[1]
+        while got < depth:
+            k = min(page, depth - got)
+            pages.append(self.index.search_after_keys_tensor(q, k, pages[-1][:, -1].contiguous()))
+            got += k
+        D, I = keys_to_results(torch.cat(pages, dim=1), self.id_map)
+        return D.cpu().numpy().astype(np.float64), I.cpu().numpy()
+
+    def behind(self, query_embeddings, passage_ids, n):
+        """The n rows an unbounded search lists right BEHIND each query's named passage -- negatives from just below the gold
+        passage; the mirror of ahead_of: passage_ids int64 [nq] EXTERNAL ids -> (D float64 [nq,n], I int64 [nq,n] EXTERNAL
+        ids) like search(), n <= HAC_MAX_K.  The cursor is (score() of the passage, its row): rows that tie its score and come
+        later are included, the passage itself never is.  A passage no block holds, or one whose score is NaN, gives an
+        empty list (-FLT_MAX / -1)."""
+        q = np.ascontiguousarray(self._host_queries(query_embeddings), dtype=np.float32)
+        pid = np.asarray(passage_ids)
+        if pid.ndim != 1:
+            raise ValueError(f"behind: passage_ids must be [nq], got shape {pid.shape}")
+        rows = self.rows_of(pid)                                  # (-1 where no block holds the id: the exhausted cursor)
+        scores = self.index.score_ids(q, rows[:, None])[:, 0]
+        D, I = self.index.search_after(q, n, (scores, rows))
+        return D.astype(np.float64), np.where(I >= 0, self._ids[np.maximum(I, 0)], -1)
+
     def reconstruct(self, passage_ids):
         """passage_ids int64 [n] -> float32 [n,768], the embeddings as the blocks hold them (all-ones words for an absent id)."""
         return self.index.reconstruct_batch(self.rows_of(passage_ids))

@@ -31,7 +31,8 @@ class ShardedSearcher:
     count_ahead(q, ref_scores, ref_bounds [nq, m]) -> int64 [nq, m]    (default: index.count_ahead_tensor)
     local_among_keys(q, k, local_cand [nq, m], pos_base) -> [nq, k]    (default: index.search_among_keys_tensor)
     local_masked_keys(q, k, local_masks [n_masks, W], mask_of, pos_base) -> [nq, k]   (default: index.search_masked_keys_tensor)
-    The eight hooks exist so that the distributed plumbing can be exercised on CPU with
+    local_after_keys(q, k, after_keys [nq] or None, pos_base) -> [nq, k]   (default: index.search_after_keys_tensor)
+    The nine hooks exist so that the distributed plumbing can be exercised on CPU with
     gloo and a test double; the product path always uses the HIP defaults.
     n_local: rows this rank holds (default: index.ntotal when rank() / search_among() is called).
 
@@ -42,7 +43,8 @@ class ShardedSearcher:
     """
 
     def __init__(self, index, shard_base, group=None, id_map=None, local_keys=None, merge=None, to_results=None, filter=None,
-                 local_scores=None, count_ahead=None, n_local=None, local_among_keys=None, local_masked_keys=None):
+                 local_scores=None, count_ahead=None, n_local=None, local_among_keys=None, local_masked_keys=None,
+                 local_after_keys=None):
         from . import index as _index
         self.index = index
         self.shard_base = int(shard_base)
@@ -57,6 +59,7 @@ class ShardedSearcher:
         self._n_local = n_local
         self._local_among_keys = local_among_keys or (lambda q, k, cand, base: index.search_among_keys_tensor(q, k, cand, pos_base=base))
         self._local_masked_keys = local_masked_keys or (lambda q, k, masks, mask_of, base: index.search_masked_keys_tensor(q, k, masks, mask_of, pos_base=base))
+        self._local_after_keys = local_after_keys or (lambda q, k, after_keys, base: index.search_after_keys_tensor(q, k, after_keys, pos_base=base))
 
     def _gather_and_merge(self, keys):
         if not dist.is_initialized():
@@ -112,6 +115,23 @@ class ShardedSearcher:
         + r --, the same number of masks on every rank; mask_of int64 [nq] (or None: one mask, or one per query) is identical on
         every rank.  Every rank searches its rows under its masks, then the same one all-gather and merge as search_keys, at k."""
         return self._to_results(self.search_masked_keys(q, k, local_masks, mask_of), self.id_map)
+
+    def search_after_keys(self, q, k, after_keys=None):
+        """The merged keys [nq, k] of search_after; their last column is the cursor of the next page."""
+        if after_keys is not None:
+            if after_keys.dim() != 1 or after_keys.shape[0] != q.shape[0]:
+                raise ValueError(f"after_keys must be [nq] with nq = {q.shape[0]}, got shape {tuple(after_keys.shape)}")
+            if after_keys.dtype != torch.int64:
+                raise ValueError(f"after_keys must be int64 (the view of the packed keys), got {after_keys.dtype}")
+        return self._gather_and_merge(self._local_after_keys(q, k, after_keys, self.shard_base))
+
+    def search_after(self, q, k, after_keys=None):
+        """The next page over the whole sharded corpus -> (D, I) like search(): per query the k best rows whose key lies below
+        after_keys [nq] (int64 view of the packed keys, GLOBAL positions, identical on every rank: index.cursor_keys, or the last
+        column of search_keys / search_after_keys; 0 = an exhausted list, -1 = the start, None = every query from the start).
+        Nothing is translated: a key carries a global position, and every rank searches with pos_base = shard_base, so the same
+        comparison holds on every rank.  Then the same one all-gather and merge as search_keys, at k."""
+        return self._to_results(self.search_after_keys(q, k, after_keys), self.id_map)
 
     def rank(self, q, ids):
         """Exact rank of named rows over the whole sharded corpus: ids int64 [nq, m] GLOBAL positions (shard_base + local row),

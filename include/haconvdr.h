@@ -467,6 +467,78 @@ int hac_index_search_grouped(hac_index *idx, const float *q, int64_t nq, int k, 
 int hac_index_search_grouped_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const int64_t *group_of_dev, int64_t n_labels, float *D_dev,
                                     int64_t *I_dev, int64_t *G_dev /* may be NULL */, const int64_t *id_map_dev, void *hip_stream);
 
+/* ---- search behind a cursor: exact top-k resuming at a per-query (score, row) position ---------------------------------------
+ * Every list of the calls above ends at HAC_MAX_K; rank_ids gives positions, not lists, and range_search a list only for a
+ * radius known beforehand.  This call gives the NEXT page: more results in a conversation, hard negatives from a rank window
+ * deeper than HAC_MAX_K, the rows right behind a gold passage, a corpus listed in pieces that fit memory -- at a cost per page
+ * that does not grow with the depth.  For a query q, a cursor (s_ref, b) and k:
+ *   after(q, s_ref, b, k) = the first k of { rows r in [0, ntotal) : s(q, r) not NaN and
+ *                                            (s(q, r) < s_ref or (s(q, r) == s_ref and r > b)) }
+ *                           by (score desc, row asc), padded with D = -FLT_MAX, I = -1
+ * s is the canonical score: the k-ordered fmaf chain plus the "+ 0.0f" of a packed key, the same bits search returns.  The
+ * comparisons are float comparisons: -0.0 == +0.0, and +-Inf are ordinary scores.  The condition is
+ * make_key(s, r) < make_key(s_ref, b), with key = ord(score) << 32 | ~position: the complement of count_ahead's predicate minus
+ * the cursor's own slot.
+ * Cursor values:
+ *   b >= 0                  as above.  b need not be a row of the index; at or above ntotal no row tying s_ref is eligible.
+ *   b == -1                 a padding slot of an earlier list: that list had ended.  The result is padding only, whatever s_ref
+ *                           is -- so (D[:, -1], I[:, -1]) of any page is a valid cursor for the next one (a padding cursor
+ *                           (-FLT_MAX, -1) taken literally would list the rows scoring -FLT_MAX or -Inf a second time).
+ *   b == HAC_AFTER_START    from the start: every row whose score is not NaN is eligible, s_ref is not read.
+ *   b < -2                  a mistake: the host form returns HAC_ERR_INVALID, names the query and writes nothing; the *_device
+ *                           forms give that query an empty list and no error -- the split the by-id calls make.
+ *   s_ref NaN               an empty list.
+ *   both pointers NULL      every query starts from the start (only one of them NULL: HAC_ERR_INVALID).
+ * Key form of the cursor, one uint64 per query in the position space of pos_base: row r is eligible iff
+ * make_key(s, pos_base + r) < after_key.  0, the empty slot of a key list, is an exhausted list and gives an empty result;
+ * all-ones is the start (no row packs to either value); a NULL after_keys_dev starts every query from the start.  The last
+ * column of any sorted key list is therefore the cursor of the next page: of hac_index_search_keys_device, of a merged list of
+ * shards, of this call's own keys form.
+ * Identities (proved on the CPU over the oracle by tests/test_index_after.py, asserted on the GPU):
+ *   - with a start cursor, after == search(q, k), bit for bit at every k;
+ *   - D, I = search(q, K) on any route, I[j] >= 0: after(q, D[j], I[j], k) is the entries j+1 .. j+k of an unbounded search,
+ *     search(q, K)[j+1 : j+1+k] wherever that fits in K;
+ *   - pages chained through their last entries, concatenated up to the first padding slot, are the unbounded search:
+ *     range_search(q, -inf) followed by the rows scoring -Inf; no NaN-scoring row, no row twice, the page after the end is
+ *     padding only;
+ *   - rank_ids(q, I_page)[j] == rank_ids(q, cursor row) + 1 + j when the cursor names a row with a non-NaN score;
+ *   - after(q, s_ref, b, k) == search_masked(q, k, M), M the per-query mask of { r : key(s(q, r), r) < key(s_ref, b) };
+ *   - count_ahead(q, s_ref, b) + [row b exists and scores s_ref] + len(after(q, s_ref, b, unbounded)) == the number of rows
+ *     whose score is not NaN.
+ * 1 <= k <= HAC_MAX_K; nq == 0 is HAC_OK and touches nothing; ntotal == 0 gives padding only.
+ *
+ * How (csrc/after.inc): after_bounds_kernel turns the cursors into each query's exclusive upper key bound (NaN score, row -1 or
+ * row < -2: 0; row -2: all-ones; otherwise the key of (s_ref + 0.0f, min(row, 2^32 - 1))).  scan16_after_kernel is a copy of
+ * scan16_kernel over every 64-row group -- the same row stream, the same bit-exact MFMA chain, the same candidate buffers and
+ * compaction -- whose epilogue appends a row only if its key is below the lane's own query's bound.  A row is tested before it
+ * becomes a candidate, so every threshold comes from eligible rows and is a proven lower bound of the answer's k-th score: the
+ * result does not depend on the number of row streams, the launch cuts or the order of work.  No threshold seeding: a sample of
+ * rows would give bounds the rows behind the cursor cannot meet.  select_keys_kernel finishes, as in search.
+ * Cost (by arithmetic, NOT measured here; DESIGN.md records one timing): a page costs ceil(nq / QT) passes over the rows at the exact scan's stream rate,
+ * QT = 16 queries and fewer at large k (QT = 4 at k = 2048, d = 768), whatever the depth of the cursor; a listing to depth K
+ * costs ceil(K / k) pages.
+ *
+ * Host form: synchronous, on the index's own stream; queries and their bounds are staged in chunks of ~64 MiB.  It works on a
+ * multi-device index: the cursor is in the index's numbering, and each shard searches behind a bound of its own,
+ * (ord(s_ref) << 32) + (2^32 - 1 - b_local) in 64 bits, b_local = (the shard's rows at global positions <= b) - 1 -- with
+ * b_local = -1 that is (ord + 1) << 32, every row of the shard tying s_ref.  The lists are remapped and merged at k on the first
+ * device like search's.
+ * Device forms: single-device index (HAC_ERR_UNSUPPORTED otherwise), 16-byte aligned q_dev; they enqueue on hip_stream and
+ * never read back.  id_map_dev remaps the RESULT only, as in hac_index_search_device: cursor rows are always the index's own
+ * rows, so a caller that maps ids pages with the keys form.  The keys form writes the sorted packed keys [nq, k] with positions
+ * pos_base + row.  The workspaces grow by the rule of the search workspaces: run one call of the largest (nq, k) before
+ * capturing into a HIP graph.  Test switches (hac_index_set_option): "after_p" = "auto" | 1..4096 row streams per query tile,
+ * "debug_after_tiles" = 0 | the most query tiles per launch.  hac_index_last_plan afterwards reads
+ * "scan16_after_kernel<W=4> grid=(P,T) QT=.. C=.. lds=.. launches=..".
+ * Out of scope: an fp16 prefilter or a GEMM-shaped many-query route for cursor searches (the first page of a listing may take
+ * search's: its last key is a cursor); cursors for the excluding / among / masked / grouped variants. */
+#define HAC_AFTER_START (-2)
+int hac_index_search_after(hac_index *idx, const float *q, int64_t nq, int k, const float *after_score, const int64_t *after_row, float *D, int64_t *I);
+int hac_index_search_after_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const float *after_score_dev, const int64_t *after_row_dev,
+                                  float *D_dev, int64_t *I_dev, const int64_t *id_map_dev, void *hip_stream);
+int hac_index_search_after_keys_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const uint64_t *after_keys_dev, uint64_t *keys_dev,
+                                       uint32_t pos_base, void *hip_stream);
+
 /* ---- removing rows: faiss's IndexFlat::remove_ids(IDSelectorBatch(ids)), in place ------------------------------------------
  * The rows named by ids disappear; every surviving row keeps its bits and its relative order; the survivors are renumbered
  * densely from 0 -- survivor number j is row j of np.delete(x, unique(ids), axis=0) --; ntotal drops by the number of DISTINCT
