@@ -1143,6 +1143,7 @@ u32 next_pow2(u32 v) {
 #include "masked.inc"
 #include "grouped.inc"
 #include "after.inc"
+#include "at_rank.inc"
 
 // Every instantiation of the two templated scan kernels, once: init raises each one's dynamic-LDS limit from these tables and
 // the launches look their kernel up in them, so an instantiation that is launched is one whose limit was raised.
@@ -1202,6 +1203,8 @@ struct DeviceIndex {
         int debug_masked_tiles = 0;      // tests: search_masked's query tiles per launch (0 = by the list workspace), so that a small call spans several launches
         int after_p = 0;                 // search_after: row streams per query tile; 0 = as make_plan sizes scan16's (tests pin 1: one workgroup walks every group)
         int debug_after_tiles = 0;       // tests: search_after's query tiles per launch (0 = by QUERY_CHUNK), so that a small call spans several launches
+        int at_rank_p = 0;               // entries_at: row streams per pair tile; 0 = as count_ahead sizes its own (tests pin 1: one workgroup walks every group)
+        int debug_at_rank_tiles = 0;     // tests: entries_at's pair tiles per launch (0 = by QUERY_CHUNK), so that a small call spans several launches
     } tune;
     // Passes of the prefilter's main scan (search_keys_split) and where they end (row groups, whole rounds).  A refresh costs a
     // kernel tail + a selection (~0.1 ms): only scans of a few milliseconds are cut, and only with seeded thresholds (the refresh
@@ -1328,6 +1331,13 @@ struct DeviceIndex {
         } else if (n == "debug_after_tiles") {
             if (!parse_int(v, 0, 65535, t)) return fail(HAC_ERR_INVALID, "index option debug_after_tiles = '%s': an integer 0..65535", v.c_str());
             tune.debug_after_tiles = (int)t;
+        } else if (n == "at_rank_p") {
+            if (v == "auto") t = 0;
+            else if (!parse_int(v, 1, 4096, t)) return fail(HAC_ERR_INVALID, "index option at_rank_p = '%s': auto | an integer 1..4096", v.c_str());
+            tune.at_rank_p = (int)t;
+        } else if (n == "debug_at_rank_tiles") {
+            if (!parse_int(v, 0, 65535, t)) return fail(HAC_ERR_INVALID, "index option debug_at_rank_tiles = '%s': an integer 0..65535", v.c_str());
+            tune.debug_at_rank_tiles = (int)t;
         } else if (n == "seed_groups_max") {
             if (!parse_int(v, 0, LONG_MAX, t)) return fail(HAC_ERR_INVALID, "index option seed_groups_max = '%s': an integer >= 0 (0 = 14 sqrt(groups))", v.c_str());
             tune.seed_groups_max = t <= 0 ? 0 : (int)std::max<long>(768, std::min<long>(t, 1 << 30));
@@ -1423,6 +1433,7 @@ struct DeviceIndex {
             for (const ScanhEntry &e : SCANH_TABLE) HAC_HIP(hipFuncSetAttribute((const void *)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             HAC_HIP(hipFuncSetAttribute((const void *)count_ahead_kernel<RANK_MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             HAC_HIP(hipFuncSetAttribute((const void *)range_emit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
+            HAC_HIP(hipFuncSetAttribute((const void *)rank_hist_kernel<AT_BITS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             // (DYNAMIC LDS: without it a large k, whose candidate buffers pass the default 64 KiB, fails to launch)
             HAC_HIP(hipFuncSetAttribute((const void *)scan16_masked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             HAC_HIP(hipFuncSetAttribute((const void *)scan16_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
@@ -1449,7 +1460,7 @@ struct DeviceIndex {
         for (PinBuf *b : {&h_pin, &h_fb, &h_stage[0], &h_stage[1]}) b->release();
         for (GrowBuf *b : {&ws_partial, &ws_pcnt, &ws_seedkeys, &ws_thr, &ws_thrglob, &ws_q, &ws_qt, &ws_keys, &ws_D, &ws_I, &ws_stage[0],
                            &ws_stage[1], &ws_err, &ws_norm, &ws_qsplit, &ws_delta, &ws_cand, &ws_akeys, &ws_fail, &ws_stat, &ws_fbidx[0], &ws_fbidx[1],
-                           &ws_fbq[0], &ws_fbq[1], &ws_fbkeys[0], &ws_fbkeys[1], &ws_ids, &ws_rank, &ws_range, &ws_among, &ws_mgroups, &ws_mcnt, &ws_masks, &ws_labels, &ws_after})
+                           &ws_fbq[0], &ws_fbq[1], &ws_fbkeys[0], &ws_fbkeys[1], &ws_ids, &ws_rank, &ws_range, &ws_among, &ws_mgroups, &ws_mcnt, &ws_masks, &ws_labels, &ws_after, &ws_atrank})
             b->release();
         if (h_err) (void)hipHostFree(h_err);
         if (h_plan) (void)hipHostFree(h_plan);
@@ -1870,6 +1881,7 @@ struct DeviceIndex {
     GrowBuf ws_mgroups, ws_mcnt;   // search inside a bitmap (search_keys_masked): one launch's group lists u32 [tiles][G], the call's counters u32 [tiles]
     GrowBuf ws_masks;          // its host form (search_host.inc: masked_shard): a chunk's masks and mask_of
     GrowBuf ws_labels;         // search by group, host form (search_host.inc: grouped_shard): the shard's slice of the labels
+    GrowBuf ws_atrank;         // entry at a rank (rows_host.inc: entries_at_keys_device): a launch's pair states and histograms, the call's keys
     GrowBuf ws_after;          // search behind a cursor (search_host.inc): the bounds u64 [queries] of a (score, row) call, or of a host chunk
 
     char last_plan[320] = "none";

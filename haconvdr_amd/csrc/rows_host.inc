@@ -1,8 +1,8 @@
-// Rows by id, their rank, range search and removal (hac_index_reconstruct*, hac_index_score_ids*, hac_index_rank_ids*,
-// hac_index_count_ahead_device, hac_index_range_search*, hac_index_remove_ids): everything between the C ABI and the kernels of
-// flat_ip.hip ("rows by id"), rank.inc, range.inc and remove.inc.  Included by flat_ip.hip behind hac_index; free functions
+// Rows by id, their rank, the entry at a rank, range search and removal (hac_index_reconstruct*, hac_index_score_ids*,
+// hac_index_rank_ids*, hac_index_count_ahead_device, hac_index_entries_at*, hac_index_range_search*, hac_index_remove_ids): everything
+// between the C ABI and the kernels of flat_ip.hip ("rows by id"), rank.inc, at_rank.inc, range.inc and remove.inc.  Included by flat_ip.hip behind hac_index; free functions
 // over one shard (DeviceIndex &), which lends its segment table, its stream, its pinned slab, its staging buffers and the
-// workspaces ws_q / ws_ids / ws_D / ws_I / ws_rank / ws_range -- nothing of the search state (remove_rows_shard alone changes
+// workspaces ws_q / ws_ids / ws_D / ws_I / ws_rank / ws_atrank / ws_range -- nothing of the search state (remove_rows_shard alone changes
 // the segments).  The searches that return top-k keys are search_host.inc's, which follows and uses the helpers here.
 namespace {
 
@@ -99,6 +99,92 @@ int rank_ids_device(DeviceIndex &x, const float *q_dev, int64_t nq, const int64_
     HAC_TRY(x.ws_rank.reserve((size_t)nq * m * 12));
     HAC_TRY(score_ids_device(x, q_dev, nq, ids_dev, m, rank_scores(x, nq, m), st));
     return count_ahead_device(x, "rank_ids", q_dev, nq, rank_scores(x, nq, m), ids_dev, true, m, rank_dev, st);
+}
+
+// ---- entry at a rank (at_rank.inc).  The digits a selection runs over: every score digit, and the position digits from the
+// highest one in which two rows of the index can differ -- the low key words of positions pos_base .. pos_base + ntotal - 1 are
+// consecutive, so the digits above the highest bit in which the first and the last differ are the same for every row and go
+// into the prefix from the start (const_bits).  passes = 32 / BITS + ceil(bit_length(pos_base ^ (pos_base + ntotal - 1)) / BITS).
+struct AtDigits { int passes; u64 const_bits; };
+AtDigits at_rank_digits(u32 pos_base, int64_t ntotal) {
+    const u32 lo_first = 0xFFFFFFFFu - pos_base, lo_last = 0xFFFFFFFFu - (u32)(pos_base + (u64)ntotal - 1);
+    int bits = 0;
+    for (u32 v = lo_first ^ lo_last; v; v >>= 1) ++bits;
+    const int npos = (bits + AT_BITS - 1) / AT_BITS;
+    const u64 mask = npos * AT_BITS >= 32 ? 0ull : (0xFFFFFFFFull >> (npos * AT_BITS)) << (npos * AT_BITS);
+    return AtDigits{32 / AT_BITS + npos, (u64)lo_first & mask};
+}
+// The workspace of one call: a launch's pair states and histograms (reused by the next launch, in stream order), then -- the
+// forms that return D / I -- the call's keys.  It grows by the rule of the search workspaces.
+constexpr int64_t AT_LAUNCH_PAIRS = DeviceIndex::QUERY_CHUNK;
+constexpr size_t AT_PAIR_BYTES = sizeof(AtState) + ((size_t)4 << AT_BITS);
+// keys_out[i][j] = entry_at(q[i], ranks[i][j]) as a packed key in the position space of pos_base, 0 = padding (a rank outside
+// [0, |L(q[i])|)); keys_out == null: into the workspace (*keys_ws)
+int entries_at_keys_device(DeviceIndex &x, const char *what, const float *q_dev, int64_t nq, const int64_t *ranks_dev, int64_t m, u64 *keys_out, u32 pos_base,
+                           hipStream_t st, u64 **keys_ws = nullptr) {
+    if (nq == 0 || m == 0) return HAC_OK;
+    HAC_TRY(check_rank_size(what, nq, m));
+    if (m > ((int64_t)1 << 38) / nq) return fail(HAC_ERR_UNSUPPORTED, "%s: %lld x %lld pairs in one call exceed the grid", what, (long long)nq, (long long)m);
+    HAC_TRY(check_dev_ptr(q_dev, what));
+    if ((uint64_t)pos_base + (uint64_t)x.ntotal > 0xFFFFFFFFull) return fail(HAC_ERR_UNSUPPORTED, "row positions exceed 32 bits");
+    const int64_t N = nq * m;
+    const int QT = (int)std::min<int64_t>(16, N);
+    const int64_t tiles_all = (N + QT - 1) / QT;
+    int64_t TL = AT_LAUNCH_PAIRS / 16;
+    if (x.tune.debug_at_rank_tiles > 0) TL = std::min<int64_t>(TL, x.tune.debug_at_rank_tiles);
+    TL = std::min(TL, tiles_all);
+    const int64_t PL = std::min(N, TL * QT);   // pairs per launch
+    HAC_TRY(x.ws_atrank.reserve((size_t)PL * AT_PAIR_BYTES + (keys_out ? 0 : (size_t)N * 8)));
+    AtState *state = (AtState *)x.ws_atrank.p;
+    u32 *hist = (u32 *)(state + PL);
+    if (!keys_out) *keys_ws = keys_out = (u64 *)(hist + ((size_t)PL << AT_BITS));
+    if (x.ntotal == 0) {
+        HAC_HIP(hipMemsetAsync(keys_out, 0, (size_t)N * 8, st));
+        return HAC_OK;
+    }
+    HAC_TRY(x.upload_segs(st));
+    HAC_HIP(hipMemsetAsync(hist, 0, (size_t)PL * 4 << AT_BITS, st));
+    const u32 G = (u32)((x.ntotal + GROUP_ROWS - 1) / GROUP_ROWS);
+    const AtDigits dg = at_rank_digits(pos_base, x.ntotal);
+    for (int64_t off = 0; off < N; off += PL) {
+        const int64_t n = std::min(PL, N - off);
+        ScanArgs a = x.scan_args(q_dev, n);   // (the queries of the whole call: a pair finds its own)
+        a.QT = (int)std::min<int64_t>(16, n);
+        a.n_items = G;
+        a.pos_base = pos_base;
+        const int T = (int)((n + a.QT - 1) / a.QT);
+        const size_t lds = at_rank_lds(x.K4, a.QT, AT_BITS);
+        // resident workgroups per CU: LDS-limited, and 3 by the kernel's registers, as count_ahead_kernel
+        const long P = x.row_streams(lds, SCAN_WAVES, 3, T, G, x.tune.at_rank_p);
+        AtArgs ra{state, hist, (long)m, (long)off, 0};
+        for (int p = 0; p < dg.passes; ++p) {
+            // the score digits from the top, then the position digits that can differ, down to bit 0
+            ra.shift = p < 32 / AT_BITS ? 64 - AT_BITS * (p + 1) : AT_BITS * (dg.passes - 1 - p);
+            HAC_TRY(x.prof_begin(st));   // (hac_index_set_profiling: every pass is a timed scan, in launch order)
+            rank_hist_kernel<AT_BITS><<<dim3((unsigned)P, (unsigned)T), dim3(SCAN_WAVES * 64), lds, st>>>(a, ra);
+            HAC_HIP(hipGetLastError());
+            HAC_TRY(x.prof_end(st));
+            rank_narrow_kernel<AT_BITS><<<dim3((unsigned)n), dim3(64), 0, st>>>(hist, state, (const long long *)ranks_dev + off, ra.shift, dg.const_bits,
+                                                                               p == dg.passes - 1 ? keys_out + off : nullptr);
+            HAC_HIP(hipGetLastError());
+        }
+        if (off == 0) {
+            snprintf(x.last_plan, sizeof x.last_plan, "rank_hist_kernel<BITS=%d> grid=(%ld,%d) QT=%d passes=%d lds=%zu", AT_BITS, P, T, a.QT, dg.passes, lds);
+            x.plan_text_slot = -1;
+        }
+    }
+    return HAC_OK;
+}
+// (D, I)[i][j] = entry_at(q[i], ranks[i][j]): the keys into the workspace, then keys_to_results_kernel, with or without id_map
+int entries_at_device(DeviceIndex &x, const float *q_dev, int64_t nq, const int64_t *ranks_dev, int64_t m, float *D_dev, int64_t *I_dev,
+                      const int64_t *id_map_dev, hipStream_t st) {
+    if (nq == 0 || m == 0) return HAC_OK;
+    u64 *keys = nullptr;
+    HAC_TRY(entries_at_keys_device(x, "entries_at_device", q_dev, nq, ranks_dev, m, nullptr, 0u, st, &keys));
+    const int64_t N = nq * m;
+    keys_to_results_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st>>>(keys, (long)N, (const long long *)id_map_dev, D_dev, (long long *)I_dev);
+    HAC_HIP(hipGetLastError());
+    return HAC_OK;
 }
 
 // ---- range search (range.inc).  The workspace of one call of (nq, cap): control words, counters, lims, the two key buffers
@@ -321,6 +407,23 @@ float key_score_host(u64 key) {
     return f;
 }
 int64_t key_row_host(u64 key) { return (int64_t)(0xFFFFFFFFu - (u32)key); }
+
+// (D, I)[i][j] = entry_at(q[i], ranks[i][j]): the ranks are values, not ids, so nothing is checked or skipped; the pairs' keys
+// come back through I's own memory (8 bytes per pair either way) and are unpacked in place.  16 bytes per pair.
+int entries_at_host(DeviceIndex &x, const float *q, int64_t nq, const int64_t *ranks, int64_t m, float *D, int64_t *I) {
+    const PairPlane planes[] = {{ranks, 8, &x.ws_ids}};
+    u64 *keys = reinterpret_cast<u64 *>(I);
+    HAC_TRY(pair_matrix_host(x, q, nq, m, planes, keys, x.ws_I, false, 0, [&](int64_t nqc, int64_t mc) {
+        return entries_at_keys_device(x, "entries_at", (const float *)x.ws_q.p, nqc, (const int64_t *)x.ws_ids.p, mc, (u64 *)x.ws_I.p, 0u, x.stream);
+    }));
+    for (int64_t i = 0; i < nq * m; ++i) {
+        u64 key;
+        std::memcpy(&key, &keys[i], 8);
+        D[i] = key ? key_score_host(key) : -FLT_MAX;
+        I[i] = key ? key_row_host(key) : -1;
+    }
+    return HAC_OK;
+}
 
 // Range search over one shard's rows: lims [nq + 1] always; when the shard's total fits cap, its keys, every query's segment
 // sorted, the rows in the numbering of the whole index (several devices: remap_keys, which keeps a sorted list sorted).
@@ -664,6 +767,30 @@ int hac_index_rank_ids(hac_index *idx, const float *q, int64_t nq, const int64_t
         rank[i] = sum;
     }
     return HAC_OK;
+}
+
+int hac_index_entries_at_keys_device(hac_index *idx, const float *q_dev, int64_t nq, const int64_t *ranks_dev, int64_t m, uint64_t *keys_dev, uint32_t pos_base,
+                                     void *hip_stream) {
+    return on_single_shard(idx, "entries_at_keys_device", [&](DeviceIndex &s) -> int {
+        if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q_dev || !ranks_dev || !keys_dev))) return fail(HAC_ERR_INVALID, "entries_at_keys_device: bad arguments");
+        return entries_at_keys_device(s, "entries_at_keys_device", q_dev, nq, ranks_dev, m, (u64 *)keys_dev, pos_base, (hipStream_t)hip_stream);
+    });
+}
+
+int hac_index_entries_at_device(hac_index *idx, const float *q_dev, int64_t nq, const int64_t *ranks_dev, int64_t m, float *D_dev, int64_t *I_dev,
+                                const int64_t *id_map_dev, void *hip_stream) {
+    return on_single_shard(idx, "entries_at_device", [&](DeviceIndex &s) -> int {
+        if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q_dev || !ranks_dev || !D_dev || !I_dev))) return fail(HAC_ERR_INVALID, "entries_at_device: bad arguments");
+        return entries_at_device(s, q_dev, nq, ranks_dev, m, D_dev, I_dev, id_map_dev, (hipStream_t)hip_stream);
+    });
+}
+
+int hac_index_entries_at(hac_index *idx, const float *q, int64_t nq, const int64_t *ranks, int64_t m, float *D, int64_t *I) {
+    // (no multi-device form: the position digits of shards whose rows map to index rows through several spans do not line up)
+    return on_single_shard(idx, "entries_at", [&](DeviceIndex &s) -> int {
+        if (nq < 0 || m < 0 || (nq > 0 && m > 0 && (!q || !ranks || !D || !I))) return fail(HAC_ERR_INVALID, "entries_at: bad arguments");
+        return entries_at_host(s, q, nq, ranks, m, D, I);
+    });
 }
 
 int hac_index_range_search_device(hac_index *idx, const float *q_dev, int64_t nq, const float *radius_dev, int64_t cap, int64_t *lims_dev, float *D_dev,

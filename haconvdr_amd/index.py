@@ -32,6 +32,15 @@ def _keep_alive(stream, *tensors):
         t.record_stream(stream)
 
 
+def _on_stream(stream):
+    """Context in which torch's own kernels run on ``stream`` (a torch stream, a raw hipStream_t or None = the current stream)."""
+    import contextlib
+    import torch
+    if stream is None:
+        return contextlib.nullcontext()
+    return torch.cuda.stream(stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(int(stream)))
+
+
 # ---- the pointers the C ABI takes: of a float32 / int64 ndarray, of a CUDA tensor (None: null)
 def _f32p(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
@@ -557,6 +566,89 @@ def _after_keys_args_tensor(q, k, after_keys, pos_base, d, what="search_after_ke
     return q, k, after_keys, int(pos_base)
 
 
+# ---- ranks of entries_at / search_at (include/haconvdr.h, "entry at a rank"): values, not ids -- any integer is allowed
+def _as_ranks(ranks, what):
+    """ranks -> contiguous int64 [nq, m]; integers only (a float rank is a mistake, not a position)."""
+    a = np.asarray(ranks)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"{what}: ranks must be integers, got dtype {a.dtype}")
+    if a.ndim != 2:
+        raise ValueError(f"{what}: ranks must have 2 dimension(s), got shape {a.shape}")
+    if a.dtype == np.uint64 and a.size and int(a.max()) > np.iinfo(np.int64).max:
+        raise ValueError(f"{what}: rank {int(a.max())} does not fit int64")
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def _rank_args(q, ranks, d, what="entries_at"):
+    """(q float32 [nq, d], ranks int64 [nq, m]) of entries_at."""
+    q = _as_queries(q, d, what)
+    ranks = _as_ranks(ranks, what)
+    if ranks.shape[0] != q.shape[0]:
+        raise ValueError(f"{what}: {q.shape[0]} queries but ranks of shape {ranks.shape} (one list per query)")
+    return q, ranks
+
+
+def _rank_args_tensor(q, ranks, d, what="entries_at_tensor"):
+    """(q float32 CUDA [nq, d], ranks int64 CUDA [nq, m]) of entries_at_tensor / entry_keys_at_tensor."""
+    import torch
+    q = _queries_tensor(q, d, what)
+    if not isinstance(ranks, torch.Tensor) or not ranks.is_cuda:
+        raise ValueError(f"{what}: ranks must be a CUDA tensor")
+    if ranks.dtype != torch.int64:
+        raise ValueError(f"{what}: ranks must be int64, got {ranks.dtype}")
+    if ranks.dim() != 2:
+        raise ValueError(f"{what}: ranks must have 2 dimension(s), got shape {tuple(ranks.shape)}")
+    if ranks.shape[0] != q.shape[0]:
+        raise ValueError(f"{what}: {q.shape[0]} queries but ranks of shape {tuple(ranks.shape)} (one list per query)")
+    if ranks.device != q.device:
+        raise ValueError(f"{what}: q on {q.device} but ranks on {ranks.device}")
+    return q, ranks.contiguous()
+
+
+def _as_pos_base(pos_base, what):
+    if isinstance(pos_base, bool) or not isinstance(pos_base, (int, np.integer)) or not 0 <= int(pos_base) <= 0xFFFFFFFF:
+        raise ValueError(f"{what}: pos_base must be an integer in [0, 2^32), got {pos_base!r}")
+    return int(pos_base)
+
+
+def _as_start(start, nq, what):
+    """start of search_at -> contiguous int64 [nq]: an integer (one start for every query) or one per query, all >= 0."""
+    if isinstance(start, bool):
+        raise ValueError(f"{what}: start must be an integer or int64 [nq], got {start!r}")
+    a = np.asarray(start)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"{what}: start must be integers, got dtype {a.dtype}")
+    if a.ndim == 0:
+        a = np.full(nq, a)
+    elif a.shape != (nq,):
+        raise ValueError(f"{what}: {nq} queries but start of shape {a.shape} (an integer, or one per query)")
+    if a.dtype == np.uint64 and a.size and int(a.max()) > np.iinfo(np.int64).max:
+        raise ValueError(f"{what}: start {int(a.max())} does not fit int64")
+    a = np.ascontiguousarray(a, dtype=np.int64)
+    if a.size and int(a.min()) < 0:
+        at = int(np.flatnonzero(a < 0)[0])
+        raise ValueError(f"{what}: start {int(a[at])} of query {at} is negative (a rank of the unbounded search, >= 0)")
+    return a
+
+
+def _start_tensor(start, q, what):
+    """start of search_at*_tensor -> int64 CUDA [nq]: an integer >= 0, or an int64 CUDA tensor [nq] on q's device (its values
+    are the device's to read: a negative one gives that query an empty list)."""
+    import torch
+    nq = q.shape[0]
+    if isinstance(start, torch.Tensor):
+        if not start.is_cuda or start.dtype != torch.int64:
+            raise ValueError(f"{what}: start must be an integer or an int64 CUDA tensor [nq], got {start.dtype} on {start.device}")
+        if tuple(start.shape) != (nq,):
+            raise ValueError(f"{what}: {nq} queries but start of shape {tuple(start.shape)} (an integer, or one per query)")
+        if start.device != q.device:
+            raise ValueError(f"{what}: q on {q.device} but start on {start.device}")
+        return start.contiguous()
+    if isinstance(start, bool) or not isinstance(start, (int, np.integer)) or int(start) < 0:
+        raise ValueError(f"{what}: start must be an integer >= 0 or an int64 CUDA tensor [nq], got {start!r}")
+    return torch.full((nq,), int(start), dtype=torch.int64, device=q.device)
+
+
 def _filter_args(keys, exclude_pos, k, what="filter_keys"):
     """(keys int64 CUDA [nq, kin], exclude_pos int64 CUDA [nq, e], k in [1, kin]) of filter_keys."""
     keys = _ids_tensor(keys, 2, what)
@@ -735,6 +827,31 @@ class FlatIPIndex:
         _lib.check(_lib.lib().hac_index_rank_ids(self._h, _f32p(q), q.shape[0], _i64p(ids), ids.shape[1], _i64p(R)))
         return R
 
+    # ---- entry at a rank (include/haconvdr.h, "entry at a rank") -------------
+    def entries_at(self, q, ranks):
+        """What sits at a rank: q float32 [nq, d], ranks int64 [nq, m] -> (D float32, I int64) of ranks.shape, the entry at
+        0-based position ranks[i, j] of an unbounded search of q[i] (order: score desc, row asc) -- rank_ids' inverse, with no
+        ceiling at HAC_MAX_K and at a cost that does not grow with the rank.  Ranks are values, not ids: any rank outside the
+        list (negative, or at or beyond the number of rows whose score is not NaN) gives padding, -FLT_MAX / -1, never an error.
+        entries_at(q, arange(k)) == search(q, k).  Single-device indexes only.  One pass over the rows per key digit (5 - 8) and
+        16 (query, rank) pairs."""
+        q, ranks = _rank_args(q, ranks, self.d)
+        D, I = _host_results(ranks.shape)
+        _lib.check(_lib.lib().hac_index_entries_at(self._h, _f32p(q), q.shape[0], _i64p(ranks), ranks.shape[1], _f32p(D), _i64p(I)))
+        return D, I
+
+    def search_at(self, q, k, start):
+        """The entries [start, start + k) of the unbounded search: (D float32 [nq, k], I int64 [nq, k]).  start: an integer or
+        int64 [nq], >= 0 (ValueError otherwise).  It is search_after behind entries_at(q, start - 1); a query with start == 0 gets
+        the start cursor (search(q, k)), a start at or past the end gives padding only.  One entries_at of one rank per query
+        plus one page, whatever the depth."""
+        q = _as_queries(q, self.d, "search_at")
+        k = _as_k(k, "search_at")
+        start = _as_start(start, q.shape[0], "search_at")
+        Dc, Ic = self.entries_at(q, (start - 1)[:, None])
+        rows = np.where(start == 0, AFTER_START, Ic[:, 0]).astype(np.int64)   # (-1 from a start past the end: the exhausted list)
+        return self.search_after(q, k, (np.ascontiguousarray(Dc[:, 0]), rows))
+
     # ---- range search (include/haconvdr.h, "range search") ------------------
     RANGE_FIRST_CAP = 1024   # results per query the first call of range_search makes room for
 
@@ -892,6 +1009,52 @@ class FlatIPIndex:
                                                                  _stream_ptr(stream)))
         _keep_alive(stream, q, keys, *(() if after_keys is None else (after_keys,)))
         return keys
+
+    def entries_at_tensor(self, q, ranks, id_map=None, stream=None):
+        """entries_at on the device: q float32 CUDA [nq, d], ranks int64 CUDA [nq, m] -> (D float32, I int64) CUDA of
+        ranks.shape.  id_map: optional int64 CUDA [ntotal], I = id_map[row].  No host sync; the launches depend on (nq, m) and
+        the index's size only; capturable after one call of the largest (nq, m)."""
+        q, ranks = _rank_args_tensor(q, ranks, self.d)
+        id_map = _check_id_map_tensor(id_map, q, "entries_at_tensor")
+        D, I = _device_results(tuple(ranks.shape), q.device)
+        _lib.check(_lib.lib().hac_index_entries_at_device(self._h, _devp(q), q.shape[0], _devp(ranks), ranks.shape[1], _devp(D), _devp(I), _devp(id_map),
+                                                          _stream_ptr(stream)))
+        _keep_alive(stream, q, ranks, D, I, *(() if id_map is None else (id_map,)))
+        return D, I
+
+    def entry_keys_at_tensor(self, q, ranks, pos_base=0, stream=None):
+        """entries_at_tensor's packed keys (int64 view of uint64) of ranks.shape, positions pos_base + row, 0 = padding: the key
+        space of search_keys_tensor and of search_after_keys_tensor's cursors, so a column of it is the cursor of the page
+        behind those entries."""
+        import torch
+        q, ranks = _rank_args_tensor(q, ranks, self.d, "entry_keys_at_tensor")
+        pos_base = _as_pos_base(pos_base, "entry_keys_at_tensor")
+        keys = torch.empty(tuple(ranks.shape), dtype=torch.int64, device=q.device)
+        _lib.check(_lib.lib().hac_index_entries_at_keys_device(self._h, _devp(q), q.shape[0], _devp(ranks), ranks.shape[1], _devp(keys), pos_base,
+                                                               _stream_ptr(stream)))
+        _keep_alive(stream, q, ranks, keys)
+        return keys
+
+    def search_at_keys_tensor(self, q, k, start, pos_base=0, stream=None):
+        """search_at's sorted packed keys (int64 view of uint64) [nq, k], positions pos_base + row, composed on the device:
+        the cursor is where(start == 0, the start, entry_keys_at_tensor(q, start - 1)), fed to search_after_keys_tensor.
+        start: an integer >= 0 or int64 CUDA [nq] (a negative entry gives that query an empty list).  No host sync."""
+        import torch
+        q = _queries_tensor(q, self.d, "search_at_keys_tensor")
+        k = _as_k(k, "search_at_keys_tensor")
+        with _on_stream(stream):   # (torch's own kernels between the two library calls go where those go)
+            start = _start_tensor(start, q, "search_at_keys_tensor")
+            cursor = self.entry_keys_at_tensor(q, (start - 1)[:, None], pos_base, stream)[:, 0]
+            cursor = torch.where(start == 0, torch.full_like(cursor, -1), cursor).contiguous()
+        return self.search_after_keys_tensor(q, k, cursor, pos_base, stream)
+
+    def search_at_tensor(self, q, k, start, id_map=None, stream=None):
+        """search_at on the device -> (D float32 [nq, k], I int64 [nq, k]) CUDA tensors; id_map: optional int64 CUDA [ntotal],
+        I = id_map[row].  No host sync."""
+        q = _queries_tensor(q, self.d, "search_at_tensor")
+        id_map = _check_id_map_tensor(id_map, q, "search_at_tensor")
+        keys = self.search_at_keys_tensor(q, k, start, 0, stream)
+        return keys_to_results(keys, id_map, stream)
 
     def search_keys_tensor(self, q, k, pos_base=0, stream=None):
         """Packed top-k keys (int64 view of uint64) [nq, k]; the unit exchanged between shards."""

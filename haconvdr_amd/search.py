@@ -421,6 +421,39 @@ class ResidentCorpus:
         D, I = keys_to_results(torch.cat(pages, dim=1), self.id_map)
         return D.cpu().numpy().astype(np.float64), I.cpu().numpy()
 
+    def search_window(self, query_embeddings, start, n):
+        """The ranks [start, start + n) of an unbounded search WITHOUT the ranks in front of them -- hard negatives from a rank
+        window, page 57 of a listing: query_embeddings float32 [nq,768] (numpy or CUDA tensor), start an integer >= 0 or int64
+        [nq], n >= 1 -> (D float64 [nq,n], I int64 [nq,n] EXTERNAL passage ids), padded with -FLT_MAX / -1 behind the last row
+        whose score is not NaN.  The first page stands behind the entry at rank start - 1 (index.search_at_keys_tensor: its cost
+        does not grow with start); beyond HAC_MAX_K rows the window is paged like search_deep.  Over ROWS, like search()."""
+        import torch
+        from . import _lib
+        from .index import _as_start, keys_to_results
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 1:
+            raise ValueError(f"search_window: n must be an integer >= 1, got {n!r}")
+        n = int(n)
+        q = query_embeddings if isinstance(query_embeddings, torch.Tensor) else torch.from_numpy(
+            np.ascontiguousarray(query_embeddings, dtype=np.float32))
+        q = q.to(self.dev)
+        start = torch.from_numpy(_as_start(start, q.shape[0], "search_window")).to(self.dev)
+        page = _lib.HAC_MAX_K
+        pages = [self.index.search_at_keys_tensor(q, min(page, n), start)]
+        got = pages[0].shape[1]
+        while got < n:
+            k = min(page, n - got)
+            pages.append(self.index.search_after_keys_tensor(q, k, pages[-1][:, -1].contiguous()))
+            got += k
+        D, I = keys_to_results(torch.cat(pages, dim=1), self.id_map)
+        return D.cpu().numpy().astype(np.float64), I.cpu().numpy()
+
+    def score_at_rank(self, query_embeddings, ranks):
+        """The score at a rank -- the radius that makes range_search return exactly that many rows, score quantiles of the
+        corpus: query_embeddings float32 [nq,768], ranks int64 [nq, m] -> float64 [nq, m], the score of the entry at each
+        0-based rank of an unbounded search; -FLT_MAX where the rank lies outside the list (index.entries_at)."""
+        q = np.ascontiguousarray(self._host_queries(query_embeddings), dtype=np.float32)
+        return self.index.entries_at(q, ranks)[0].astype(np.float64)
+
     def behind(self, query_embeddings, passage_ids, n):
         """The n rows an unbounded search lists right BEHIND each query's named passage -- negatives from just below the gold
         passage; the mirror of ahead_of: passage_ids int64 [nq] EXTERNAL ids -> (D float64 [nq,n], I int64 [nq,n] EXTERNAL

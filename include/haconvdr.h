@@ -539,6 +539,66 @@ int hac_index_search_after_device(hac_index *idx, const float *q_dev, int64_t nq
 int hac_index_search_after_keys_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const uint64_t *after_keys_dev, uint64_t *keys_dev,
                                        uint32_t pos_base, void *hip_stream);
 
+/* ---- entry at a rank: what sits at position t of a query's unbounded ranking? -------------------------------------------------
+ * rank_ids answers row -> rank, count_ahead (score, row) -> rows ahead, search_after cursor -> next page, range_search radius ->
+ * list.  This is the missing inverse, rank -> entry, at a cost that does not grow with the rank: hard negatives from a rank
+ * window without the pages in front of it, page 57 of a listing without pages 1 - 56, the score at a rank (the radius that makes
+ * range_search return exactly n rows; score quantiles of a corpus), an independent check of rank_ids.
+ * For a query q let L(q) be the rows r in [0, ntotal) whose canonical score s(q, r) is not NaN, ordered by make_key(s, r)
+ * descending, i.e. by (score desc with -0.0 == +0.0, row asc).  s is the canonical score: the k-ordered fmaf chain plus the
+ * "+ 0.0f" of a packed key, the same bits search returns.
+ *   entry_at(q, t) = the t-th entry of that order (0-based) when 0 <= t < |L(q)|;
+ *                    otherwise padding: key 0, D = -FLT_MAX, I = -1.
+ * No ceiling at HAC_MAX_K.  A NaN-scoring row is never an entry; +-Inf are ordinary scores; a row scoring exactly -FLT_MAX is a
+ * real entry (I >= 0), not padding.  ntotal == 0 gives padding only; nq == 0 or m == 0 is HAC_OK and touches nothing.  ranks
+ * [nq][m] are VALUES, not ids: any rank outside [0, |L(q)|), negative ones included, gives padding and is never an error, on
+ * the host form too.
+ * Identities (proved on the CPU over the oracle by tests/test_index_at_rank.py, asserted on the GPU):
+ *   - entries_at(q, 0 .. k-1) == search(q, k) bit for bit on any route, padding included;
+ *   - rank_ids(q, I_at)[i][j] == ranks[i][j] wherever I_at >= 0;
+ *   - entries_at(q, rank_ids(q, ids)) returns ids and score_ids(q, ids) wherever the rank is >= 0;
+ *   - search_after(q, k, entries_at(q, t)) == the entries t+1 .. t+k of the unbounded search;
+ *   - with c = range_count(q, radius): D_at(c-1) > radius >= D_at(c) when both exist;
+ *   - |L(q)| is the smallest t that gives padding.
+ *
+ * How (csrc/at_rank.inc): a radix selection over the 64-bit key, 8 bits at a time from the top, per (query, rank) pair.  A pair
+ * takes one query slot of a 16-wide tile -- a query with m ranks appears m times -- and carries, on the device, the key prefix
+ * found so far and the rank that remains inside it.  rank_hist_kernel is count_ahead_kernel's pass (the same row stream, the same
+ * bit-exact MFMA chain) with an epilogue that, for every row whose key agrees with the pair's prefix, adds 1 to the bin of the
+ * key's next digit: histograms in LDS, flushed with integer atomics, so the result is a pure function of the inputs whatever
+ * the row streams, launch cuts and order.  rank_narrow_kernel walks a pair's 256 bins from the top, extends the prefix by the
+ * bin that holds the remaining rank and subtracts the rows above it.  A rank outside [0, total of the first histogram) marks
+ * the pair dead: key 0.  After the last digit the prefix is the key; hac_keys_to_results_device's kernel makes D / I.
+ * Passes over the rows per tile of 16 pairs: 4 score digits + the position digits in which two rows of the index can differ,
+ *   passes = 4 + ceil(bit_length(pos_base ^ (pos_base + ntotal - 1)) / 8)        (pos_base = 0 outside the keys form)
+ * i.e. 5 up to 256 rows, 6 up to 65 536, 7 up to 16.7M, 8 beyond; the higher position digits are the same for every row and
+ * the host fills them in.  Pairs go out in launches of 1024.  There is one path: no shortcut through search for shallow ranks.
+ * Cost (by arithmetic, NOT measured here; DESIGN.md section 2 records the one timing taken): ceil(nq * m / 16) * passes passes
+ * over the rows at the exact scan's stream rate -- 16 ranks of one query cost what 16 queries with one rank each cost; the
+ * epilogue looks at every group in the first pass and, behind the second digit, at almost none.  search_at = one entries_at of
+ * one rank per query plus one search_after page, at any depth.
+ *
+ * Host form: synchronous, on the index's own stream; queries, ranks and keys are staged in chunks of ~64 MiB like rank_ids.
+ * Device forms: 16-byte aligned q_dev; they enqueue on hip_stream and never read back; the number and shape of the launches
+ * depend on (nq, m) and the index's size only.  id_map_dev remaps I as in hac_index_search_device.  The keys form writes the
+ * packed keys [nq][m] with positions pos_base + row, in the key space of hac_index_search_keys_device and of
+ * hac_index_search_after_keys_device's cursors: an entry's key is the cursor of the page behind it.  The rule of the other keys
+ * forms holds for pos_base: pos_base + ntotal > 2^32 - 1 is HAC_ERR_UNSUPPORTED ("row positions exceed 32 bits") and nothing
+ * is enqueued.  The workspace (1040 bytes per pair of a launch, 8 more per pair of the call for the forms that return D / I)
+ * grows by the rule of the search workspaces: run one call of the largest (nq, m) before capturing into a HIP graph.
+ * Test switches (hac_index_set_option): "at_rank_p" = "auto" | 1..4096 row streams per pair tile, "debug_at_rank_tiles" = 0 | the
+ * most pair tiles per launch.  hac_index_last_plan afterwards reads "rank_hist_kernel<BITS=8> grid=(P,T) QT=.. passes=.. lds=..".
+ * Out of scope: multi-device (in-process sharded) indexes -- the position digits of shards whose rows map to index rows through
+ * several spans do not line up: all three entry points return HAC_ERR_UNSUPPORTED and write nothing;
+ * haconvdr_amd.sharded.ShardedSearcher -- with one contiguous shard_base per rank the histograms of the ranks simply add, which
+ * is why the keys form takes pos_base, but the per-pass all-reduce is not built; an fp16-prefilter or GEMM-shaped many-query
+ * route; ranks inside the masked / grouped / among / excluding variants. */
+int hac_index_entries_at(hac_index *idx, const float *q, int64_t nq, const int64_t *ranks, int64_t m, float *D, int64_t *I);
+int hac_index_entries_at_device(hac_index *idx, const float *q_dev, int64_t nq, const int64_t *ranks_dev, int64_t m, float *D_dev, int64_t *I_dev,
+                                const int64_t *id_map_dev, void *hip_stream);
+int hac_index_entries_at_keys_device(hac_index *idx, const float *q_dev, int64_t nq, const int64_t *ranks_dev, int64_t m, uint64_t *keys_dev,
+                                     uint32_t pos_base, void *hip_stream);
+
 /* ---- removing rows: faiss's IndexFlat::remove_ids(IDSelectorBatch(ids)), in place ------------------------------------------
  * The rows named by ids disappear; every surviving row keeps its bits and its relative order; the survivors are renumbered
  * densely from 0 -- survivor number j is row j of np.delete(x, unique(ids), axis=0) --; ntotal drops by the number of DISTINCT
@@ -604,6 +664,8 @@ int hac_index_last_status(hac_index *idx);
  * bitmap": row streams per query tile; the most query tiles per launch, 0 = by the list workspace).  Same bits either way.
  * "grouped_p" = "auto" | "1" .. "4096" and "debug_grouped_tiles" = integer >= 0: the same two switches of hac_index_search_grouped*
  * ("search by group").  Same bits either way.
+ * "after_p" / "debug_after_tiles" and "at_rank_p" / "debug_at_rank_tiles": the same pairs of hac_index_search_after* ("search behind
+ * a cursor") and hac_index_entries_at* ("entry at a rank").  Same bits either way.
  * Any other name or value is HAC_ERR_INVALID (never a silent default).
  * The HAC_<NAME> environment variables give the defaults and are read once, in hac_index_create. */
 int hac_index_set_option(hac_index *idx, const char *name, const char *value);
