@@ -39,10 +39,8 @@ __device__ __forceinline__ float after_score_cap(u64 bound) {
 // i is group i, i < a.n_items (all groups: no list).  Uses a.segs, a.nseg, a.q, a.nq, a.K4, a.k, a.C, a.QT, a.n_rows,
 // a.n_items, a.thr_glob, a.partial, a.partial_cnt, a.pos_base of ScanArgs; bounds: [a.nq] of this launch, or null (the start
 // for every query).
-// The loop is a COPY of scan16_kernel's -- the same ring, the same HAC_MFMA4 chain, the same sched_barrier placement, the same
-// candidate buffers, compaction, thr_glob exchange and flush_survivors -- not a shared __device__ function: that kernel's
-// register allocation is pinned by the comments in its loop and stays untouched by this file (as masked.inc and grouped.inc
-// did).  What must hold here:
+// Built from scan16_core.inc as scan16_kernel is: scan16_stage_queries, scan16_group_scores, scan16_row / rows_valid,
+// scan16_compact_round and scan16_flush; the row-stream cursor and the append epilogue are its own.  What must hold here:
 //   KEY TEST BEFORE APPEND  a row becomes a candidate only if make_key(s, pos_base + row) < bound, in addition to s >= th and
 //       row < rows_valid: never a selection first and a filter afterwards, which could leave fewer than k eligible rows in a
 //       list the selection has cut.
@@ -69,10 +67,7 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_after_kernel(ScanArgs 
     u32 *cnt = reinterpret_cast<u32 *>(cand + (size_t)QTr * C);            // [16]
     float *thr = reinterpret_cast<float *>(cnt + 16);                      // [16]
 
-    for (int idx = tid; idx < K4 * QTr; idx += SCAN_WAVES * 64) {
-        const int k4 = idx / QTr, j = idx - k4 * QTr;
-        ldsQ[idx] = as_global(a.q)[(size_t)(q0 + j) * K4 + k4];
-    }
+    scan16_stage_queries(ldsQ, a.q, K4, QTr, tid, [q0](int j) { return q0 + j; });
     if (tid < 16) {
         cnt[tid] = 0;
         thr[tid] = -INFINITY;
@@ -103,36 +98,8 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_after_kernel(ScanArgs 
         const bool have_next = nitem < a.n_items;
         f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (have) {
-            gf4ptr np = have_next ? group_ptr(a, nitem) + lane : gp;
-            const int NB = K4 / PF;
-            // clean entry state for the chunk loop (see scanq_kernel): counted vmcnt(PF-1) inside
-            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only, once per group
-            // B (query) fragments run one chunk ahead of the MFMAs; the sched_barrier after every
-            // chunk pins "consume ring[i] -> refill ring[i]" in program order (see scan16_kernel)
-            f4 bcur = qb[0], bnxt;
-            for (int tb = 0; tb < NB - 1; ++tb) {
-#pragma unroll
-                for (int i = 0; i < PF; ++i) {
-                    const int t = tb * PF + i;
-                    bnxt = qb[(t + 1) * QTr];
-                    const f4 av = ring[i];
-                    HAC_MFMA4(av, bcur)
-                    ring[i] = gp[(t + PF) * 64];   // refill AFTER the MFMAs that read ring[i] (see scan16_kernel)
-                    bcur = bnxt;
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < PF; ++i) {
-                const int t = (NB - 1) * PF + i;
-                bnxt = qb[(i + 1 < PF ? t + 1 : 0) * QTr];
-                const f4 av = ring[i];
-                HAC_MFMA4(av, bcur)
-                ring[i] = np[i * 64];  // next group's first chunks stay in flight across the epilogue
-                bcur = bnxt;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            gp = np;
+            const gf4ptr np = have_next ? group_ptr(a, nitem) + lane : gp;
+            scan16_group_scores(acc, ring, gp, np, qb, QTr, K4);
         }
 
         __syncthreads();  // (A) last round's compactions are complete
@@ -142,15 +109,13 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_after_kernel(ScanArgs 
 #pragma unroll
             for (int rr = 0; rr < 16; ++rr) anyp |= (acc[rr] >= th && acc[rr] <= cap);
             if (__any(anyp)) {
-                const long rem = a.n_rows - (long)g * GROUP_ROWS;
-                const int rows_valid = rem < GROUP_ROWS ? (int)rem : GROUP_ROWS;   // rows behind it: zeros, or stale after reset() + a smaller add()
-                const int rbase = 4 * (lane >> 4);
+                const int nvalid = rows_valid(a.n_rows, g);
                 if (j < QTr) {
 #pragma unroll
                     for (int rr = 0; rr < 16; ++rr) {
-                        const int row = 16 * (rr >> 2) + rbase + (rr & 3);
+                        const int row = scan16_row(rr, lane);
                         const float s = acc[rr];
-                        if (s >= th && row < rows_valid) {   // (a NaN score fails s >= th: th is -inf or a score)
+                        if (s >= th && row < nvalid) {   // (a NaN score fails s >= th: th is -inf or a score)
                             const u64 key = make_key(s, a.pos_base + g * GROUP_ROWS + row);
                             if (key < bound) {   // KEY TEST BEFORE APPEND
                                 const u32 pos = atomicAdd(&cnt[j], 1u);
@@ -162,35 +127,12 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_after_kernel(ScanArgs 
             }
         }
         __syncthreads();  // (B) all appends of this round are visible
-        for (int jj = w; jj < QTr; jj += SCAN_WAVES) {
-            const u32 n = cnt[jj];
-            float t_new = -INFINITY;
-            if (n > hw) {  // wave-uniform
-                wave_sort_desc(cand + (size_t)jj * C, n, lane);
-                t_new = ord2f((u32)(cand[(size_t)jj * C + a.k - 1] >> 32));   // THRESHOLDS FROM ELIGIBLE ROWS ONLY: the buffer holds nothing else
-            }
-            if (lane == 0) {
-                float t_cur = thr[jj];
-                if (n > hw) {
-                    cnt[jj] = a.k;
-                    if (t_new > t_cur) {
-                        t_cur = t_new;
-                        atomicMax(&a.thr_glob[q0 + jj], f2ord(t_new));
-                    }
-                }
-                const u32 go = __hip_atomic_load(&a.thr_glob[q0 + jj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (go != 0u) t_cur = fmaxf(t_cur, ord2f(go));
-                thr[jj] = t_cur;
-            }
-        }
+        // THRESHOLDS FROM ELIGIBLE ROWS ONLY: the buffers hold nothing else
+        scan16_compact_round(cand, cnt, thr, a.thr_glob + q0, C, a.k, hw, QTr, w, lane);
         item = nitem;
         have = have_next;
     }
 
     __syncthreads();
-    for (int jj = w; jj < QTr; jj += SCAN_WAVES) {
-        const u32 n = cnt[jj];
-        u64 *b = cand + (size_t)jj * C;
-        flush_survivors(a, gridDim.x, q0 + jj, b, n, lane);
-    }
+    scan16_flush(a, gridDim.x, q0, QTr, cand, cnt, C, w, lane);
 }

@@ -29,7 +29,8 @@ constexpr size_t at_rank_lds(int K4, int QT, int BITS) { return (size_t)K4 * QT 
 
 // Workgroup = (row stream blockIdx.x, tile of <= 16 pairs blockIdx.y).  Uses a.segs, a.nseg, a.q (the queries of the whole
 // call), a.nq (the PAIRS of this launch), a.K4, a.QT, a.n_rows, a.n_items (groups, from group 0), a.pos_base of ScanArgs.
-// The inner loop is a copy of count_ahead_kernel's (rank.inc says why it is not a shared __device__ function).
+// Built from scan16_core.inc as count_ahead_kernel is: scan16_stage_queries (a slot's row of a.q is its pair's query),
+// scan16_group_scores, scan16_row / rows_valid; the row-stream cursor is written out here.
 // The epilogue: every (pair, row) with a non-NaN score and row < n_rows whose key agrees with the pair's prefix above the digit
 // adds 1 to bin digit(key) of the pair's histogram in LDS; the workgroup's histograms go to global memory with one integer
 // atomic per non-empty bin.  Integer sums: the result is a pure function of the inputs, whatever P, the launch cuts, the order.
@@ -58,11 +59,7 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void rank_hist_kernel(ScanArgs a, 
     u64 *pfx = reinterpret_cast<u64 *>(hist + 16 * BINS);                       // [16]
     u32 *alive = reinterpret_cast<u32 *>(pfx + 16);                             // [16]
 
-    for (int idx = tid; idx < K4 * QTr; idx += SCAN_WAVES * 64) {
-        const int k4 = idx / QTr, j = idx - k4 * QTr;
-        const long qi = (ra.pair0 + q0 + j) / ra.m;   // the pair's query
-        ldsQ[idx] = as_global(a.q)[(size_t)qi * K4 + k4];
-    }
+    scan16_stage_queries(ldsQ, a.q, K4, QTr, tid, [&](int j) { return (ra.pair0 + q0 + j) / ra.m; });   // the pair's query
     for (int i = tid; i < 16 * BINS; i += SCAN_WAVES * 64) hist[i] = 0u;
     if (tid < 16) {
         bool live = tid < QTr;
@@ -100,33 +97,8 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void rank_hist_kernel(ScanArgs a, 
         const bool have_next = nitem < a.n_items;
         f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (have) {
-            gf4ptr np = have_next ? group_ptr(a, nitem) + lane : gp;
-            const int NB = K4 / PF;
-            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only, once per group (see scan16_kernel)
-            f4 bcur = qb[0], bnxt;
-            for (int tb = 0; tb < NB - 1; ++tb) {
-#pragma unroll
-                for (int i = 0; i < PF; ++i) {
-                    const int t = tb * PF + i;
-                    bnxt = qb[(t + 1) * QTr];
-                    const f4 av = ring[i];
-                    HAC_MFMA4(av, bcur)
-                    ring[i] = gp[(t + PF) * 64];   // refill after the MFMAs that read the slot
-                    bcur = bnxt;
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < PF; ++i) {
-                const int t = (NB - 1) * PF + i;
-                bnxt = qb[(i + 1 < PF ? t + 1 : 0) * QTr];
-                const f4 av = ring[i];
-                HAC_MFMA4(av, bcur)
-                ring[i] = np[i * 64];  // next group's first chunks stay in flight across the epilogue
-                bcur = bnxt;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            gp = np;
+            const gf4ptr np = have_next ? group_ptr(a, nitem) + lane : gp;
+            scan16_group_scores(acc, ring, gp, np, qb, QTr, K4);
 
             // GATE (a NaN score may pass it: the epilogue drops it; rows past n_rows that pass are masked below)
             bool anyp = live && first;
@@ -136,16 +108,14 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void rank_hist_kernel(ScanArgs a, 
                 anyp = anyp && live;
             }
             if (__any(anyp)) {
-                const long rem = a.n_rows - (long)g * GROUP_ROWS;
-                const int rows_valid = rem < GROUP_ROWS ? (int)rem : GROUP_ROWS;   // rows behind it: zeros, or stale after reset() + a smaller add()
-                const int rbase = 4 * (lane >> 4);
+                const int nvalid = rows_valid(a.n_rows, g);
                 if (live) {
                     u32 cd = 0u, cc = 0u;   // CONTENTION: the run of equal digits so far
 #pragma unroll
                     for (int rr = 0; rr < 16; ++rr) {
-                        const int row = 16 * (rr >> 2) + rbase + (rr & 3);
+                        const int row = scan16_row(rr, lane);
                         const float s = acc[rr];
-                        if (s == s && row < rows_valid) {
+                        if (s == s && row < nvalid) {
                             const u64 key = make_key(s, a.pos_base + g * GROUP_ROWS + row);
                             if (first || ((key ^ prefix) >> hs) == 0ull) {
                                 const u32 dg = (u32)(key >> shift) & (u32)(BINS - 1);

@@ -467,6 +467,8 @@ __device__ __forceinline__ void flush_survivors(const ScanArgs &a, u32 n_streams
     acc = __builtin_amdgcn_mfma_f32_16x16x1f32((av).z, (bv).z, acc, 0, 0, 0);    \
     acc = __builtin_amdgcn_mfma_f32_16x16x1f32((av).w, (bv).w, acc, 0, 0, 0);
 
+#include "scan16_core.inc"
+
 __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_kernel(ScanArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
@@ -484,10 +486,7 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_kernel(ScanArgs a) {
     u32 *cnt = reinterpret_cast<u32 *>(cand + (size_t)QTr * C);            // [16]
     float *thr = reinterpret_cast<float *>(cnt + 16);                      // [16]
 
-    for (int idx = tid; idx < K4 * QTr; idx += SCAN_WAVES * 64) {
-        const int k4 = idx / QTr, j = idx - k4 * QTr;
-        ldsQ[idx] = as_global(a.q)[(size_t)(q0 + j) * K4 + k4];
-    }
+    scan16_stage_queries(ldsQ, a.q, K4, QTr, tid, [q0](int j) { return q0 + j; });
     if (tid < 16) {
         cnt[tid] = 0;
         thr[tid] = (tid < QTr && a.thr_init) ? a.thr_init[q0 + tid] : -INFINITY;
@@ -514,40 +513,8 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_kernel(ScanArgs a) {
         const bool have_next = nitem < a.n_items;
         f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (have) {
-            gf4ptr np = have_next ? group_ptr(a, a.g_first + nitem * a.g_step) + lane : gp;
-            const int NB = K4 / PF;
-            // clean entry state for the chunk loop (see scanq_kernel): counted vmcnt(PF-1) inside
-            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only, once per group
-            // B (query) fragments run one chunk ahead of the MFMAs; the sched_barrier after every
-            // chunk pins "consume ring[i] -> refill ring[i]" in program order, otherwise hipcc
-            // clusters the eight refills at the end of the block and waits vmcnt(0) on them.
-            f4 bcur = qb[0], bnxt;
-            for (int tb = 0; tb < NB - 1; ++tb) {
-#pragma unroll
-                for (int i = 0; i < PF; ++i) {
-                    const int t = tb * PF + i;
-                    bnxt = qb[(t + 1) * QTr];
-                    const f4 av = ring[i];
-                    HAC_MFMA4(av, bcur)
-                    // refill AFTER the MFMAs that read ring[i]: the load can then reuse the register;
-                    // issued before them it gets a fresh one and hipcc copies it back at the loop
-                    // end behind vmcnt(7)...vmcnt(0) — a full drain every PF chunks
-                    ring[i] = gp[(t + PF) * 64];
-                    bcur = bnxt;
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < PF; ++i) {
-                const int t = (NB - 1) * PF + i;
-                bnxt = qb[(i + 1 < PF ? t + 1 : 0) * QTr];
-                const f4 av = ring[i];
-                HAC_MFMA4(av, bcur)
-                ring[i] = np[i * 64];  // next group's first chunks stay in flight across the epilogue
-                bcur = bnxt;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            gp = np;
+            const gf4ptr np = have_next ? group_ptr(a, a.g_first + nitem * a.g_step) + lane : gp;
+            scan16_group_scores(acc, ring, gp, np, qb, QTr, K4);
         }
 
         __syncthreads();  // (A) last round's compactions are complete
@@ -557,15 +524,13 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_kernel(ScanArgs a) {
 #pragma unroll
             for (int rr = 0; rr < 16; ++rr) anyp |= (acc[rr] >= th);
             if (__any(anyp)) {
-                const long rem = a.n_rows - (long)g * GROUP_ROWS;
-                const int rows_valid = rem < GROUP_ROWS ? (int)rem : GROUP_ROWS;
-                const int rbase = 4 * (lane >> 4);
+                const int nvalid = rows_valid(a.n_rows, g);
                 if (j < QTr) {
 #pragma unroll
                     for (int rr = 0; rr < 16; ++rr) {
-                        const int row = 16 * (rr >> 2) + rbase + (rr & 3);
+                        const int row = scan16_row(rr, lane);
                         const float s = acc[rr];
-                        if (s >= th && row < rows_valid) {
+                        if (s >= th && row < nvalid) {
                             const u32 pos = atomicAdd(&cnt[j], 1u);
                             cand[(size_t)j * C + pos] = make_key(s, a.pos_base + g * GROUP_ROWS + row);
                         }
@@ -574,37 +539,13 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_kernel(ScanArgs a) {
             }
         }
         __syncthreads();  // (B) all appends of this round are visible
-        for (int jj = w; jj < QTr; jj += SCAN_WAVES) {
-            const u32 n = cnt[jj];
-            float t_new = -INFINITY;
-            if (n > hw) {  // wave-uniform
-                wave_sort_desc(cand + (size_t)jj * C, n, lane);
-                t_new = ord2f((u32)(cand[(size_t)jj * C + a.k - 1] >> 32));
-            }
-            if (lane == 0) {
-                float t_cur = thr[jj];
-                if (n > hw) {
-                    cnt[jj] = a.k;
-                    if (t_new > t_cur) {
-                        t_cur = t_new;
-                        atomicMax(&a.thr_glob[q0 + jj], f2ord(t_new));
-                    }
-                }
-                const u32 go = __hip_atomic_load(&a.thr_glob[q0 + jj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (go != 0u) t_cur = fmaxf(t_cur, ord2f(go));
-                thr[jj] = t_cur;
-            }
-        }
+        scan16_compact_round(cand, cnt, thr, a.thr_glob + q0, C, a.k, hw, QTr, w, lane);
         item = nitem;
         have = have_next;
     }
 
     __syncthreads();
-    for (int jj = w; jj < QTr; jj += SCAN_WAVES) {
-        const u32 n = cnt[jj];
-        u64 *b = cand + (size_t)jj * C;
-        flush_survivors(a, vg.nx, q0 + jj, b, n, lane);
-    }
+    scan16_flush(a, vg.nx, q0, QTr, cand, cnt, C, w, lane);
 }
 
 // ------------------------------------------------------------------ scan kernel, many queries

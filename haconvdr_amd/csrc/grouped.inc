@@ -63,10 +63,10 @@ __device__ u32 wave_dedup(u64 *buf, u64 *scr, u32 n, u32 k, const GroupArgs &g, 
 // scan16_kernel with per-label candidate lists.  Workgroup = (row stream blockIdx.x, tile of <= QT queries blockIdx.y); uses
 // a.segs, a.nseg, a.q, a.nq, a.K4, a.k, a.C, a.QT, a.n_rows, a.n_items, a.thr_glob, a.partial, a.partial_cnt, a.pos_base of
 // ScanArgs (a.thr_init is not read: there is no seeding and no fp16 prefilter, a sample of rows says nothing about groups).
-// The loop is a COPY of scan16_kernel's -- the same row stream, the same HAC_MFMA4 chain, the same ring and sched_barrier
-// placement, the same append epilogue and flush_survivors -- not a shared __device__ function: that kernel's register allocation
-// is pinned by the comments in its loop and stays untouched by this file (as masked.inc did).  LDS: scan16's, plus one scratch
-// array u64 [C] per compacting wave ([min(SCAN_WAVES, QTr)][C]).  What must hold here:
+// Built from scan16_core.inc as scan16_kernel is: scan16_stage_queries, scan16_group_scores, scan16_row / rows_valid; the
+// row-stream cursor and the append epilogue are its own copies of scan16_kernel's, the compaction round and the flush are its
+// own dedup variants.  LDS: scan16's, plus one scratch array u64 [C] per compacting wave ([min(SCAN_WAVES, QTr)][C]).  What
+// must hold here:
 //   DEDUP BEFORE THRESHOLD  a threshold is the k-th key of a compaction that left k DISTINCT labels: the k-th best of k distinct
 //       groups' entries, hence a proven lower bound of the k-th group score (every group's representative is at least its entry).
 //       A row below it can be no group's representative in the answer.  A threshold only filters such rows, so the result does
@@ -97,10 +97,7 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_grouped_kernel(ScanArg
     float *thr = reinterpret_cast<float *>(cnt + 16);                      // [16]
     u64 *scr = scratch + (size_t)min(w, QTr - 1) * C;
 
-    for (int idx = tid; idx < K4 * QTr; idx += SCAN_WAVES * 64) {
-        const int k4 = idx / QTr, j = idx - k4 * QTr;
-        ldsQ[idx] = as_global(a.q)[(size_t)(q0 + j) * K4 + k4];
-    }
+    scan16_stage_queries(ldsQ, a.q, K4, QTr, tid, [q0](int j) { return q0 + j; });
     if (tid < 16) {
         cnt[tid] = 0;
         thr[tid] = -INFINITY;
@@ -114,7 +111,7 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_grouped_kernel(ScanArg
     const u32 nrounds = (a.n_items + stride - 1) / stride;
     const u32 hw = (u32)C - 64u * SCAN_WAVES;  // compaction high-water mark (>= k)
 
-    // Uniform values that only the epilogue and the compactions use live in vector registers: the copy has the labels and the
+    // Uniform values that only the epilogue and the compactions use live in vector registers: this kernel has the labels and the
     // scratch array more than scan16_kernel to keep in scalar ones, which are full there (no spills; masked.inc does the same)
     u32 pos_base = a.pos_base;
     u32 *tglob = a.thr_glob + q0;
@@ -136,36 +133,8 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_grouped_kernel(ScanArg
         const bool have_next = nitem < a.n_items;
         f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (have) {
-            gf4ptr np = have_next ? group_ptr(a, nitem) + lane : gp;
-            const int NB = K4 / PF;
-            // clean entry state for the chunk loop (see scanq_kernel): counted vmcnt(PF-1) inside
-            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only, once per group
-            // B (query) fragments run one chunk ahead of the MFMAs; the sched_barrier after every
-            // chunk pins "consume ring[i] -> refill ring[i]" in program order (see scan16_kernel)
-            f4 bcur = qb[0], bnxt;
-            for (int tb = 0; tb < NB - 1; ++tb) {
-#pragma unroll
-                for (int i = 0; i < PF; ++i) {
-                    const int t = tb * PF + i;
-                    bnxt = qb[(t + 1) * QTr];
-                    const f4 av = ring[i];
-                    HAC_MFMA4(av, bcur)
-                    ring[i] = gp[(t + PF) * 64];   // refill AFTER the MFMAs that read ring[i] (see scan16_kernel)
-                    bcur = bnxt;
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < PF; ++i) {
-                const int t = (NB - 1) * PF + i;
-                bnxt = qb[(i + 1 < PF ? t + 1 : 0) * QTr];
-                const f4 av = ring[i];
-                HAC_MFMA4(av, bcur)
-                ring[i] = np[i * 64];  // next group's first chunks stay in flight across the epilogue
-                bcur = bnxt;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            gp = np;
+            const gf4ptr np = have_next ? group_ptr(a, nitem) + lane : gp;
+            scan16_group_scores(acc, ring, gp, np, qb, QTr, K4);
         }
 
         __syncthreads();  // (A) last round's compactions are complete
@@ -175,15 +144,13 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_grouped_kernel(ScanArg
 #pragma unroll
             for (int rr = 0; rr < 16; ++rr) anyp |= (acc[rr] >= th);
             if (__any(anyp)) {
-                const long rem = n_rows - (long)g * GROUP_ROWS;
-                const int rows_valid = rem < GROUP_ROWS ? (int)rem : GROUP_ROWS;   // rows behind it: zeros, or stale after reset() + a smaller add()
-                const int rbase = 4 * (lane >> 4);
+                const int nvalid = rows_valid(n_rows, g);
                 if (j < QTr) {
 #pragma unroll
                     for (int rr = 0; rr < 16; ++rr) {
-                        const int row = 16 * (rr >> 2) + rbase + (rr & 3);
+                        const int row = scan16_row(rr, lane);
                         const float s = acc[rr];
-                        if (s >= th && row < rows_valid) {   // (a NaN score fails s >= th: th is -inf or a score)
+                        if (s >= th && row < nvalid) {   // (a NaN score fails s >= th: th is -inf or a score)
                             const u32 pos = atomicAdd(&cnt[j], 1u);
                             cand[(size_t)j * C + pos] = make_key(s, pos_base + g * GROUP_ROWS + row);
                         }

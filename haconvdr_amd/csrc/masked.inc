@@ -60,9 +60,9 @@ __global__ __launch_bounds__(256) void mask_groups_kernel(MaskArgs m, int nq, in
 // of the tile is group groups[tile][i], i < n_groups[tile].  Uses a.segs, a.nseg, a.q, a.nq, a.K4, a.k, a.C, a.QT, a.n_rows,
 // a.thr_glob, a.partial, a.partial_cnt, a.pos_base of ScanArgs (a.thr_init is not read: there is no seeding, a sample of
 // unmasked rows would give bounds the masked set cannot meet).
-// The loop is a COPY of scan16_kernel's -- the same ring, the same HAC_MFMA4 chain, the same sched_barrier placement, the same
-// candidate buffers, compaction and flush_survivors -- not a shared __device__ function: that kernel's register allocation is
-// pinned by the comments in its loop and stays untouched by this file (as rank.inc and range.inc did).  What must hold here:
+// Built from scan16_core.inc as scan16_kernel is: scan16_stage_queries, scan16_group_wait and scan16_group_mfma (the next group's mask
+// word is loaded between them), scan16_row / rows_valid, scan16_compact_round and scan16_flush; the cursor over the list and the
+// append epilogue are its own.  What must hold here:
 //   BIT TEST BEFORE APPEND  a row becomes a candidate only if the lane's own query's mask word has its bit: never a selection
 //       first and a filter afterwards, which could leave fewer than k selected rows in a list the selection has cut.
 //   THRESHOLDS FROM SELECTED ROWS ONLY  hence every key in a candidate buffer is a selected row's, and a threshold -- the k-th key
@@ -91,10 +91,7 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_masked_kernel(ScanArgs
     u32 *cnt = reinterpret_cast<u32 *>(cand + (size_t)QTr * C);            // [16]
     float *thr = reinterpret_cast<float *>(cnt + 16);                      // [16]
 
-    for (int idx = tid; idx < K4 * QTr; idx += SCAN_WAVES * 64) {
-        const int k4 = idx / QTr, j = idx - k4 * QTr;
-        ldsQ[idx] = as_global(a.q)[(size_t)(q0 + j) * K4 + k4];
-    }
+    scan16_stage_queries(ldsQ, a.q, K4, QTr, tid, [q0](int j) { return q0 + j; });
     if (tid < 16) {
         cnt[tid] = 0;
         thr[tid] = -INFINITY;
@@ -112,7 +109,7 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_masked_kernel(ScanArgs
     const long mi = j < QTr ? mask_row(m, q0 + j) : -1l;
     gu64ptr mrow = (gu64ptr)(m.masks + (size_t)(mi >= 0 ? mi : 0) * m.words);
 
-    // Uniform values the epilogue and the compaction use in vector instructions only live in vector registers: the copy has the
+    // Uniform values the epilogue and the compaction use in vector instructions only live in vector registers: this kernel has the
     // list pointer and two group numbers more than scan16_kernel to keep in scalar ones, which are full there (no spills)
     u32 pos_base = a.pos_base;
     u32 *tglob = a.thr_glob + q0;
@@ -135,38 +132,11 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_masked_kernel(ScanArgs
         f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (have) {
             if (have_next) g_next = list[nitem];
-            gf4ptr np = have_next ? group_ptr(a, g_next) + lane : gp;
-            const int NB = K4 / PF;
-            // clean entry state for the chunk loop (see scanq_kernel): counted vmcnt(PF-1) inside
-            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only, once per group
+            const gf4ptr np = have_next ? group_ptr(a, g_next) + lane : gp;
+            scan16_group_wait();
             // the next group's mask word travels under this group's MFMAs (g_next == g without a next group: a live address)
             mw_next = mrow[g_next];
-            // B (query) fragments run one chunk ahead of the MFMAs; the sched_barrier after every
-            // chunk pins "consume ring[i] -> refill ring[i]" in program order (see scan16_kernel)
-            f4 bcur = qb[0], bnxt;
-            for (int tb = 0; tb < NB - 1; ++tb) {
-#pragma unroll
-                for (int i = 0; i < PF; ++i) {
-                    const int t = tb * PF + i;
-                    bnxt = qb[(t + 1) * QTr];
-                    const f4 av = ring[i];
-                    HAC_MFMA4(av, bcur)
-                    ring[i] = gp[(t + PF) * 64];   // refill AFTER the MFMAs that read ring[i] (see scan16_kernel)
-                    bcur = bnxt;
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < PF; ++i) {
-                const int t = (NB - 1) * PF + i;
-                bnxt = qb[(i + 1 < PF ? t + 1 : 0) * QTr];
-                const f4 av = ring[i];
-                HAC_MFMA4(av, bcur)
-                ring[i] = np[i * 64];  // next group's first chunks stay in flight across the epilogue
-                bcur = bnxt;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            gp = np;
+            scan16_group_mfma(acc, ring, gp, np, qb, QTr, K4);
         }
 
         __syncthreads();  // (A) last round's compactions are complete
@@ -177,16 +147,14 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_masked_kernel(ScanArgs
 #pragma unroll
             for (int rr = 0; rr < 16; ++rr) anyp |= (acc[rr] >= th);
             if (__any(anyp && sel != 0ull)) {
-                const long rem = a.n_rows - (long)g * GROUP_ROWS;
-                const int rows_valid = rem < GROUP_ROWS ? (int)rem : GROUP_ROWS;   // rows behind it: zeros, or stale after reset() + a smaller add()
-                const int rbase = 4 * (lane >> 4);
+                const int nvalid = rows_valid(a.n_rows, g);
                 if (j < QTr) {
 #pragma unroll
                     for (int rr = 0; rr < 16; ++rr) {
-                        const int row = 16 * (rr >> 2) + rbase + (rr & 3);
+                        const int row = scan16_row(rr, lane);
                         const float s = acc[rr];
                         // BIT TEST BEFORE APPEND (a NaN score fails s >= th: th is -inf or a score)
-                        if (s >= th && row < rows_valid && ((sel >> row) & 1ull)) {
+                        if (s >= th && row < nvalid && ((sel >> row) & 1ull)) {
                             const u32 pos = atomicAdd(&cnt[j], 1u);
                             cand[(size_t)j * C + pos] = make_key(s, pos_base + g * GROUP_ROWS + row);
                         }
@@ -195,27 +163,8 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_masked_kernel(ScanArgs
             }
         }
         __syncthreads();  // (B) all appends of this round are visible
-        for (int jj = w; jj < QTr; jj += SCAN_WAVES) {
-            const u32 n = cnt[jj];
-            float t_new = -INFINITY;
-            if (n > hw) {  // wave-uniform
-                wave_sort_desc(cand + (size_t)jj * C, n, lane);
-                t_new = ord2f((u32)(cand[(size_t)jj * C + a.k - 1] >> 32));   // THRESHOLDS FROM SELECTED ROWS ONLY: the buffer holds nothing else
-            }
-            if (lane == 0) {
-                float t_cur = thr[jj];
-                if (n > hw) {
-                    cnt[jj] = a.k;
-                    if (t_new > t_cur) {
-                        t_cur = t_new;
-                        atomicMax(&tglob[jj], f2ord(t_new));
-                    }
-                }
-                const u32 go = __hip_atomic_load(&tglob[jj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (go != 0u) t_cur = fmaxf(t_cur, ord2f(go));
-                thr[jj] = t_cur;
-            }
-        }
+        // THRESHOLDS FROM SELECTED ROWS ONLY: the buffers hold nothing else
+        scan16_compact_round(cand, cnt, thr, tglob, C, a.k, hw, QTr, w, lane);
         item = nitem;
         have = have_next;
         g = g_next;
@@ -223,9 +172,5 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_masked_kernel(ScanArgs
     }
 
     __syncthreads();
-    for (int jj = w; jj < QTr; jj += SCAN_WAVES) {
-        const u32 n = cnt[jj];
-        u64 *b = cand + (size_t)jj * C;
-        flush_survivors(a, gridDim.x, q0 + jj, b, n, lane);
-    }
+    scan16_flush(a, gridDim.x, q0, QTr, cand, cnt, C, w, lane);
 }

@@ -32,8 +32,8 @@ constexpr int RANGE_CURSOR = 0, RANGE_TOTAL = 1, RANGE_FITS = 2, RANGE_CTL_WORDS
 constexpr size_t range_lds(int K4, int QT) { return (size_t)K4 * QT * 16 + 64 + (size_t)SCAN_WAVES * 16 * 4; }
 
 // Workgroup = (row stream blockIdx.x, tile of <= 16 queries blockIdx.y).  Uses a.segs, a.nseg, a.q, a.nq, a.K4, a.QT, a.n_rows,
-// a.n_items (groups, from group 0) of ScanArgs.  The inner loop is a copy of count_ahead_kernel's (rank.inc says why it is
-// not shared).
+// a.n_items (groups, from group 0) of ScanArgs.  Built from scan16_core.inc as count_ahead_kernel is: scan16_stage_queries,
+// scan16_group_scores, scan16_row / rows_valid; the row-stream cursor is written out here.
 __global__ __launch_bounds__(SCAN_WAVES * 64) void range_emit_kernel(ScanArgs a, RangeArgs ra) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
@@ -47,10 +47,7 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void range_emit_kernel(ScanArgs a,
     float *rad_lds = reinterpret_cast<float *>(smem + (size_t)K4 * a.QT * 16);      // [16]
     u32 *red = reinterpret_cast<u32 *>(rad_lds + 16);                               // [SCAN_WAVES][16]
 
-    for (int idx = tid; idx < K4 * QTr; idx += SCAN_WAVES * 64) {
-        const int k4 = idx / QTr, j = idx - k4 * QTr;
-        ldsQ[idx] = as_global(a.q)[(size_t)(q0 + j) * K4 + k4];
-    }
+    scan16_stage_queries(ldsQ, a.q, K4, QTr, tid, [q0](int j) { return q0 + j; });
     // a slot past the tile gets the radius no score exceeds (so does a NaN radius, by the compare itself)
     if (tid < 16) rad_lds[tid] = tid < QTr ? ra.radius[q0 + tid] : INFINITY;
     __syncthreads();
@@ -76,33 +73,8 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void range_emit_kernel(ScanArgs a,
         const bool have_next = nitem < a.n_items;
         f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (have) {
-            gf4ptr np = have_next ? group_ptr(a, nitem) + lane : gp;
-            const int NB = K4 / PF;
-            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only, once per group (see scan16_kernel)
-            f4 bcur = qb[0], bnxt;
-            for (int tb = 0; tb < NB - 1; ++tb) {
-#pragma unroll
-                for (int i = 0; i < PF; ++i) {
-                    const int t = tb * PF + i;
-                    bnxt = qb[(t + 1) * QTr];
-                    const f4 av = ring[i];
-                    HAC_MFMA4(av, bcur)
-                    ring[i] = gp[(t + PF) * 64];   // refill after the MFMAs that read the slot
-                    bcur = bnxt;
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < PF; ++i) {
-                const int t = (NB - 1) * PF + i;
-                bnxt = qb[(i + 1 < PF ? t + 1 : 0) * QTr];
-                const f4 av = ring[i];
-                HAC_MFMA4(av, bcur)
-                ring[i] = np[i * 64];  // next group's first chunks stay in flight across the epilogue
-                bcur = bnxt;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            gp = np;
+            const gf4ptr np = have_next ? group_ptr(a, nitem) + lane : gp;
+            scan16_group_scores(acc, ring, gp, np, qb, QTr, K4);
 
             // a group none of whose scores exceeds its query's radius emits nothing: the common case
             // (a NaN score or radius compares false; rows past n_rows that pass are masked below)
@@ -110,15 +82,10 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void range_emit_kernel(ScanArgs a,
 #pragma unroll
             for (int rr = 0; rr < 16; ++rr) anyp |= (acc[rr] > rad);
             if (__any(anyp)) {
-                const long rem = a.n_rows - (long)g * GROUP_ROWS;
-                const int rows_valid = rem < GROUP_ROWS ? (int)rem : GROUP_ROWS;   // rows behind it: zeros, or stale after reset() + a smaller add()
-                const int rbase = 4 * (lane >> 4);
+                const int nvalid = rows_valid(a.n_rows, g);
                 u32 tot = 0;   // wave-uniform: the wave's hits in this group
 #pragma unroll
-                for (int rr = 0; rr < 16; ++rr) {
-                    const int row = 16 * (rr >> 2) + rbase + (rr & 3);
-                    tot += (u32)__popcll(__ballot(acc[rr] > rad && row < rows_valid));
-                }
+                for (int rr = 0; rr < 16; ++rr) tot += (u32)__popcll(__ballot(acc[rr] > rad && scan16_row(rr, lane) < nvalid));
                 if (tot != 0u) {
                     // one atomic per wave and group: the wave's pairs are a dense run of the staging buffer, a lane's slot
                     // is the run's start + the hits before it (ballot + prefix)
@@ -132,9 +99,9 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void range_emit_kernel(ScanArgs a,
                     u32 base = 0;
 #pragma unroll
                     for (int rr = 0; rr < 16; ++rr) {
-                        const int row = 16 * (rr >> 2) + rbase + (rr & 3);
+                        const int row = scan16_row(rr, lane);
                         const float s = acc[rr];
-                        const bool hit = s > rad && row < rows_valid;
+                        const bool hit = s > rad && row < nvalid;
                         const u64 vote = __ballot(hit);
                         if (hit) {
                             const u64 at = start + base + (u32)__popcll(vote & below);

@@ -21,8 +21,8 @@ constexpr size_t rank_lds(int K4, int QT, int MT) { return (size_t)K4 * QT * 16 
 
 // Workgroup = (row stream blockIdx.x, tile of <= 16 queries blockIdx.y, chunk of MT references blockIdx.z).  Uses a.segs, a.nseg,
 // a.q, a.nq, a.K4, a.QT, a.n_rows, a.n_items (groups, from group 0) of ScanArgs.
-// The inner loop is a copy of scan16_kernel's, not a shared __device__ function: that kernel's register allocation is pinned
-// by the comments in its loop and stays untouched by this file.
+// Built from scan16_core.inc: scan16_stage_queries, scan16_group_scores, scan16_row / rows_valid; the row-stream cursor is
+// written out here, and the waves of a workgroup meet at no barrier inside it.
 template <int MT>
 __global__ __launch_bounds__(SCAN_WAVES * 64) void count_ahead_kernel(ScanArgs a, RankArgs ra) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -39,10 +39,7 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void count_ahead_kernel(ScanArgs a
     float *minref = reinterpret_cast<float *>(refkey + 16 * MT);                    // [16]
     u32 *red = reinterpret_cast<u32 *>(minref + 16);                                // [SCAN_WAVES][16][MT]
 
-    for (int idx = tid; idx < K4 * QTr; idx += SCAN_WAVES * 64) {
-        const int k4 = idx / QTr, j = idx - k4 * QTr;
-        ldsQ[idx] = as_global(a.q)[(size_t)(q0 + j) * K4 + k4];
-    }
+    scan16_stage_queries(ldsQ, a.q, K4, QTr, tid, [q0](int j) { return q0 + j; });
     // the references of this chunk as keys; one that can never be behind a row (NaN score, negative bound, a slot past m or
     // past the tile) is the all-ones key, which no row's key exceeds
     if (tid < 16) {
@@ -88,33 +85,8 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void count_ahead_kernel(ScanArgs a
         const bool have_next = nitem < a.n_items;
         f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (have) {
-            gf4ptr np = have_next ? group_ptr(a, nitem) + lane : gp;
-            const int NB = K4 / PF;
-            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only, once per group (see scan16_kernel)
-            f4 bcur = qb[0], bnxt;
-            for (int tb = 0; tb < NB - 1; ++tb) {
-#pragma unroll
-                for (int i = 0; i < PF; ++i) {
-                    const int t = tb * PF + i;
-                    bnxt = qb[(t + 1) * QTr];
-                    const f4 av = ring[i];
-                    HAC_MFMA4(av, bcur)
-                    ring[i] = gp[(t + PF) * 64];   // refill after the MFMAs that read the slot
-                    bcur = bnxt;
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < PF; ++i) {
-                const int t = (NB - 1) * PF + i;
-                bnxt = qb[(i + 1 < PF ? t + 1 : 0) * QTr];
-                const f4 av = ring[i];
-                HAC_MFMA4(av, bcur)
-                ring[i] = np[i * 64];  // next group's first chunks stay in flight across the epilogue
-                bcur = bnxt;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            gp = np;
+            const gf4ptr np = have_next ? group_ptr(a, nitem) + lane : gp;
+            scan16_group_scores(acc, ring, gp, np, qb, QTr, K4);
 
             // a group none of whose scores reaches the chunk's smallest reference score counts for nothing: the common case
             // (a NaN score compares false; rows past n_rows that pass are masked below)
@@ -122,18 +94,16 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void count_ahead_kernel(ScanArgs a
 #pragma unroll
             for (int rr = 0; rr < 16; ++rr) anyp |= (acc[rr] >= mref);
             if (__any(anyp)) {
-                const long rem = a.n_rows - (long)g * GROUP_ROWS;
-                const int rows_valid = rem < GROUP_ROWS ? (int)rem : GROUP_ROWS;   // rows behind it: zeros, or stale after reset() + a smaller add()
-                const int rbase = 4 * (lane >> 4);
+                const int nvalid = rows_valid(a.n_rows, g);
                 u64 rk[MT];
 #pragma unroll
                 for (int t = 0; t < MT; ++t) rk[t] = refkey[jc * MT + t];
 #pragma unroll
                 for (int rr = 0; rr < 16; ++rr) {
-                    const int row = 16 * (rr >> 2) + rbase + (rr & 3);
+                    const int row = scan16_row(rr, lane);
                     const float s = acc[rr];
                     // f2ord of a positive NaN sorts above every score: a NaN row gets the key nothing is behind
-                    const u64 key = (s == s && row < rows_valid) ? make_key(s, g * GROUP_ROWS + row) : 0ull;
+                    const u64 key = (s == s && row < nvalid) ? make_key(s, g * GROUP_ROWS + row) : 0ull;
 #pragma unroll
                     for (int t = 0; t < MT; ++t) cnt[t] += key > rk[t] ? 1u : 0u;
                 }
