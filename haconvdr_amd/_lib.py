@@ -60,6 +60,10 @@ def _declare(L):
     L.hac_index_search_masked.argtypes = [vp, c_f32p, i64, ctypes.c_int, u64p, i64, i64, ctypes.POINTER(i64), c_f32p, ctypes.POINTER(i64)]
     L.hac_index_search_masked_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, i64, i64, vp, vp, vp, vp, vp]
     L.hac_index_search_masked_keys_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, i64, i64, vp, vp, ctypes.c_uint32, vp]
+    L.hac_index_search_masked_after.argtypes = [vp, c_f32p, i64, ctypes.c_int, u64p, i64, i64, ctypes.POINTER(i64), c_f32p, ctypes.POINTER(i64), c_f32p,
+                                                ctypes.POINTER(i64)]
+    L.hac_index_search_masked_after_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.hac_index_search_masked_after_keys_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, i64, i64, vp, vp, vp, ctypes.c_uint32, vp]
     L.hac_index_search_grouped.argtypes = [vp, c_f32p, i64, ctypes.c_int, ctypes.POINTER(i64), i64, c_f32p, ctypes.POINTER(i64), ctypes.POINTER(i64)]
     L.hac_index_search_grouped_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, i64, vp, vp, vp, vp, vp]
     L.hac_index_search_after.argtypes = [vp, c_f32p, i64, ctypes.c_int, c_f32p, ctypes.POINTER(i64), c_f32p, ctypes.POINTER(i64)]
@@ -114,6 +118,7 @@ def _declare(L):
                  "hac_index_search_masked", "hac_index_search_masked_device", "hac_index_search_masked_keys_device",
                  "hac_index_search_grouped", "hac_index_search_grouped_device",
                  "hac_index_search_after", "hac_index_search_after_device", "hac_index_search_after_keys_device",
+                 "hac_index_search_masked_after", "hac_index_search_masked_after_device", "hac_index_search_masked_after_keys_device",
                  "hac_index_entries_at", "hac_index_entries_at_device", "hac_index_entries_at_keys_device"):
         getattr(L, name).restype = ctypes.c_int
 
@@ -132,7 +137,8 @@ EXPORTED_SYMBOLS = (
     "hac_index_search_masked", "hac_index_search_masked_device", "hac_index_search_masked_keys_device",
     "hac_index_search_grouped", "hac_index_search_grouped_device",
     "hac_index_search_after", "hac_index_search_after_device", "hac_index_search_after_keys_device",
-    "hac_index_entries_at", "hac_index_entries_at_device", "hac_index_entries_at_keys_device",
+    "hac_index_search_masked_after", "hac_index_search_masked_after_device", "hac_index_search_masked_after_keys_device",
+    "hac_index_entries_at","hac_index_entries_at_device", "hac_index_entries_at_keys_device",
     "hac_encoder_create", "hac_encoder_destroy", "hac_encoder_set_weight", "hac_encoder_finalize", "hac_encoder_forward",
     "hac_encoder_forward_device", "hac_encoder_set_option", "hac_encoder_last_plan", "hac_encoder_set_profiling", "hac_encoder_profile_drain",
     "hac_encoder_profile_drain_class", "hac_encoder_last_clock", "hac_encoder_attention_redo", "hac_encoder_layer_state",

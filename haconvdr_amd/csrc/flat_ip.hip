@@ -1084,6 +1084,7 @@ u32 next_pow2(u32 v) {
 #include "masked.inc"
 #include "grouped.inc"
 #include "after.inc"
+#include "masked_after.inc"
 #include "at_rank.inc"
 
 // Every instantiation of the two templated scan kernels, once: init raises each one's dynamic-LDS limit from these tables and
@@ -1379,6 +1380,7 @@ struct DeviceIndex {
             HAC_HIP(hipFuncSetAttribute((const void *)scan16_masked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             HAC_HIP(hipFuncSetAttribute((const void *)scan16_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             HAC_HIP(hipFuncSetAttribute((const void *)scan16_after_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
+            HAC_HIP(hipFuncSetAttribute((const void *)scan16_masked_after_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
             HAC_HIP(hipFuncSetAttribute((const void *)grouped_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, grouped_select_cm(HAC_MAX_K) * 16));   // (beside its static words)
             attr_done[device] = true;
         }
@@ -2112,6 +2114,20 @@ struct DeviceIndex {
     // after one call of the largest shape a call allocates nothing and can be captured.
     int search_keys_masked(const float *q_dev, int64_t nq, int k, const u64 *masks_dev, int64_t n_masks, int64_t words, const int64_t *mask_of_dev,
                            u64 *keys_out, u32 pos_base, hipStream_t st) {
+        return masked_keys(false, q_dev, nq, k, masks_dev, n_masks, words, mask_of_dev, nullptr, keys_out, pos_base, st);
+    }
+    // ---- search inside a bitmap, behind a cursor (masked_after.inc).  search_keys_masked with bounds_dev u64 [nq] on the
+    // device, each query's exclusive upper key bound in the position space of pos_base (null: every query starts from the
+    // start): the same plan, the same cut into launches, the same workspaces and options, scan16_masked_after_kernel in
+    // scan16_masked_kernel's place; a launch works at its own offset into the bounds too.  Allocates nothing after one call of
+    // the largest shape.
+    int search_keys_masked_after(const float *q_dev, int64_t nq, int k, const u64 *masks_dev, int64_t n_masks, int64_t words, const int64_t *mask_of_dev,
+                                 const u64 *bounds_dev, u64 *keys_out, u32 pos_base, hipStream_t st) {
+        return masked_keys(true, q_dev, nq, k, masks_dev, n_masks, words, mask_of_dev, bounds_dev, keys_out, pos_base, st);
+    }
+    // the two above: cursor says which kernel scans the lists (bounds_dev is read only with it)
+    int masked_keys(bool cursor, const float *q_dev, int64_t nq, int k, const u64 *masks_dev, int64_t n_masks, int64_t words, const int64_t *mask_of_dev,
+                    const u64 *bounds_dev, u64 *keys_out, u32 pos_base, hipStream_t st) {
         if (nq == 0) return HAC_OK;
         HAC_TRY(check_search_args(q_dev, pos_base));
         if (ntotal == 0) {
@@ -2134,8 +2150,8 @@ struct DeviceIndex {
         HAC_TRY(ws_thrglob.reserve(((size_t)TL * QT + THR_CTL_WORDS) * 4));
         HAC_HIP(hipMemsetAsync(ws_mcnt.p, 0, (size_t)pl0.n_qtiles * 4, st));
         const unsigned gx = (G + 255u) / 256u;
-        snprintf(last_plan, sizeof last_plan, "mask_groups_kernel grid=(%u,%lld) scan16_masked_kernel<W=%d> grid=(%d,%lld) QT=%d C=%d lds=%zu launches=%lld", gx,
-                 (long long)TL, SCAN_WAVES, pl.P, (long long)TL, QT, pl.C, pl.lds_scan, (long long)launches);
+        snprintf(last_plan, sizeof last_plan, "mask_groups_kernel grid=(%u,%lld) %s<W=%d> grid=(%d,%lld) QT=%d C=%d lds=%zu launches=%lld", gx,
+                 (long long)TL, cursor ? "scan16_masked_after_kernel" : "scan16_masked_kernel", SCAN_WAVES, pl.P, (long long)TL, QT, pl.C, pl.lds_scan, (long long)launches);
         plan_text_slot = -1;
         const int np2 = (int)next_pow2((u32)k);
         return tl.each(nq, [&](int64_t l, int64_t off, int64_t n, int64_t tiles) -> int {
@@ -2153,7 +2169,10 @@ struct DeviceIndex {
             HAC_HIP(hipGetLastError());
             HAC_TRY(reset_topk_scan((size_t)n, (size_t)tiles * QT, st));
             HAC_TRY(prof_begin(st));
-            scan16_masked_kernel<<<dim3((unsigned)pl.P, (unsigned)tiles), dim3(SCAN_WAVES * 64), pl.lds_scan, st>>>(a, m);
+            if (cursor)
+                scan16_masked_after_kernel<<<dim3((unsigned)pl.P, (unsigned)tiles), dim3(SCAN_WAVES * 64), pl.lds_scan, st>>>(a, m, bounds_dev ? bounds_dev + off : nullptr);
+            else
+                scan16_masked_kernel<<<dim3((unsigned)pl.P, (unsigned)tiles), dim3(SCAN_WAVES * 64), pl.lds_scan, st>>>(a, m);
             HAC_HIP(hipGetLastError());
             HAC_TRY(prof_end(st));
             select_keys_kernel<<<dim3((unsigned)n), dim3(256), (size_t)np2 * 8, st>>>((const u64 *)ws_partial.p, (size_t)pl.P * k, (const u32 *)ws_pcnt.p,

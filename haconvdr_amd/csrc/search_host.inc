@@ -1,6 +1,6 @@
 // The searches that return top-k keys (hac_index_search*, hac_index_search_excluding*, hac_index_search_among*,
-// hac_index_search_masked*, hac_index_search_grouped*, hac_index_search_after*): everything between the C ABI and
-// DeviceIndex::search_keys / search_keys_masked / search_keys_grouped / search_keys_after and the kernels of among.inc.  Included by flat_ip.hip behind rows_host.inc (whose
+// hac_index_search_masked*, hac_index_search_grouped*, hac_index_search_after*, hac_index_search_masked_after*): everything between the C ABI and
+// DeviceIndex::search_keys / search_keys_masked / search_keys_masked_after / search_keys_grouped / search_keys_after and the kernels of among.inc.  Included by flat_ip.hip behind rows_host.inc (whose
 // pin_slab, check_host_ids, RowLocator and key_*_host it uses).  Every host form is built from the same plain pieces, each of
 // which exists once: a shard's frame around its staging (shard_keys), the chunked query upload (for_query_chunks), the remap to
 // positions of the whole index (remap_keys), the gather and merge on shard 0 (reserve_merge_ws, gather_shard_keys,
@@ -315,19 +315,22 @@ MaskChunk pack_mask_chunk(const int64_t *mask_of, int64_t left, size_t q_bytes, 
 // query.  The chunks are pack_mask_chunk's, 64 MiB each: how many queries one holds depends on the masks they name, so this
 // loop is not for_query_chunks.  With several devices the slice is cut out of the caller's mask span by span (SpanDesc: local0,
 // count, global0).
-int masked_shard(hac_index *idx, int si, const float *q, int64_t nq, int k, const u64 *masks, int64_t words, const int64_t *mask_of) {
+// bounds: null (search_masked), or the shard's own bound of every query (search_masked_after: shard_bounds_host), which
+// travels behind the chunk's mask_of in the slab, 8 more bytes per query, into ws_after.
+int masked_shard(hac_index *idx, int si, const float *q, int64_t nq, int k, const u64 *masks, int64_t words, const int64_t *mask_of, const u64 *bounds = nullptr) {
     return shard_keys(idx, si, nq, k, [&](DeviceIndex &x) -> int {
         const bool sliced = idx->shards.size() > 1;
         const int64_t Wl = (x.ntotal + 63) / 64;   // words of a local mask
-        const size_t q_bytes = (size_t)x.d * 4, m_bytes = (size_t)Wl * 8;
+        const size_t q_bytes = (size_t)x.d * 4, m_bytes = (size_t)Wl * 8, b_bytes = bounds ? 8 : 0;
         for (int64_t q0 = 0; q0 < nq;) {
-            const MaskChunk c = pack_mask_chunk(mask_of + q0, nq - q0, q_bytes, m_bytes, (size_t)64 << 20);
+            const MaskChunk c = pack_mask_chunk(mask_of + q0, nq - q0, q_bytes + b_bytes, m_bytes, (size_t)64 << 20);
             const int64_t nqc = c.queries();
             const size_t nm = c.slot_of.size();
             HAC_TRY(x.ws_q.reserve(nqc * q_bytes));
             HAC_TRY(x.ws_masks.reserve(nm * m_bytes + (size_t)nqc * 8));
-            char *slab = nullptr;   // queries, masks, mask_of
-            HAC_TRY(pin_slab(x, nqc * q_bytes + nm * m_bytes + (size_t)nqc * 8, slab));
+            if (bounds) HAC_TRY(x.ws_after.reserve((size_t)nqc * 8));
+            char *slab = nullptr;   // queries, masks, mask_of (, bounds)
+            HAC_TRY(pin_slab(x, nqc * q_bytes + nm * m_bytes + (size_t)nqc * (8 + b_bytes), slab));
             std::memcpy(slab, q + (size_t)q0 * x.d, nqc * q_bytes);
             u64 *hm = reinterpret_cast<u64 *>(slab + nqc * q_bytes);
             for (size_t s = 0; s < nm; ++s) {
@@ -344,8 +347,15 @@ int masked_shard(hac_index *idx, int si, const float *q, int64_t nq, int k, cons
             HAC_HIP(hipMemcpyAsync(x.ws_q.p, slab, nqc * q_bytes, hipMemcpyHostToDevice, x.stream));
             HAC_HIP(hipMemcpyAsync(x.ws_masks.p, hm, nm * m_bytes + (size_t)nqc * 8, hipMemcpyHostToDevice, x.stream));
             const u64 *md = (const u64 *)x.ws_masks.p;
-            HAC_TRY(x.search_keys_masked((const float *)x.ws_q.p, nqc, k, md, (int64_t)nm, Wl, (const int64_t *)(md + nm * Wl), (u64 *)x.ws_keys.p + (size_t)q0 * k, 0u,
-                                         x.stream));
+            if (bounds) {
+                u64 *hb = hm + nm * Wl + nqc;
+                std::memcpy(hb, bounds + q0, (size_t)nqc * 8);
+                HAC_HIP(hipMemcpyAsync(x.ws_after.p, hb, (size_t)nqc * 8, hipMemcpyHostToDevice, x.stream));
+                HAC_TRY(x.search_keys_masked_after((const float *)x.ws_q.p, nqc, k, md, (int64_t)nm, Wl, (const int64_t *)(md + nm * Wl), (const u64 *)x.ws_after.p,
+                                                   (u64 *)x.ws_keys.p + (size_t)q0 * k, 0u, x.stream));
+            } else
+                HAC_TRY(x.search_keys_masked((const float *)x.ws_q.p, nqc, k, md, (int64_t)nm, Wl, (const int64_t *)(md + nm * Wl), (u64 *)x.ws_keys.p + (size_t)q0 * k, 0u,
+                                             x.stream));
             HAC_HIP(hipStreamSynchronize(x.stream));   // (the slab is the next chunk's)
             q0 += nqc;
         }
@@ -409,6 +419,51 @@ u64 cursor_bound_host(float s, int64_t r) {
     std::memcpy(&b, &s, 4);
     const u32 ord = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
     return ((u64)ord << 32) + (u64)(0xFFFFFFFFll - std::min<int64_t>(r, 0xFFFFFFFFll));
+}
+
+// Every shard's bound of every query of a host call with cursors (after_score, after_row: both null, or both [nq], the rows
+// checked >= -2), bounds[shard][query]; `what` names the call in a message.  The cursor is in the numbering of the whole index:
+// a shard's bound names its last row at or before the cursor's row, b_local = (its rows at global positions <= b) - 1 -- a
+// shard's local order is the global order, so its rows tying s_ref behind b are exactly its rows behind b_local; -1 makes every
+// tying row of the shard eligible (cursor_bound_host).  No cursors: all-ones, the start, everywhere.
+int shard_bounds_host(const char *what, hac_index *idx, int64_t nq, const float *after_score, const int64_t *after_row, std::vector<std::vector<u64>> &bounds) {
+    const int S = (int)idx->shards.size();
+    bounds.assign(S, std::vector<u64>((size_t)nq, ~0ull));
+    if (!after_row) return HAC_OK;
+    const RowLocator loc(idx);   // (one device: no spans, never asked)
+    std::vector<int32_t> at;
+    if (S > 1) {   // the span of every cursor row the index holds
+        std::vector<int64_t> inside((size_t)nq);
+        for (int64_t i = 0; i < nq; ++i) inside[(size_t)i] = after_row[i] < idx->ntotal ? std::max<int64_t>(after_row[i], -1) : -1;
+        at = loc.locate(inside.data(), (size_t)nq);
+    }
+    for (int64_t i = 0; i < nq; ++i) {
+        const int64_t b = after_row[i];
+        const float s = after_score[i];
+        if (b == HAC_AFTER_START) continue;
+        for (int si = 0; si < S; ++si) {
+            int64_t r = b;
+            if (S > 1 && b >= idx->ntotal) r = idx->shards[si]->ntotal - 1;   // every row of the shard lies before b
+            else if (S > 1 && b >= 0) {
+                const int32_t a = at[(size_t)i];
+                if (a < 0) return fail(HAC_ERR_INTERNAL, "%s: no span holds row %lld of %lld", what, (long long)b, (long long)idx->ntotal);
+                r = loc.rows_below(a, b, si) - (loc.shard(a) == si ? 0 : 1);
+            }
+            bounds[si][(size_t)i] = (b < 0 || s != s) ? 0ull : cursor_bound_host(s, r);
+        }
+    }
+    return HAC_OK;
+}
+// the cursor pointers and rows of a host call: both given or both null, every row >= -2
+int check_host_cursors(const char *what, int64_t nq, const float *after_score, const int64_t *after_row) {
+    if ((after_score == nullptr) != (after_row == nullptr))
+        return fail(HAC_ERR_INVALID, "%s: after_score and after_row go together: both given, or both null (every query from the start)", what);
+    if (after_row)
+        for (int64_t i = 0; i < nq; ++i)
+            if (after_row[i] < HAC_AFTER_START)
+                return fail(HAC_ERR_INVALID, "%s: after_row[%lld] = %lld of query %lld is below %d (a row, -1 = an exhausted list, %d = the start)", what, (long long)i,
+                            (long long)after_row[i], (long long)i, HAC_AFTER_START, HAC_AFTER_START);
+    return HAC_OK;
 }
 
 // The host form on one shard (shard_keys): every query under ITS shard's bound.  The queries go in chunks of ~64 MiB, each
@@ -660,51 +715,83 @@ int hac_index_search_after_device(hac_index *idx, const float *q_dev, int64_t nq
 int hac_index_search_after(hac_index *idx, const float *q, int64_t nq, int k, const float *after_score, const int64_t *after_row, float *D, int64_t *I) {
     if (!idx) return fail(HAC_ERR_INVALID, "null index");
     HAC_TRY(check_after_args("search_after", nq, k, nq <= 0 || (q && D && I)));
-    if ((after_score == nullptr) != (after_row == nullptr))
-        return fail(HAC_ERR_INVALID, "search_after: after_score and after_row go together: both given, or both null (every query from the start)");
+    HAC_TRY(check_host_cursors("search_after", nq, after_score, after_row));
     if (nq == 0) return HAC_OK;
-    if (after_row)
-        for (int64_t i = 0; i < nq; ++i)
-            if (after_row[i] < HAC_AFTER_START)
-                return fail(HAC_ERR_INVALID, "search_after: after_row[%lld] = %lld of query %lld is below %d (a row, -1 = an exhausted list, %d = the start)", (long long)i,
-                            (long long)after_row[i], (long long)i, HAC_AFTER_START, HAC_AFTER_START);
     if (idx->ntotal == 0) {
         fill_padding((size_t)nq * k, D, I);
         return HAC_OK;
     }
-    // Every shard searches its own rows behind its own bound (one host thread each).  The cursor is in the numbering of the
-    // whole index: a shard's bound names its last row at or before the cursor's row, b_local = (its rows at global positions
-    // <= b) - 1 -- a shard's local order is the global order, so its rows tying s_ref behind b are exactly its rows behind
-    // b_local; -1 makes every tying row of the shard eligible (cursor_bound_host).  The slabs are remapped and merged at k on the
-    // first device, as search merges them.
+    // Every shard searches its own rows behind its own bound (one host thread each: shard_bounds_host).  The slabs are remapped
+    // and merged at k on the first device, as search merges them.
     const int S = (int)idx->shards.size();
-    std::vector<std::vector<u64>> bounds(S, std::vector<u64>((size_t)nq, ~0ull));
-    if (after_row) {
-        const RowLocator loc(idx);   // (one device: no spans, never asked)
-        std::vector<int32_t> at;
-        if (S > 1) {   // the span of every cursor row the index holds
-            std::vector<int64_t> inside((size_t)nq);
-            for (int64_t i = 0; i < nq; ++i) inside[(size_t)i] = after_row[i] < idx->ntotal ? std::max<int64_t>(after_row[i], -1) : -1;
-            at = loc.locate(inside.data(), (size_t)nq);
-        }
-        for (int64_t i = 0; i < nq; ++i) {
-            const int64_t b = after_row[i];
-            const float s = after_score[i];
-            if (b == HAC_AFTER_START) continue;
-            for (int si = 0; si < S; ++si) {
-                int64_t r = b;
-                if (S > 1 && b >= idx->ntotal) r = idx->shards[si]->ntotal - 1;   // every row of the shard lies before b
-                else if (S > 1 && b >= 0) {
-                    const int32_t a = at[(size_t)i];
-                    if (a < 0) return fail(HAC_ERR_INTERNAL, "search_after: no span holds row %lld of %lld", (long long)b, (long long)idx->ntotal);
-                    r = loc.rows_below(a, b, si) - (loc.shard(a) == si ? 0 : 1);
-                }
-                bounds[si][(size_t)i] = (b < 0 || s != s) ? 0ull : cursor_bound_host(s, r);
-            }
-        }
-    }
+    std::vector<std::vector<u64>> bounds;
+    HAC_TRY(shard_bounds_host("search_after", idx, nq, after_score, after_row, bounds));
     if (S > 1) HAC_TRY(reserve_merge_ws(idx, (size_t)nq * k));
     HAC_TRY(for_each_shard(idx, [&](int si) { return after_shard(idx, si, q, nq, k, bounds[si].data()); }));
+    return shard_keys_to_host(idx, nq, k, D, I);
+}
+
+int hac_index_search_masked_after_keys_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const uint64_t *masks_dev, int64_t n_masks, int64_t words,
+                                              const int64_t *mask_of_dev, const uint64_t *after_keys_dev, uint64_t *keys_dev, uint32_t pos_base, void *hip_stream) {
+    return on_single_shard(idx, "search_masked_after_keys_device", [&](DeviceIndex &s) -> int {
+        const bool ptrs = nq <= 0 || (q_dev && keys_dev && (masks_dev || words == 0));
+        HAC_TRY(check_after_args("search_masked_after_keys_device", nq, k, ptrs));
+        HAC_TRY(check_masked_args("search_masked_after_keys_device", idx, nq, k, n_masks, words, mask_of_dev != nullptr, ptrs));
+        if (nq == 0) return HAC_OK;
+        return s.search_keys_masked_after(q_dev, nq, k, (const u64 *)masks_dev, n_masks, words, mask_of_dev, (const u64 *)after_keys_dev, (u64 *)keys_dev, pos_base,
+                                          (hipStream_t)hip_stream);
+    });
+}
+
+int hac_index_search_masked_after_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const uint64_t *masks_dev, int64_t n_masks, int64_t words,
+                                         const int64_t *mask_of_dev, const float *after_score_dev, const int64_t *after_row_dev, float *D_dev, int64_t *I_dev,
+                                         const int64_t *id_map_dev, void *hip_stream) {
+    return on_single_shard(idx, "search_masked_after_device", [&](DeviceIndex &s) -> int {
+        const bool ptrs = nq <= 0 || (q_dev && D_dev && I_dev && (masks_dev || words == 0));
+        HAC_TRY(check_after_args("search_masked_after_device", nq, k, ptrs));
+        HAC_TRY(check_masked_args("search_masked_after_device", idx, nq, k, n_masks, words, mask_of_dev != nullptr, ptrs));
+        if ((after_score_dev == nullptr) != (after_row_dev == nullptr))
+            return fail(HAC_ERR_INVALID, "search_masked_after_device: after_score and after_row go together: both given, or both null (every query from the start)");
+        if (nq == 0) return HAC_OK;
+        hipStream_t st = (hipStream_t)hip_stream;
+        const u64 *bounds = nullptr;
+        if (after_row_dev) {
+            HAC_TRY(s.ws_after.reserve((size_t)nq * 8));
+            after_bounds_kernel<<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st>>>(after_score_dev, (const long long *)after_row_dev, (long)nq, (u64 *)s.ws_after.p);
+            HAC_HIP(hipGetLastError());
+            bounds = (const u64 *)s.ws_after.p;
+        }
+        return keys_then_results(s, nq, k, id_map_dev, D_dev, I_dev, hip_stream, [&](u64 *keys) {
+            return s.search_keys_masked_after(q_dev, nq, k, (const u64 *)masks_dev, n_masks, words, mask_of_dev, bounds, keys, 0u, st);
+        });
+    });
+}
+
+int hac_index_search_masked_after(hac_index *idx, const float *q, int64_t nq, int k, const uint64_t *masks, int64_t n_masks, int64_t words, const int64_t *mask_of,
+                                  const float *after_score, const int64_t *after_row, float *D, int64_t *I) {
+    if (!idx) return fail(HAC_ERR_INVALID, "null index");
+    const bool ptrs = nq <= 0 || (q && D && I && (masks || words == 0));
+    HAC_TRY(check_after_args("search_masked_after", nq, k, ptrs));
+    HAC_TRY(check_masked_args("search_masked_after", idx, nq, k, n_masks, words, mask_of != nullptr, ptrs));
+    HAC_TRY(check_host_cursors("search_masked_after", nq, after_score, after_row));
+    if (nq == 0) return HAC_OK;
+    std::vector<int64_t> mo((size_t)nq);
+    for (int64_t i = 0; i < nq; ++i) {
+        mo[(size_t)i] = mask_of ? mask_of[i] : (n_masks == 1 ? 0 : i);
+        if (mo[(size_t)i] < 0 || mo[(size_t)i] >= n_masks)
+            return fail(HAC_ERR_INVALID, "search_masked_after: mask_of[%lld] = %lld of query %lld is outside [0, %lld)", (long long)i, (long long)mo[(size_t)i],
+                        (long long)i, (long long)n_masks);
+    }
+    if (idx->ntotal == 0) {
+        fill_padding((size_t)nq * k, D, I);
+        return HAC_OK;
+    }
+    // Every shard searches its own rows under its own slice of every mask, behind its own bound (one host thread each), in the
+    // numbering of the whole index; the slabs are merged at k on the first device, as search merges them.
+    std::vector<std::vector<u64>> bounds;
+    HAC_TRY(shard_bounds_host("search_masked_after", idx, nq, after_score, after_row, bounds));
+    if (idx->shards.size() > 1) HAC_TRY(reserve_merge_ws(idx, (size_t)nq * k));
+    HAC_TRY(for_each_shard(idx, [&](int si) { return masked_shard(idx, si, q, nq, k, (const u64 *)masks, words, mo.data(), bounds[si].data()); }));
     return shard_keys_to_host(idx, nq, k, D, I);
 }
 

@@ -723,18 +723,28 @@ class FlatIPIndex:
         _lib.check(_lib.lib().hac_index_search_among(self._h, _f32p(q), q.shape[0], k, _i64p(cand), cand.shape[1], _f32p(D), _i64p(I)))
         return D, I
 
-    def search_masked(self, q, k, masks, mask_of=None):
+    def search_masked(self, q, k, masks, mask_of=None, after=None):
         """search(q, k) over the rows a bitmap selects: masks bool [ntotal] or [n_masks, ntotal], or packed uint64 / int64
         [W] or [n_masks, W] (pack_mask; W = ceil(ntotal / 64)); mask_of int64 [nq] names each query's mask and may be None with
         one mask (every query uses it) or nq masks (query i uses mask i); an entry outside [0, n_masks) raises HacError.  Rows
         whose score is NaN are in no list; k may exceed the selected rows (the tail is padding).  Any number of rows may be
         selected (include/haconvdr.h, "search inside a bitmap"); faiss: SearchParameters(sel=IDSelectorBitmap(n, bitmap)),
-        IDSelectorRange (range_mask), IDSelectorNot (~mask)."""
+        IDSelectorRange (range_mask), IDSelectorNot (~mask).
+        after: None, or search_after's cursor pair (scores float32 [nq], rows int64 [nq]): the next page of the SELECTED rows,
+        those behind each query's cursor, e.g. (D[:, -1], I[:, -1]) of the page before under the same masks.  The cursor row need
+        not be selected and need not exist; row -1 gives padding, AFTER_START the start, a row below -2 raises ValueError
+        (include/haconvdr.h, "search inside a bitmap, behind a cursor")."""
         q, k, words, mask_of = _masked_args(q, k, masks, mask_of, self.d, self.ntotal)
         D, I = _host_results((q.shape[0], k))
         null_i = ctypes.POINTER(ctypes.c_int64)()
-        _lib.check(_lib.lib().hac_index_search_masked(self._h, _f32p(q), q.shape[0], k, words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
-                                                      words.shape[0], words.shape[1], null_i if mask_of is None else _i64p(mask_of), _f32p(D), _i64p(I)))
+        wp = words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        if after is None:
+            _lib.check(_lib.lib().hac_index_search_masked(self._h, _f32p(q), q.shape[0], k, wp, words.shape[0], words.shape[1],
+                                                          null_i if mask_of is None else _i64p(mask_of), _f32p(D), _i64p(I)))
+        else:
+            _, _, scores, rows = _after_args(q, k, after, self.d, "search_masked")
+            _lib.check(_lib.lib().hac_index_search_masked_after(self._h, _f32p(q), q.shape[0], k, wp, words.shape[0], words.shape[1],
+                                                                null_i if mask_of is None else _i64p(mask_of), _f32p(scores), _i64p(rows), _f32p(D), _i64p(I)))
         return D, I
 
     def search_grouped(self, q, k, group_of, return_groups=False):
@@ -949,27 +959,45 @@ class FlatIPIndex:
         _keep_alive(stream, q, cand, keys)
         return keys
 
-    def search_masked_tensor(self, q, k, masks, mask_of=None, id_map=None, stream=None):
+    def search_masked_tensor(self, q, k, masks, mask_of=None, id_map=None, stream=None, after=None):
         """search_tensor over the rows a bitmap selects: masks packed int64 CUDA [n_masks, W] (pack_mask of a bool CUDA tensor),
         mask_of int64 CUDA [nq] or None (one mask, or one per query); a query whose mask_of entry is outside [0, n_masks) gets
-        an empty list and no error.  id_map: optional int64 CUDA [ntotal], I = id_map[row].  No host sync; capturable after one
-        call of the largest (nq, k, n_masks)."""
+        an empty list and no error.  id_map: optional int64 CUDA [ntotal], I = id_map[row].  after: None, or search_after_tensor's
+        cursor pair (scores float32 CUDA [nq], rows int64 CUDA [nq]) -- the selected rows behind each query's cursor; a cursor
+        row below -2 gives an empty list, and id_map remaps the result only.  No host sync; capturable after one call of the
+        largest (nq, k, n_masks)."""
         q, k, masks, mask_of, id_map = _masked_args_tensor(q, k, masks, mask_of, id_map, self.d, self.ntotal)
+        if after is None:
+            D, I = _device_results((q.shape[0], k), q.device)
+            _lib.check(_lib.lib().hac_index_search_masked_device(self._h, _devp(q), q.shape[0], k, _devp(masks), masks.shape[0], masks.shape[1], _devp(mask_of),
+                                                                 _devp(D), _devp(I), _devp(id_map), _stream_ptr(stream)))
+            _keep_alive(stream, q, masks, D, I, *(t for t in (mask_of, id_map) if t is not None))
+            return D, I
+        _, _, scores, rows, _ = _after_args_tensor(q, k, after, None, self.d, "search_masked_tensor")
         D, I = _device_results((q.shape[0], k), q.device)
-        _lib.check(_lib.lib().hac_index_search_masked_device(self._h, _devp(q), q.shape[0], k, _devp(masks), masks.shape[0], masks.shape[1], _devp(mask_of),
-                                                             _devp(D), _devp(I), _devp(id_map), _stream_ptr(stream)))
-        _keep_alive(stream, q, masks, D, I, *(t for t in (mask_of, id_map) if t is not None))
+        _lib.check(_lib.lib().hac_index_search_masked_after_device(self._h, _devp(q), q.shape[0], k, _devp(masks), masks.shape[0], masks.shape[1], _devp(mask_of),
+                                                                   _devp(scores), _devp(rows), _devp(D), _devp(I), _devp(id_map), _stream_ptr(stream)))
+        _keep_alive(stream, q, masks, scores, rows, D, I, *(t for t in (mask_of, id_map) if t is not None))
         return D, I
 
-    def search_masked_keys_tensor(self, q, k, masks, mask_of=None, pos_base=0, stream=None):
+    def search_masked_keys_tensor(self, q, k, masks, mask_of=None, pos_base=0, stream=None, after_keys=None):
         """search_masked_tensor's sorted packed keys (int64 view of uint64) [nq, k], positions pos_base + row: the unit exchanged
-        between shards (merge_keys, keys_to_results)."""
+        between shards (merge_keys, keys_to_results).  after_keys: None, or int64 CUDA [nq] packed cursors in the same position
+        space, as search_after_keys_tensor takes them (cursor_keys, or the last column of the page before; 0 = an exhausted
+        list, -1 = the start): the selected rows whose key lies below the query's cursor."""
         import torch
         q, k, masks, mask_of, _ = _masked_args_tensor(q, k, masks, mask_of, None, self.d, self.ntotal, "search_masked_keys_tensor")
+        if after_keys is None:
+            keys = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
+            _lib.check(_lib.lib().hac_index_search_masked_keys_device(self._h, _devp(q), q.shape[0], k, _devp(masks), masks.shape[0], masks.shape[1],
+                                                                      _devp(mask_of), _devp(keys), int(pos_base), _stream_ptr(stream)))
+            _keep_alive(stream, q, masks, keys, *(() if mask_of is None else (mask_of,)))
+            return keys
+        _, _, after_keys, pos_base = _after_keys_args_tensor(q, k, after_keys, pos_base, self.d, "search_masked_keys_tensor")
         keys = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
-        _lib.check(_lib.lib().hac_index_search_masked_keys_device(self._h, _devp(q), q.shape[0], k, _devp(masks), masks.shape[0], masks.shape[1],
-                                                                  _devp(mask_of), _devp(keys), int(pos_base), _stream_ptr(stream)))
-        _keep_alive(stream, q, masks, keys, *(() if mask_of is None else (mask_of,)))
+        _lib.check(_lib.lib().hac_index_search_masked_after_keys_device(self._h, _devp(q), q.shape[0], k, _devp(masks), masks.shape[0], masks.shape[1],
+                                                                        _devp(mask_of), _devp(after_keys), _devp(keys), pos_base, _stream_ptr(stream)))
+        _keep_alive(stream, q, masks, after_keys, keys, *(() if mask_of is None else (mask_of,)))
         return keys
 
     def search_grouped_tensor(self, q, k, group_of, id_map=None, return_groups=False, stream=None):

@@ -393,13 +393,26 @@ class ResidentCorpus:
         return self.range_search(q, radius)
 
     # ---- lists deeper than HAC_MAX_K, and the rows behind a passage (index.search_after*) ---------------------------
-    def search_deep(self, query_embeddings, depth, page=1024):
+    def _within_masks(self, within, within_of, nq, what):
+        """(words int64 [n_masks, W], mask_of int64 [nq] or None) of a within= / within_of= pair, checked on the host as
+        search(within=) checks them (the tensor forms would answer a mask outside [0, n_masks) with an empty list)."""
+        from .index import _as_masks
+        words, mask_of = _as_masks(within, within_of, nq, self.ntotal, what)
+        if mask_of is not None and mask_of.size and (mask_of.min() < 0 or mask_of.max() >= words.shape[0]):
+            raise ValueError(f"{what}: within_of names a mask outside [0, {words.shape[0]})")
+        return words, mask_of
+
+    def search_deep(self, query_embeddings, depth, page=1024, within=None, within_of=None):
         """search() to ANY depth: query_embeddings float32 [nq,768] (numpy or CUDA tensor) -> (D float64 [nq,depth], I int64
         [nq,depth] EXTERNAL passage ids), the head of an unbounded search, padded with -FLT_MAX / -1 behind the last row whose
         score is not NaN.  The list is fetched in pages of `page` <= HAC_MAX_K rows: page one through search's own routes
         (index.search_keys_tensor), every later page behind the last key of the page before it
         (index.search_after_keys_tensor), each at the cost of an exact scan whatever its depth; the keys are unpacked once, at
-        the end.  Over ROWS, like search()."""
+        the end.  Over ROWS, like search().
+        within / within_of: masks over the rows as in search(within=) -- the list is then the head of the unbounded search of
+        the SELECTED rows ("more results, but only from this topic"): page one through index.search_masked_keys_tensor, every
+        later page behind the last key of the page before it under the same masks (after_keys=), each at the cost of the
+        masks' own groups."""
         import torch
         from . import _lib
         from .index import keys_to_results
@@ -409,14 +422,25 @@ class ResidentCorpus:
         depth, page = int(depth), int(page)
         if page > _lib.HAC_MAX_K:
             raise ValueError(f"search_deep: page = {page} exceeds {_lib.HAC_MAX_K}")
+        if within_of is not None and within is None:
+            raise ValueError("search_deep: within_of without within")
         q = query_embeddings if isinstance(query_embeddings, torch.Tensor) else torch.from_numpy(
             np.ascontiguousarray(query_embeddings, dtype=np.float32))
         q = q.to(self.dev)
-        pages = [self.index.search_keys_tensor(q, min(page, depth))]
+        if within is None:
+            first = lambda k: self.index.search_keys_tensor(q, k)
+            later = lambda k, cursor: self.index.search_after_keys_tensor(q, k, cursor)
+        else:
+            words, mask_of = self._within_masks(within, within_of, q.shape[0], "search_deep(within=)")
+            masks = torch.from_numpy(words).to(self.dev)
+            mask_of = None if mask_of is None else torch.from_numpy(mask_of).to(self.dev)
+            first = lambda k: self.index.search_masked_keys_tensor(q, k, masks, mask_of)
+            later = lambda k, cursor: self.index.search_masked_keys_tensor(q, k, masks, mask_of, after_keys=cursor)
+        pages = [first(min(page, depth))]
         got = pages[0].shape[1]
         while got < depth:
             k = min(page, depth - got)
-            pages.append(self.index.search_after_keys_tensor(q, k, pages[-1][:, -1].contiguous()))
+            pages.append(later(k, pages[-1][:, -1].contiguous()))
             got += k
         D, I = keys_to_results(torch.cat(pages, dim=1), self.id_map)
         return D.cpu().numpy().astype(np.float64), I.cpu().numpy()
@@ -454,19 +478,28 @@ class ResidentCorpus:
         q = np.ascontiguousarray(self._host_queries(query_embeddings), dtype=np.float32)
         return self.index.entries_at(q, ranks)[0].astype(np.float64)
 
-    def behind(self, query_embeddings, passage_ids, n):
+    def behind(self, query_embeddings, passage_ids, n, within=None, within_of=None):
         """The n rows an unbounded search lists right BEHIND each query's named passage -- negatives from just below the gold
         passage; the mirror of ahead_of: passage_ids int64 [nq] EXTERNAL ids -> (D float64 [nq,n], I int64 [nq,n] EXTERNAL
         ids) like search(), n <= HAC_MAX_K.  The cursor is (score() of the passage, its row): rows that tie its score and come
         later are included, the passage itself never is.  A passage no block holds, or one whose score is NaN, gives an
-        empty list (-FLT_MAX / -1)."""
+        empty list (-FLT_MAX / -1).
+        within / within_of: masks over the rows as in search(within=) -- the n SELECTED rows right behind the passage ("the n
+        passages behind the gold one that the user has not seen"); the passage's own row need not be selected
+        (index.search_masked(after=))."""
         q = np.ascontiguousarray(self._host_queries(query_embeddings), dtype=np.float32)
         pid = np.asarray(passage_ids)
         if pid.ndim != 1:
             raise ValueError(f"behind: passage_ids must be [nq], got shape {pid.shape}")
+        if within_of is not None and within is None:
+            raise ValueError("behind: within_of without within")
         rows = self.rows_of(pid)                                  # (-1 where no block holds the id: the exhausted cursor)
         scores = self.index.score_ids(q, rows[:, None])[:, 0]
-        D, I = self.index.search_after(q, n, (scores, rows))
+        if within is None:
+            D, I = self.index.search_after(q, n, (scores, rows))
+        else:
+            words, mask_of = self._within_masks(within, within_of, q.shape[0], "behind(within=)")
+            D, I = self.index.search_masked(q, n, words, mask_of, after=(scores, rows))
         return D.astype(np.float64), np.where(I >= 0, self._ids[np.maximum(I, 0)], -1)
 
     def reconstruct(self, passage_ids):

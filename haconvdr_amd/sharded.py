@@ -32,7 +32,9 @@ class ShardedSearcher:
     local_among_keys(q, k, local_cand [nq, m], pos_base) -> [nq, k]    (default: index.search_among_keys_tensor)
     local_masked_keys(q, k, local_masks [n_masks, W], mask_of, pos_base) -> [nq, k]   (default: index.search_masked_keys_tensor)
     local_after_keys(q, k, after_keys [nq] or None, pos_base) -> [nq, k]   (default: index.search_after_keys_tensor)
-    The nine hooks exist so that the distributed plumbing can be exercised on CPU with
+    local_masked_after_keys(q, k, local_masks, mask_of, after_keys [nq] or None, pos_base) -> [nq, k]
+                                                           (default: index.search_masked_keys_tensor(after_keys=))
+    The ten hooks exist so that the distributed plumbing can be exercised on CPU with
     gloo and a test double; the product path always uses the HIP defaults.
     n_local: rows this rank holds (default: index.ntotal when rank() / search_among() is called).
 
@@ -44,7 +46,7 @@ class ShardedSearcher:
 
     def __init__(self, index, shard_base, group=None, id_map=None, local_keys=None, merge=None, to_results=None, filter=None,
                  local_scores=None, count_ahead=None, n_local=None, local_among_keys=None, local_masked_keys=None,
-                 local_after_keys=None):
+                 local_after_keys=None, local_masked_after_keys=None):
         from . import index as _index
         self.index = index
         self.shard_base = int(shard_base)
@@ -60,6 +62,8 @@ class ShardedSearcher:
         self._local_among_keys = local_among_keys or (lambda q, k, cand, base: index.search_among_keys_tensor(q, k, cand, pos_base=base))
         self._local_masked_keys = local_masked_keys or (lambda q, k, masks, mask_of, base: index.search_masked_keys_tensor(q, k, masks, mask_of, pos_base=base))
         self._local_after_keys = local_after_keys or (lambda q, k, after_keys, base: index.search_after_keys_tensor(q, k, after_keys, pos_base=base))
+        self._local_masked_after_keys = local_masked_after_keys or (
+            lambda q, k, masks, mask_of, after_keys, base: index.search_masked_keys_tensor(q, k, masks, mask_of, pos_base=base, after_keys=after_keys))
 
     def _gather_and_merge(self, keys):
         if not dist.is_initialized():
@@ -132,6 +136,29 @@ class ShardedSearcher:
         Nothing is translated: a key carries a global position, and every rank searches with pos_base = shard_base, so the same
         comparison holds on every rank.  Then the same one all-gather and merge as search_keys, at k."""
         return self._to_results(self.search_after_keys(q, k, after_keys), self.id_map)
+
+    def search_masked_after_keys(self, q, k, local_masks, mask_of=None, after_keys=None):
+        """The merged keys [nq, k] of search_masked_after; their last column is the cursor of the next page."""
+        if local_masks.dim() != 2 or local_masks.dtype != torch.int64:
+            raise ValueError(f"local_masks must be packed int64 [n_masks, W], got {local_masks.dtype} {tuple(local_masks.shape)}")
+        if mask_of is not None and (mask_of.dim() != 1 or mask_of.shape[0] != q.shape[0] or mask_of.dtype != torch.int64):
+            raise ValueError(f"mask_of must be int64 [nq] with nq = {q.shape[0]}, got {mask_of.dtype} {tuple(mask_of.shape)}")
+        if mask_of is None and local_masks.shape[0] not in (1, q.shape[0]):
+            raise ValueError(f"{local_masks.shape[0]} masks for {q.shape[0]} queries and no mask_of: needs one mask, one per query, or mask_of")
+        if after_keys is not None:
+            if after_keys.dim() != 1 or after_keys.shape[0] != q.shape[0]:
+                raise ValueError(f"after_keys must be [nq] with nq = {q.shape[0]}, got shape {tuple(after_keys.shape)}")
+            if after_keys.dtype != torch.int64:
+                raise ValueError(f"after_keys must be int64 (the view of the packed keys), got {after_keys.dtype}")
+        return self._gather_and_merge(self._local_masked_after_keys(q, k, local_masks, mask_of, after_keys, self.shard_base))
+
+    def search_masked_after(self, q, k, local_masks, mask_of=None, after_keys=None):
+        """The next page of the rows a bitmap selects, over the whole sharded corpus -> (D, I) like search().  local_masks and
+        mask_of as in search_masked (THIS RANK'S OWN rows, the same number of masks on every rank); after_keys as in search_after
+        (int64 [nq], GLOBAL positions, identical on every rank; 0 = an exhausted list, -1 = the start, None = every query from
+        the start).  Nothing is translated: every rank searches its rows under its masks with pos_base = shard_base, so the same
+        key comparison holds on every rank.  Then the same one all-gather and merge as search_keys, at k."""
+        return self._to_results(self.search_masked_after_keys(q, k, local_masks, mask_of, after_keys), self.id_map)
 
     def rank(self, q, ids):
         """Exact rank of named rows over the whole sharded corpus: ids int64 [nq, m] GLOBAL positions (shard_base + local row),

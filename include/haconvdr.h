@@ -531,13 +531,62 @@ int hac_index_search_grouped_device(hac_index *idx, const float *q_dev, int64_t 
  * "debug_after_tiles" = 0 | the most query tiles per launch.  hac_index_last_plan afterwards reads
  * "scan16_after_kernel<W=4> grid=(P,T) QT=.. C=.. lds=.. launches=..".
  * Out of scope: an fp16 prefilter or a GEMM-shaped many-query route for cursor searches (the first page of a listing may take
- * search's: its last key is a cursor); cursors for the excluding / among / masked / grouped variants. */
+ * search's: its last key is a cursor); cursors for the excluding / among / grouped variants (the masked one: the next section). */
 #define HAC_AFTER_START (-2)
 int hac_index_search_after(hac_index *idx, const float *q, int64_t nq, int k, const float *after_score, const int64_t *after_row, float *D, int64_t *I);
 int hac_index_search_after_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const float *after_score_dev, const int64_t *after_row_dev,
                                   float *D_dev, int64_t *I_dev, const int64_t *id_map_dev, void *hip_stream);
 int hac_index_search_after_keys_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const uint64_t *after_keys_dev, uint64_t *keys_dev,
                                        uint32_t pos_base, void *hip_stream);
+
+/* ---- search inside a bitmap, behind a cursor: exact pages of the rows a bitmap selects ---------------------------------------
+ * "More results, but only from this topic"; hard negatives from ranks 2000 .. 4999 of the passages of one source; the n passages
+ * right behind the gold passage that the user has not seen.  For a query q, its mask M, a cursor (s_ref, b) and k:
+ *   masked_after(q, M, s_ref, b, k) = the first k of
+ *       { r in [0, n_rows) : bit r of M set, s(q, r) not NaN, make_key(s(q, r), pos_base + r) < bound }
+ *       by (score desc, row asc), padded with -FLT_MAX / -1
+ * bound is search_after's per-query exclusive upper key bound: make_key(s_ref, b) by after_bounds_kernel's rule (a NaN score,
+ * row -1 and a row below -2 give 0, an exhausted list; HAC_AFTER_START gives all-ones, the start), or the key form's after_key
+ * as it stands.  M is the query's own mask by search_masked's rule (mask_of; or one mask for every query; or mask i for query
+ * i), in search_masked's layout; bits at or above ntotal select nothing.  s is the canonical score, the bits search, score_ids
+ * and every other route return.
+ * What follows (proved on the CPU over the oracle by tests/test_index_masked_after.py, asserted on the GPU):
+ *   - the cursor row need not be selected by the mask, and need not exist: the bound is a key, not a row;
+ *   - an all-ones mask gives search_after; the start cursor gives search_masked, bit for bit at every k;
+ *   - pages chained with cursor = (D[:, -1], I[:, -1]) under the same masks list exactly the unbounded masked list, in order:
+ *     nothing twice, nothing missing, ties continued by row, and a padding cursor (row -1) gives padding.
+ * Arguments: the union of the two parents' -- words == ceil(ntotal / 64), n_masks >= 1 when nq > 0, 1 <= k <= HAC_MAX_K,
+ * after_score and after_row both given or both NULL (the start for every query).  nq == 0 is HAC_OK and touches nothing;
+ * ntotal == 0 gives padding only.  The host form refuses, with the query named and nothing written, a mask_of entry outside
+ * [0, n_masks), a cursor row below -2, and one cursor pointer without the other; the *_device forms give such a query an empty
+ * list and no error.
+ *
+ * How (csrc/masked_after.inc): mask_groups_kernel's lists and after_bounds_kernel's bounds as they are;
+ * scan16_masked_after_kernel is scan16_masked_kernel with the lane's own query's bound loaded once.  Its epilogue appends a row
+ * only if s >= th, row < rows_valid, the lane's own mask bit is set AND key < bound: every test before the append, so every
+ * threshold is the k-th key of some rows that are selected and behind the cursor -- a proven lower bound of the answer's k-th
+ * score, whatever the row streams, the list order or the launch cuts.  No threshold seeding.  select_keys_kernel finishes.
+ * Cost (by arithmetic; DESIGN.md records one timing): what search_masked costs at that mask -- the tile's selected groups per
+ * ceil(nq / QT) tiles -- at any depth; the extra work is one u64 comparison per candidate that already passed s >= th.
+ *
+ * Host form: synchronous; works on a multi-device index: every shard searches its own rows under its slice of the masks
+ * (search_masked's chunks, 8 more bytes per query for the bound) behind a bound of its own (search_after's rule, computed by
+ * the same function), remapped and merged at k on the first device.
+ * Device forms: single-device index, 16-byte aligned q_dev, enqueue on hip_stream and never read back.  id_map_dev remaps the
+ * RESULT only.  The keys form takes after_keys_dev (NULL: the start) and writes sorted packed keys [nq, k] in the position
+ * space of pos_base; its last column is the cursor of the next page.  Capturable after one call of the largest
+ * (nq, k, n_masks).  Test switches: search_masked's "masked_p" and "debug_masked_tiles".  hac_index_last_plan afterwards reads
+ * "mask_groups_kernel grid=(..) scan16_masked_after_kernel<W=4> grid=(P,tiles) QT=.. C=.. lds=.. launches=..".
+ * Out of scope: cursors for grouped, among and excluding; a masked entries_at / search_at; a prefilter-backed or many-query
+ * masked scan; skipping groups by cursor. */
+int hac_index_search_masked_after(hac_index *idx, const float *q, int64_t nq, int k, const uint64_t *masks, int64_t n_masks, int64_t words,
+                                  const int64_t *mask_of, const float *after_score, const int64_t *after_row, float *D, int64_t *I);
+int hac_index_search_masked_after_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const uint64_t *masks_dev, int64_t n_masks, int64_t words,
+                                         const int64_t *mask_of_dev, const float *after_score_dev, const int64_t *after_row_dev, float *D_dev,
+                                         int64_t *I_dev, const int64_t *id_map_dev, void *hip_stream);
+int hac_index_search_masked_after_keys_device(hac_index *idx, const float *q_dev, int64_t nq, int k, const uint64_t *masks_dev, int64_t n_masks,
+                                              int64_t words, const int64_t *mask_of_dev, const uint64_t *after_keys_dev, uint64_t *keys_dev,
+                                              uint32_t pos_base, void *hip_stream);
 
 /* ---- entry at a rank: what sits at position t of a query's unbounded ranking? -------------------------------------------------
  * rank_ids answers row -> rank, count_ahead (score, row) -> rows ahead, search_after cursor -> next page, range_search radius ->
