@@ -1084,7 +1084,7 @@ u32 next_pow2(u32 v) {
 #include "masked.inc"
 #include "grouped.inc"
 #include "after.inc"
-#include "masked_after.inc"
+#include "scan16_filter.inc"
 #include "at_rank.inc"
 
 // Every instantiation of the two templated scan kernels, once: init raises each one's dynamic-LDS limit from these tables and
@@ -1904,7 +1904,7 @@ struct DeviceIndex {
         size_t lds_scan;
     };
 
-    // The query tiles of a call (search_keys_masked, search_keys_grouped) in launches of whole tiles: at most `most` tiles each
+    // The query tiles of a call (search_keys_filtered, search_keys_grouped) in launches of whole tiles: at most `most` tiles each
     // (a debug option > 0 lowers it: tests cut a small call into several launches), at least one.
     struct TileLaunches {
         int QT;
@@ -1996,7 +1996,7 @@ struct DeviceIndex {
         a.n_rows = (long)ntotal;
         return a;
     }
-    // ... and those of a launch that collects every query's survivors for a top-k select (run_scan, search_keys_masked,
+    // ... and those of a launch that collects every query's survivors for a top-k select (run_scan, search_keys_filtered,
     // search_keys_grouped): the plan's tile, the survivors' buffers and counters, the thresholds
     ScanArgs topk_scan_args(const float *q_dev, int64_t nq, int k, const Plan &pl, u32 pos_base) const {
         ScanArgs a = scan_args(q_dev, nq);
@@ -2013,6 +2013,41 @@ struct DeviceIndex {
     int reset_topk_scan(size_t nq, size_t nq_pad, hipStream_t st) {
         HAC_HIP(hipMemsetAsync(ws_pcnt.p, 0, nq * 4, st));
         return clear_thrglob(nq_pad, st);
+    }
+    // one such launch of a filtered search (search_keys_filtered, search_keys_grouped): the reset in front of it, the launch
+    // itself as a timed scan (hac_index_set_profiling)
+    template <class Launch>
+    int launch_topk_scan(size_t nq, size_t nq_pad, hipStream_t st, Launch launch) {
+        HAC_TRY(reset_topk_scan(nq, nq_pad, st));
+        HAC_TRY(prof_begin(st));
+        launch();
+        HAC_HIP(hipGetLastError());
+        return prof_end(st);
+    }
+    // behind such a launch over `tiles` query tiles: the workgroups' survivors sit densely per query, radix select of the k
+    // best, one sort of k keys -> keys_out [nq][k] (nq_dev: search_keys_exact's)
+    int select_topk_keys(const Plan &pl, int64_t nq, int64_t tiles, int k, u64 *keys_out, const int *nq_dev, hipStream_t st) {
+        const int np2 = (int)next_pow2((u32)k);
+        select_keys_kernel<<<dim3((unsigned)nq), dim3(256), (size_t)np2 * 8, st>>>((const u64 *)ws_partial.p, (size_t)pl.P * k, (const u32 *)ws_pcnt.p,
+                                                                                   (u32)((size_t)pl.P * k), k, np2, keys_out, nullptr, nq_dev, (int)nq,
+                                                                                   (u32)(pl.P * tiles), (u32)pl.QT, thrglob(), (u32 *)ws_err.p);
+        HAC_HIP(hipGetLastError());
+        return HAC_OK;
+    }
+    // The lines that open every search_keys_* of one device: nothing to do without queries, the argument check (check: not
+    // for search_keys_exact, whose caller has made it), zeroed lists from an empty index, the segment table on the device.
+    // -> G, the groups of the index; 0: the call is answered.
+    int open_search(bool check, const float *q_dev, int64_t nq, int k, u64 *keys_out, u32 pos_base, hipStream_t st, u32 &G) {
+        G = 0;
+        if (nq == 0) return HAC_OK;
+        if (check) HAC_TRY(check_search_args(q_dev, pos_base));
+        if (ntotal == 0) {
+            HAC_HIP(hipMemsetAsync(keys_out, 0, (size_t)nq * k * 8, st));
+            return HAC_OK;
+        }
+        HAC_TRY(upload_segs(st));
+        G = (u32)((ntotal + GROUP_ROWS - 1) / GROUP_ROWS);
+        return HAC_OK;
     }
     int run_scan(const Plan &pl, const float *q_dev, int64_t nq, int k, u32 G, const float *thr_init, u32 pos_base, hipStream_t st, const int *nq_dev, bool cleared) {
         ScanArgs a = topk_scan_args(q_dev, nq, k, pl, pos_base);
@@ -2041,13 +2076,9 @@ struct DeviceIndex {
     // seeding (fewer launches on a path that is empty in the common case), the scan's workgroups are shared among the live
     // query tiles (vgrid), and rows of keys_out beyond *nq_dev are left alone.
     int search_keys_exact(const float *q_dev, int64_t nq, int k, u64 *keys_out, u32 pos_base, hipStream_t st, const int *nq_dev = nullptr, bool cleared = false) {
-        if (nq == 0) return HAC_OK;
-        if (ntotal == 0) {
-            HAC_HIP(hipMemsetAsync(keys_out, 0, (size_t)nq * k * 8, st));
-            return HAC_OK;
-        }
-        HAC_TRY(upload_segs(st));
-        const u32 G = (u32)((ntotal + GROUP_ROWS - 1) / GROUP_ROWS);
+        u32 G;
+        HAC_TRY(open_search(false, q_dev, nq, k, keys_out, pos_base, st, G));
+        if (!G) return HAC_OK;
         Plan pl;
         HAC_TRY(make_plan(nq, k, G, pl));
         // device-side count: a live tile may own every workgroup of the grid; QT * (P * n_qtiles) * k keys bound any split
@@ -2092,142 +2123,100 @@ struct DeviceIndex {
             plan_text_slot = -1;   // (last_plan is this search's text; older device-decided searches still deliver their counts)
         }
         HAC_TRY(run_scan(pl, q_dev, nq, k, G, thr_init, pos_base, st, nq_dev, cleared));
-        // the workgroups' survivors sit densely per query: radix select of the k best, one sort of k keys
-        const int np2 = (int)next_pow2((u32)k);
-        select_keys_kernel<<<dim3((unsigned)nq), dim3(256), (size_t)np2 * 8, st>>>((const u64 *)ws_partial.p, (size_t)pl.P * k,
-                                                                                   (const u32 *)ws_pcnt.p, (u32)((size_t)pl.P * k), k, np2,
-                                                                                   keys_out, nullptr, nq_dev, (int)nq, (u32)(pl.P * pl.n_qtiles),
-                                                                                   (u32)pl.QT, thrglob(), (u32 *)ws_err.p);
-        HAC_HIP(hipGetLastError());
-        return HAC_OK;
+        return select_topk_keys(pl, nq, pl.n_qtiles, k, keys_out, nq_dev, st);
     }
 
-    // ---- search inside a bitmap (masked.inc).  keys_out: device u64 [nq][k]; masks u64 [n_masks][words], mask_of int64 [nq] or
-    // null (n_masks == 1: mask 0, n_masks == nq: mask i for query i), all on the device; arguments checked by the entry points
-    // (words == ceil(ntotal / 64) above all: the kernels index a mask row by the group).
-    // A kind-0 plan at any nq (QT and C by make_plan's scan16 arithmetic), NO threshold seeding (thr_init stays null: a sample
-    // of unmasked rows gives bounds the masked set may not meet), then the existing select_keys_kernel.  The queries are cut
-    // into launches of whole tiles so that the list workspace u32 [tiles][G] stays within 64 MiB and, like search_keys, within
-    // QUERY_CHUNK queries; every launch holds at least one tile and works at offsets of its own into the queries, mask_of (or
-    // the masks, when query i uses mask i), the counters and keys_out.  The lists, the survivors and the thresholds are one
-    // launch's and are reused by the next, in stream order.  Every workspace is a GrowBuf sized by (nq, k) and the rows alone:
-    // after one call of the largest shape a call allocates nothing and can be captured.
+    // ---- search inside a bitmap (masked.inc), behind a cursor (after.inc), or both: the three kernels of scan16_filter.inc.
+    // keys_out: device u64 [nq][k]; arguments checked by the entry points.
+    //   mask (null: every row, and then behind a cursor)  masks u64 [n_masks][words], mask_of int64 [nq] or null (n_masks == 1:
+    //       mask 0, n_masks == nq: mask i for query i), all on the device, as mask_desc fills them in (words == ceil(ntotal / 64)
+    //       above all: the kernels index a mask row by the group); the fields of one launch are set here.
+    //   cursor (always, without a mask)  bounds_dev u64 [nq] on the device, each query's exclusive upper key bound in the position
+    //       space of pos_base (null: every query starts from the start); not read without cursor.
+    // A kind-0 plan at any nq (QT and C by make_plan's scan16 arithmetic), over a tile's list of groups with a mask and over every
+    // group without, NO threshold seeding (thr_init stays null: a sample of rows -- unmasked ones, ones ahead of the cursor --
+    // gives bounds the eligible rows may not meet), then the existing select_keys_kernel.  The queries are cut into launches of
+    // whole tiles, like search_keys within QUERY_CHUNK queries and, with a mask, so that the list workspace u32 [tiles][G] stays
+    // within 64 MiB; every launch holds at least one tile and works at offsets of its own into the queries, mask_of (or the
+    // masks, when query i uses mask i), the bounds, the counters and keys_out.  The lists, the survivors and the thresholds are
+    // one launch's and are reused by the next, in stream order.  With a mask and a cursor: the same plan, the same cut into
+    // launches, the same workspaces and options as with the mask alone, scan16_masked_after_kernel in scan16_masked_kernel's
+    // place.  Every workspace is a GrowBuf sized by (nq, k) and the rows alone: after one call of the largest shape a call
+    // allocates nothing and can be captured.
+    static MaskArgs mask_desc(const u64 *masks_dev, int64_t n_masks, int64_t words, const int64_t *mask_of_dev) {
+        MaskArgs m{};
+        m.masks = masks_dev;
+        m.mask_of = (const long long *)mask_of_dev;
+        m.n_masks = (long)n_masks;
+        m.words = (long)words;
+        return m;
+    }
     int search_keys_masked(const float *q_dev, int64_t nq, int k, const u64 *masks_dev, int64_t n_masks, int64_t words, const int64_t *mask_of_dev,
                            u64 *keys_out, u32 pos_base, hipStream_t st) {
-        return masked_keys(false, q_dev, nq, k, masks_dev, n_masks, words, mask_of_dev, nullptr, keys_out, pos_base, st);
+        const MaskArgs mask = mask_desc(masks_dev, n_masks, words, mask_of_dev);
+        return search_keys_filtered(q_dev, nq, k, &mask, false, nullptr, keys_out, pos_base, st);
     }
-    // ---- search inside a bitmap, behind a cursor (masked_after.inc).  search_keys_masked with bounds_dev u64 [nq] on the
-    // device, each query's exclusive upper key bound in the position space of pos_base (null: every query starts from the
-    // start): the same plan, the same cut into launches, the same workspaces and options, scan16_masked_after_kernel in
-    // scan16_masked_kernel's place; a launch works at its own offset into the bounds too.  Allocates nothing after one call of
-    // the largest shape.
     int search_keys_masked_after(const float *q_dev, int64_t nq, int k, const u64 *masks_dev, int64_t n_masks, int64_t words, const int64_t *mask_of_dev,
                                  const u64 *bounds_dev, u64 *keys_out, u32 pos_base, hipStream_t st) {
-        return masked_keys(true, q_dev, nq, k, masks_dev, n_masks, words, mask_of_dev, bounds_dev, keys_out, pos_base, st);
+        const MaskArgs mask = mask_desc(masks_dev, n_masks, words, mask_of_dev);
+        return search_keys_filtered(q_dev, nq, k, &mask, true, bounds_dev, keys_out, pos_base, st);
     }
-    // the two above: cursor says which kernel scans the lists (bounds_dev is read only with it)
-    int masked_keys(bool cursor, const float *q_dev, int64_t nq, int k, const u64 *masks_dev, int64_t n_masks, int64_t words, const int64_t *mask_of_dev,
-                    const u64 *bounds_dev, u64 *keys_out, u32 pos_base, hipStream_t st) {
-        if (nq == 0) return HAC_OK;
-        HAC_TRY(check_search_args(q_dev, pos_base));
-        if (ntotal == 0) {
-            HAC_HIP(hipMemsetAsync(keys_out, 0, (size_t)nq * k * 8, st));
-            return HAC_OK;
-        }
-        HAC_TRY(upload_segs(st));
-        const u32 G = (u32)((ntotal + GROUP_ROWS - 1) / GROUP_ROWS);
-        Plan pl0, pl;
-        HAC_TRY(make_plan(nq, k, G, pl0, true));
-        const int QT = pl0.QT;
-        const TileLaunches tl(pl0, std::min<int64_t>(((int64_t)64 << 20) / ((int64_t)G * 4), QUERY_CHUNK / QT), tune.debug_masked_tiles);
-        const int64_t TL = tl.TL, QL = tl.QL, launches = tl.launches;
-        // P for the tiles of one launch (at most 4 resident workgroups per CU, as scan16: the same shape); QT and C as above
-        HAC_TRY(make_plan(std::min(nq, QL), k, G, pl, true, tune.masked_p));
-        HAC_TRY(ws_mgroups.reserve((size_t)TL * G * 4));
-        HAC_TRY(ws_mcnt.reserve((size_t)pl0.n_qtiles * 4));
-        HAC_TRY(ws_partial.reserve((size_t)std::min(nq, QL) * pl.P * k * 8));
-        HAC_TRY(ws_pcnt.reserve((size_t)std::min(nq, QL) * 4));
-        HAC_TRY(ws_thrglob.reserve(((size_t)TL * QT + THR_CTL_WORDS) * 4));
-        HAC_HIP(hipMemsetAsync(ws_mcnt.p, 0, (size_t)pl0.n_qtiles * 4, st));
-        const unsigned gx = (G + 255u) / 256u;
-        snprintf(last_plan, sizeof last_plan, "mask_groups_kernel grid=(%u,%lld) %s<W=%d> grid=(%d,%lld) QT=%d C=%d lds=%zu launches=%lld", gx,
-                 (long long)TL, cursor ? "scan16_masked_after_kernel" : "scan16_masked_kernel", SCAN_WAVES, pl.P, (long long)TL, QT, pl.C, pl.lds_scan, (long long)launches);
-        plan_text_slot = -1;
-        const int np2 = (int)next_pow2((u32)k);
-        return tl.each(nq, [&](int64_t l, int64_t off, int64_t n, int64_t tiles) -> int {
-            MaskArgs m{};
-            m.per_query = (!mask_of_dev && n_masks != 1) ? 1 : 0;
-            m.masks = m.per_query ? masks_dev + (size_t)off * words : masks_dev;
-            m.mask_of = mask_of_dev ? (const long long *)mask_of_dev + off : nullptr;
-            m.n_masks = (long)n_masks;
-            m.words = (long)words;
-            m.groups = (u32 *)ws_mgroups.p;
-            m.n_groups = (u32 *)ws_mcnt.p + l * TL;
-            m.G = G;
-            const ScanArgs a = topk_scan_args(q_dev + (size_t)off * d, n, k, pl, pos_base);
-            mask_groups_kernel<<<dim3(gx, (unsigned)tiles), dim3(256), 0, st>>>(m, (int)n, QT, (long)ntotal);
-            HAC_HIP(hipGetLastError());
-            HAC_TRY(reset_topk_scan((size_t)n, (size_t)tiles * QT, st));
-            HAC_TRY(prof_begin(st));
-            if (cursor)
-                scan16_masked_after_kernel<<<dim3((unsigned)pl.P, (unsigned)tiles), dim3(SCAN_WAVES * 64), pl.lds_scan, st>>>(a, m, bounds_dev ? bounds_dev + off : nullptr);
-            else
-                scan16_masked_kernel<<<dim3((unsigned)pl.P, (unsigned)tiles), dim3(SCAN_WAVES * 64), pl.lds_scan, st>>>(a, m);
-            HAC_HIP(hipGetLastError());
-            HAC_TRY(prof_end(st));
-            select_keys_kernel<<<dim3((unsigned)n), dim3(256), (size_t)np2 * 8, st>>>((const u64 *)ws_partial.p, (size_t)pl.P * k, (const u32 *)ws_pcnt.p,
-                                                                                      (u32)((size_t)pl.P * k), k, np2, keys_out + (size_t)off * k, nullptr, nullptr, (int)n,
-                                                                                      (u32)(pl.P * tiles), (u32)QT, thrglob(), (u32 *)ws_err.p);
-            HAC_HIP(hipGetLastError());
-            return HAC_OK;
-        });
-    }
-
-    // ---- search behind a cursor (after.inc).  keys_out: device u64 [nq][k]; bounds_dev u64 [nq] on the device, each query's
-    // exclusive upper key bound in the position space of pos_base (null: every query starts from the start); arguments checked
-    // by the entry points.
-    // A kind-0 plan at any nq (QT and C by make_plan's scan16 arithmetic) over every group, NO threshold seeding (thr_init stays
-    // null: a sample of rows gives bounds the rows behind the cursor may not meet), then the existing select_keys_kernel.  The
-    // queries go in launches of whole tiles, at most QUERY_CHUNK queries each; the survivors and the thresholds are one launch's
-    // and are reused by the next, in stream order.  Every workspace is a GrowBuf sized by (nq, k) and the rows alone: after one
-    // call of the largest shape a call allocates nothing and can be captured.
     int search_keys_after(const float *q_dev, int64_t nq, int k, const u64 *bounds_dev, u64 *keys_out, u32 pos_base, hipStream_t st) {
-        if (nq == 0) return HAC_OK;
-        HAC_TRY(check_search_args(q_dev, pos_base));
-        if (ntotal == 0) {
-            HAC_HIP(hipMemsetAsync(keys_out, 0, (size_t)nq * k * 8, st));
-            return HAC_OK;
-        }
-        HAC_TRY(upload_segs(st));
-        const u32 G = (u32)((ntotal + GROUP_ROWS - 1) / GROUP_ROWS);
+        return search_keys_filtered(q_dev, nq, k, nullptr, true, bounds_dev, keys_out, pos_base, st);
+    }
+    int search_keys_filtered(const float *q_dev, int64_t nq, int k, const MaskArgs *mask, bool cursor, const u64 *bounds_dev, u64 *keys_out, u32 pos_base,
+                             hipStream_t st) {
+        u32 G;
+        HAC_TRY(open_search(true, q_dev, nq, k, keys_out, pos_base, st, G));
+        if (!G) return HAC_OK;
         Plan pl0, pl;
         HAC_TRY(make_plan(nq, k, G, pl0, true));
         const int QT = pl0.QT;
-        const TileLaunches tl(pl0, QUERY_CHUNK / QT, tune.debug_after_tiles);
+        const int64_t most = mask ? std::min<int64_t>(((int64_t)64 << 20) / ((int64_t)G * 4), QUERY_CHUNK / QT) : QUERY_CHUNK / QT;
+        const TileLaunches tl(pl0, most, mask ? tune.debug_masked_tiles : tune.debug_after_tiles);
         const int64_t TL = tl.TL, QL = tl.QL, launches = tl.launches;
         // P for the tiles of one launch (at most 4 resident workgroups per CU, as scan16: the same shape); QT and C as above
-        HAC_TRY(make_plan(std::min(nq, QL), k, G, pl, true, tune.after_p));
+        HAC_TRY(make_plan(std::min(nq, QL), k, G, pl, true, mask ? tune.masked_p : tune.after_p));
         HAC_TRY(ws_partial.reserve((size_t)std::min(nq, QL) * pl.P * k * 8));
         HAC_TRY(ws_pcnt.reserve((size_t)std::min(nq, QL) * 4));
         HAC_TRY(ws_thrglob.reserve(((size_t)TL * QT + THR_CTL_WORDS) * 4));
-        snprintf(last_plan, sizeof last_plan, "scan16_after_kernel<W=%d> grid=(%d,%lld) QT=%d C=%d lds=%zu launches=%lld", SCAN_WAVES, pl.P, (long long)TL, QT, pl.C,
-                 pl.lds_scan, (long long)launches);
+        const unsigned gx = (G + 255u) / 256u;   // mask_groups_kernel's
+        if (mask) {
+            HAC_TRY(ws_mgroups.reserve((size_t)TL * G * 4));
+            HAC_TRY(ws_mcnt.reserve((size_t)pl0.n_qtiles * 4));
+            HAC_HIP(hipMemsetAsync(ws_mcnt.p, 0, (size_t)pl0.n_qtiles * 4, st));
+            snprintf(last_plan, sizeof last_plan, "mask_groups_kernel grid=(%u,%lld) %s<W=%d> grid=(%d,%lld) QT=%d C=%d lds=%zu launches=%lld", gx,
+                     (long long)TL, cursor ? "scan16_masked_after_kernel" : "scan16_masked_kernel", SCAN_WAVES, pl.P, (long long)TL, QT, pl.C, pl.lds_scan, (long long)launches);
+        } else {
+            snprintf(last_plan, sizeof last_plan, "scan16_after_kernel<W=%d> grid=(%d,%lld) QT=%d C=%d lds=%zu launches=%lld", SCAN_WAVES, pl.P, (long long)TL, QT, pl.C,
+                     pl.lds_scan, (long long)launches);
+        }
         plan_text_slot = -1;
-        const int np2 = (int)next_pow2((u32)k);
-        return tl.each(nq, [&](int64_t, int64_t off, int64_t n, int64_t tiles) -> int {
+        return tl.each(nq, [&](int64_t l, int64_t off, int64_t n, int64_t tiles) -> int {
             ScanArgs a = topk_scan_args(q_dev + (size_t)off * d, n, k, pl, pos_base);
-            a.g_step = 1;
-            a.n_items = G;
-            HAC_TRY(reset_topk_scan((size_t)n, (size_t)tiles * QT, st));
-            HAC_TRY(prof_begin(st));
-            scan16_after_kernel<<<dim3((unsigned)pl.P, (unsigned)tiles), dim3(SCAN_WAVES * 64), pl.lds_scan, st>>>(a, bounds_dev ? bounds_dev + off : nullptr);
-            HAC_HIP(hipGetLastError());
-            HAC_TRY(prof_end(st));
-            select_keys_kernel<<<dim3((unsigned)n), dim3(256), (size_t)np2 * 8, st>>>((const u64 *)ws_partial.p, (size_t)pl.P * k, (const u32 *)ws_pcnt.p,
-                                                                                      (u32)((size_t)pl.P * k), k, np2, keys_out + (size_t)off * k, nullptr, nullptr, (int)n,
-                                                                                      (u32)(pl.P * tiles), (u32)QT, thrglob(), (u32 *)ws_err.p);
-            HAC_HIP(hipGetLastError());
-            return HAC_OK;
+            const u64 *bounds = bounds_dev ? bounds_dev + off : nullptr;
+            const dim3 grid((unsigned)pl.P, (unsigned)tiles), block(SCAN_WAVES * 64);
+            MaskArgs m{};
+            if (mask) {
+                m = *mask;
+                m.per_query = (!m.mask_of && m.n_masks != 1) ? 1 : 0;
+                if (m.per_query) m.masks += (size_t)off * m.words;
+                if (m.mask_of) m.mask_of += off;
+                m.groups = (u32 *)ws_mgroups.p;
+                m.n_groups = (u32 *)ws_mcnt.p + l * TL;
+                m.G = G;
+                mask_groups_kernel<<<dim3(gx, (unsigned)tiles), dim3(256), 0, st>>>(m, (int)n, QT, (long)ntotal);
+                HAC_HIP(hipGetLastError());
+            } else {
+                a.g_step = 1;
+                a.n_items = G;
+            }
+            HAC_TRY(launch_topk_scan((size_t)n, (size_t)tiles * QT, st, [&] {
+                if (!mask) scan16_after_kernel<<<grid, block, pl.lds_scan, st>>>(a, bounds);
+                else if (cursor) scan16_masked_after_kernel<<<grid, block, pl.lds_scan, st>>>(a, m, bounds);
+                else scan16_masked_kernel<<<grid, block, pl.lds_scan, st>>>(a, m);
+            }));
+            return select_topk_keys(pl, n, tiles, k, keys_out + (size_t)off * k, nullptr, st);
         });
     }
 
@@ -2256,14 +2245,9 @@ struct DeviceIndex {
         return HAC_OK;
     }
     int search_keys_grouped(const float *q_dev, int64_t nq, int k, const int64_t *group_of_dev, u64 *keys_out, hipStream_t st) {
-        if (nq == 0) return HAC_OK;
-        HAC_TRY(check_search_args(q_dev, 0u));
-        if (ntotal == 0) {
-            HAC_HIP(hipMemsetAsync(keys_out, 0, (size_t)nq * k * 8, st));
-            return HAC_OK;
-        }
-        HAC_TRY(upload_segs(st));
-        const u32 G = (u32)((ntotal + GROUP_ROWS - 1) / GROUP_ROWS);
+        u32 G;
+        HAC_TRY(open_search(true, q_dev, nq, k, keys_out, 0u, st, G));
+        if (!G) return HAC_OK;
         Plan pl;
         HAC_TRY(grouped_plan(nq, k, pl));
         const int QT = pl.QT;
@@ -2286,11 +2270,9 @@ struct DeviceIndex {
             ScanArgs a = topk_scan_args(q_dev + (size_t)off * d, n, k, pl, 0u);
             a.g_step = 1;
             a.n_items = G;
-            HAC_TRY(reset_topk_scan((size_t)n, (size_t)tiles * QT, st));
-            HAC_TRY(prof_begin(st));
-            scan16_grouped_kernel<<<dim3((unsigned)pl.P, (unsigned)tiles), dim3(SCAN_WAVES * 64), pl.lds_scan, st>>>(a, gr);
-            HAC_HIP(hipGetLastError());
-            HAC_TRY(prof_end(st));
+            HAC_TRY(launch_topk_scan((size_t)n, (size_t)tiles * QT, st, [&] {
+                scan16_grouped_kernel<<<dim3((unsigned)pl.P, (unsigned)tiles), dim3(SCAN_WAVES * 64), pl.lds_scan, st>>>(a, gr);
+            }));
             grouped_select_kernel<<<dim3((unsigned)n), dim3(256), (size_t)Cm * 16, st>>>((const u64 *)ws_partial.p, 0, 0, (size_t)pl.P * k, (const u32 *)ws_pcnt.p,
                                                                                          (u32)((size_t)pl.P * k), k, Cm, gr, keys_out + (size_t)off * k);
             HAC_HIP(hipGetLastError());

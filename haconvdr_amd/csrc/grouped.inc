@@ -112,7 +112,7 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void scan16_grouped_kernel(ScanArg
     const u32 hw = (u32)C - 64u * SCAN_WAVES;  // compaction high-water mark (>= k)
 
     // Uniform values that only the epilogue and the compactions use live in vector registers: this kernel has the labels and the
-    // scratch array more than scan16_kernel to keep in scalar ones, which are full there (no spills; masked.inc does the same)
+    // scratch array more than scan16_kernel to keep in scalar ones, which are full there (no spills; scan16_filter.inc does the same)
     u32 pos_base = a.pos_base;
     u32 *tglob = a.thr_glob + q0;
     GroupArgs grv = gr;

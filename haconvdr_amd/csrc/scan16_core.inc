@@ -1,11 +1,13 @@
-// The parts scan16_kernel and the six kernels of its shape are built from: included by flat_ip.hip in front of scan16_kernel.
-// (scan16_masked_kernel, scan16_grouped_kernel, scan16_after_kernel, count_ahead_kernel, range_emit_kernel, rank_hist_kernel.)
-// Forced-inline device functions only: every kernel keeps its own __global__ function, its own epilogue and its own register
-// allocation, and the chunk loop each one compiles to is the one it had when the loop was written out in it.
+// The parts scan16_kernel and the kernels of its shape are built from: included by flat_ip.hip in front of scan16_kernel.
+// (scan16_filter.inc's body -- scan16_masked_kernel, scan16_after_kernel, scan16_masked_after_kernel --, scan16_grouped_kernel,
+// count_ahead_kernel, range_emit_kernel, rank_hist_kernel.)
+// Forced-inline device functions only: every kernel keeps its own __global__ function and its own register allocation, and the
+// chunk loop each one compiles to is the one it had when the loop was written out in it.
 // Not here, on purpose (LABNOTES, "One shared row loop"): the row-stream cursor (item, have, nitem, have_next, np) -- written
 // as one function that takes the round as a callable it cost scan16_after_kernel, scan16_grouped_kernel and rank_hist_kernel
-// 14 to 16 VGPRs each, by value and by reference alike, so every kernel spells it out -- and the append epilogues, whose
-// BEFORE APPEND rules read best as the dozen lines they are.
+// 14 to 16 VGPRs each, by value and by reference alike, so every body spells it out -- and the append epilogues, whose
+// BEFORE APPEND rules read best as the dozen lines they are.  (The three filtered kernels share cursor and epilogue as ONE
+// body with two compile-time questions, scan16_filter.inc: a whole body instantiated three times, not a callable.)
 //
 // A wave scores one T64 group (64 rows, lane l streams row l's chunks) against the <= 16 queries of its tile with
 // v_mfma_f32_16x16x1: accumulator slot rr of lane l is the score of row scan16_row(rr, l) and query l & 15.

@@ -735,16 +735,15 @@ class FlatIPIndex:
         not be selected and need not exist; row -1 gives padding, AFTER_START the start, a row below -2 raises ValueError
         (include/haconvdr.h, "search inside a bitmap, behind a cursor")."""
         q, k, words, mask_of = _masked_args(q, k, masks, mask_of, self.d, self.ntotal)
-        D, I = _host_results((q.shape[0], k))
-        null_i = ctypes.POINTER(ctypes.c_int64)()
-        wp = words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
-        if after is None:
-            _lib.check(_lib.lib().hac_index_search_masked(self._h, _f32p(q), q.shape[0], k, wp, words.shape[0], words.shape[1],
-                                                          null_i if mask_of is None else _i64p(mask_of), _f32p(D), _i64p(I)))
-        else:
+        if after is not None:
             _, _, scores, rows = _after_args(q, k, after, self.d, "search_masked")
-            _lib.check(_lib.lib().hac_index_search_masked_after(self._h, _f32p(q), q.shape[0], k, wp, words.shape[0], words.shape[1],
-                                                                null_i if mask_of is None else _i64p(mask_of), _f32p(scores), _i64p(rows), _f32p(D), _i64p(I)))
+        D, I = _host_results((q.shape[0], k))
+        head = (self._h, _f32p(q), q.shape[0], k, words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), words.shape[0], words.shape[1],
+                ctypes.POINTER(ctypes.c_int64)() if mask_of is None else _i64p(mask_of))
+        if after is None:
+            _lib.check(_lib.lib().hac_index_search_masked(*head, _f32p(D), _i64p(I)))
+        else:
+            _lib.check(_lib.lib().hac_index_search_masked_after(*head, _f32p(scores), _i64p(rows), _f32p(D), _i64p(I)))
         return D, I
 
     def search_grouped(self, q, k, group_of, return_groups=False):
@@ -967,17 +966,18 @@ class FlatIPIndex:
         row below -2 gives an empty list, and id_map remaps the result only.  No host sync; capturable after one call of the
         largest (nq, k, n_masks)."""
         q, k, masks, mask_of, id_map = _masked_args_tensor(q, k, masks, mask_of, id_map, self.d, self.ntotal)
-        if after is None:
-            D, I = _device_results((q.shape[0], k), q.device)
-            _lib.check(_lib.lib().hac_index_search_masked_device(self._h, _devp(q), q.shape[0], k, _devp(masks), masks.shape[0], masks.shape[1], _devp(mask_of),
-                                                                 _devp(D), _devp(I), _devp(id_map), _stream_ptr(stream)))
-            _keep_alive(stream, q, masks, D, I, *(t for t in (mask_of, id_map) if t is not None))
-            return D, I
-        _, _, scores, rows, _ = _after_args_tensor(q, k, after, None, self.d, "search_masked_tensor")
+        cursor = ()
+        if after is not None:
+            _, _, scores, rows, _ = _after_args_tensor(q, k, after, None, self.d, "search_masked_tensor")
+            cursor = (scores, rows)
         D, I = _device_results((q.shape[0], k), q.device)
-        _lib.check(_lib.lib().hac_index_search_masked_after_device(self._h, _devp(q), q.shape[0], k, _devp(masks), masks.shape[0], masks.shape[1], _devp(mask_of),
-                                                                   _devp(scores), _devp(rows), _devp(D), _devp(I), _devp(id_map), _stream_ptr(stream)))
-        _keep_alive(stream, q, masks, scores, rows, D, I, *(t for t in (mask_of, id_map) if t is not None))
+        head = (self._h, _devp(q), q.shape[0], k, _devp(masks), masks.shape[0], masks.shape[1], _devp(mask_of))
+        tail = (_devp(D), _devp(I), _devp(id_map), _stream_ptr(stream))
+        if after is None:
+            _lib.check(_lib.lib().hac_index_search_masked_device(*head, *tail))
+        else:
+            _lib.check(_lib.lib().hac_index_search_masked_after_device(*head, _devp(scores), _devp(rows), *tail))
+        _keep_alive(stream, q, masks, *cursor, D, I, *(t for t in (mask_of, id_map) if t is not None))
         return D, I
 
     def search_masked_keys_tensor(self, q, k, masks, mask_of=None, pos_base=0, stream=None, after_keys=None):
@@ -987,17 +987,18 @@ class FlatIPIndex:
         list, -1 = the start): the selected rows whose key lies below the query's cursor."""
         import torch
         q, k, masks, mask_of, _ = _masked_args_tensor(q, k, masks, mask_of, None, self.d, self.ntotal, "search_masked_keys_tensor")
-        if after_keys is None:
-            keys = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
-            _lib.check(_lib.lib().hac_index_search_masked_keys_device(self._h, _devp(q), q.shape[0], k, _devp(masks), masks.shape[0], masks.shape[1],
-                                                                      _devp(mask_of), _devp(keys), int(pos_base), _stream_ptr(stream)))
-            _keep_alive(stream, q, masks, keys, *(() if mask_of is None else (mask_of,)))
-            return keys
-        _, _, after_keys, pos_base = _after_keys_args_tensor(q, k, after_keys, pos_base, self.d, "search_masked_keys_tensor")
+        cursor = ()
+        if after_keys is not None:
+            _, _, after_keys, pos_base = _after_keys_args_tensor(q, k, after_keys, pos_base, self.d, "search_masked_keys_tensor")
+            cursor = (after_keys,)
         keys = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
-        _lib.check(_lib.lib().hac_index_search_masked_after_keys_device(self._h, _devp(q), q.shape[0], k, _devp(masks), masks.shape[0], masks.shape[1],
-                                                                        _devp(mask_of), _devp(after_keys), _devp(keys), pos_base, _stream_ptr(stream)))
-        _keep_alive(stream, q, masks, after_keys, keys, *(() if mask_of is None else (mask_of,)))
+        head = (self._h, _devp(q), q.shape[0], k, _devp(masks), masks.shape[0], masks.shape[1], _devp(mask_of))
+        tail = (_devp(keys), int(pos_base), _stream_ptr(stream))
+        if after_keys is None:
+            _lib.check(_lib.lib().hac_index_search_masked_keys_device(*head, *tail))
+        else:
+            _lib.check(_lib.lib().hac_index_search_masked_after_keys_device(*head, _devp(after_keys), *tail))
+        _keep_alive(stream, q, masks, *cursor, keys, *(() if mask_of is None else (mask_of,)))
         return keys
 
     def search_grouped_tensor(self, q, k, group_of, id_map=None, return_groups=False, stream=None):

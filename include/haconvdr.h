@@ -376,7 +376,7 @@ int hac_index_search_among_keys_device(hac_index *idx, const float *q_dev, int64
  * mask_of out of range: the host form returns HAC_ERR_INVALID for an entry outside [0, n_masks), names the query and writes
  * nothing; in the *_device forms that query gets an empty list, all padding, and no error -- the split the by-id calls make.
  *
- * How (csrc/masked.inc): mask_groups_kernel builds, per query tile, the list of the 64-row groups in which the OR of the tile's
+ * How (csrc/masked.inc, csrc/scan16_filter.inc): mask_groups_kernel builds, per query tile, the list of the 64-row groups in which the OR of the tile's
  * queries' mask words is non-zero (clipped to ntotal in the last group; ballot + prefix, one atomic per wave; the order of a
  * list is unspecified and does not matter).  scan16_masked_kernel is a copy of scan16_kernel whose work items are that list:
  * the same row stream, the same bit-exact MFMA chain, the same candidate buffers and compaction; its epilogue appends a row
@@ -507,7 +507,7 @@ int hac_index_search_grouped_device(hac_index *idx, const float *q_dev, int64_t 
  *     whose score is not NaN.
  * 1 <= k <= HAC_MAX_K; nq == 0 is HAC_OK and touches nothing; ntotal == 0 gives padding only.
  *
- * How (csrc/after.inc): after_bounds_kernel turns the cursors into each query's exclusive upper key bound (NaN score, row -1 or
+ * How (csrc/after.inc, csrc/scan16_filter.inc): after_bounds_kernel turns the cursors into each query's exclusive upper key bound (NaN score, row -1 or
  * row < -2: 0; row -2: all-ones; otherwise the key of (s_ref + 0.0f, min(row, 2^32 - 1))).  scan16_after_kernel is a copy of
  * scan16_kernel over every 64-row group -- the same row stream, the same bit-exact MFMA chain, the same candidate buffers and
  * compaction -- whose epilogue appends a row only if its key is below the lane's own query's bound.  A row is tested before it
@@ -561,7 +561,7 @@ int hac_index_search_after_keys_device(hac_index *idx, const float *q_dev, int64
  * [0, n_masks), a cursor row below -2, and one cursor pointer without the other; the *_device forms give such a query an empty
  * list and no error.
  *
- * How (csrc/masked_after.inc): mask_groups_kernel's lists and after_bounds_kernel's bounds as they are;
+ * How (csrc/scan16_filter.inc): mask_groups_kernel's lists and after_bounds_kernel's bounds as they are;
  * scan16_masked_after_kernel is scan16_masked_kernel with the lane's own query's bound loaded once.  Its epilogue appends a row
  * only if s >= th, row < rows_valid, the lane's own mask bit is set AND key < bound: every test before the append, so every
  * threshold is the k-th key of some rows that are selected and behind the cursor -- a proven lower bound of the answer's k-th

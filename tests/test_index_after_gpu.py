@@ -1,4 +1,4 @@
-"""search_after: hac_index_search_after* (after_bounds_kernel and scan16_after_kernel of csrc/after.inc) through FlatIPIndex,
+"""search_after: hac_index_search_after* (after_bounds_kernel of csrc/after.inc and scan16_after_kernel of csrc/scan16_filter.inc) through FlatIPIndex,
 i.e. the C ABI.
 
 Every assertion is equality of I and of the bits of D with tests/after_ref.py, the definition of include/haconvdr.h restated

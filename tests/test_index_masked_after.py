@@ -88,7 +88,7 @@ def test_masked_after_kernel_uses_no_scratch_and_spills_nothing():
     assert int(re.search(r"VGPRs Spill: (\d+)", mine[0]).group(1)) == 0
     assert int(re.search(r"SGPRs Spill: (\d+)", mine[0]).group(1)) == 0
     assert int(re.search(r"VGPRs: (\d+)", mine[0]).group(1)) <= 256
-    # the parents keep their one block each: the new kernel is a function of its own, not a template instance of theirs
+    # the parents keep their one block each: every kernel is a `__global__` function of its own (they call one shared body)
     for parent in ("scan16_masked_kernel", "scan16_after_kernel", "mask_groups_kernel", "after_bounds_kernel"):
         assert len([b for b in blocks if re.search(r"\d+%s[A-Z]" % parent, b.split("\n", 1)[0])]) == 1, parent
 

@@ -1,4 +1,4 @@
-"""search_masked behind a cursor: hac_index_search_masked_after* (scan16_masked_after_kernel of csrc/masked_after.inc behind
+"""search_masked behind a cursor: hac_index_search_masked_after* (scan16_masked_after_kernel of csrc/scan16_filter.inc behind
 mask_groups_kernel and after_bounds_kernel) through FlatIPIndex, i.e. the C ABI.
 
 Every assertion is equality of I and of the bits of D (or of the packed keys) with tests/masked_after_ref.py, the definition of

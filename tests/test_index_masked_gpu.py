@@ -1,4 +1,4 @@
-"""search_masked: hac_index_search_masked* (mask_groups_kernel and scan16_masked_kernel of csrc/masked.inc) through FlatIPIndex,
+"""search_masked: hac_index_search_masked* (mask_groups_kernel of csrc/masked.inc and scan16_masked_kernel of csrc/scan16_filter.inc) through FlatIPIndex,
 i.e. the C ABI.
 
 Every assertion is equality of I and of the bits of D with tests/masked_ref.py, the definition of include/haconvdr.h restated
