@@ -43,11 +43,11 @@ def _on_stream(stream):
 
 # ---- the pointers the C ABI takes: of a float32 / int64 ndarray, of a CUDA tensor (None: null)
 def _f32p(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    return ctypes.POINTER(ctypes.c_float)() if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
 
 
 def _i64p(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    return ctypes.POINTER(ctypes.c_int64)() if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
 
 
 def _devp(t):
@@ -64,17 +64,58 @@ def _device_results(shape, device):
     return torch.empty(shape, dtype=torch.float32, device=device), torch.empty(shape, dtype=torch.int64, device=device)
 
 
-# ---- argument checks of the rows-by-id calls: no handle needed, a mistake raises ValueError before the library is called
-def _as_ids(ids, ndim, what):
-    """ids -> contiguous int64 ndarray of `ndim` dimensions; integers only (a float id is a mistake, not a row)."""
-    a = np.asarray(ids)
+def _device_i64(shape, device):
+    """the int64 CUDA tensor a call fills: packed keys [.., k], ranks, counts, labels, lims"""
+    import torch
+    return torch.empty(shape, dtype=torch.int64, device=device)
+
+
+# ---- argument checks: no handle needed, a mistake raises ValueError before the library is called.  Two primitives, one per
+# form -- _int_array for what the host calls take, _tensor_arg for what the tensor calls take -- and the per-call checks below,
+# which compose them.  A message names the call (`what`) and the argument and says what it got.
+def _check_shape(got, name, what, ndim, shape, hint):
+    """shape: the wanted shape, None = any length; or ndim: the wanted rank."""
+    got = tuple(got)
+    if shape is not None:
+        if len(got) != len(shape) or any(w is not None and w != g for w, g in zip(shape, got)):
+            want = ", ".join("*" if w is None else str(w) for w in shape)
+            raise ValueError(f"{what}: {name} must have shape [{want}], got {got} {hint}".rstrip())
+    elif ndim is not None and len(got) != ndim:
+        raise ValueError(f"{what}: {name} must have {ndim} dimension(s), got shape {got} {hint}".rstrip())
+
+
+def _int_array(a, name, what, *, ndim=None, shape=None, hint=""):
+    """a -> contiguous int64 ndarray of the wanted rank or shape; integers only (a float id is a mistake, not a row), and
+    a uint64 only where int64 holds its values."""
+    a = np.asarray(a)
     if a.dtype.kind not in "iu":
-        raise ValueError(f"{what}: ids must be integers, got dtype {a.dtype}")
-    if a.ndim != ndim:
-        raise ValueError(f"{what}: ids must have {ndim} dimension(s), got shape {a.shape}")
+        raise ValueError(f"{what}: {name} must be integers, got dtype {a.dtype}")
+    _check_shape(a.shape, name, what, ndim, shape, hint)
     if a.dtype == np.uint64 and a.size and int(a.max()) > np.iinfo(np.int64).max:
-        raise ValueError(f"{what}: id {int(a.max())} does not fit int64")
+        raise ValueError(f"{what}: {name}: {int(a.max())} does not fit int64")
     return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def _tensor_arg(t, name, what, *, dtype, ndim=None, shape=None, like=None, optional=False, hint=""):
+    """t -> t.contiguous() (t itself where it is contiguous: no allocation inside a capture), after the checks every tensor
+    form owes the kernels, which get a raw device pointer: a CUDA tensor, of torch's dtype named `dtype` (None: any), of the
+    wanted rank or shape, on the device of `like`.  optional: None passes through."""
+    import torch
+    if t is None and optional:
+        return None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        got = f"a tensor on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{what}: {name} must be a CUDA tensor, got {got} {hint}".rstrip())
+    if dtype is not None and t.dtype != getattr(torch, dtype):
+        raise ValueError(f"{what}: {name} must be {dtype}, got {t.dtype} {hint}".rstrip())
+    _check_shape(t.shape, name, what, ndim, shape, hint)
+    if like is not None and t.device != like.device:
+        raise ValueError(f"{what}: {name} on {t.device} but the tensor it goes with (q, or the keys) on {like.device}")
+    return t.contiguous()
+
+
+def _as_ids(ids, ndim, what):
+    return _int_array(ids, "ids", what, ndim=ndim)
 
 
 def _remove_args(ids, ntotal, what="remove_ids"):
@@ -106,10 +147,7 @@ def _as_queries(q, d, what):
 def _pair_args(q, ids, d, what):
     """(q float32 [nq, d], ids int64 [nq, m]) of score_ids / rank_ids."""
     q = _as_queries(q, d, what)
-    ids = _as_ids(ids, 2, what)
-    if ids.shape[0] != q.shape[0]:
-        raise ValueError(f"{what}: {q.shape[0]} queries but ids of shape {ids.shape} (one list per query)")
-    return q, ids
+    return q, _int_array(ids, "ids", what, shape=(q.shape[0], None), hint="(one list per query)")
 
 
 def _as_k(k, what):
@@ -119,49 +157,32 @@ def _as_k(k, what):
 
 
 def _ids_tensor(ids, ndim, what):
-    import torch
-    if not isinstance(ids, torch.Tensor) or not ids.is_cuda:
-        raise ValueError(f"{what}: ids must be a CUDA tensor")
-    if ids.dtype != torch.int64:
-        raise ValueError(f"{what}: ids must be int64, got {ids.dtype}")
-    if ids.dim() != ndim:
-        raise ValueError(f"{what}: ids must have {ndim} dimension(s), got shape {tuple(ids.shape)}")
-    return ids.contiguous()
+    return _tensor_arg(ids, "ids", what, dtype="int64", ndim=ndim)
 
 
 def _queries_tensor(q, d, what):
-    import torch
-    if not isinstance(q, torch.Tensor) or not q.is_cuda:
-        raise ValueError(f"{what}: q must be a CUDA tensor")
+    q = _tensor_arg(q, "q", what, dtype=None)
     if not q.dtype.is_floating_point or q.dim() != 2 or q.shape[1] != d:
         raise ValueError(f"{what} expects [nq, {d}] float32, got {q.dtype} {tuple(q.shape)}")
-    return q.contiguous().float()
+    return q.float()
+
+
+def _check_id_map_tensor(id_map, q, what):
+    return _tensor_arg(id_map, "id_map", what, dtype="int64", ndim=1, like=q, optional=True, hint="(int64 CUDA [ntotal], or None)")
 
 
 def _pair_args_tensor(q, ids, d, what):
     """(q float32 CUDA [nq, d], ids int64 CUDA [nq, m]) of score_ids_tensor / rank_ids_tensor / count_ahead_tensor."""
     q = _queries_tensor(q, d, what)
-    ids = _ids_tensor(ids, 2, what)
-    if ids.shape[0] != q.shape[0]:
-        raise ValueError(f"{what}: {q.shape[0]} queries but ids of shape {tuple(ids.shape)} (one list per query)")
-    if ids.device != q.device:
-        raise ValueError(f"{what}: q on {q.device} but ids on {ids.device}")
-    return q, ids
+    return q, _tensor_arg(ids, "ids", what, dtype="int64", shape=(q.shape[0], None), like=q, hint="(one list per query)")
 
 
 def _count_args_tensor(q, ref_scores, ref_bounds, d, what="count_ahead_tensor"):
     """(q float32 CUDA [nq, d], ref_scores float32 CUDA [nq, m], ref_bounds int64 CUDA [nq, m]) of count_ahead_tensor."""
-    import torch
     q, ref_bounds = _pair_args_tensor(q, ref_bounds, d, what)
-    if not isinstance(ref_scores, torch.Tensor) or not ref_scores.is_cuda:
-        raise ValueError(f"{what}: ref_scores must be a CUDA tensor")
-    if ref_scores.dtype != torch.float32:
-        raise ValueError(f"{what}: ref_scores must be float32 (the bits a search returns), got {ref_scores.dtype}")
-    if tuple(ref_scores.shape) != tuple(ref_bounds.shape):
-        raise ValueError(f"{what}: ref_scores of shape {tuple(ref_scores.shape)} but ref_bounds of shape {tuple(ref_bounds.shape)}")
-    if ref_scores.device != q.device:
-        raise ValueError(f"{what}: q on {q.device} but ref_scores on {ref_scores.device}")
-    return q, ref_scores.contiguous(), ref_bounds
+    ref_scores = _tensor_arg(ref_scores, "ref_scores", what, dtype="float32", shape=tuple(ref_bounds.shape), like=q,
+                             hint="(the bits a search returns, one per entry of ref_bounds)")
+    return q, ref_scores, ref_bounds
 
 
 def _as_radius(radius, nq, what):
@@ -191,24 +212,10 @@ def _range_args(q, radius, d, what="range_search"):
 
 def _range_args_tensor(q, radius, cap, id_map, d, what="range_search_tensor"):
     """(q float32 CUDA [nq, d], radius float32 CUDA [nq], cap, id_map int64 CUDA [ntotal] or None) of range_search_tensor."""
-    import torch
     q = _queries_tensor(q, d, what)
-    if not isinstance(radius, torch.Tensor) or not radius.is_cuda:
-        raise ValueError(f"{what}: radius must be a CUDA tensor")
-    if radius.dtype != torch.float32:
-        raise ValueError(f"{what}: radius must be float32 (the precision the scores are compared in), got {radius.dtype}")
-    if tuple(radius.shape) != (q.shape[0],):
-        raise ValueError(f"{what}: {q.shape[0]} queries but radius of shape {tuple(radius.shape)} (one per query)")
-    if radius.device != q.device:
-        raise ValueError(f"{what}: q on {q.device} but radius on {radius.device}")
-    cap = _as_cap(cap, what)
-    if id_map is not None:
-        if not isinstance(id_map, torch.Tensor) or not id_map.is_cuda or id_map.dtype != torch.int64 or id_map.dim() != 1:
-            raise ValueError(f"{what}: id_map must be an int64 CUDA tensor [ntotal]")
-        if id_map.device != q.device:
-            raise ValueError(f"{what}: q on {q.device} but id_map on {id_map.device}")
-        id_map = id_map.contiguous()
-    return q, radius.contiguous(), cap, id_map
+    radius = _tensor_arg(radius, "radius", what, dtype="float32", shape=(q.shape[0],), like=q,
+                         hint="(one per query, in the precision the scores are compared in)")
+    return q, radius, _as_cap(cap, what), _check_id_map_tensor(id_map, q, what)
 
 
 def _check_exclude_shape(nq, k, shape, what):
@@ -222,7 +229,7 @@ def _exclude_args(q, k, exclude, d, what="search_excluding"):
     """(q float32 [nq, d], k, exclude int64 [nq, e]) of search_excluding."""
     q = _as_queries(q, d, what)
     k = _as_k(k, what)
-    exclude = _as_ids(exclude, 2, what)
+    exclude = _int_array(exclude, "exclude", what, ndim=2)
     _check_exclude_shape(q.shape[0], k, exclude.shape, what)
     return q, k, exclude
 
@@ -230,10 +237,8 @@ def _exclude_args(q, k, exclude, d, what="search_excluding"):
 def _exclude_args_tensor(q, k, exclude, d, what="search_excluding_tensor"):
     q = _queries_tensor(q, d, what)
     k = _as_k(k, what)
-    exclude = _ids_tensor(exclude, 2, what)
+    exclude = _tensor_arg(exclude, "exclude", what, dtype="int64", ndim=2, like=q)
     _check_exclude_shape(q.shape[0], k, exclude.shape, what)
-    if exclude.device != q.device:
-        raise ValueError(f"{what}: q on {q.device} but exclude on {exclude.device}")
     return q, k, exclude
 
 
@@ -248,27 +253,18 @@ def _among_args(q, k, cand, d, what="search_among"):
     """(q float32 [nq, d], k, cand int64 [nq, m]) of search_among."""
     q = _as_queries(q, d, what)
     k = _as_k(k, what)
-    cand = _as_ids(cand, 2, what)
+    cand = _int_array(cand, "cand", what, ndim=2)
     _check_among_shape(q.shape[0], cand.shape, what)
     return q, k, cand
 
 
 def _among_args_tensor(q, k, cand, id_map, d, what="search_among_tensor"):
     """(q float32 CUDA [nq, d], k, cand int64 CUDA [nq, m], id_map int64 CUDA [ntotal] or None) of search_among*_tensor."""
-    import torch
     q = _queries_tensor(q, d, what)
     k = _as_k(k, what)
-    cand = _ids_tensor(cand, 2, what)
+    cand = _tensor_arg(cand, "cand", what, dtype="int64", ndim=2, like=q)
     _check_among_shape(q.shape[0], cand.shape, what)
-    if cand.device != q.device:
-        raise ValueError(f"{what}: q on {q.device} but cand on {cand.device}")
-    if id_map is not None:
-        if not isinstance(id_map, torch.Tensor) or not id_map.is_cuda or id_map.dtype != torch.int64 or id_map.dim() != 1:
-            raise ValueError(f"{what}: id_map must be an int64 CUDA tensor [ntotal]")
-        if id_map.device != q.device:
-            raise ValueError(f"{what}: q on {q.device} but id_map on {id_map.device}")
-        id_map = id_map.contiguous()
-    return q, k, cand, id_map
+    return q, k, cand, _check_id_map_tensor(id_map, q, what)
 
 
 # ---- bitmaps of search_masked (include/haconvdr.h, "search inside a bitmap"): row r is bit r & 63 of word r >> 6
@@ -351,10 +347,8 @@ def _as_masks(masks, mask_of, nq, ntotal, what):
     if a.shape[0] < 1:
         raise ValueError(f"{what}: needs at least one mask")
     if mask_of is not None:
-        mask_of = _as_ids(mask_of, 1, what)
-        _check_mask_of(mask_of.shape, a.shape[0], nq, what)   # (its values: the library refuses one outside [0, n_masks), as it refuses ids)
-    else:
-        _check_mask_of(None, a.shape[0], nq, what)
+        mask_of = _int_array(mask_of, "mask_of", what, ndim=1)   # (its values: the library refuses one outside [0, n_masks), as it refuses ids)
+    _check_mask_of(None if mask_of is None else mask_of.shape, a.shape[0], nq, what)
     return a, mask_of
 
 
@@ -368,76 +362,35 @@ def _masked_args(q, k, masks, mask_of, d, ntotal, what="search_masked"):
 
 def _masked_args_tensor(q, k, masks, mask_of, id_map, d, ntotal, what="search_masked_tensor"):
     """(q float32 CUDA [nq, d], k, masks int64 CUDA [n_masks, W], mask_of int64 CUDA [nq] or None, id_map) of search_masked*_tensor."""
-    import torch
     q = _queries_tensor(q, d, what)
     k = _as_k(k, what)
-    if not isinstance(masks, torch.Tensor) or not masks.is_cuda:
-        raise ValueError(f"{what}: masks must be a CUDA tensor (pack_mask of a bool tensor)")
-    if masks.dtype != torch.int64:
-        raise ValueError(f"{what}: masks must be packed int64 words, got {masks.dtype}")
-    if masks.dim() != 2 or masks.shape[0] < 1 or masks.shape[1] != mask_words(ntotal):
-        raise ValueError(f"{what}: masks must be [n_masks >= 1, {mask_words(ntotal)}] for {ntotal} rows, got shape {tuple(masks.shape)} "
-                         "(packed before an add or a remove?)")
-    if masks.device != q.device:
-        raise ValueError(f"{what}: q on {q.device} but masks on {masks.device}")
-    if mask_of is not None:
-        if not isinstance(mask_of, torch.Tensor) or not mask_of.is_cuda or mask_of.dtype != torch.int64:
-            raise ValueError(f"{what}: mask_of must be an int64 CUDA tensor [nq]")
-        _check_mask_of(mask_of.shape, masks.shape[0], q.shape[0], what)
-        if mask_of.device != q.device:
-            raise ValueError(f"{what}: q on {q.device} but mask_of on {mask_of.device}")
-        mask_of = mask_of.contiguous()
-    else:
-        _check_mask_of(None, masks.shape[0], q.shape[0], what)
-    if id_map is not None:
-        if not isinstance(id_map, torch.Tensor) or not id_map.is_cuda or id_map.dtype != torch.int64 or id_map.dim() != 1:
-            raise ValueError(f"{what}: id_map must be an int64 CUDA tensor [ntotal]")
-        if id_map.device != q.device:
-            raise ValueError(f"{what}: q on {q.device} but id_map on {id_map.device}")
-        id_map = id_map.contiguous()
-    return q, k, masks.contiguous(), mask_of, id_map
+    masks = _tensor_arg(masks, "masks", what, dtype="int64", shape=(None, mask_words(ntotal)), like=q,
+                        hint=f"(pack_mask of a bool tensor: packed words [n_masks >= 1, W] for {ntotal} rows; packed before an add or a remove?)")
+    if masks.shape[0] < 1:
+        raise ValueError(f"{what}: needs at least one mask")
+    mask_of = _tensor_arg(mask_of, "mask_of", what, dtype="int64", like=q, optional=True)
+    _check_mask_of(None if mask_of is None else mask_of.shape, masks.shape[0], q.shape[0], what)
+    return q, k, masks, mask_of, _check_id_map_tensor(id_map, q, what)
 
 
 # ---- labels of search_grouped (include/haconvdr.h, "search by group"): one int64 label in [0, 2^32) per row
+_LABELS_HINT = "(one label per row of the index; labels made before an add or a remove?)"
+
+
 def _grouped_args(q, k, group_of, d, ntotal, what="search_grouped"):
     """(q float32 [nq, d], k, group_of int64 [ntotal]) of search_grouped.  The values are the library's to check: it names the
     first row whose label lies outside [0, 2^32)."""
     q = _as_queries(q, d, what)
     k = _as_k(k, what)
-    a = np.asarray(group_of)
-    if a.dtype.kind not in "iu":
-        raise ValueError(f"{what}: group_of must be integers, got dtype {a.dtype}")
-    if a.ndim != 1:
-        raise ValueError(f"{what}: group_of must have 1 dimension, one label per row, got shape {a.shape}")
-    if a.shape[0] != ntotal:
-        raise ValueError(f"{what}: {a.shape[0]} labels but the index holds {ntotal} rows (labels made before an add or a remove?)")
-    if a.dtype == np.uint64 and a.size and int(a.max()) > np.iinfo(np.int64).max:
-        raise ValueError(f"{what}: label {int(a.max())} does not fit int64")
-    return q, k, np.ascontiguousarray(a, dtype=np.int64)
+    return q, k, _int_array(group_of, "group_of", what, shape=(ntotal,), hint=_LABELS_HINT)
 
 
 def _grouped_args_tensor(q, k, group_of, id_map, d, ntotal, what="search_grouped_tensor"):
     """(q float32 CUDA [nq, d], k, group_of int64 CUDA [ntotal], id_map int64 CUDA [ntotal] or None) of search_grouped_tensor."""
-    import torch
     q = _queries_tensor(q, d, what)
     k = _as_k(k, what)
-    if not isinstance(group_of, torch.Tensor) or not group_of.is_cuda:
-        raise ValueError(f"{what}: group_of must be a CUDA tensor")
-    if group_of.dtype != torch.int64:
-        raise ValueError(f"{what}: group_of must be int64, got {group_of.dtype}")
-    if group_of.dim() != 1:
-        raise ValueError(f"{what}: group_of must have 1 dimension, one label per row, got shape {tuple(group_of.shape)}")
-    if group_of.shape[0] != ntotal:
-        raise ValueError(f"{what}: {group_of.shape[0]} labels but the index holds {ntotal} rows (labels made before an add or a remove?)")
-    if group_of.device != q.device:
-        raise ValueError(f"{what}: q on {q.device} but group_of on {group_of.device}")
-    if id_map is not None:
-        if not isinstance(id_map, torch.Tensor) or not id_map.is_cuda or id_map.dtype != torch.int64 or id_map.dim() != 1:
-            raise ValueError(f"{what}: id_map must be an int64 CUDA tensor [ntotal]")
-        if id_map.device != q.device:
-            raise ValueError(f"{what}: q on {q.device} but id_map on {id_map.device}")
-        id_map = id_map.contiguous()
-    return q, k, group_of.contiguous(), id_map
+    group_of = _tensor_arg(group_of, "group_of", what, dtype="int64", shape=(ntotal,), like=q, hint=_LABELS_HINT)
+    return q, k, group_of, _check_id_map_tensor(id_map, q, what)
 
 
 # ---- cursors of search_after (include/haconvdr.h, "search behind a cursor"): a (score, row) pair per query, or a packed key
@@ -449,9 +402,7 @@ def cursor_keys(scores, rows, pos_base=0):
     same shape and kind (ndarray or CUDA tensor), in the position space of pos_base: search_after_keys_tensor's after_keys.  The
     rule of after_bounds_kernel: a NaN score, row -1 (a padding slot) and a row below -2 give 0, the exhausted list; row
     AFTER_START gives all-ones, the start; otherwise ord(score + 0.0) << 32 | 2^32 - 1 - min(pos_base + row, 2^32 - 1)."""
-    if isinstance(pos_base, bool) or not isinstance(pos_base, (int, np.integer)) or not 0 <= int(pos_base) <= 0xFFFFFFFF:
-        raise ValueError(f"cursor_keys: pos_base must be an integer in [0, 2^32), got {pos_base!r}")
-    pos_base = int(pos_base)
+    pos_base = _as_pos_base(pos_base, "cursor_keys")
     if hasattr(scores, "is_cuda") or hasattr(rows, "is_cuda"):
         import torch
         if not (isinstance(scores, torch.Tensor) and isinstance(rows, torch.Tensor)) or scores.device != rows.device:
@@ -482,127 +433,57 @@ def cursor_keys(scores, rows, pos_base=0):
     return keys.astype(np.uint64).view(np.int64)
 
 
-def _after_args(q, k, after, d, what="search_after"):
-    """(q float32 [nq, d], k, scores float32 [nq] or None, rows int64 [nq] or None) of search_after; after: None (every query
-    from the start) or a pair (scores [nq] float32 -- the bits a search returned --, rows [nq] integers >= -2)."""
-    q = _as_queries(q, d, what)
-    k = _as_k(k, what)
+_CURSOR_HINT = "(one per query; the scores are the bits a search returns)"
+
+
+def _cursor(after, nq, what):
+    """after of search_after / search_masked(after=) -> (scores float32 [nq], rows int64 [nq]), or (None, None) for None."""
     if after is None:
-        return q, k, None, None
+        return None, None
     if not isinstance(after, (tuple, list)) or len(after) != 2:
         raise ValueError(f"{what}: after must be None or a pair (scores [nq], rows [nq])")
     scores = np.asarray(after[0])
-    if scores.dtype != np.float32:
-        raise ValueError(f"{what}: cursor scores must be float32 (the bits a search returns), got dtype {scores.dtype}")
-    if scores.shape != (q.shape[0],):
-        raise ValueError(f"{what}: {q.shape[0]} queries but cursor scores of shape {scores.shape} (one per query)")
-    rows = np.asarray(after[1])
-    if rows.dtype.kind not in "iu":
-        raise ValueError(f"{what}: cursor rows must be integers, got dtype {rows.dtype}")
-    if rows.shape != (q.shape[0],):
-        raise ValueError(f"{what}: {q.shape[0]} queries but cursor rows of shape {rows.shape} (one per query)")
-    rows = _as_ids(rows, 1, what)
+    if scores.dtype != np.float32 or scores.shape != (nq,):
+        raise ValueError(f"{what}: cursor scores must be float32 [{nq}], got {scores.dtype} {scores.shape} {_CURSOR_HINT}")
+    rows = _int_array(after[1], "cursor rows", what, shape=(nq,), hint=_CURSOR_HINT)
     if rows.size and int(rows.min()) < AFTER_START:
         at = int(np.flatnonzero(rows < AFTER_START)[0])
         raise ValueError(f"{what}: cursor row {int(rows[at])} of query {at} is below {AFTER_START} (a row, -1 = an exhausted list, "
                          f"{AFTER_START} = the start)")
-    return q, k, np.ascontiguousarray(scores), rows
+    return np.ascontiguousarray(scores), rows
 
 
-def _check_id_map_tensor(id_map, q, what):
-    import torch
-    if id_map is None:
-        return None
-    if not isinstance(id_map, torch.Tensor) or not id_map.is_cuda or id_map.dtype != torch.int64 or id_map.dim() != 1:
-        raise ValueError(f"{what}: id_map must be an int64 CUDA tensor [ntotal]")
-    if id_map.device != q.device:
-        raise ValueError(f"{what}: q on {q.device} but id_map on {id_map.device}")
-    return id_map.contiguous()
+def _cursor_tensor(after, q, what):
+    """after of search_after_tensor / search_masked_tensor(after=) -> (scores float32 CUDA [nq], rows int64 CUDA [nq]), or
+    (None, None) for None.  The rows' values are the device's to read: one below -2 gives that query an empty list."""
+    if after is None:
+        return None, None
+    if not isinstance(after, (tuple, list)) or len(after) != 2:
+        raise ValueError(f"{what}: after must be None or a pair (scores [nq], rows [nq])")
+    return (_tensor_arg(after[0], "cursor scores", what, dtype="float32", shape=(q.shape[0],), like=q, hint=_CURSOR_HINT),
+            _tensor_arg(after[1], "cursor rows", what, dtype="int64", shape=(q.shape[0],), like=q, hint=_CURSOR_HINT))
+
+
+def _cursor_keys_tensor(after_keys, q, what):
+    """after_keys of search_after_keys_tensor / search_masked_keys_tensor(after_keys=) -> int64 CUDA [nq], or None."""
+    return _tensor_arg(after_keys, "after_keys", what, dtype="int64", shape=(q.shape[0],), like=q, optional=True,
+                       hint="(one per query: cursor_keys, or the last column of a key list, the int64 view of the packed uint64 keys)")
+
+
+def _after_args(q, k, after, d, what="search_after"):
+    """(q float32 [nq, d], k, scores float32 [nq] or None, rows int64 [nq] or None) of search_after; after: None (every query
+    from the start) or a pair (scores [nq] float32 -- the bits a search returned --, rows [nq] integers >= -2)."""
+    q = _as_queries(q, d, what)
+    return (q, _as_k(k, what), *_cursor(after, q.shape[0], what))
 
 
 def _after_args_tensor(q, k, after, id_map, d, what="search_after_tensor"):
     """(q float32 CUDA [nq, d], k, scores float32 CUDA [nq] or None, rows int64 CUDA [nq] or None, id_map) of
-    search_after_tensor.  The rows' values are the device's to read: one below -2 gives that query an empty list."""
-    import torch
+    search_after_tensor."""
     q = _queries_tensor(q, d, what)
     k = _as_k(k, what)
     id_map = _check_id_map_tensor(id_map, q, what)
-    if after is None:
-        return q, k, None, None, id_map
-    if not isinstance(after, (tuple, list)) or len(after) != 2:
-        raise ValueError(f"{what}: after must be None or a pair (scores [nq], rows [nq])")
-    scores, rows = after
-    if not isinstance(scores, torch.Tensor) or not scores.is_cuda or not isinstance(rows, torch.Tensor) or not rows.is_cuda:
-        raise ValueError(f"{what}: cursor scores and rows must be CUDA tensors")
-    if scores.dtype != torch.float32:
-        raise ValueError(f"{what}: cursor scores must be float32 (the bits a search returns), got {scores.dtype}")
-    if rows.dtype != torch.int64:
-        raise ValueError(f"{what}: cursor rows must be int64, got {rows.dtype}")
-    for name, t in (("scores", scores), ("rows", rows)):
-        if tuple(t.shape) != (q.shape[0],):
-            raise ValueError(f"{what}: {q.shape[0]} queries but cursor {name} of shape {tuple(t.shape)} (one per query)")
-        if t.device != q.device:
-            raise ValueError(f"{what}: q on {q.device} but cursor {name} on {t.device}")
-    return q, k, scores.contiguous(), rows.contiguous(), id_map
-
-
-def _after_keys_args_tensor(q, k, after_keys, pos_base, d, what="search_after_keys_tensor"):
-    """(q float32 CUDA [nq, d], k, after_keys int64 CUDA [nq] or None, pos_base) of search_after_keys_tensor."""
-    import torch
-    q = _queries_tensor(q, d, what)
-    k = _as_k(k, what)
-    if isinstance(pos_base, bool) or not isinstance(pos_base, (int, np.integer)) or not 0 <= int(pos_base) <= 0xFFFFFFFF:
-        raise ValueError(f"{what}: pos_base must be an integer in [0, 2^32), got {pos_base!r}")
-    if after_keys is not None:
-        if not isinstance(after_keys, torch.Tensor) or not after_keys.is_cuda:
-            raise ValueError(f"{what}: after_keys must be a CUDA tensor (cursor_keys, or the last column of a key list)")
-        if after_keys.dtype != torch.int64:
-            raise ValueError(f"{what}: after_keys must be int64 (the view of the packed uint64 keys), got {after_keys.dtype}")
-        if tuple(after_keys.shape) != (q.shape[0],):
-            raise ValueError(f"{what}: {q.shape[0]} queries but after_keys of shape {tuple(after_keys.shape)} (one per query)")
-        if after_keys.device != q.device:
-            raise ValueError(f"{what}: q on {q.device} but after_keys on {after_keys.device}")
-        after_keys = after_keys.contiguous()
-    return q, k, after_keys, int(pos_base)
-
-
-# ---- ranks of entries_at / search_at (include/haconvdr.h, "entry at a rank"): values, not ids -- any integer is allowed
-def _as_ranks(ranks, what):
-    """ranks -> contiguous int64 [nq, m]; integers only (a float rank is a mistake, not a position)."""
-    a = np.asarray(ranks)
-    if a.dtype.kind not in "iu":
-        raise ValueError(f"{what}: ranks must be integers, got dtype {a.dtype}")
-    if a.ndim != 2:
-        raise ValueError(f"{what}: ranks must have 2 dimension(s), got shape {a.shape}")
-    if a.dtype == np.uint64 and a.size and int(a.max()) > np.iinfo(np.int64).max:
-        raise ValueError(f"{what}: rank {int(a.max())} does not fit int64")
-    return np.ascontiguousarray(a, dtype=np.int64)
-
-
-def _rank_args(q, ranks, d, what="entries_at"):
-    """(q float32 [nq, d], ranks int64 [nq, m]) of entries_at."""
-    q = _as_queries(q, d, what)
-    ranks = _as_ranks(ranks, what)
-    if ranks.shape[0] != q.shape[0]:
-        raise ValueError(f"{what}: {q.shape[0]} queries but ranks of shape {ranks.shape} (one list per query)")
-    return q, ranks
-
-
-def _rank_args_tensor(q, ranks, d, what="entries_at_tensor"):
-    """(q float32 CUDA [nq, d], ranks int64 CUDA [nq, m]) of entries_at_tensor / entry_keys_at_tensor."""
-    import torch
-    q = _queries_tensor(q, d, what)
-    if not isinstance(ranks, torch.Tensor) or not ranks.is_cuda:
-        raise ValueError(f"{what}: ranks must be a CUDA tensor")
-    if ranks.dtype != torch.int64:
-        raise ValueError(f"{what}: ranks must be int64, got {ranks.dtype}")
-    if ranks.dim() != 2:
-        raise ValueError(f"{what}: ranks must have 2 dimension(s), got shape {tuple(ranks.shape)}")
-    if ranks.shape[0] != q.shape[0]:
-        raise ValueError(f"{what}: {q.shape[0]} queries but ranks of shape {tuple(ranks.shape)} (one list per query)")
-    if ranks.device != q.device:
-        raise ValueError(f"{what}: q on {q.device} but ranks on {ranks.device}")
-    return q, ranks.contiguous()
+    return (q, k, *_cursor_tensor(after, q, what), id_map)
 
 
 def _as_pos_base(pos_base, what):
@@ -611,20 +492,35 @@ def _as_pos_base(pos_base, what):
     return int(pos_base)
 
 
+def _after_keys_args_tensor(q, k, after_keys, pos_base, d, what="search_after_keys_tensor"):
+    """(q float32 CUDA [nq, d], k, after_keys int64 CUDA [nq] or None, pos_base) of search_after_keys_tensor."""
+    q = _queries_tensor(q, d, what)
+    k = _as_k(k, what)
+    pos_base = _as_pos_base(pos_base, what)
+    return q, k, _cursor_keys_tensor(after_keys, q, what), pos_base
+
+
+# ---- ranks of entries_at / search_at (include/haconvdr.h, "entry at a rank"): values, not ids -- any integer is allowed
+def _rank_args(q, ranks, d, what="entries_at"):
+    """(q float32 [nq, d], ranks int64 [nq, m]) of entries_at."""
+    q = _as_queries(q, d, what)
+    return q, _int_array(ranks, "ranks", what, shape=(q.shape[0], None), hint="(one list per query)")
+
+
+def _rank_args_tensor(q, ranks, d, what="entries_at_tensor"):
+    """(q float32 CUDA [nq, d], ranks int64 CUDA [nq, m]) of entries_at_tensor / entry_keys_at_tensor."""
+    q = _queries_tensor(q, d, what)
+    return q, _tensor_arg(ranks, "ranks", what, dtype="int64", shape=(q.shape[0], None), like=q, hint="(one list per query)")
+
+
 def _as_start(start, nq, what):
     """start of search_at -> contiguous int64 [nq]: an integer (one start for every query) or one per query, all >= 0."""
     if isinstance(start, bool):
         raise ValueError(f"{what}: start must be an integer or int64 [nq], got {start!r}")
     a = np.asarray(start)
-    if a.dtype.kind not in "iu":
-        raise ValueError(f"{what}: start must be integers, got dtype {a.dtype}")
-    if a.ndim == 0:
+    if a.ndim == 0 and a.dtype.kind in "iu":
         a = np.full(nq, a)
-    elif a.shape != (nq,):
-        raise ValueError(f"{what}: {nq} queries but start of shape {a.shape} (an integer, or one per query)")
-    if a.dtype == np.uint64 and a.size and int(a.max()) > np.iinfo(np.int64).max:
-        raise ValueError(f"{what}: start {int(a.max())} does not fit int64")
-    a = np.ascontiguousarray(a, dtype=np.int64)
+    a = _int_array(a, "start", what, shape=(nq,), hint="(an integer, or one per query)")
     if a.size and int(a.min()) < 0:
         at = int(np.flatnonzero(a < 0)[0])
         raise ValueError(f"{what}: start {int(a[at])} of query {at} is negative (a rank of the unbounded search, >= 0)")
@@ -636,31 +532,23 @@ def _start_tensor(start, q, what):
     are the device's to read: a negative one gives that query an empty list)."""
     import torch
     nq = q.shape[0]
-    if isinstance(start, torch.Tensor):
-        if not start.is_cuda or start.dtype != torch.int64:
-            raise ValueError(f"{what}: start must be an integer or an int64 CUDA tensor [nq], got {start.dtype} on {start.device}")
-        if tuple(start.shape) != (nq,):
-            raise ValueError(f"{what}: {nq} queries but start of shape {tuple(start.shape)} (an integer, or one per query)")
-        if start.device != q.device:
-            raise ValueError(f"{what}: q on {q.device} but start on {start.device}")
-        return start.contiguous()
-    if isinstance(start, bool) or not isinstance(start, (int, np.integer)) or int(start) < 0:
+    if isinstance(start, bool) or not isinstance(start, (int, np.integer)):
+        return _tensor_arg(start, "start", what, dtype="int64", shape=(nq,), like=q, hint="(an integer >= 0, or an int64 CUDA tensor [nq])")
+    if int(start) < 0:
         raise ValueError(f"{what}: start must be an integer >= 0 or an int64 CUDA tensor [nq], got {start!r}")
     return torch.full((nq,), int(start), dtype=torch.int64, device=q.device)
 
 
 def _filter_args(keys, exclude_pos, k, what="filter_keys"):
     """(keys int64 CUDA [nq, kin], exclude_pos int64 CUDA [nq, e], k in [1, kin]) of filter_keys."""
-    keys = _ids_tensor(keys, 2, what)
-    exclude_pos = _ids_tensor(exclude_pos, 2, what)
+    keys = _tensor_arg(keys, "keys", what, dtype="int64", ndim=2)
+    exclude_pos = _tensor_arg(exclude_pos, "exclude_pos", what, dtype="int64", ndim=2, like=keys)
     k = _as_k(k, what)
     if keys.shape[1] > _lib.HAC_MAX_K or k > keys.shape[1]:
         raise ValueError(f"{what}: needs k = {k} <= kin = {keys.shape[1]} <= {_lib.HAC_MAX_K}")
     if exclude_pos.shape[0] != keys.shape[0] or exclude_pos.shape[1] >= _lib.HAC_MAX_K:
         raise ValueError(f"{what}: keys of shape {tuple(keys.shape)} but exclude_pos of shape {tuple(exclude_pos.shape)} "
                          f"(one list of fewer than {_lib.HAC_MAX_K} positions per query)")
-    if exclude_pos.device != keys.device:
-        raise ValueError(f"{what}: keys on {keys.device} but exclude_pos on {exclude_pos.device}")
     return keys, exclude_pos, k
 
 
@@ -735,11 +623,9 @@ class FlatIPIndex:
         not be selected and need not exist; row -1 gives padding, AFTER_START the start, a row below -2 raises ValueError
         (include/haconvdr.h, "search inside a bitmap, behind a cursor")."""
         q, k, words, mask_of = _masked_args(q, k, masks, mask_of, self.d, self.ntotal)
-        if after is not None:
-            _, _, scores, rows = _after_args(q, k, after, self.d, "search_masked")
+        scores, rows = _cursor(after, q.shape[0], "search_masked")
         D, I = _host_results((q.shape[0], k))
-        head = (self._h, _f32p(q), q.shape[0], k, words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), words.shape[0], words.shape[1],
-                ctypes.POINTER(ctypes.c_int64)() if mask_of is None else _i64p(mask_of))
+        head = (self._h, _f32p(q), q.shape[0], k, words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), words.shape[0], words.shape[1], _i64p(mask_of))
         if after is None:
             _lib.check(_lib.lib().hac_index_search_masked(*head, _f32p(D), _i64p(I)))
         else:
@@ -755,8 +641,7 @@ class FlatIPIndex:
         q, k, group_of = _grouped_args(q, k, group_of, self.d, self.ntotal)
         D, I = _host_results((q.shape[0], k))
         G = np.empty((q.shape[0], k), np.int64) if return_groups else None
-        _lib.check(_lib.lib().hac_index_search_grouped(self._h, _f32p(q), q.shape[0], k, _i64p(group_of), group_of.shape[0], _f32p(D), _i64p(I),
-                                                       ctypes.POINTER(ctypes.c_int64)() if G is None else _i64p(G)))
+        _lib.check(_lib.lib().hac_index_search_grouped(self._h, _f32p(q), q.shape[0], k, _i64p(group_of), group_of.shape[0], _f32p(D), _i64p(I), _i64p(G)))
         return (D, I, G) if return_groups else (D, I)
 
     def search_after(self, q, k, after=None):
@@ -768,9 +653,7 @@ class FlatIPIndex:
         costs the same at any depth (include/haconvdr.h, "search behind a cursor")."""
         q, k, scores, rows = _after_args(q, k, after, self.d)
         D, I = _host_results((q.shape[0], k))
-        null_f, null_i = ctypes.POINTER(ctypes.c_float)(), ctypes.POINTER(ctypes.c_int64)()
-        _lib.check(_lib.lib().hac_index_search_after(self._h, _f32p(q), q.shape[0], k, null_f if scores is None else _f32p(scores),
-                                                     null_i if rows is None else _i64p(rows), _f32p(D), _i64p(I)))
+        _lib.check(_lib.lib().hac_index_search_after(self._h, _f32p(q), q.shape[0], k, _f32p(scores), _i64p(rows), _f32p(D), _i64p(I)))
         return D, I
 
     def reset(self):
@@ -867,9 +750,8 @@ class FlatIPIndex:
     def _range_call(self, q, radius, cap):
         lims = np.empty(q.shape[0] + 1, np.int64)
         D, I = _host_results((cap,))
-        null_f, null_i = ctypes.POINTER(ctypes.c_float)(), ctypes.POINTER(ctypes.c_int64)()
         _lib.check(_lib.lib().hac_index_range_search(self._h, _f32p(q), q.shape[0], _f32p(radius), cap, _i64p(lims),
-                                                     _f32p(D) if cap else null_f, _i64p(I) if cap else null_i))
+                                                     _f32p(D if cap else None), _i64p(I if cap else None)))
         return lims, D, I
 
     def range_search(self, q, radius):
@@ -896,12 +778,11 @@ class FlatIPIndex:
         I int64 [cap]) CUDA tensors; no host sync.  lims is always exact.  If lims[nq] <= cap, D and I are filled in
         [0, lims[nq]) and untouched behind; otherwise their contents are unspecified: compare lims[nq] with cap and call again.
         id_map: optional int64 CUDA [ntotal], I = id_map[row].  Capturable after one call of the largest (nq, cap)."""
-        import torch
         q, radius, cap, id_map = _range_args_tensor(q, radius, cap, id_map, self.d)
-        lims = torch.empty((q.shape[0] + 1,), dtype=torch.int64, device=q.device)
+        lims = _device_i64((q.shape[0] + 1,), q.device)
         D, I = _device_results((cap,), q.device)
-        _lib.check(_lib.lib().hac_index_range_search_device(self._h, _devp(q), q.shape[0], _devp(radius), cap, _devp(lims), _devp(D) if cap else _devp(None),
-                                                            _devp(I) if cap else _devp(None), _devp(id_map), _stream_ptr(stream)))
+        _lib.check(_lib.lib().hac_index_range_search_device(self._h, _devp(q), q.shape[0], _devp(radius), cap, _devp(lims), _devp(D if cap else None),
+                                                            _devp(I if cap else None), _devp(id_map), _stream_ptr(stream)))
         _keep_alive(stream, q, radius, lims, D, I, *(() if id_map is None else (id_map,)))
         return lims, D, I
 
@@ -921,19 +802,21 @@ class FlatIPIndex:
         tensor [ntotal], fuses ``passage_embedding2id[I]`` (:110)."""
         assert q.is_cuda and q.dim() == 2 and q.shape[1] == self.d
         q = q.contiguous().float()
+        id_map = _check_id_map_tensor(id_map, q, "search_tensor")
         D, I = _device_results((q.shape[0], k), q.device)
         _lib.check(_lib.lib().hac_index_search_device(self._h, _devp(q), q.shape[0], int(k), _devp(D), _devp(I), _devp(id_map), _stream_ptr(stream)))
-        _keep_alive(stream, q, D, I)
+        _keep_alive(stream, q, D, I, *(() if id_map is None else (id_map,)))
         return D, I
 
     def search_excluding_tensor(self, q, k, exclude, id_map=None, stream=None):
         """search_tensor over (rows minus the query's excluded rows): exclude int64 CUDA [nq, e] ROW ids (not id_map's), any id
         outside [0, ntotal) is ignored.  No host sync; capturable after one call of the largest (nq, k + e)."""
         q, k, exclude = _exclude_args_tensor(q, k, exclude, self.d)
+        id_map = _check_id_map_tensor(id_map, q, "search_excluding_tensor")
         D, I = _device_results((q.shape[0], k), q.device)
         _lib.check(_lib.lib().hac_index_search_excluding_device(self._h, _devp(q), q.shape[0], k, _devp(exclude), exclude.shape[1], _devp(D), _devp(I),
                                                                 _devp(id_map), _stream_ptr(stream)))
-        _keep_alive(stream, q, exclude, D, I)
+        _keep_alive(stream, q, exclude, D, I, *(() if id_map is None else (id_map,)))
         return D, I
 
     def search_among_tensor(self, q, k, cand, id_map=None, stream=None):
@@ -950,11 +833,11 @@ class FlatIPIndex:
     def search_among_keys_tensor(self, q, k, cand, pos_base=0, stream=None):
         """search_among_tensor's sorted packed keys (int64 view of uint64) [nq, k], positions pos_base + row: the unit exchanged
         between shards (merge_keys, keys_to_results)."""
-        import torch
         q, k, cand, _ = _among_args_tensor(q, k, cand, None, self.d, "search_among_keys_tensor")
-        keys = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
+        pos_base = _as_pos_base(pos_base, "search_among_keys_tensor")
+        keys = _device_i64((q.shape[0], k), q.device)
         _lib.check(_lib.lib().hac_index_search_among_keys_device(self._h, _devp(q), q.shape[0], k, _devp(cand), cand.shape[1], _devp(keys),
-                                                                 int(pos_base), _stream_ptr(stream)))
+                                                                 pos_base, _stream_ptr(stream)))
         _keep_alive(stream, q, cand, keys)
         return keys
 
@@ -966,10 +849,7 @@ class FlatIPIndex:
         row below -2 gives an empty list, and id_map remaps the result only.  No host sync; capturable after one call of the
         largest (nq, k, n_masks)."""
         q, k, masks, mask_of, id_map = _masked_args_tensor(q, k, masks, mask_of, id_map, self.d, self.ntotal)
-        cursor = ()
-        if after is not None:
-            _, _, scores, rows, _ = _after_args_tensor(q, k, after, None, self.d, "search_masked_tensor")
-            cursor = (scores, rows)
+        scores, rows = _cursor_tensor(after, q, "search_masked_tensor")
         D, I = _device_results((q.shape[0], k), q.device)
         head = (self._h, _devp(q), q.shape[0], k, _devp(masks), masks.shape[0], masks.shape[1], _devp(mask_of))
         tail = (_devp(D), _devp(I), _devp(id_map), _stream_ptr(stream))
@@ -977,7 +857,7 @@ class FlatIPIndex:
             _lib.check(_lib.lib().hac_index_search_masked_device(*head, *tail))
         else:
             _lib.check(_lib.lib().hac_index_search_masked_after_device(*head, _devp(scores), _devp(rows), *tail))
-        _keep_alive(stream, q, masks, *cursor, D, I, *(t for t in (mask_of, id_map) if t is not None))
+        _keep_alive(stream, q, masks, D, I, *(t for t in (scores, rows, mask_of, id_map) if t is not None))
         return D, I
 
     def search_masked_keys_tensor(self, q, k, masks, mask_of=None, pos_base=0, stream=None, after_keys=None):
@@ -985,30 +865,27 @@ class FlatIPIndex:
         between shards (merge_keys, keys_to_results).  after_keys: None, or int64 CUDA [nq] packed cursors in the same position
         space, as search_after_keys_tensor takes them (cursor_keys, or the last column of the page before; 0 = an exhausted
         list, -1 = the start): the selected rows whose key lies below the query's cursor."""
-        import torch
         q, k, masks, mask_of, _ = _masked_args_tensor(q, k, masks, mask_of, None, self.d, self.ntotal, "search_masked_keys_tensor")
-        cursor = ()
-        if after_keys is not None:
-            _, _, after_keys, pos_base = _after_keys_args_tensor(q, k, after_keys, pos_base, self.d, "search_masked_keys_tensor")
-            cursor = (after_keys,)
-        keys = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
+        if after_keys is not None:   # (without a cursor pos_base goes to the library as it is, as in search_keys_tensor)
+            pos_base = _as_pos_base(pos_base, "search_masked_keys_tensor")
+            after_keys = _cursor_keys_tensor(after_keys, q, "search_masked_keys_tensor")
+        keys = _device_i64((q.shape[0], k), q.device)
         head = (self._h, _devp(q), q.shape[0], k, _devp(masks), masks.shape[0], masks.shape[1], _devp(mask_of))
         tail = (_devp(keys), int(pos_base), _stream_ptr(stream))
         if after_keys is None:
             _lib.check(_lib.lib().hac_index_search_masked_keys_device(*head, *tail))
         else:
             _lib.check(_lib.lib().hac_index_search_masked_after_keys_device(*head, _devp(after_keys), *tail))
-        _keep_alive(stream, q, masks, *cursor, keys, *(() if mask_of is None else (mask_of,)))
+        _keep_alive(stream, q, masks, keys, *(t for t in (after_keys, mask_of) if t is not None))
         return keys
 
     def search_grouped_tensor(self, q, k, group_of, id_map=None, return_groups=False, stream=None):
         """search_grouped on the device: group_of int64 CUDA [ntotal]; a row whose label lies outside [0, 2^32) is in no list and
         raises nothing.  id_map: optional int64 CUDA [ntotal], I = id_map[row]; G (with return_groups) stays the row's own label.
         No host sync; capturable after one call of the largest (nq, k)."""
-        import torch
         q, k, group_of, id_map = _grouped_args_tensor(q, k, group_of, id_map, self.d, self.ntotal)
         D, I = _device_results((q.shape[0], k), q.device)
-        G = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device) if return_groups else None
+        G = _device_i64((q.shape[0], k), q.device) if return_groups else None
         _lib.check(_lib.lib().hac_index_search_grouped_device(self._h, _devp(q), q.shape[0], k, _devp(group_of), group_of.shape[0], _devp(D), _devp(I),
                                                               _devp(G), _devp(id_map), _stream_ptr(stream)))
         _keep_alive(stream, q, group_of, D, I, *(t for t in (G, id_map) if t is not None))
@@ -1031,9 +908,8 @@ class FlatIPIndex:
         between shards (merge_keys, keys_to_results).  after_keys: int64 CUDA [nq] packed cursors in the same position space
         (cursor_keys, or the last column of any sorted key list: search_keys_tensor's, a merged list's, this call's own); 0 = an
         exhausted list, -1 (all-ones) = the start; None starts every query from the start."""
-        import torch
         q, k, after_keys, pos_base = _after_keys_args_tensor(q, k, after_keys, pos_base, self.d)
-        keys = torch.empty((q.shape[0], k), dtype=torch.int64, device=q.device)
+        keys = _device_i64((q.shape[0], k), q.device)
         _lib.check(_lib.lib().hac_index_search_after_keys_device(self._h, _devp(q), q.shape[0], k, _devp(after_keys), _devp(keys), pos_base,
                                                                  _stream_ptr(stream)))
         _keep_alive(stream, q, keys, *(() if after_keys is None else (after_keys,)))
@@ -1055,10 +931,9 @@ class FlatIPIndex:
         """entries_at_tensor's packed keys (int64 view of uint64) of ranks.shape, positions pos_base + row, 0 = padding: the key
         space of search_keys_tensor and of search_after_keys_tensor's cursors, so a column of it is the cursor of the page
         behind those entries."""
-        import torch
         q, ranks = _rank_args_tensor(q, ranks, self.d, "entry_keys_at_tensor")
         pos_base = _as_pos_base(pos_base, "entry_keys_at_tensor")
-        keys = torch.empty(tuple(ranks.shape), dtype=torch.int64, device=q.device)
+        keys = _device_i64(tuple(ranks.shape), q.device)
         _lib.check(_lib.lib().hac_index_entries_at_keys_device(self._h, _devp(q), q.shape[0], _devp(ranks), ranks.shape[1], _devp(keys), pos_base,
                                                                _stream_ptr(stream)))
         _keep_alive(stream, q, ranks, keys)
@@ -1125,9 +1000,8 @@ class FlatIPIndex:
     def rank_ids_tensor(self, q, ids, stream=None):
         """q: float32 CUDA [nq, d], ids: int64 CUDA [nq, m] -> int64 CUDA [nq, m], rank_ids without a host sync.  Any id outside
         [0, ntotal), -1 included, ranks -1.  Capturable after one call of the largest (nq, m)."""
-        import torch
         q, ids = _pair_args_tensor(q, ids, self.d, "rank_ids_tensor")
-        R = torch.empty(tuple(ids.shape), dtype=torch.int64, device=q.device)
+        R = _device_i64(tuple(ids.shape), q.device)
         _lib.check(_lib.lib().hac_index_rank_ids_device(self._h, _devp(q), q.shape[0], _devp(ids), ids.shape[1], _devp(R), _stream_ptr(stream)))
         _keep_alive(stream, q, ids, R)
         return R
@@ -1137,9 +1011,8 @@ class FlatIPIndex:
         whose score is not NaN and beats (ref_scores[i, j], ref_bounds[i, j]): s > s_ref, or s == s_ref and r < bound.
         q float32 CUDA [nq, d], ref_scores float32 CUDA [nq, m], ref_bounds int64 CUDA [nq, m] -> int64 CUDA [nq, m]; -1 for a
         NaN reference score or a negative bound; a bound above ntotal behaves like ntotal.  No host sync."""
-        import torch
         q, ref_scores, ref_bounds = _count_args_tensor(q, ref_scores, ref_bounds, self.d)
-        C = torch.empty(tuple(ref_bounds.shape), dtype=torch.int64, device=q.device)
+        C = _device_i64(tuple(ref_bounds.shape), q.device)
         _lib.check(_lib.lib().hac_index_count_ahead_device(self._h, _devp(q), q.shape[0], _devp(ref_scores), _devp(ref_bounds), ref_bounds.shape[1],
                                                            _devp(C), _stream_ptr(stream)))
         _keep_alive(stream, q, ref_scores, ref_bounds, C)
@@ -1189,9 +1062,8 @@ def merge_keys(lists, stream=None):
 def filter_keys(keys, exclude_pos, k, stream=None):
     """keys [nq, kin] sorted per-query lists, exclude_pos int64 CUDA [nq, e] global positions (< 0 or > 0xFFFFFFFF = padding)
     -> [nq, k]: each query's first k keys whose position is not excluded, in order, the rest 0."""
-    import torch
     keys, exclude_pos, k = _filter_args(keys, exclude_pos, k)
-    out = torch.empty((keys.shape[0], k), dtype=torch.int64, device=keys.device)
+    out = _device_i64((keys.shape[0], k), keys.device)
     _lib.check(_lib.lib().hac_filter_keys_device(keys.device.index or 0, _devp(keys), keys.shape[0], keys.shape[1], _devp(exclude_pos),
                                                  exclude_pos.shape[1], k, _devp(out), _stream_ptr(stream)))
     _keep_alive(stream, keys, exclude_pos, out)

@@ -20,6 +20,24 @@ def shard_range(n_total, rank, world_size):
     return lo, min(n_total, lo + per)
 
 
+# The two checks below see host tensors too (the hooks' test doubles run on CPU), so they ask for dtype and shape only.
+def _check_local_masks(local_masks, mask_of, q):
+    if local_masks.dim() != 2 or local_masks.dtype != torch.int64:
+        raise ValueError(f"local_masks must be packed int64 [n_masks, W], got {local_masks.dtype} {tuple(local_masks.shape)}")
+    if mask_of is not None and (mask_of.dim() != 1 or mask_of.shape[0] != q.shape[0] or mask_of.dtype != torch.int64):
+        raise ValueError(f"mask_of must be int64 [nq] with nq = {q.shape[0]}, got {mask_of.dtype} {tuple(mask_of.shape)}")
+    if mask_of is None and local_masks.shape[0] not in (1, q.shape[0]):
+        raise ValueError(f"{local_masks.shape[0]} masks for {q.shape[0]} queries and no mask_of: needs one mask, one per query, or mask_of")
+
+
+def _check_after_keys(after_keys, q):
+    if after_keys is not None:
+        if after_keys.dim() != 1 or after_keys.shape[0] != q.shape[0]:
+            raise ValueError(f"after_keys must be [nq] with nq = {q.shape[0]}, got shape {tuple(after_keys.shape)}")
+        if after_keys.dtype != torch.int64:
+            raise ValueError(f"after_keys must be int64 (the view of the packed keys), got {after_keys.dtype}")
+
+
 class ShardedSearcher:
     """search(q, k) over a corpus sharded across the ranks of ``group``.
 
@@ -105,12 +123,7 @@ class ShardedSearcher:
 
     def search_masked_keys(self, q, k, local_masks, mask_of=None):
         """The merged keys [nq, k] of search_masked."""
-        if local_masks.dim() != 2 or local_masks.dtype != torch.int64:
-            raise ValueError(f"local_masks must be packed int64 [n_masks, W], got {local_masks.dtype} {tuple(local_masks.shape)}")
-        if mask_of is not None and (mask_of.dim() != 1 or mask_of.shape[0] != q.shape[0] or mask_of.dtype != torch.int64):
-            raise ValueError(f"mask_of must be int64 [nq] with nq = {q.shape[0]}, got {mask_of.dtype} {tuple(mask_of.shape)}")
-        if mask_of is None and local_masks.shape[0] not in (1, q.shape[0]):
-            raise ValueError(f"{local_masks.shape[0]} masks for {q.shape[0]} queries and no mask_of: needs one mask, one per query, or mask_of")
+        _check_local_masks(local_masks, mask_of, q)
         return self._gather_and_merge(self._local_masked_keys(q, k, local_masks, mask_of, self.shard_base))
 
     def search_masked(self, q, k, local_masks, mask_of=None):
@@ -122,11 +135,7 @@ class ShardedSearcher:
 
     def search_after_keys(self, q, k, after_keys=None):
         """The merged keys [nq, k] of search_after; their last column is the cursor of the next page."""
-        if after_keys is not None:
-            if after_keys.dim() != 1 or after_keys.shape[0] != q.shape[0]:
-                raise ValueError(f"after_keys must be [nq] with nq = {q.shape[0]}, got shape {tuple(after_keys.shape)}")
-            if after_keys.dtype != torch.int64:
-                raise ValueError(f"after_keys must be int64 (the view of the packed keys), got {after_keys.dtype}")
+        _check_after_keys(after_keys, q)
         return self._gather_and_merge(self._local_after_keys(q, k, after_keys, self.shard_base))
 
     def search_after(self, q, k, after_keys=None):
@@ -139,17 +148,8 @@ class ShardedSearcher:
 
     def search_masked_after_keys(self, q, k, local_masks, mask_of=None, after_keys=None):
         """The merged keys [nq, k] of search_masked_after; their last column is the cursor of the next page."""
-        if local_masks.dim() != 2 or local_masks.dtype != torch.int64:
-            raise ValueError(f"local_masks must be packed int64 [n_masks, W], got {local_masks.dtype} {tuple(local_masks.shape)}")
-        if mask_of is not None and (mask_of.dim() != 1 or mask_of.shape[0] != q.shape[0] or mask_of.dtype != torch.int64):
-            raise ValueError(f"mask_of must be int64 [nq] with nq = {q.shape[0]}, got {mask_of.dtype} {tuple(mask_of.shape)}")
-        if mask_of is None and local_masks.shape[0] not in (1, q.shape[0]):
-            raise ValueError(f"{local_masks.shape[0]} masks for {q.shape[0]} queries and no mask_of: needs one mask, one per query, or mask_of")
-        if after_keys is not None:
-            if after_keys.dim() != 1 or after_keys.shape[0] != q.shape[0]:
-                raise ValueError(f"after_keys must be [nq] with nq = {q.shape[0]}, got shape {tuple(after_keys.shape)}")
-            if after_keys.dtype != torch.int64:
-                raise ValueError(f"after_keys must be int64 (the view of the packed keys), got {after_keys.dtype}")
+        _check_local_masks(local_masks, mask_of, q)
+        _check_after_keys(after_keys, q)
         return self._gather_and_merge(self._local_masked_after_keys(q, k, local_masks, mask_of, after_keys, self.shard_base))
 
     def search_masked_after(self, q, k, local_masks, mask_of=None, after_keys=None):
