@@ -27,122 +27,84 @@ class HacError(RuntimeError):
         self.code = code
 
 
+_int, _vp, _i64, _u32, _str = ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_char_p
+_f32p, _i64p, _u64p = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint64)
+_intp, _i32p = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int32)
+
+# Every symbol include/haconvdr.h declares, once: name -> (restype, argtypes).  _declare() and EXPORTED_SYMBOLS read this table
+# (tests/test_host_logic.py compares it with the header).
+_SIGNATURES = {
+    "hac_last_error": (_str, []),
+    "hac_version": (_str, []),
+    "hac_index_create": (_int, [_int, _intp, _int, ctypes.POINTER(_vp)]),
+    "hac_index_destroy": (None, [_vp]),
+    "hac_index_add": (_int, [_vp, _f32p, _i64]),
+    "hac_index_add_device": (_int, [_vp, _vp, _i64, _vp]),
+    "hac_index_search": (_int, [_vp, _f32p, _i64, _int, _f32p, _i64p]),
+    "hac_index_search_device": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp]),
+    "hac_index_search_keys_device": (_int, [_vp, _vp, _i64, _int, _vp, _u32, _vp]),
+    "hac_index_reset": (_int, [_vp]),
+    "hac_index_reconstruct": (_int, [_vp, _i64, _i64, _f32p]),
+    "hac_index_reconstruct_ids": (_int, [_vp, _i64p, _i64, _f32p]),
+    "hac_index_reconstruct_device": (_int, [_vp, _vp, _i64, _i64, _vp, _vp]),
+    "hac_index_score_ids": (_int, [_vp, _f32p, _i64, _i64p, _i64, _f32p]),
+    "hac_index_score_ids_device": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "hac_index_count_ahead_device": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "hac_index_rank_ids": (_int, [_vp, _f32p, _i64, _i64p, _i64, _i64p]),
+    "hac_index_rank_ids_device": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "hac_index_range_search": (_int, [_vp, _f32p, _i64, _f32p, _i64, _i64p, _f32p, _i64p]),
+    "hac_index_range_search_device": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "hac_index_remove_ids": (_int, [_vp, _i64p, _i64, _i64p]),
+    "hac_index_search_among": (_int, [_vp, _f32p, _i64, _int, _i64p, _i64, _f32p, _i64p]),
+    "hac_index_search_among_device": (_int, [_vp, _vp, _i64, _int, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "hac_index_search_among_keys_device": (_int, [_vp, _vp, _i64, _int, _vp, _i64, _vp, _u32, _vp]),
+    "hac_index_search_masked": (_int, [_vp, _f32p, _i64, _int, _u64p, _i64, _i64, _i64p, _f32p, _i64p]),
+    "hac_index_search_masked_device": (_int, [_vp, _vp, _i64, _int, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "hac_index_search_masked_keys_device": (_int, [_vp, _vp, _i64, _int, _vp, _i64, _i64, _vp, _vp, _u32, _vp]),
+    "hac_index_search_masked_after": (_int, [_vp, _f32p, _i64, _int, _u64p, _i64, _i64, _i64p, _f32p, _i64p, _f32p, _i64p]),
+    "hac_index_search_masked_after_device": (_int, [_vp, _vp, _i64, _int, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hac_index_search_masked_after_keys_device": (_int, [_vp, _vp, _i64, _int, _vp, _i64, _i64, _vp, _vp, _vp, _u32, _vp]),
+    "hac_index_search_grouped": (_int, [_vp, _f32p, _i64, _int, _i64p, _i64, _f32p, _i64p, _i64p]),
+    "hac_index_search_grouped_device": (_int, [_vp, _vp, _i64, _int, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "hac_index_search_after": (_int, [_vp, _f32p, _i64, _int, _f32p, _i64p, _f32p, _i64p]),
+    "hac_index_search_after_device": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hac_index_search_after_keys_device": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _u32, _vp]),
+    "hac_index_entries_at": (_int, [_vp, _f32p, _i64, _i64p, _i64, _f32p, _i64p]),
+    "hac_index_entries_at_device": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "hac_index_entries_at_keys_device": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _u32, _vp]),
+    "hac_index_ntotal": (_i64, [_vp]),
+    "hac_index_set_option": (_int, [_vp, _str, _str]),
+    "hac_index_set_profiling": (_int, [_vp, _int]),
+    "hac_index_profile_drain": (_int, [_vp, _f32p, _int, _intp]),
+    "hac_index_last_plan": (_str, [_vp]),
+    "hac_index_last_status": (_int, [_vp]),
+    "hac_merge_keys_device": (_int, [_int, _vp, _int, _i64, _int, _vp, _vp]),
+    "hac_keys_to_results_device": (_int, [_int, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "hac_filter_keys_device": (_int, [_int, _vp, _i64, _int, _vp, _int, _int, _vp, _vp]),
+    "hac_index_search_excluding": (_int, [_vp, _f32p, _i64, _int, _i64p, _int, _f32p, _i64p]),
+    "hac_index_search_excluding_device": (_int, [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp]),
+    "hac_encoder_create": (_int, [_vp, _int, ctypes.POINTER(_vp)]),
+    "hac_encoder_destroy": (None, [_vp]),
+    "hac_encoder_set_weight": (_int, [_vp, _str, _f32p, ctypes.c_size_t]),
+    "hac_encoder_finalize": (_int, [_vp]),
+    "hac_encoder_forward": (_int, [_vp, _i32p, _i32p, _int, _int, _f32p]),
+    "hac_encoder_forward_device": (_int, [_vp, _vp, _vp, _int, _int, _int, _vp, _vp]),
+    "hac_encoder_set_option": (_int, [_vp, _str, _str]),
+    "hac_encoder_last_plan": (_str, [_vp]),
+    "hac_encoder_set_profiling": (_int, [_vp, _int]),
+    "hac_encoder_profile_drain": (_int, [_vp, _f32p, _int, _intp]),
+    "hac_encoder_profile_drain_class": (_int, [_vp, _int, _f32p, _int, _intp]),
+    "hac_encoder_last_clock": (_int, [_vp, _u64p]),
+    "hac_encoder_attention_redo": (_int, [_vp, ctypes.POINTER(ctypes.c_longlong)]),
+    "hac_encoder_layer_state": (_int, [_vp, _i32p, _i32p, _int, _int, _int, _f32p, _f32p, _f32p]),
+}
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+
+
 def _declare(L):
-    c_f32p = ctypes.POINTER(ctypes.c_float)
-    vp = ctypes.c_void_p
-    i64 = ctypes.c_int64
-    L.hac_last_error.restype = ctypes.c_char_p
-    L.hac_version.restype = ctypes.c_char_p
-    L.hac_index_create.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(vp)]
-    L.hac_index_destroy.argtypes = [vp]
-    L.hac_index_destroy.restype = None
-    L.hac_index_add.argtypes = [vp, c_f32p, i64]
-    L.hac_index_add_device.argtypes = [vp, vp, i64, vp]
-    L.hac_index_search.argtypes = [vp, c_f32p, i64, ctypes.c_int, c_f32p, ctypes.POINTER(i64)]
-    L.hac_index_search_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, vp, vp, vp]
-    L.hac_index_search_keys_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, ctypes.c_uint32, vp]
-    L.hac_index_reset.argtypes = [vp]
-    L.hac_index_reconstruct.argtypes = [vp, i64, i64, c_f32p]
-    L.hac_index_reconstruct_ids.argtypes = [vp, ctypes.POINTER(i64), i64, c_f32p]
-    L.hac_index_reconstruct_device.argtypes = [vp, vp, i64, i64, vp, vp]
-    L.hac_index_score_ids.argtypes = [vp, c_f32p, i64, ctypes.POINTER(i64), i64, c_f32p]
-    L.hac_index_score_ids_device.argtypes = [vp, vp, i64, vp, i64, vp, vp]
-    L.hac_index_count_ahead_device.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp]
-    L.hac_index_rank_ids.argtypes = [vp, c_f32p, i64, ctypes.POINTER(i64), i64, ctypes.POINTER(i64)]
-    L.hac_index_rank_ids_device.argtypes = [vp, vp, i64, vp, i64, vp, vp]
-    L.hac_index_range_search.argtypes = [vp, c_f32p, i64, c_f32p, i64, ctypes.POINTER(i64), c_f32p, ctypes.POINTER(i64)]
-    L.hac_index_range_search_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp]
-    L.hac_index_remove_ids.argtypes = [vp, ctypes.POINTER(i64), i64, ctypes.POINTER(i64)]
-    L.hac_index_search_among.argtypes = [vp, c_f32p, i64, ctypes.c_int, ctypes.POINTER(i64), i64, c_f32p, ctypes.POINTER(i64)]
-    L.hac_index_search_among_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, i64, vp, vp, vp, vp]
-    L.hac_index_search_among_keys_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, i64, vp, ctypes.c_uint32, vp]
-    u64p = ctypes.POINTER(ctypes.c_uint64)
-    L.hac_index_search_masked.argtypes = [vp, c_f32p, i64, ctypes.c_int, u64p, i64, i64, ctypes.POINTER(i64), c_f32p, ctypes.POINTER(i64)]
-    L.hac_index_search_masked_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, i64, i64, vp, vp, vp, vp, vp]
-    L.hac_index_search_masked_keys_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, i64, i64, vp, vp, ctypes.c_uint32, vp]
-    L.hac_index_search_masked_after.argtypes = [vp, c_f32p, i64, ctypes.c_int, u64p, i64, i64, ctypes.POINTER(i64), c_f32p, ctypes.POINTER(i64), c_f32p,
-                                                ctypes.POINTER(i64)]
-    L.hac_index_search_masked_after_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp]
-    L.hac_index_search_masked_after_keys_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, i64, i64, vp, vp, vp, ctypes.c_uint32, vp]
-    L.hac_index_search_grouped.argtypes = [vp, c_f32p, i64, ctypes.c_int, ctypes.POINTER(i64), i64, c_f32p, ctypes.POINTER(i64), ctypes.POINTER(i64)]
-    L.hac_index_search_grouped_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, i64, vp, vp, vp, vp, vp]
-    L.hac_index_search_after.argtypes = [vp, c_f32p, i64, ctypes.c_int, c_f32p, ctypes.POINTER(i64), c_f32p, ctypes.POINTER(i64)]
-    L.hac_index_search_after_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, vp, vp, vp, vp, vp]
-    L.hac_index_search_after_keys_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, vp, ctypes.c_uint32, vp]
-    L.hac_index_entries_at.argtypes = [vp, c_f32p, i64, ctypes.POINTER(i64), i64, c_f32p, ctypes.POINTER(i64)]
-    L.hac_index_entries_at_device.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp]
-    L.hac_index_entries_at_keys_device.argtypes = [vp, vp, i64, vp, i64, vp, ctypes.c_uint32, vp]
-    L.hac_index_ntotal.argtypes = [vp]
-    L.hac_index_ntotal.restype = i64
-    L.hac_index_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p]
-    L.hac_index_set_profiling.argtypes = [vp, ctypes.c_int]
-    L.hac_index_profile_drain.argtypes = [vp, c_f32p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
-    L.hac_index_last_plan.argtypes = [vp]
-    L.hac_index_last_status.argtypes = [vp]
-    L.hac_index_last_status.restype = ctypes.c_int
-    L.hac_index_last_plan.restype = ctypes.c_char_p
-    L.hac_merge_keys_device.argtypes = [ctypes.c_int, vp, ctypes.c_int, i64, ctypes.c_int, vp, vp]
-    L.hac_keys_to_results_device.argtypes = [ctypes.c_int, vp, i64, vp, vp, vp, vp]
-    L.hac_filter_keys_device.argtypes = [ctypes.c_int, vp, i64, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp]
-    L.hac_index_search_excluding.argtypes = [vp, c_f32p, i64, ctypes.c_int, ctypes.POINTER(i64), ctypes.c_int, c_f32p, ctypes.POINTER(i64)]
-    L.hac_index_search_excluding_device.argtypes = [vp, vp, i64, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp]
-    L.hac_encoder_create.argtypes = [vp, ctypes.c_int, ctypes.POINTER(vp)]
-    L.hac_encoder_destroy.argtypes = [vp]
-    L.hac_encoder_destroy.restype = None
-    L.hac_encoder_set_weight.argtypes = [vp, ctypes.c_char_p, c_f32p, ctypes.c_size_t]
-    L.hac_encoder_finalize.argtypes = [vp]
-    L.hac_encoder_forward.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int, c_f32p]
-    L.hac_encoder_forward_device.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
-    L.hac_encoder_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p]
-    L.hac_encoder_last_plan.argtypes = [vp]
-    L.hac_encoder_last_plan.restype = ctypes.c_char_p
-    L.hac_encoder_set_profiling.argtypes = [vp, ctypes.c_int]
-    L.hac_encoder_profile_drain.argtypes = [vp, c_f32p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
-    L.hac_encoder_profile_drain_class.argtypes = [vp, ctypes.c_int, c_f32p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
-    L.hac_encoder_last_clock.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-    L.hac_encoder_attention_redo.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
-    L.hac_encoder_layer_state.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_int, c_f32p, c_f32p, c_f32p]
-    for name in ("hac_encoder_create", "hac_encoder_set_weight", "hac_encoder_finalize", "hac_encoder_forward",
-                 "hac_encoder_forward_device", "hac_encoder_set_option", "hac_encoder_set_profiling", "hac_encoder_profile_drain",
-                 "hac_encoder_profile_drain_class", "hac_encoder_last_clock", "hac_encoder_attention_redo", "hac_encoder_layer_state"):
-        getattr(L, name).restype = ctypes.c_int
-    for name in ("hac_index_create", "hac_index_add", "hac_index_add_device", "hac_index_search",
-                 "hac_index_search_device", "hac_index_search_keys_device", "hac_index_reset",
-                 "hac_index_set_option", "hac_index_set_profiling", "hac_index_profile_drain", "hac_merge_keys_device",
-                 "hac_keys_to_results_device", "hac_index_reconstruct", "hac_index_reconstruct_ids", "hac_index_reconstruct_device",
-                 "hac_index_score_ids", "hac_index_score_ids_device", "hac_filter_keys_device", "hac_index_search_excluding",
-                 "hac_index_search_excluding_device", "hac_index_count_ahead_device", "hac_index_rank_ids", "hac_index_rank_ids_device",
-                 "hac_index_range_search", "hac_index_range_search_device", "hac_index_remove_ids",
-                 "hac_index_search_among", "hac_index_search_among_device", "hac_index_search_among_keys_device",
-                 "hac_index_search_masked", "hac_index_search_masked_device", "hac_index_search_masked_keys_device",
-                 "hac_index_search_grouped", "hac_index_search_grouped_device",
-                 "hac_index_search_after", "hac_index_search_after_device", "hac_index_search_after_keys_device",
-                 "hac_index_search_masked_after", "hac_index_search_masked_after_device", "hac_index_search_masked_after_keys_device",
-                 "hac_index_entries_at", "hac_index_entries_at_device", "hac_index_entries_at_keys_device"):
-        getattr(L, name).restype = ctypes.c_int
-
-
-# every symbol include/haconvdr.h declares (checked by tests/test_cabi_symbols.py)
-EXPORTED_SYMBOLS = (
-    "hac_last_error", "hac_version", "hac_index_create", "hac_index_destroy", "hac_index_add",
-    "hac_index_add_device", "hac_index_search", "hac_index_search_device", "hac_index_search_keys_device",
-    "hac_index_reset", "hac_index_ntotal", "hac_index_set_option", "hac_index_set_profiling", "hac_index_profile_drain", "hac_index_last_plan",
-    "hac_index_last_status", "hac_merge_keys_device", "hac_keys_to_results_device", "hac_filter_keys_device",
-    "hac_index_search_excluding", "hac_index_search_excluding_device",
-    "hac_index_reconstruct", "hac_index_reconstruct_ids", "hac_index_reconstruct_device", "hac_index_score_ids", "hac_index_score_ids_device",
-    "hac_index_count_ahead_device", "hac_index_rank_ids", "hac_index_rank_ids_device",
-    "hac_index_range_search", "hac_index_range_search_device", "hac_index_remove_ids",
-    "hac_index_search_among", "hac_index_search_among_device", "hac_index_search_among_keys_device",
-    "hac_index_search_masked", "hac_index_search_masked_device", "hac_index_search_masked_keys_device",
-    "hac_index_search_grouped", "hac_index_search_grouped_device",
-    "hac_index_search_after", "hac_index_search_after_device", "hac_index_search_after_keys_device",
-    "hac_index_search_masked_after", "hac_index_search_masked_after_device", "hac_index_search_masked_after_keys_device",
-    "hac_index_entries_at","hac_index_entries_at_device", "hac_index_entries_at_keys_device",
-    "hac_encoder_create", "hac_encoder_destroy", "hac_encoder_set_weight", "hac_encoder_finalize", "hac_encoder_forward",
-    "hac_encoder_forward_device", "hac_encoder_set_option", "hac_encoder_last_plan", "hac_encoder_set_profiling", "hac_encoder_profile_drain",
-    "hac_encoder_profile_drain_class", "hac_encoder_last_clock", "hac_encoder_attention_redo", "hac_encoder_layer_state",
-)
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
 
 
 class EncoderConfig(ctypes.Structure):

@@ -1469,7 +1469,22 @@ struct Plan {
 
 }  // namespace
 
-struct hac_encoder {
+// Every workspace of an encoder.  hac_encoder derives from this and hac_encoder_destroy releases the whole struct at once
+// (release_all): a buffer declared here cannot be left out.
+struct EncoderWorkspaces {
+    GrowBuf ws_x, ws_xb, ws_q, ws_k, ws_vt, ws_ctx, ws_y, ws_h, ws_seq, ws_ids, ws_mask, ws_out, ws_cls, ws_stats;
+    GrowBuf ws_ksplit;                    // classic path, small batches: split-K partial sums of the RESID GEMMs
+    GrowBuf ws_yb, ws_part, ws_idstats;   // gemm8 path: bf16 copy of the attention-block rows, row-sum partials, (0, 1) statistics
+    GrowBuf ws_pool;                      // pooling = mean: [2][B][768] fp32, the pooled rows | the head's projection
+    GrowBuf ws_xb_lo, ws_q_lo, ws_k_lo, ws_vt_lo, ws_ctx_lo, ws_h_lo, ws_cls_lo;   // the lo twins of the activations an MFMA reads
+    GrowBuf ws_gids, ws_gmask, ws_gout;   // a captured forward's private inputs and output (forward_graph)
+    GrowBuf ws_dump;                      // hac_encoder_layer_state: the unpacked rows, statistics and normalized rows
+    GrowBuf ws_identgb;                   // [2][768]: gamma = 1, beta = 0
+    GrowBuf ws_redo;                      // [16] per-layer counts | [B * 12] item flags of the attention fix-up pass (attn_pipe.inc)
+    GrowBuf ws_clk;                       // [4] u64: hac_encoder_last_clock
+};
+
+struct hac_encoder : EncoderWorkspaces {
     hac_encoder_config cfg;
     int device = 0;
     hipStream_t stream = nullptr;
@@ -1479,17 +1494,11 @@ struct hac_encoder {
     float *word = nullptr, *posw = nullptr, *typew = nullptr, *embg = nullptr, *embb = nullptr;
     float *wh = nullptr, *bh = nullptr, *ng = nullptr, *nb = nullptr;
     bool finalized = false;
-    // workspace
-    GrowBuf ws_x, ws_xb, ws_q, ws_k, ws_vt, ws_ctx, ws_y, ws_h, ws_seq, ws_ids, ws_mask, ws_out, ws_cls, ws_stats;
-    GrowBuf ws_ksplit;                    // classic path, small batches: split-K partial sums of the RESID GEMMs
-    GrowBuf ws_yb, ws_part, ws_idstats;   // gemm8 path: bf16 copy of the attention-block rows, row-sum partials, (0, 1) statistics
     size_t idstats_rows = 0;
     int precision = 0;                    // 0: bf16 operands; 1: split (hi + lo pairs, three MFMAs per product: split.inc)
     bool split_weights = false;           // the lo twins of the weights exist
     int model = 0;                        // 0: roberta (roberta.* tensors, HF position rule, L <= max_pos - 2); 1: bert (bert.* tensors, pos = t, L <= max_pos)
     int pooling = 0;                      // 0: first (the <s> row, models.py:56); 1: mean (masked mean of the last layer's rows, models.py:57-61)
-    GrowBuf ws_pool;                      // pooling = mean: [2][B][768] fp32, the pooled rows | the head's projection
-    GrowBuf ws_xb_lo, ws_q_lo, ws_k_lo, ws_vt_lo, ws_ctx_lo, ws_h_lo, ws_cls_lo;   // the lo twins of the activations an MFMA reads
     int attn_mode = 0;                    // 0: streaming single-pass attention; 1: two-pass kernels (cross-check)
     int attn_pipe = -1;                   // streaming attention of whole items (no query split, not the <s>-only layer): two query blocks per wave, woven (attn_pipe.inc); 0: the one-block kernel everywhere
     int gemm_mode = -1;                   // -1: by size, 0: classic kernels only, 1: gemm8 whenever the batch has a full tile (tests)
@@ -1528,10 +1537,6 @@ struct hac_encoder {
     std::map<uint64_t, GraphEntry> graphs;
     hipEvent_t graph_done = nullptr;      // recorded behind every replay on the caller's stream: an exec is destroyed only after it
     bool graph_done_armed = false;
-    GrowBuf ws_gids, ws_gmask, ws_gout;
-    GrowBuf ws_dump;                      // hac_encoder_layer_state: the unpacked rows, statistics and normalized rows
-    GrowBuf ws_identgb;                   // [2][768]: gamma = 1, beta = 0
-    GrowBuf ws_redo;                      // [16] per-layer counts | [B * 12] item flags of the attention fix-up pass (attn_pipe.inc)
     // Layers whose items mostly fail the woven kernel's check (near one-hot attention: a property of the weights more than of the batch) would
     // pay for both kernels every time (measured with logits x 100: 28.4 against 14.4 ms per forward).  The per-layer counts of a forward come
     // back through a pinned copy and an event nobody waits for; a later forward that finds them routes such layers through the one-block kernel
@@ -1542,7 +1547,6 @@ struct hac_encoder {
     long redo_items = 0;                  // items per layer (B x 12) of the forward whose counts are pending
     unsigned pipe_skip_mask = 0;          // bit l: layer l goes straight to the one-block kernel
     unsigned forwards_since_retry = 0;
-    GrowBuf ws_clk;                       // [4] u64: hac_encoder_last_clock
     bool clk_valid = false;
     hipEvent_t clk_ev = nullptr;          // recorded behind the launch that wrote ws_clk: what hac_encoder_last_clock waits for (not the whole device)
 };
@@ -1908,6 +1912,11 @@ int dump_state(hac_encoder *e, const Fwd &f, const LayerDump &d, int li) {
     return hipGetLastError() == hipSuccess ? HAC_OK : fail(HAC_ERR_HIP, "layer_state_kernel launch failed");
 }
 
+// Dynamic LDS of the launches below, by name: LDS_KERNELS raises each kernel's limit to the same names.
+constexpr size_t LDS_HALF_CU = 80 * 1024, LDS_WHOLE_CU = 160 * 1024;   // kernels that run two workgroups / one workgroup to a CU
+constexpr size_t GEMM128_LDS = 4 * 128 * 128 + 4 * 4096, GEMM256_LDS = 4 * 256 * 128 + 8 * 4096;   // classic GEMMs: 2 stages + per-wave patches
+constexpr size_t attn_twopass_lds(int rows) { return (size_t)rows * 256; }   // two-pass attention: L32 rows, at most 256 / 512 (max_len)
+
 // Attention of the bf16 families, inside its profiling class: the query split, then the woven / one-block / two-pass kernels.
 int attention(hac_encoder *e, const Fwd &f, int li, bool last) {
     const hipStream_t st = f.st;
@@ -1935,20 +1944,20 @@ int attention(hac_encoder *e, const Fwd &f, int li, bool last) {
     if (e->attn_mode == 0) {           // persistent streaming kernels, one launch per length class
         if (att_pipe) {   // whole items: the woven two-blocks-per-wave form, then the items it flagged through the one-block kernels (bit-identical results)
             const bool both = e->attn_pipe > 0;   // "all" (tests): the short class through the 4-wave instantiation too
-            if (L32 > 256) attention_pipe_kernel<8><<<dim3(e->n_cu), dim3(512), 163840, st>>>(a);
-            if (both) attention_pipe_kernel<4><<<dim3(2 * e->n_cu), dim3(256), 81920, st>>>(a);
-            else attention_stream_kernel<8><<<dim3(2 * e->n_cu), dim3(512), 81920, st>>>(a);
+            if (L32 > 256) attention_pipe_kernel<8><<<dim3(e->n_cu), dim3(512), LDS_WHOLE_CU, st>>>(a);
+            if (both) attention_pipe_kernel<4><<<dim3(2 * e->n_cu), dim3(256), LDS_HALF_CU, st>>>(a);
+            else attention_stream_kernel<8><<<dim3(2 * e->n_cu), dim3(512), LDS_HALF_CU, st>>>(a);
             a.fixup = 1;
-            if (L32 > 256) attention_stream_kernel<16><<<dim3(e->n_cu), dim3(1024), 163840, st>>>(a);
-            if (both) attention_stream_kernel<8><<<dim3(2 * e->n_cu), dim3(512), 81920, st>>>(a);
+            if (L32 > 256) attention_stream_kernel<16><<<dim3(e->n_cu), dim3(1024), LDS_WHOLE_CU, st>>>(a);
+            if (both) attention_stream_kernel<8><<<dim3(2 * e->n_cu), dim3(512), LDS_HALF_CU, st>>>(a);
             e->plan.attn_pipe = 1;
         } else {
-            if (L32 > 256) attention_stream_kernel<16><<<dim3(e->n_cu), dim3(1024), 163840, st>>>(a);
-            if (!att_one) attention_stream_kernel<8><<<dim3(2 * e->n_cu), dim3(512), 81920, st>>>(a);
+            if (L32 > 256) attention_stream_kernel<16><<<dim3(e->n_cu), dim3(1024), LDS_WHOLE_CU, st>>>(a);
+            if (!att_one) attention_stream_kernel<8><<<dim3(2 * e->n_cu), dim3(512), LDS_HALF_CU, st>>>(a);
         }
     } else {                           // two-pass kernels, one workgroup per (sequence, head): kept as a cross-check
-        attention_kernel<8, 1><<<dim3(NH, B), dim3(512), (size_t)(L32 < 256 ? L32 : 256) * 256, st>>>(a);
-        if (L32 > 256) attention_kernel<16, 1><<<dim3(NH, B), dim3(1024), (size_t)L32 * 256, st>>>(a);
+        attention_kernel<8, 1><<<dim3(NH, B), dim3(512), attn_twopass_lds(L32 < 256 ? L32 : 256), st>>>(a);
+        if (L32 > 256) attention_kernel<16, 1><<<dim3(NH, B), dim3(1024), attn_twopass_lds(L32), st>>>(a);
     }
     return prof_end(e, 1 + HAC_ENC_CLASS_ATTN, st);
 }
@@ -1969,12 +1978,12 @@ PrevLN prev_ln(const hac_encoder *e, const Fwd &f, int li) {
 // ---- classic family: persistent bf16 GEMMs on 128^2 tiles, or 256^2 tiles once those fill the chip (Fwd::big)
 template <int EPI>
 void launch_gemm128(const hac_encoder *e, const GemmArgs &g, hipStream_t st) {
-    gemm_bf16_nt_kernel<EPI, 2><<<dim3((unsigned)(e->n_cu * 2)), dim3(256), (size_t)4 * 128 * 128 + (size_t)4 * 4096, st>>>(g);   // 2 stages + per-wave patches
+    gemm_bf16_nt_kernel<EPI, 2><<<dim3((unsigned)(e->n_cu * 2)), dim3(256), GEMM128_LDS, st>>>(g);
 }
 template <int EPI>
 int gemm_classic(hac_encoder *e, const Fwd &f, const GemmArgs &g, int cls) {
     if (f.big)
-        HAC_PROFILED(e, f.st, cls, gemm_bf16_nt_kernel<EPI, 4><<<dim3((unsigned)e->n_cu), dim3(512), (size_t)4 * 256 * 128 + (size_t)8 * 4096, f.st>>>(g));
+        HAC_PROFILED(e, f.st, cls, gemm_bf16_nt_kernel<EPI, 4><<<dim3((unsigned)e->n_cu), dim3(512), GEMM256_LDS, f.st>>>(g));
     else HAC_PROFILED(e, f.st, cls, launch_gemm128<EPI>(e, g, f.st));
     return HAC_OK;
 }
@@ -2025,7 +2034,7 @@ int stagger8(const hac_encoder *e, const Fwd &f, int N, int n_tile0, int steps) 
 // (non-temporal output stores for the q / k / v and h streams, not for the residual stream: see g8_store16)
 template <int EPI>
 void launch_gemm8(const hac_encoder *e, const Gemm8Args &a, hipStream_t st) {
-    gemm8_kernel<EPI, EPI != EPI8_RESID><<<dim3((unsigned)e->n_cu), dim3(512), 163840, st>>>(a);
+    gemm8_kernel<EPI, EPI != EPI8_RESID><<<dim3((unsigned)e->n_cu), dim3(512), LDS_WHOLE_CU, st>>>(a);
 }
 // A = the previous layer's un-normalized output rows (bf16) + their statistics; layer 0: the normalized embedding rows
 int qkv_gemm8(hac_encoder *e, const Fwd &f, int li, bool last, Gemm8Args &a) {
@@ -2431,27 +2440,31 @@ int finalize_layer(hac_encoder *e, int i) {
     return HAC_OK;
 }
 
-// every kernel launched with more than 64 KB of dynamic LDS
-void raise_lds_limits() {
-    (void)hipFuncSetAttribute((const void *)attention_kernel<8, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void *)attention_kernel<16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    (void)hipFuncSetAttribute((const void *)attention_stream_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
-    (void)hipFuncSetAttribute((const void *)attention_stream_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    (void)hipFuncSetAttribute((const void *)attention_pipe_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
-    (void)hipFuncSetAttribute((const void *)attention_pipe_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_QKV, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
-    (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_RESID, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
-    (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_GELU, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 81920);
-    (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_QKV, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_RESID, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    (void)hipFuncSetAttribute((const void *)gemm_bf16_nt_kernel<EPI_GELU, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    (void)hipFuncSetAttribute((const void *)gemm_split_nt_kernel<EPI_QKV>, hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_GEMM_LDS);
-    (void)hipFuncSetAttribute((const void *)gemm_split_nt_kernel<EPI_RESID>, hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_GEMM_LDS);
-    (void)hipFuncSetAttribute((const void *)gemm_split_nt_kernel<EPI_GELU>, hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_GEMM_LDS);
-    (void)hipFuncSetAttribute((const void *)attention_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * ATS_STAGE);
-    (void)hipFuncSetAttribute((const void *)gemm8_kernel<EPI8_QKV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    (void)hipFuncSetAttribute((const void *)gemm8_kernel<EPI8_RESID, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    (void)hipFuncSetAttribute((const void *)gemm8_kernel<EPI8_GELU, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
+// Every kernel launched with 64 KB of dynamic LDS or more, and the most its launches ask for (the names the launches use)
+const LdsKernel LDS_KERNELS[] = {
+    {attention_kernel<8, 1>, attn_twopass_lds(256)},
+    {attention_kernel<16, 1>, attn_twopass_lds(512)},
+    {attention_stream_kernel<8>, LDS_HALF_CU},
+    {attention_stream_kernel<16>, LDS_WHOLE_CU},
+    {attention_pipe_kernel<4>, LDS_HALF_CU},
+    {attention_pipe_kernel<8>, LDS_WHOLE_CU},
+    {gemm_bf16_nt_kernel<EPI_QKV, 2>, GEMM128_LDS},
+    {gemm_bf16_nt_kernel<EPI_RESID, 2>, GEMM128_LDS},
+    {gemm_bf16_nt_kernel<EPI_GELU, 2>, GEMM128_LDS},
+    {gemm_bf16_nt_kernel<EPI_QKV, 4>, GEMM256_LDS},
+    {gemm_bf16_nt_kernel<EPI_RESID, 4>, GEMM256_LDS},
+    {gemm_bf16_nt_kernel<EPI_GELU, 4>, GEMM256_LDS},
+    {gemm_split_nt_kernel<EPI_QKV>, SPLIT_GEMM_LDS},
+    {gemm_split_nt_kernel<EPI_RESID>, SPLIT_GEMM_LDS},
+    {gemm_split_nt_kernel<EPI_GELU>, SPLIT_GEMM_LDS},
+    {attention_split_kernel, 2 * ATS_STAGE},
+    {gemm8_kernel<EPI8_QKV, true>, LDS_WHOLE_CU},
+    {gemm8_kernel<EPI8_RESID, false>, LDS_WHOLE_CU},
+    {gemm8_kernel<EPI8_GELU, true>, LDS_WHOLE_CU},
+};
+int raise_lds_limits() {
+    for (const LdsKernel &k : LDS_KERNELS) HAC_HIP(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.bytes));
+    return HAC_OK;
 }
 
 }  // namespace
@@ -2478,11 +2491,12 @@ int hac_encoder_create(const hac_encoder_config *cfg, int device, hac_encoder **
         delete e;
         return fail(HAC_ERR_HIP, "hipStreamCreate failed");
     }
-    raise_lds_limits();
+    int rc = raise_lds_limits();
     const char *m = getenv("HAC_ENC_GEMM");
-    if (m && !parse_gemm_mode(m, &e->gemm_mode)) {
-        delete e;
-        return fail(HAC_ERR_INVALID, "HAC_ENC_GEMM = '%s': auto | classic | 8phase", m);
+    if (rc == HAC_OK && m && !parse_gemm_mode(m, &e->gemm_mode)) rc = fail(HAC_ERR_INVALID, "HAC_ENC_GEMM = '%s': auto | classic | 8phase", m);
+    if (rc != HAC_OK) {
+        hac_encoder_destroy(e);   // (the error slot keeps rc's message: destroy reports nothing)
+        return rc;
     }
     {
         hipDeviceProp_t prop;
@@ -2506,10 +2520,7 @@ void hac_encoder_destroy(hac_encoder *e) {
         (void)hipEventDestroy(e->redo_ev);
     }
     if (e->h_redo) (void)hipHostFree(e->h_redo);
-    for (GrowBuf *b : {&e->ws_x, &e->ws_xb, &e->ws_q, &e->ws_k, &e->ws_vt, &e->ws_ctx, &e->ws_y, &e->ws_h, &e->ws_seq, &e->ws_ids, &e->ws_mask, &e->ws_out, &e->ws_cls, &e->ws_stats, &e->ws_yb, &e->ws_part, &e->ws_idstats,
-                       &e->ws_gids, &e->ws_gmask, &e->ws_gout, &e->ws_ksplit, &e->ws_identgb, &e->ws_clk, &e->ws_redo, &e->ws_dump,
-                       &e->ws_xb_lo, &e->ws_q_lo, &e->ws_k_lo, &e->ws_vt_lo, &e->ws_ctx_lo, &e->ws_h_lo, &e->ws_cls_lo, &e->ws_pool})
-        b->release();
+    release_all<EncoderWorkspaces>(*e);
     if (e->h_pin) (void)hipHostFree(e->h_pin);
     if (e->h_len) (void)hipHostFree(e->h_len);
     for (auto &pl : e->pools)
@@ -2658,59 +2669,38 @@ int hac_encoder_layer_state(hac_encoder *e, const int32_t *ids, const int32_t *m
 
 int hac_encoder_set_option(hac_encoder *e, const char *name, const char *value) {
     if (!e || !name || !value) return fail(HAC_ERR_INVALID, "set_option: null argument");
-    const std::string n(name), v(value);
-    // a value outside the documented set is an error, never a silent default (a mistyped value in a cross-check test would
-    // otherwise exercise the wrong kernels and still pass)
-    if (n == "gemm") {
-        if (!parse_gemm_mode(value, &e->gemm_mode)) return fail(HAC_ERR_INVALID, "encoder option gemm = '%s': auto | classic | 8phase", value);
-    } else if (n == "precision") {
-        if (v != "bf16" && v != "split") return fail(HAC_ERR_INVALID, "encoder option precision = '%s': bf16 | split", value);
-        e->precision = v == "split" ? 1 : 0;
-    } else if (n == "model") {
+    // every option of the encoder, once (hac_common.h: Option): the name, its documented values and the member each goes to
+    using Opt = Option<hac_encoder>;
+#define TO(FIELD) HAC_OPT_TO(hac_encoder, FIELD)
+    static const Opt table[] = {
+        Opt::custom_form("gemm", "auto | classic | 8phase", [](hac_encoder &e, const char *v) { return parse_gemm_mode(v, &e.gemm_mode); }),
+        Opt::choice("precision", TO(precision), {{"bf16", 0}, {"split", 1}}),
         // (the tensor names, the position rule and the length bound follow it: chosen before the first tensor arrives, then fixed)
-        if (v != "roberta" && v != "bert") return fail(HAC_ERR_INVALID, "encoder option model = '%s': roberta | bert", value);
-        if (!e->raw.empty()) return fail(HAC_ERR_INVALID, "encoder option model = '%s': must be set before the first hac_encoder_set_weight", value);
-        e->model = v == "bert" ? 1 : 0;
-    } else if (n == "pooling") {
-        if (v != "first" && v != "mean") return fail(HAC_ERR_INVALID, "encoder option pooling = '%s': first | mean", value);
-        e->pooling = v == "mean" ? 1 : 0;
-    } else if (n == "attn") {
-        if (v != "stream" && v != "twopass") return fail(HAC_ERR_INVALID, "encoder option attn = '%s': stream | twopass", value);
-        e->attn_mode = v == "twopass" ? 1 : 0;
-    } else if (n == "attn_pipe") {
-        if (v != "auto" && v != "off" && v != "all") return fail(HAC_ERR_INVALID, "encoder option attn_pipe = '%s': auto | off | all", value);
-        e->attn_pipe = v == "off" ? 0 : (v == "all" ? 1 : -1);
-    } else if (n == "attn_qsplit") {
-        if (v != "auto" && v != "off") return fail(HAC_ERR_INVALID, "encoder option attn_qsplit = '%s': auto | off", value);
-        e->attn_qsplit = v == "off" ? 0 : -1;
-    } else if (n == "g8_stagger") {
-        if (v != "auto" && v != "off") return fail(HAC_ERR_INVALID, "encoder option g8_stagger = '%s': auto | off", value);
-        e->g8_stagger = v == "off" ? 0 : -1;
-    } else if (n == "attn_qs_pin") {
-        if (v != "0" && v != "1" && v != "2" && v != "4" && v != "8" && v != "16") return fail(HAC_ERR_INVALID, "encoder option attn_qs_pin = '%s': 0 | 1 | 2 | 4 | 8 | 16", value);
-        e->attn_qs_pin = atoi(v.c_str());
-        drop_graphs(e);
-    } else if (n == "ksplit_pin") {
-        int a = 0, b = 0;
-        if (sscanf(v.c_str(), "%d/%d", &a, &b) != 2 || a < 0 || b < 0 || a > 16 || b > 16) return fail(HAC_ERR_INVALID, "encoder option ksplit_pin = '%s': a/b with 0 <= a, b <= 16", value);
-        e->ks_pin_out = a;
-        e->ks_pin_down = b;
-        drop_graphs(e);
-    } else if (n == "ksplit") {
-        if (v != "auto" && v != "off") return fail(HAC_ERR_INVALID, "encoder option ksplit = '%s': auto | off", value);
-        e->ksplit_mode = v == "off" ? 0 : -1;
-    } else if (n == "graph") {
-        if (v != "auto" && v != "off") return fail(HAC_ERR_INVALID, "encoder option graph = '%s': auto | off", value);
-        e->graph_mode = v == "off" ? 0 : -1;
-    } else if (n == "max_tokens") {
-        char *end = nullptr;
-        const long t = strtol(value, &end, 10);
-        if (end == value || *end || t < 4096) return fail(HAC_ERR_INVALID, "encoder option max_tokens = '%s': an integer >= 4096", value);
-        e->max_tokens = t;
-    } else {
-        return fail(HAC_ERR_INVALID, "unknown encoder option '%s'", name);
-    }
-    return HAC_OK;
+        Opt::custom_form("model", "roberta | bert, before the first hac_encoder_set_weight", [](hac_encoder &e, const char *v) {
+            const bool bert = !strcmp(v, "bert");
+            if ((!bert && strcmp(v, "roberta") != 0) || !e.raw.empty()) return false;
+            e.model = bert ? 1 : 0;
+            return true;
+        }),
+        Opt::choice("pooling", TO(pooling), {{"first", 0}, {"mean", 1}}),
+        Opt::choice("attn", TO(attn_mode), {{"stream", 0}, {"twopass", 1}}),
+        Opt::choice("attn_pipe", TO(attn_pipe), {{"auto", -1}, {"off", 0}, {"all", 1}}),
+        Opt::choice("attn_qsplit", TO(attn_qsplit), {{"auto", -1}, {"off", 0}}),
+        Opt::choice("g8_stagger", TO(g8_stagger), {{"auto", -1}, {"off", 0}}),
+        Opt::choice("attn_qs_pin", TO(attn_qs_pin), {{"0", 0}, {"1", 1}, {"2", 2}, {"4", 4}, {"8", 8}, {"16", 16}}, [](hac_encoder &e) { drop_graphs(&e); }),
+        Opt::custom_form("ksplit_pin", "a/b with 0 <= a, b <= 16", [](hac_encoder &e, const char *v) {
+            int a = 0, b = 0;
+            if (sscanf(v, "%d/%d", &a, &b) != 2 || a < 0 || b < 0 || a > 16 || b > 16) return false;
+            e.ks_pin_out = a;
+            e.ks_pin_down = b;
+            return true;
+        }, [](hac_encoder &e) { drop_graphs(&e); }),
+        Opt::choice("ksplit", TO(ksplit_mode), {{"auto", -1}, {"off", 0}}),
+        Opt::choice("graph", TO(graph_mode), {{"auto", -1}, {"off", 0}}),
+        Opt::integer("max_tokens", TO(max_tokens), 4096, LONG_MAX),
+    };
+#undef TO
+    return apply_option("encoder", table, *e, name, value);
 }
 
 const char *hac_encoder_last_plan(hac_encoder *e) {

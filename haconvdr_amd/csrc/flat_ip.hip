@@ -1111,7 +1111,32 @@ struct Segment {
     int64_t r_rows = 0;      // rows of it that are current
 };
 
-struct DeviceIndex {
+// Every workspace of a one-device index.  DeviceIndex derives from this and destroy() releases the whole struct at once
+// (release_all): a buffer declared here cannot be left out.
+struct IndexWorkspaces {
+    GrowBuf ws_partial, ws_pcnt, ws_seedkeys, ws_thr, ws_thrglob, ws_q, ws_qt, ws_keys, ws_D, ws_I, ws_stage[2];
+    // split-bf16 prefilter path (scan_split.inc)
+    GrowBuf ws_norm, ws_qsplit, ws_delta, ws_cand, ws_akeys, ws_fail, ws_stat;
+    GrowBuf ws_err;            // [0] device error bits (sticky until read), [1] workgroups that hit a pass bound (ScanArgs::err)
+    GrowBuf ws_fbidx[2], ws_fbq[2], ws_fbkeys[2];   // per cascade level: failed queries, their matrix, their keys
+    PinBuf h_fb;               // u32 words: [0] failed queries, [1] max |s~ - s| / delta (float bits), [2..] flags / indices
+    PinBuf h_stage[2];
+    // Small host<->device traffic (queries, results, segment table) always goes through
+    // pinned memory: pageable hipMemcpyAsync is not reliably stream-ordered on this stack.
+    PinBuf h_pin;
+    GrowBuf ws_ids, ws_rank;   // the by-id calls (rows_host.inc): a chunk's ids; the rank calls' counters and reference scores
+    GrowBuf ws_range;          // range search (rows_host.inc: RangeWs): control words, counters, cursors, staging and the two key buffers
+    GrowBuf ws_among;          // search among named rows (search_host.inc: among_keys_device): a chunk's [queries][P] candidate keys
+    GrowBuf ws_mgroups, ws_mcnt;   // search inside a bitmap (search_keys_masked): one launch's group lists u32 [tiles][G], the call's counters u32 [tiles]
+    GrowBuf ws_masks;          // its host form (search_host.inc: masked_shard): a chunk's masks and mask_of
+    GrowBuf ws_labels;         // search by group, host form (search_host.inc: grouped_shard): the shard's slice of the labels
+    GrowBuf ws_atrank;         // entry at a rank (rows_host.inc: entries_at_keys_device): a launch's pair states and histograms, the call's keys
+    GrowBuf ws_after;          // search behind a cursor (search_host.inc): the bounds u64 [queries] of a (score, row) call, or of a host chunk
+};
+
+int raise_lds_limits(int device);   // (LDS_KERNELS, behind the kernels' host-side sizing rules)
+
+struct DeviceIndex : IndexWorkspaces {
     int d = 0, K4 = 0, device = 0, n_cu = 256;
     hipStream_t stream = nullptr;  // for the synchronous host API
     hipStream_t stream2 = nullptr; // rescoring of one query chunk runs here, under the next chunk's scan
@@ -1186,121 +1211,47 @@ struct DeviceIndex {
         if (const char *e = getenv("HAC_SCANQ_WAVES")) tune.scanq_waves = e[0] == '4' ? 4 : 8;
         if (getenv("HAC_SCAN_NO_P8")) tune.no_p8 = true;
     }
-    // v as one whole decimal integer in [lo, hi]
-    static bool parse_int(const std::string &v, long lo, long hi, long &out) {
-        char *end = nullptr;
-        const long t = strtol(v.c_str(), &end, 10);
-        if (v.empty() || *end || t < lo || t > hi) return false;
-        out = t;
-        return true;
-    }
-    // a value outside the documented set is an error, never a silent default (a mistyped value in a cross-check test
-    // would otherwise exercise the wrong kernels and still pass)
+    // Every option of the index, once (hac_common.h: Option): the name, its documented values and the member of Tuning each goes to.
     int set_option(const char *name, const char *value) {
-        const std::string n(name), v(value ? value : "");
-        long t = 0;
-        auto one_of = [&](std::initializer_list<const char *> allowed) {
-            for (const char *a : allowed)
-                if (v == a) return true;
-            std::string list;
-            for (const char *a : allowed) list += std::string(list.empty() ? "" : " | ") + a;
-            (void)fail(HAC_ERR_INVALID, "index option %s = '%s': %s", name, v.c_str(), list.c_str());
-            return false;
+        using Opt = Option<Tuning>;
+#define TO(FIELD) HAC_OPT_TO(Tuning, FIELD)
+        static const Opt table[] = {
+            Opt::choice("split", TO(split), {{"0", 0}, {"1", 1}, {"auto", -1}}),
+            Opt::choice("split_terms", TO(split_terms), {{"1", 1}, {"3", 3}}),
+            Opt::choice("force_scan16", TO(force_scan16), {{"0", 0}, {"1", 1}}),
+            Opt::choice("scanq_nt", TO(scanq_nt), {{"0", 0}, {"1", 1}, {"2", 2}, {"3", 3}, {"4", 4}}),
+            Opt::choice("scanq_waves", TO(scanq_waves), {{"4", 4}, {"8", 8}}),
+            Opt::choice("scan_no_p8", TO(no_p8), {{"0", 0}, {"1", 1}}),
+            Opt::choice("split_decide", TO(split_decide), {{"auto", -1}, {"host", 0}, {"device", 1}}),
+            Opt::custom_form("scan_pass_cuts", "auto | a,b with 1 <= a < b <= 900", [](Tuning &t, const char *v) {
+                int a = 0, b = 0;
+                if (strcmp(v, "auto") != 0 && (sscanf(v, "%d,%d", &a, &b) != 2 || a < 1 || b <= a || b > 900)) return false;
+                t.pass_cut[0] = a;
+                t.pass_cut[1] = b;
+                return true;
+            }),
+            Opt::choice("scan_passes", TO(scan_passes), {{"auto", 0}, {"1", 1}, {"2", 2}, {"3", 3}, {"4", 4}, {"5", 5}}),
+            Opt::choice("scan_halfq", TO(no_halfq), {{"0", 1}, {"1", 0}}),
+            Opt::choice("fp16_image", TO(image_eager), {{"lazy", 0}, {"eager", 1}}),
+            Opt::choice("rescore_rows", TO(rescore_rows), {{"0", 0}, {"1", 1}, {"auto", -1}}),
+            Opt::integer("debug_oom", TO(debug_oom), 0, 1000),
+            Opt::integer("debug_max_pass", TO(debug_max_pass), 0, 1000000),
+            Opt::integer("masked_p", TO(masked_p), 1, 4096, true),
+            Opt::integer("grouped_p", TO(grouped_p), 1, 4096, true),
+            Opt::integer("after_p", TO(after_p), 1, 4096, true),
+            Opt::integer("at_rank_p", TO(at_rank_p), 1, 4096, true),
+            Opt::integer("debug_masked_tiles", TO(debug_masked_tiles), 0, 65535),
+            Opt::integer("debug_grouped_tiles", TO(debug_grouped_tiles), 0, 65535),
+            Opt::integer("debug_after_tiles", TO(debug_after_tiles), 0, 65535),
+            Opt::integer("debug_at_rank_tiles", TO(debug_at_rank_tiles), 0, 65535),
+            // (0 = 14 sqrt(groups); any other value is brought into [768, 2^30])
+            Opt::integer("seed_groups_max", [](Tuning &t, long v) { t.seed_groups_max = v <= 0 ? 0 : (int)std::max<long>(768, std::min<long>(v, 1 << 30)); }, 0, LONG_MAX),
         };
-        if (n == "split") {
-            if (!one_of({"0", "1", "auto"})) return HAC_ERR_INVALID;
-            tune.split = v == "0" ? 0 : (v == "1" ? 1 : -1);
-        } else if (n == "split_terms") {
-            if (!one_of({"1", "3"})) return HAC_ERR_INVALID;
-            tune.split_terms = v == "3" ? 3 : 1;
-        } else if (n == "force_scan16") {
-            if (!one_of({"0", "1"})) return HAC_ERR_INVALID;
-            tune.force_scan16 = v == "1";
-        } else if (n == "scanq_nt") {
-            if (!one_of({"0", "1", "2", "3", "4"})) return HAC_ERR_INVALID;
-            tune.scanq_nt = atoi(v.c_str());
-        } else if (n == "scanq_waves") {
-            if (!one_of({"4", "8"})) return HAC_ERR_INVALID;
-            tune.scanq_waves = v == "4" ? 4 : 8;
-        } else if (n == "scan_no_p8") {
-            if (!one_of({"0", "1"})) return HAC_ERR_INVALID;
-            tune.no_p8 = v == "1";
-        } else if (n == "split_decide") {
-            if (!one_of({"auto", "host", "device"})) return HAC_ERR_INVALID;
-            tune.split_decide = v == "host" ? 0 : (v == "device" ? 1 : -1);
-        } else if (n == "scan_pass_cuts") {
-            int a = 0, b = 0;
-            if (v == "auto") a = b = 0;
-            else if (sscanf(v.c_str(), "%d,%d", &a, &b) != 2 || a < 1 || b <= a || b > 900) return HAC_ERR_INVALID;
-            tune.pass_cut[0] = a;
-            tune.pass_cut[1] = b;
-        } else if (n == "scan_passes") {
-            if (!one_of({"auto", "1", "2", "3", "4", "5"})) return HAC_ERR_INVALID;
-            tune.scan_passes = v == "auto" ? 0 : atoi(v.c_str());
-        } else if (n == "scan_halfq") {
-            if (!one_of({"0", "1"})) return HAC_ERR_INVALID;
-            tune.no_halfq = v == "0";
-        } else if (n == "fp16_image") {
-            if (!one_of({"lazy", "eager"})) return HAC_ERR_INVALID;
-            tune.image_eager = v == "eager";
-        } else if (n == "rescore_rows") {
-            if (!one_of({"0", "1", "auto"})) return HAC_ERR_INVALID;
-            tune.rescore_rows = v == "0" ? 0 : (v == "1" ? 1 : -1);
-        } else if (n == "debug_oom") {
-            if (!parse_int(v, 0, 1000, t)) return fail(HAC_ERR_INVALID, "index option debug_oom = '%s': an integer 0..1000", v.c_str());
-            tune.debug_oom = (int)t;
-        } else if (n == "debug_max_pass") {
-            if (!parse_int(v, 0, 1000000, t)) return fail(HAC_ERR_INVALID, "index option debug_max_pass = '%s': an integer >= 0", v.c_str());
-            tune.debug_max_pass = (int)t;
-        } else if (n == "masked_p") {
-            if (v == "auto") t = 0;
-            else if (!parse_int(v, 1, 4096, t)) return fail(HAC_ERR_INVALID, "index option masked_p = '%s': auto | an integer 1..4096", v.c_str());
-            tune.masked_p = (int)t;
-        } else if (n == "grouped_p") {
-            if (v == "auto") t = 0;
-            else if (!parse_int(v, 1, 4096, t)) return fail(HAC_ERR_INVALID, "index option grouped_p = '%s': auto | an integer 1..4096", v.c_str());
-            tune.grouped_p = (int)t;
-        } else if (n == "debug_grouped_tiles") {
-            if (!parse_int(v, 0, 65535, t)) return fail(HAC_ERR_INVALID, "index option debug_grouped_tiles = '%s': an integer 0..65535", v.c_str());
-            tune.debug_grouped_tiles = (int)t;
-        } else if (n == "debug_masked_tiles") {
-            if (!parse_int(v, 0, 65535, t)) return fail(HAC_ERR_INVALID, "index option debug_masked_tiles = '%s': an integer 0..65535", v.c_str());
-            tune.debug_masked_tiles = (int)t;
-        } else if (n == "after_p") {
-            if (v == "auto") t = 0;
-            else if (!parse_int(v, 1, 4096, t)) return fail(HAC_ERR_INVALID, "index option after_p = '%s': auto | an integer 1..4096", v.c_str());
-            tune.after_p = (int)t;
-        } else if (n == "debug_after_tiles") {
-            if (!parse_int(v, 0, 65535, t)) return fail(HAC_ERR_INVALID, "index option debug_after_tiles = '%s': an integer 0..65535", v.c_str());
-            tune.debug_after_tiles = (int)t;
-        } else if (n == "at_rank_p") {
-            if (v == "auto") t = 0;
-            else if (!parse_int(v, 1, 4096, t)) return fail(HAC_ERR_INVALID, "index option at_rank_p = '%s': auto | an integer 1..4096", v.c_str());
-            tune.at_rank_p = (int)t;
-        } else if (n == "debug_at_rank_tiles") {
-            if (!parse_int(v, 0, 65535, t)) return fail(HAC_ERR_INVALID, "index option debug_at_rank_tiles = '%s': an integer 0..65535", v.c_str());
-            tune.debug_at_rank_tiles = (int)t;
-        } else if (n == "seed_groups_max") {
-            if (!parse_int(v, 0, LONG_MAX, t)) return fail(HAC_ERR_INVALID, "index option seed_groups_max = '%s': an integer >= 0 (0 = 14 sqrt(groups))", v.c_str());
-            tune.seed_groups_max = t <= 0 ? 0 : (int)std::max<long>(768, std::min<long>(t, 1 << 30));
-        } else {
-            return fail(HAC_ERR_INVALID, "unknown index option '%s'", name);
-        }
-        return HAC_OK;
+#undef TO
+        return apply_option("index", table, tune, name, value ? value : "");
     }
-    GrowBuf ws_partial, ws_pcnt, ws_seedkeys, ws_thr, ws_thrglob, ws_q, ws_qt, ws_keys, ws_D, ws_I, ws_stage[2];
-    // split-bf16 prefilter path (scan_split.inc)
-    GrowBuf ws_norm, ws_qsplit, ws_delta, ws_cand, ws_akeys, ws_fail, ws_stat;
-    GrowBuf ws_err;            // [0] device error bits (sticky until read), [1] workgroups that hit a pass bound (ScanArgs::err)
-    u32 *h_err = nullptr;      // pinned copy
-
-    GrowBuf ws_fbidx[2], ws_fbq[2], ws_fbkeys[2];   // per cascade level: failed queries, their matrix, their keys
-    PinBuf h_fb;               // u32 words: [0] failed queries, [1] max |s~ - s| / delta (float bits), [2..] flags / indices
+    u32 *h_err = nullptr;      // pinned copy of ws_err
     long split_searches = 0, split_fallback_queries = 0;
-    PinBuf h_stage[2];
-    // Small host<->device traffic (queries, results, segment table) always goes through
-    // pinned memory: pageable hipMemcpyAsync is not reliably stream-ordered on this stack.
-    PinBuf h_pin;
     SegDesc *h_segs = nullptr;
     int pin_reserve(size_t bytes) { return bytes <= h_pin.cap ? HAC_OK : h_pin.reserve(bytes + bytes / 4, bytes); }
     hipEvent_t stage_ev[2] = {nullptr, nullptr};
@@ -1364,26 +1315,7 @@ struct DeviceIndex {
             h_plan[2 * i] = h_plan[2 * i + 1] = 0u;
             HAC_HIP(hipEventCreateWithFlags(&ev_plan[i], hipEventDisableTiming));
         }
-        static bool attr_done[64] = {false};
-        if (device < 64 && !attr_done[device]) {
-            HAC_HIP(hipFuncSetAttribute((const void *)scan16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)LDS_LIMIT));
-            HAC_HIP(hipFuncSetAttribute((const void *)merge_keys_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)(64 * 1024)));
-            for (const ScanqEntry &e : SCANQ_TABLE) HAC_HIP(hipFuncSetAttribute((const void *)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
-            HAC_HIP(hipFuncSetAttribute((const void *)sample_scores_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(64 * 1024)));
-            for (const ScanhEntry &e : SCANH_TABLE) HAC_HIP(hipFuncSetAttribute((const void *)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
-            HAC_HIP(hipFuncSetAttribute((const void *)count_ahead_kernel<RANK_MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
-            HAC_HIP(hipFuncSetAttribute((const void *)range_emit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
-            HAC_HIP(hipFuncSetAttribute((const void *)rank_hist_kernel<AT_BITS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
-            // (DYNAMIC LDS: without it a large k, whose candidate buffers pass the default 64 KiB, fails to launch)
-            HAC_HIP(hipFuncSetAttribute((const void *)scan16_masked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
-            HAC_HIP(hipFuncSetAttribute((const void *)scan16_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
-            HAC_HIP(hipFuncSetAttribute((const void *)scan16_after_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
-            HAC_HIP(hipFuncSetAttribute((const void *)scan16_masked_after_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
-            HAC_HIP(hipFuncSetAttribute((const void *)grouped_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, grouped_select_cm(HAC_MAX_K) * 16));   // (beside its static words)
-            attr_done[device] = true;
-        }
+        HAC_TRY(raise_lds_limits(device));
         return HAC_OK;
     }
 
@@ -1400,11 +1332,7 @@ struct DeviceIndex {
         if (h_segs) (void)hipHostFree(h_segs);
         if (d_rimg) (void)hipFree(d_rimg);
         if (h_rimg) (void)hipHostFree(h_rimg);
-        for (PinBuf *b : {&h_pin, &h_fb, &h_stage[0], &h_stage[1]}) b->release();
-        for (GrowBuf *b : {&ws_partial, &ws_pcnt, &ws_seedkeys, &ws_thr, &ws_thrglob, &ws_q, &ws_qt, &ws_keys, &ws_D, &ws_I, &ws_stage[0],
-                           &ws_stage[1], &ws_err, &ws_norm, &ws_qsplit, &ws_delta, &ws_cand, &ws_akeys, &ws_fail, &ws_stat, &ws_fbidx[0], &ws_fbidx[1],
-                           &ws_fbq[0], &ws_fbq[1], &ws_fbkeys[0], &ws_fbkeys[1], &ws_ids, &ws_rank, &ws_range, &ws_among, &ws_mgroups, &ws_mcnt, &ws_masks, &ws_labels, &ws_after, &ws_atrank})
-            b->release();
+        release_all<IndexWorkspaces>(*this);
         if (h_err) (void)hipHostFree(h_err);
         if (h_plan) (void)hipHostFree(h_plan);
         for (hipEvent_t ev : ev_plan)
@@ -1818,14 +1746,6 @@ struct DeviceIndex {
     }
     int nseg_live = 0;
 
-    GrowBuf ws_ids, ws_rank;   // the by-id calls (rows_host.inc): a chunk's ids; the rank calls' counters and reference scores
-    GrowBuf ws_range;          // range search (rows_host.inc: RangeWs): control words, counters, cursors, staging and the two key buffers
-    GrowBuf ws_among;          // search among named rows (search_host.inc: among_keys_device): a chunk's [queries][P] candidate keys
-    GrowBuf ws_mgroups, ws_mcnt;   // search inside a bitmap (search_keys_masked): one launch's group lists u32 [tiles][G], the call's counters u32 [tiles]
-    GrowBuf ws_masks;          // its host form (search_host.inc: masked_shard): a chunk's masks and mask_of
-    GrowBuf ws_labels;         // search by group, host form (search_host.inc: grouped_shard): the shard's slice of the labels
-    GrowBuf ws_atrank;         // entry at a rank (rows_host.inc: entries_at_keys_device): a launch's pair states and histograms, the call's keys
-    GrowBuf ws_after;          // search behind a cursor (search_host.inc): the bounds u64 [queries] of a (score, row) call, or of a host chunk
 
     char last_plan[320] = "none";
     // a device-decided prefilter search leaves its fallback count and err / bound on the device: plan() completes the text
@@ -2677,6 +2597,35 @@ struct DeviceIndex {
     }
 };
 
+// Every kernel whose dynamic-LDS limit is raised, and the most its launches ask for: the scan forms and the kernels built on their
+// row loop size their LDS up to LDS_LIMIT (make_plan and its kin), the merge, the sampling and the group selection by their own
+// rules.  Without the raised limit a large k, whose candidate buffers pass the default 64 KiB, fails to launch.
+constexpr size_t LDS_DEFAULT = 64 * 1024;   // what a launch may ask for without a raised limit (set all the same for the kernels that stay within it)
+const LdsKernel LDS_KERNELS[] = {
+    {scan16_kernel, LDS_LIMIT},
+    {merge_keys_kernel, LDS_DEFAULT},
+    {sample_scores_kernel, LDS_DEFAULT},
+    {count_ahead_kernel<RANK_MT>, LDS_LIMIT},
+    {range_emit_kernel, LDS_LIMIT},
+    {rank_hist_kernel<AT_BITS>, LDS_LIMIT},
+    {scan16_masked_kernel, LDS_LIMIT},
+    {scan16_grouped_kernel, LDS_LIMIT},
+    {scan16_after_kernel, LDS_LIMIT},
+    {scan16_masked_after_kernel, LDS_LIMIT},
+    {grouped_select_kernel, (size_t)DeviceIndex::grouped_select_cm(HAC_MAX_K) * 16},   // (beside its static words)
+};
+// once per device, by whichever comes first: an index on it or a hac_merge_keys_device call
+int raise_lds_limits(int device) {
+    static bool attr_done[64] = {false};
+    if (device < 0 || device >= 64 || attr_done[device]) return HAC_OK;
+    std::vector<LdsKernel> all(std::begin(LDS_KERNELS), std::end(LDS_KERNELS));
+    for (const ScanqEntry &e : SCANQ_TABLE) all.emplace_back(e.fn, LDS_LIMIT);
+    for (const ScanhEntry &e : SCANH_TABLE) all.emplace_back(e.fn, LDS_LIMIT);
+    for (const LdsKernel &k : all) HAC_HIP(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.bytes));
+    attr_done[device] = true;
+    return HAC_OK;
+}
+
 int merge_plan_lds(int k, int &Cm, size_t &lds) {
     Cm = (int)next_pow2((u32)k + MERGE_THREADS);
     lds = (size_t)Cm * 8 + 32;
@@ -2703,14 +2652,17 @@ int check_k_e(int k, int e) {
 // =============================================================================
 using namespace hac;
 
-struct hac_index {
+// the workspaces of a whole index, on shard 0's device; hac_index_destroy releases the struct at once
+struct MergeWorkspaces {
+    GrowBuf ws_lists, ws_out;   // the multi-device merge
+    GrowBuf ws_excl;   // hac_index_search_excluding: the host's exclusion lists
+    GrowBuf ws_glabels;   // hac_index_search_grouped on several devices: the whole label array (the merge reads it)
+};
+
+struct hac_index : MergeWorkspaces {
     int d = 0;
     std::vector<DeviceIndex *> shards;  // one per device (n_dev == 1 in the one-process-per-GPU deployment)
     int64_t ntotal = 0;
-    // multi-device merge workspace lives on shard 0
-    GrowBuf ws_lists, ws_out;
-    GrowBuf ws_excl;   // hac_index_search_excluding: the host's exclusion lists, on shard 0
-    GrowBuf ws_glabels;   // hac_index_search_grouped on several devices: the whole label array, on shard 0 (the merge reads it)
     // n_dev > 1: per shard, its share of every add() (see remap_positions_kernel)
     std::vector<std::vector<SpanDesc>> spans;
     std::vector<GrowBuf> ws_spans;
@@ -2810,10 +2762,7 @@ void hac_index_destroy(hac_index *idx) {
     if (!idx) return;
     if (!idx->shards.empty()) {
         DeviceGuard g(idx->shards[0]->device);
-        idx->ws_lists.release();
-        idx->ws_out.release();
-        idx->ws_glabels.release();
-        idx->ws_excl.release();
+        release_all<MergeWorkspaces>(*idx);
     }
     for (size_t i = 0; i < idx->shards.size(); ++i) {
         if (i < idx->ws_spans.size()) {
@@ -2905,11 +2854,7 @@ int hac_merge_keys_device(int device, const uint64_t *lists_dev, int n_lists, in
     int Cm;
     size_t lds;
     merge_plan_lds(k, Cm, lds);
-    static bool attr_done[64] = {false};
-    if (device >= 0 && device < 64 && !attr_done[device]) {
-        HAC_HIP(hipFuncSetAttribute((const void *)merge_keys_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(64 * 1024)));
-        attr_done[device] = true;
-    }
+    HAC_TRY(raise_lds_limits(device));
     merge_keys_kernel<<<dim3((unsigned)nq), dim3(MERGE_THREADS), lds, (hipStream_t)hip_stream>>>(
         (const u64 *)lists_dev, n_lists, (size_t)nq * k, (size_t)k, k, Cm, (u64 *)out_dev, nullptr, nullptr);
     HAC_HIP(hipGetLastError());

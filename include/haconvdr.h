@@ -378,7 +378,8 @@ int hac_index_search_among_keys_device(hac_index *idx, const float *q_dev, int64
  *
  * How (csrc/masked.inc, csrc/scan16_filter.inc): mask_groups_kernel builds, per query tile, the list of the 64-row groups in which the OR of the tile's
  * queries' mask words is non-zero (clipped to ntotal in the last group; ballot + prefix, one atomic per wave; the order of a
- * list is unspecified and does not matter).  scan16_masked_kernel is a copy of scan16_kernel whose work items are that list:
+ * list is unspecified and does not matter).  scan16_masked_kernel is the list form of the one filtered body
+ * (scan16_filter<LIST, CURSOR>, built like scan16_kernel from the shared row loop of csrc/scan16_core.inc) whose work items are that list:
  * the same row stream, the same bit-exact MFMA chain, the same candidate buffers and compaction; its epilogue appends a row
  * only if the lane's own query's mask word has the row's bit.  A row is tested before it becomes a candidate, so every
  * threshold comes from selected rows and is a proven lower bound of the masked k-th score: the result does not depend on the
@@ -436,8 +437,9 @@ int hac_index_search_masked_keys_device(hac_index *idx, const float *q_dev, int6
  * value, -1 in padding slots.  1 <= k <= HAC_MAX_K; a k whose buffers do not fit LDS fails as search does, naming k.  nq == 0 is
  * HAC_OK and touches nothing; ntotal == 0 gives padding only.
  *
- * How (csrc/grouped.inc): scan16_grouped_kernel is a copy of scan16_kernel -- the same row stream, the same bit-exact MFMA
- * chain, the same candidate buffers -- whose compaction sorts the buffer, gathers each entry's label, keeps only the best entry
+ * How (csrc/grouped.inc): scan16_grouped_kernel is built from the row loop scan16_kernel is built from
+ * (csrc/scan16_core.inc) -- the same row stream, the same bit-exact MFMA
+ * chain, the same candidate buffers -- and its own compaction sorts the buffer, gathers each entry's label, keeps only the best entry
  * of every label (a second sort, of (label << 32 | list position) words in a scratch LDS array) and cuts to k.  Only when k
  * distinct labels remain does the k-th key become the query's threshold: it is then the k-th best of k distinct groups' entries,
  * a proven lower bound of the k-th group score, so the result does not depend on the number of row streams, the launch cuts or
@@ -508,8 +510,9 @@ int hac_index_search_grouped_device(hac_index *idx, const float *q_dev, int64_t 
  * 1 <= k <= HAC_MAX_K; nq == 0 is HAC_OK and touches nothing; ntotal == 0 gives padding only.
  *
  * How (csrc/after.inc, csrc/scan16_filter.inc): after_bounds_kernel turns the cursors into each query's exclusive upper key bound (NaN score, row -1 or
- * row < -2: 0; row -2: all-ones; otherwise the key of (s_ref + 0.0f, min(row, 2^32 - 1))).  scan16_after_kernel is a copy of
- * scan16_kernel over every 64-row group -- the same row stream, the same bit-exact MFMA chain, the same candidate buffers and
+ * row < -2: 0; row -2: all-ones; otherwise the key of (s_ref + 0.0f, min(row, 2^32 - 1))).  scan16_after_kernel is the cursor form of
+ * the filtered body (scan16_filter<LIST, CURSOR>: scan16_masked_after_kernel is both forms at once), over every 64-row group -- scan16_kernel's row loop
+ * (csrc/scan16_core.inc): the same row stream, the same bit-exact MFMA chain, the same candidate buffers and
  * compaction -- whose epilogue appends a row only if its key is below the lane's own query's bound.  A row is tested before it
  * becomes a candidate, so every threshold comes from eligible rows and is a proven lower bound of the answer's k-th score: the
  * result does not depend on the number of row streams, the launch cuts or the order of work.  No threshold seeding: a sample of
@@ -715,8 +718,11 @@ int hac_index_last_status(hac_index *idx);
  * ("search by group").  Same bits either way.
  * "after_p" / "debug_after_tiles" and "at_rank_p" / "debug_at_rank_tiles": the same pairs of hac_index_search_after* ("search behind
  * a cursor") and hac_index_entries_at* ("entry at a rank").  Same bits either way.
- * Any other name or value is HAC_ERR_INVALID (never a silent default).
- * The HAC_<NAME> environment variables give the defaults and are read once, in hac_index_create. */
+ * Any other name or value is HAC_ERR_INVALID (never a silent default), hac_last_error() naming the option, the value and the
+ * allowed set; a rejected value changes nothing.
+ * Six environment variables give the defaults of the first six options and are read once, leniently (a value outside the set
+ * falls to a default), in hac_index_create: HAC_SPLIT, HAC_SPLIT_TERMS, HAC_FORCE_SCAN16, HAC_SCANQ_NT, HAC_SCANQ_WAVES and
+ * HAC_SCAN_NO_P8 (set to anything: "1").  The other options have no variable. */
 int hac_index_set_option(hac_index *idx, const char *name, const char *value);
 
 /* Profiling aid for bench.py: when enabled, the main scan kernel of every search is
